@@ -1,7 +1,9 @@
 #!/usr/bin/env python
 """Benchmarks of the tiatoolbox per-patch hot path on MI355X.  Prints ONE JSON line on rank 0.
 
-    python bench.py --gpus N --steps K --warmup W            # headline (BASELINE configs[1])
+    python bench.py --gpus N --steps K --warmup W            # headline (BASELINE configs[1]): the result line only
+    python bench.py --gpus N --steps K --warmup W --full     # + roofline, extras, configs[2]-[4], cpu_baseline (below)
+    python bench.py ... --dump-outputs DIR                   # + the last timed step's outputs as DIR/<name>.npy
     python bench.py --config semantic|hovernet|vahadane ...   # BASELINE configs[2], [3], [4] (see bench_configs.py)
 
 ``--gpus N`` with N > 1 started plainly re-launches itself as ``python -m torch.distributed.run --nproc-per-node N``
@@ -19,17 +21,25 @@ reference's f64 per-pixel arithmetic by default, uint8 out like the reference), 
 hand-written kernels only (stem: uint8 in, ``ToTensor``'s 1/255 on load, conv7x7 + bias + ReLU + max-pool; blocks: MFMA
 implicit GEMM -- the reference's arithmetic, ``vanilla.py:242``), softmax, argmax, the RCCL all-gather of the probabilities
 (N > 1) and the copy of the result dict to host NumPy.  For ``value`` the uint8 patches are already resident in HBM when the timed region starts
-(the engine's torch-tensor overload); the same call on HOST NumPy patches (H2D over PCIe included) is timed right after
-and reported as ``host_inclusive`` (engine batches of 1024 there, so that copies hide behind compute; the resident run takes its
-4096 patches as ONE engine batch: ``--micro-batch``).  ``value`` runs the engine's default ``conv_algo="auto"`` (float32 Winograd F(2x2, 3x3)
-for the 3x3 / stride-1 block convolutions -- float32 in, float32 accumulate, gated by a committed per-layer error-bound test; executed and
-effective flops reported separately).  Extras on rank 0 at N=1: ``cnn_direct`` = the same call with ``conv_algo="direct"`` (the audit mode:
-direct implicit GEMM everywhere) with its kernels' rooflines, the fp16 backbone with its measured max |dp| against the
-fp32 probabilities of the same batch (tolerance 1e-3, ``tests/engines/test_patch_predictor.py:719`` of the reference),
-the 224x224 patch size of BASELINE configs[1], and -- ``extras.configs`` -- a SHORT run of each of BASELINE configs[2]-[4]
-(``bench_configs.py``: semantic / hovernet / vahadane; value, step time, the config's roofline entry, a one-line CPU baseline), so
-that the driver's default ``python bench.py`` observes all five configurations (``--no-extras`` skips them).  With N > 1 the line also carries every rank's own step time and the
-time of the all-gather alone (``per_rank``), so that a scaling run explains itself.
+(the engine's torch-tensor overload).  ``value`` runs the engine's default ``conv_algo="auto"`` (float32 Winograd F(2x2, 3x3)
+for the 3x3 / stride-1 block convolutions -- float32 in, float32 accumulate, gated by a committed per-layer error-bound test).
+
+A plain run sets up, warms up, times ``--steps`` steps and prints the line (``value``, ``ms_per_step``, ...); with N > 1 the line
+also carries every rank's own step time (``per_rank``) and the process group it ran on (``rccl``).  Everything else takes runs of its own
+and is measured only with ``--full``: ``roofline`` (per-kernel HIP-event times, executed and effective flops, committed counter
+traffic), the same call on HOST NumPy patches (H2D over PCIe included) as ``host_inclusive`` (engine batches of 1024 there, so that
+copies hide behind compute; the resident run takes its 4096 patches as ONE engine batch: ``--micro-batch``), the time of the
+all-gather alone (``per_rank``, N > 1), ``cpu_baseline``, and extras on rank 0 at N=1: ``cnn_direct`` = the same call with
+``conv_algo="direct"`` (the audit mode: direct implicit GEMM everywhere) with its kernels' rooflines, the fp16 backbone with its
+measured max |dp| against the fp32 probabilities of the same batch (tolerance 1e-3, ``tests/engines/test_patch_predictor.py:719``
+of the reference), the 224x224 patch size of BASELINE configs[1], the classic stages (``bench_classic.py``), and --
+``extras.configs`` -- a SHORT run of each of BASELINE configs[2]-[4] (``bench_configs.py``: semantic / hovernet / vahadane; value,
+step time, the config's roofline entry, a one-line CPU baseline), so that ``python bench.py --full`` observes all five
+configurations (``--full --no-extras`` skips the extras, ``--full --no-cpu-baseline`` the CPU baseline).
+
+``--dump-outputs DIR`` writes, after the timed steps, what the last timed step returned to its caller (``probabilities``,
+``predictions``) as ``DIR/<name>.npy`` in float32 (float64 stays float64), so that two builds can be compared output for
+output: the inputs and weights are seeded, identical from run to run for the same arguments.
 """
 
 from __future__ import annotations
@@ -50,7 +60,7 @@ MFMA_PEAK_TFLOPS = {"float16": 2500.0, "bfloat16": 2500.0, "float32": 157.3}
 RESNET18_GFLOP_224 = 3.64  # 1.82 GMAC per 224x224 patch; scales with the pixel count (4.75 at 256x256)
 
 
-def parse() -> argparse.Namespace:
+def parse(argv: list[str] | None = None) -> argparse.Namespace:
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=10)
@@ -63,12 +73,47 @@ def parse() -> argparse.Namespace:
                     choices=["float32", "float16", "bfloat16"], help="CNN arithmetic (reference: float32)")
     ap.add_argument("--precision", default="f64", choices=["f32", "f64"],
                     help="per-pixel arithmetic of the stain apply kernel (reference: f64; statistics are always f64)")
+    ap.add_argument("--full", action="store_true",
+                    help="--config patch: also measure roofline, host-inclusive, extras and cpu_baseline (a plain run times the steps only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="--config patch: write the last timed step's outputs as DIR/<name>.npy (float32 / float64)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-extras", action="store_true",
-                    help="skip host-inclusive / fp16 / 224^2 extra measurements and the short runs of BASELINE configs[2]-[4]")
+                    help="with --full: skip host-inclusive / fp16 / 224^2 extra measurements and the short runs of BASELINE configs[2]-[4]")
     ap.add_argument("--cpu-sample", type=int, default=64)
     ap.add_argument("--slide", type=int, default=20000, help="--config semantic: slide edge in pixels")
-    return ap.parse_args()
+    args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.dump_outputs is not None and args.config != "patch":
+        ap.error("--dump-outputs is implemented for --config patch only")
+    return args
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(outputs: dict, out_dir: Path, limit: int = DUMP_LIMIT_BYTES) -> None:
+    """``out_dir/<name>.npy`` for every array of ``outputs``: float64 stays float64, everything else (probabilities, the integer
+    class predictions: exact below 2^24) is written as float32.  Above ``limit`` bytes in all, every array keeps the same rows of its
+    leading (patch) axis: a sample drawn with a fixed seed, so that runs with the same arguments write the same rows."""
+    import numpy as np
+
+    arrays = {}
+    for name, val in outputs.items():
+        a = np.asarray(val)
+        arrays[name] = a.astype(np.float64 if a.dtype == np.float64 else np.float32)
+    total = sum(a.nbytes for a in arrays.values())
+    if total > limit:
+        rows = {a.shape[0] for a in arrays.values()}
+        assert len(rows) == 1, f"cannot sample outputs with different leading axes: {[a.shape for a in arrays.values()]}"
+        n = rows.pop()
+        keep = max(1, int(n * limit // total))
+        idx = np.sort(np.random.default_rng(0).choice(n, keep, replace=False))
+        arrays = {k: a[idx] for k, a in arrays.items()}
+    out_dir.mkdir(parents=True, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(out_dir / f"{name}.npy", np.ascontiguousarray(a))
 
 
 # ----------------------------------------------------------------------------------------------------------------------
@@ -520,23 +565,25 @@ def bench_patch(args: argparse.Namespace) -> dict | None:
     per_rank = None
     if world_size > 1:
         torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.MAX)
-        # diagnostics for the scaling run: every rank's own step time, and the all-gather of the probabilities alone
+        # diagnostics for the scaling run: every rank's own step time, and (--full) the all-gather of the probabilities alone
         owns = torch.zeros(world_size, dtype=torch.float64, device=device)
         owns[rank] = own / args.steps * 1e3
         torch.distributed.all_reduce(owns)
-        local = torch.rand((n, 9), device=device)
-        tdist.all_gather_rows(local, n * world_size)
-        barrier()
-        t0 = time.perf_counter()
-        for _ in range(20):
-            tdist.all_gather_rows(local, n * world_size)
-        barrier()
         per_rank = {"own_ms_per_step": [round(float(v), 3) for v in owns.cpu().tolist()],
-                    "allgather_probabilities_ms": round((time.perf_counter() - t0) / 20 * 1e3, 4),
-                    "allgather_bytes_per_rank": n * 9 * 4,
                     "what": ("own = rank-local wall time per step before the closing barrier (the step already contains the "
-                             "all-gather, which synchronises the ranks); allgather = 20 back-to-back padded "
-                             "all_gather_into_tensor calls of the [patches_per_gpu, 9] float32 probabilities")}
+                             "all-gather, which synchronises the ranks)")}
+        if args.full:
+            local = torch.rand((n, 9), device=device)
+            tdist.all_gather_rows(local, n * world_size)
+            barrier()
+            t0 = time.perf_counter()
+            for _ in range(20):
+                tdist.all_gather_rows(local, n * world_size)
+            barrier()
+            per_rank["allgather_probabilities_ms"] = round((time.perf_counter() - t0) / 20 * 1e3, 4)
+            per_rank["allgather_bytes_per_rank"] = n * 9 * 4
+            per_rank["what"] += ("; allgather = 20 back-to-back padded all_gather_into_tensor calls of the [patches_per_gpu, 9] "
+                                 "float32 probabilities")
     elapsed = float(t.item())
     probs = out["probabilities"]
     assert probs.shape == (n * world_size, 9) and np.isfinite(probs).all()
@@ -552,7 +599,8 @@ def bench_patch(args: argparse.Namespace) -> dict | None:
         "scaling": "weak", "vs_baseline": None, "dtype": args.dtype, "data": "synthetic",
         "config": {"workload": (f"{n} x {hw}x{hw}x3 u8 patches/GPU in HBM, PatchPredictor(resnet18-kather100k).run(), Macenko pre-norm "
                                 f"(f64 stats, {args.precision} apply), CNN {args.dtype} hand-written HIP, conv_algo=auto (Winograd F(2x2,3x3) "
-                                f"on 3x3/s1; direct: extras.cnn_direct); seeded random weights; configs[1] 224^2: extras.patch_224"),
+                                f"on 3x3/s1; direct: extras.cnn_direct with --full); seeded random weights; configs[1] 224^2: "
+                                f"extras.patch_224 with --full"),
                    "api": "PatchPredictor.run(images, patch_mode=True, return_probabilities=True, stain_normalizer=...)",
                    "patches_per_gpu": n, "patch_size": hw, "engine_batch_size": args.micro_batch,
                    "parallelism": f"dp{world_size} (patch-sharded, all_gather of probabilities)"},
@@ -561,6 +609,10 @@ def bench_patch(args: argparse.Namespace) -> dict | None:
         assert per_rank is not None and rccl_info is not None  # a multi-GPU line always explains itself
         line["per_rank"] = per_rank
         line["rccl"] = rccl_info
+    if args.dump_outputs is not None:
+        dump_outputs(out, Path(args.dump_outputs))
+    if not args.full:
+        return line
 
     # ---- per-kernel timing with HIP events on the launch stream ------------------------------------------------
     dtype_t = {"float32": torch.float32, "float16": torch.float16, "bfloat16": torch.bfloat16}[args.dtype]

@@ -27,7 +27,7 @@ grep -h "conv3x3\|conv_mfma\|stem7x7" $OUT/${TAG}_trunk_pmc_*.txt | cut -c1-120
 # the bench reads the traffic of its dominant kernel from profiles/: make this pass visible to the runs below
 cp $OUT/${TAG}_trunk_pmc_*.txt $OUT/${TAG}_stain_pmc_*.txt $R/profiles/ 2>/dev/null
 cd $R
-timeout 900 python bench.py --steps 20 --warmup 5 > $OUT/${TAG}_bench.json 2> $OUT/${TAG}_bench.err; echo "bench rc=$?"; cut -c1-400 $OUT/${TAG}_bench.json
+timeout 900 python bench.py --full --steps 20 --warmup 5 > $OUT/${TAG}_bench.json 2> $OUT/${TAG}_bench.err; echo "bench rc=$?"; cut -c1-400 $OUT/${TAG}_bench.json
 cd /tmp
 rm -rf /tmp/rp_bench; timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/rp_bench -- \
     python $R/bench.py --steps 3 --warmup 2 --no-cpu-baseline --no-extras > $OUT/${TAG}_bench_under_rocprof.json 2> /dev/null

@@ -552,6 +552,19 @@ int tia_conv3x3_wino_nhwc_f32(const float* d_x, const float* d_u_packed, const f
                               int64_t n, int64_t h, int64_t w, int64_t cin, int64_t cout, int64_t pad_top, int64_t pad_left,
                               int64_t ho, int64_t wo, int32_t relu, void* stream);
 
+/* Winograd F(4x2, 3x3) form of the same convolution (conv3x3_wino42.hip): F(4, 3) over rows x F(2, 3) over columns, 24 instead of
+ * 36 multiplies per 4 x 2 outputs (3 per output against F(2x2)'s 4), same contract and fused epilogue as tia_conv3x3_wino_nhwc_f32,
+ * within the same 1e-5 (relative) of a direct float32 convolution.  cin % 16 == 0, cout % 64 == 0.
+ *   tia_conv_pack_weights_wino42_f32: OIHW [cout][cin][3][3] -> U = G4 g G2^T (float64, rounded once), 24 * cin * cout floats
+ *   ([pos 24][cin/16][h8 2][cout/64][hi 2][64 cout][4 channels], pos = 4 i + j, i: F(4, 3) row, j: F(2, 3) column).
+ *   tia_conv3x3_wino_form: host-only route query (no launch) -- which form the fused resnet blocks take for a 3x3 / stride-1
+ *   layer of this shape ("same" padding `pad`): 1 F(4x2), 0 F(2x2); TIA_EINVAL / TIA_ESIZE for shapes no Winograd form serves. */
+int tia_conv_pack_weights_wino42_f32(const float* d_w_oihw, int64_t cout, int64_t cin, float* d_packed, void* stream);
+int tia_conv3x3_wino42_nhwc_f32(const float* d_x, const float* d_u_packed, const float* d_bias, const float* d_residual, float* d_y,
+                                int64_t n, int64_t h, int64_t w, int64_t cin, int64_t cout, int64_t pad_top, int64_t pad_left,
+                                int64_t ho, int64_t wo, int32_t relu, void* stream);
+int tia_conv3x3_wino_form(int64_t n, int64_t h, int64_t w, int64_t cin, int64_t cout, int64_t pad);
+
 /* Host-only query (no launch): which kernel tia_conv2d_nhwc_f32[_ex] runs a float32 convolution of this shape on --
  * 0: conv_mfma_f32_kernel (register-staged 128-pixel slices), 1: conv3x3_spatial_kernel (tap reuse; tia_conv3x3_geometry says
  * which block geometry), 2: conv1x1_ring_kernel (LDS-DMA ring over 256-pixel blocks: 1x1, and kh x kw taps gathered).  For

@@ -1,6 +1,6 @@
-"""Winograd F(2x2, 3x3) vs the direct tap-reuse kernel, per 3x3 / stride-1 layer of resnet18 at a batch and patch size, and the whole
+"""Winograd F(2x2, 3x3) and F(4x2, 3x3) vs the direct tap-reuse kernel, per 3x3 / stride-1 layer of resnet18 at a batch and patch size, and the whole
 trunk.  usage: perf_wino.py [batch=1024] [patch=256]  (HIP events on the launch stream; TFLOP/s are DIRECT-convolution flops / time,
-i.e. 'effective' for the Winograd rows, whose executed MFMA flops are 16/36 of that -- printed as `exec`)."""
+i.e. 'effective' for the Winograd rows, whose executed MFMA flops are 16/36 (F(2x2)) and 24/72 (F(4x2)) of that -- printed as `exec`)."""
 import sys
 from pathlib import Path
 
@@ -8,7 +8,8 @@ import torch
 
 sys.path.insert(0, str(Path(__file__).resolve().parents[1]))
 
-from tiatoolbox_amd.models.architecture.fused import hip_conv2d, hip_conv3x3_wino, pack_conv_weights, pack_conv_weights_wino
+from tiatoolbox_amd.models.architecture.fused import (hip_conv2d, hip_conv3x3_wino, pack_conv_weights, pack_conv_weights_wino,
+                                                      pack_conv_weights_wino42)
 
 
 def ev(fn, reps=10):
@@ -28,38 +29,44 @@ def main():
     patch = int(sys.argv[2]) if len(sys.argv) > 2 else 256
     pmc = len(sys.argv) > 3 and sys.argv[3] == "pmc"
     g = torch.Generator(device="cuda").manual_seed(0)
-    tot_d = tot_w = 0.0
+    tot_d = tot_w = tot_4 = 0.0
     for c, div, count in ((64, 4, 4), (128, 8, 3), (256, 16, 3), (512, 32, 3)):
         hw = patch // div
         conv = torch.nn.Conv2d(c, c, 3, padding=1).cuda()
         x = torch.randn((n, c, hw, hw), device="cuda", generator=g).contiguous(memory_format=torch.channels_last)
         res = torch.randn_like(x)
-        wp, up = pack_conv_weights(conv), pack_conv_weights_wino(conv)
+        wp, up, u4 = pack_conv_weights(conv), pack_conv_weights_wino(conv), pack_conv_weights_wino42(conv)
         flops = 2.0 * n * hw * hw * c * c * 9
         f0 = lambda: hip_conv2d(x, wp, conv.bias, res, kernel=3, stride=1, padding=1, relu=True)  # noqa: E731
         f2 = lambda: hip_conv3x3_wino(x, up, conv.bias, res, padding=1, relu=True)  # noqa: E731
+        f4 = lambda: hip_conv3x3_wino(x, u4, conv.bias, res, padding=1, relu=True)  # noqa: E731
         if pmc:  # counter-pass workload: the 13 Winograd launches of exactly two forwards (see perf_trunk.py "pmc")
             for _ in range(2 * count):
-                f2()
+                (f2 if len(sys.argv) > 4 and sys.argv[4] == "f22" else f4)()
             continue
         for _ in range(30):  # the clocks ramp up over the first tens of milliseconds of load: an unwarmed first column reads 5-10 % slow
             f0()             # (the "direct" column of profiles/r05b..r05o_perf_wino*.txt was measured without this and is pessimistic)
-        td, tw = ev(f0), ev(f2)
+        td, tw, t4 = ev(f0), ev(f2), ev(f4)
         for _ in range(2):  # interleaved rounds, best of three
-            td, tw = min(td, ev(f0)), min(tw, ev(f2))
+            td, tw, t4 = min(td, ev(f0)), min(tw, ev(f2)), min(t4, ev(f4))
         a = hip_conv2d(x, wp, conv.bias, res, kernel=3, stride=1, padding=1, relu=False)
         b = hip_conv3x3_wino(x, up, conv.bias, res, padding=1, relu=False)
+        b4 = hip_conv3x3_wino(x, u4, conv.bias, res, padding=1, relu=False)
         rel = ((a - b).abs().max() / a.abs().max()).item()
+        rel4 = ((a - b4).abs().max() / a.abs().max()).item()
         tot_d += td * count
         tot_w += tw * count
+        tot_4 += t4 * count
         print(f"3x3 {c:3d}->{c:3d} @{hw:3d} n={n}: direct {td:6.3f} ms {flops / td / 1e9:6.1f} TF/s | winograd {tw:6.3f} ms "
-              f"{flops / tw / 1e9:6.1f} TF/s effective, {flops * 16 / 36 / tw / 1e9:6.1f} exec | x{td / tw:4.2f} | max rel diff {rel:.1e}",
-              flush=True)
+              f"{flops / tw / 1e9:6.1f} TF/s effective, {flops * 16 / 36 / tw / 1e9:6.1f} exec | x{td / tw:4.2f} | max rel diff {rel:.1e} || F(4x2) "
+              f"{t4:6.3f} ms {flops / t4 / 1e9:6.1f} TF/s effective, {flops * 24 / 72 / t4 / 1e9:6.1f} exec | x{tw / t4:4.2f} vs F(2x2) | "
+              f"max rel diff {rel4:.1e}", flush=True)
     if pmc:
         torch.cuda.synchronize()
         print("PMC forwards=2")
         return
-    print(f"13 stride-1 3x3 launches of one resnet18 forward: direct {tot_d:.2f} ms, winograd {tot_w:.2f} ms (x{tot_d / tot_w:.2f})")
+    print(f"13 stride-1 3x3 launches of one resnet18 forward: direct {tot_d:.2f} ms, winograd F(2x2) {tot_w:.2f} ms (x{tot_d / tot_w:.2f}), "
+          f"F(4x2) {tot_4:.2f} ms (x{tot_w / tot_4:.2f} vs F(2x2))")
 
 
 if __name__ == "__main__":

@@ -1,4 +1,4 @@
-"""CPU emulation of conv3x3_wino_kernel's data flow (csrc/conv3x3_wino.hip): the packed-weight layout, the LDS images the DMAs build,
+"""CPU emulation of conv3x3_wino_kernel's data flow (csrc/conv3x3_wino.hip) and of conv3x3_wino42_kernel's (csrc/conv3x3_wino42.hip): the packed-weight layout, the LDS images the DMAs build,
 every lane's fragment addresses, the MFMA operand / result layout, the two-group output transform and the epilogue's pixel mapping --
 index formula by index formula -- against torch's conv2d.  A developer check of the kernel's bookkeeping that needs no GPU
 (`python scripts/wino_emulate.py`); the GPU parity tests are tests/test_engine.py::test_winograd_*."""
@@ -249,6 +249,161 @@ def bank_check():
     print("patch reads: conflict-free")
 
 
+# ---- F(4x2, 3x3): conv3x3_wino42_kernel ------------------------------------------------------------------------------------------
+G4 = np.array([[1 / 4, 0, 0], [-1 / 6, -1 / 6, -1 / 6], [-1 / 6, 1 / 6, -1 / 6], [1 / 24, 1 / 12, 1 / 6], [1 / 24, -1 / 12, 1 / 6], [0, 0, 1]])
+G2 = np.array([[1, 0, 0], [.5, .5, .5], [.5, -.5, .5], [0, 0, 1]])
+W16_42, W8_42 = (1, 16, 16, 18, 18, 82, 18 * 82), (4, 8, 8, 10, 10, 48, 484)  # (G, TH, TW, PH, PWD, ROW, IMG)
+
+
+def pack42(w):  # wino42_pack_kernel: [pos 24 = 4 i + j][cin/16][h8 2][cout/64] blocks of [hi 2][64 cout][4 channels]
+    cout, cin = w.shape[:2]
+    n_cs, n_cb = cin // 16, cout // 64
+    U = np.einsum("ir,ocrs,js->ocij", G4, w.astype(np.float64), G2).astype(np.float32)  # [cout][cin][6][4]
+    out = np.zeros(24 * cin * cout, np.float32)
+    o, c = np.meshgrid(np.arange(cout), np.arange(cin), indexing="ij")
+    cs, h8, hi, c4, cb, col = c >> 4, (c >> 3) & 1, (c >> 2) & 1, c & 3, o >> 6, o & 63
+    for i in range(6):
+        for j in range(4):
+            block = (((i * 4 + j) * n_cs + cs) * 2 + h8) * n_cb + cb
+            out[block * 512 + (hi * 64 + col) * 4 + c4] = U[:, :, i, j]
+    return out
+
+
+def run_block42(x, upk, geo, mt_id, cb, pad, ho, wo, tiles_x, tiles_per_image):
+    n, h, w, cin = x.shape
+    cout = upk.size // (24 * cin)
+    G, TH, TW, PH, PWD, ROW, IMG = geo
+    NT = 512
+
+    def px_unit(px):
+        return (px >> 1) * 9 + (px & 1) * 4
+    A_UNITS = (G * IMG + 63) // 64 * 64
+    NA = (A_UNITS + NT - 1) // NT
+    n_cs, n_cb = cin // 16, cout // 64
+    pos_stride = n_cs * n_cb * 4096
+    img = mt_id // tiles_per_image if G == 1 else mt_id * G
+    trem = mt_id - img * tiles_per_image if G == 1 else 0
+    ty0, tx0 = (trem // tiles_x) * TH, (trem % tiles_x) * TW
+    xf = x.reshape(-1)
+    acc = np.zeros((8, 3, 2, 32, 32), np.float32)  # [wave][ii][channel tile][row = tile][col]
+    f32 = np.float32
+    for cs in range(n_cs):
+        abuf = np.zeros((A_UNITS, 4), np.float32)  # patch image (make_cen, dma_a)
+        for r in range(NA):
+            for tid in range(NT):
+                un = NT * r + tid
+                if NT * r + (tid >> 6) * 64 >= A_UNITS:
+                    continue  # dump
+                g, ug = divmod(un, IMG)
+                py, rem = divmod(ug, ROW)
+                pair, r9 = divmod(rem, 9)
+                px, chunk = 2 * pair + (r9 >> 2), (4 if r9 == 8 else r9 & 3)
+                iy, ix = ty0 - pad + py, tx0 - pad + px
+                if g < G and img + g < n and py < PH and px < PWD and chunk < 4 and 0 <= iy < h and 0 <= ix < w:
+                    off = ((((img + g) * h + iy) * w + ix) * cin * 4 + 16 * chunk + cs * 64) // 4
+                    abuf[un] = xf[off:off + 4]
+        for h8 in range(2):
+            s_step = 2 * cs + h8
+            wst = np.zeros((3072, 4), np.float32)  # weight stage (dma_w: six rounds)
+            for q in range(6):
+                soff = 4 * q * pos_stride + (s_step * n_cb + cb) * 2048
+                for wave in range(8):
+                    for lane in range(64):
+                        src = (soff + (wave & 1) * 1024 + lane * 16 + (wave >> 1) * pos_stride) // 4
+                        wst[q * 512 + wave * 64 + lane] = upk[src:src + 4]
+            for wave in range(8):
+                jcol, hrow = wave & 3, wave >> 2
+                ca, cbc = [(0, 2), (1, 2), (2, 1), (1, 3)][jcol]
+                V = np.zeros((3, 64, 4), np.float32)
+                Wv = np.zeros((3, 2, 64, 4), np.float32)
+                for lane in range(64):
+                    hi, t = lane >> 5, lane & 31
+                    fa = 4 * (t >> 3) * ROW + (t & 7) * 9 + hi if G == 1 else (t >> 3) * IMG + 4 * ((t >> 2) & 1) * ROW + (t & 3) * 9 + hi
+                    fa += 2 * h8
+                    fa_a, fa_b = fa + hrow * ROW + px_unit(ca), fa + hrow * ROW + px_unit(cbc)
+                    T = [abuf[fa_a + r * ROW] + abuf[fa_b + r * ROW] if jcol == 1 else abuf[fa_a + r * ROW] - abuf[fa_b + r * ROW]
+                         for r in range(5)]
+                    T = [t_.astype(f32) for t_ in T]
+                    edge = f32(4) * T[0] + (f32(-5) * T[2] + T[4])  # (fma chains: float32 rounding up to the fused steps)
+                    if hrow == 0:
+                        a, b = f32(-4) * T[2] + T[4], f32(-4) * T[1] + T[3]
+                        V[:, lane] = [edge, a + b, a - b]
+                    else:
+                        c, g_ = T[3] - T[1], T[2] - T[0]
+                        V[:, lane] = [f32(2) * g_ + c, f32(-2) * g_ + c, edge]
+                    fb = (12 * hrow + jcol) * 128 + hi * 64 + (lane & 31)
+                    for ii in range(3):
+                        for ct in range(2):
+                            Wv[ii, ct, lane] = wst[fb + ii * 512 + ct * 32]
+                for ii in range(3):
+                    for ct in range(2):
+                        for k in range(4):
+                            A = np.stack([V[ii, :32, k], V[ii, 32:, k]], axis=1)
+                            B = np.stack([Wv[ii, ct, :32, k], Wv[ii, ct, 32:, k]], axis=0)
+                            acc[wave, ii, ct] += (A @ B).astype(np.float32)
+    # ---- output transform: A4^T over the wave's positions, the row halves lane to lane, A2 over the waves j
+    P = np.zeros((8, 4, 2, 32, 32), np.float32)  # [wave][a][ct]
+    for wave in range(8):
+        m = acc[wave]
+        if wave >> 2 == 0:
+            s_, dd = m[1] + m[2], m[1] - m[2]
+            P[wave] = [m[0] + s_, dd, s_, dd]
+        else:
+            s_, dd = m[0] + m[1], (m[0] - m[1]) * 2
+            P[wave] = [s_, dd, s_ * 4, dd * 4 + m[2]]
+    Q = P[:4] + P[4:]  # [j][a][ct]
+    Y = [(Q[0] + Q[1]) + Q[2], Q[1] + (-Q[3] - Q[2])]  # [b][a][ct]
+    tile = np.zeros((256, 64), np.float32)
+    for e in range(16):
+        for hi in range(2):
+            tt = (e & 3) + 8 * (e >> 2) + 4 * hi
+            m00 = 4 * (tt >> 3) * TW + 2 * (tt & 7) if G == 1 else (tt >> 3) * TH * TW + 4 * ((tt >> 2) & 1) * TW + 2 * (tt & 3)
+            for a in range(4):
+                for b in range(2):
+                    for ct in range(2):
+                        tile[m00 + a * TW + b, ct * 32:ct * 32 + 32] = Y[b][a][ct][tt]
+    out = {}
+    for row in range(256):
+        g, rg = divmod(row, TH * TW)
+        oy, ox = ty0 + rg // TW, tx0 + rg % TW
+        if oy < ho and ox < wo and img + g < n:
+            out[(img + g, oy, ox)] = tile[row]
+    return out
+
+
+def check42(n, hw, cin, cout, pad=1, seed=0):
+    rng = np.random.default_rng(seed)
+    x = rng.standard_normal((n, hw, hw, cin)).astype(np.float32)
+    wgt = (rng.standard_normal((cout, cin, 3, 3)) / np.sqrt(9 * cin)).astype(np.float32)
+    ho = wo = hw + 2 * pad - 2
+    ref = F.conv2d(torch.from_numpy(x).permute(0, 3, 1, 2), torch.from_numpy(wgt), padding=pad).permute(0, 2, 3, 1).numpy()
+    upk = pack42(wgt)
+    small = ho <= 8 and wo <= 8
+    geo = W8_42 if small else W16_42
+    tiles_y = 1 if small else (ho + 15) // 16
+    tiles_x = 1 if small else (wo + 15) // 16
+    tiles = (n + 3) // 4 if small else n * tiles_y * tiles_x
+    got = np.full_like(ref, np.nan)
+    for mt in range(tiles):
+        for cb in range(cout // 64):
+            for (b, oy, ox), v in run_block42(x, upk, geo, mt, cb, pad, ho, wo, tiles_x, tiles_y * tiles_x).items():
+                got[b, oy, ox, cb * 64:cb * 64 + 64] = v
+    assert not np.isnan(got).any(), "outputs not covered"
+    err = np.abs(got - ref).max() / np.abs(ref).max()
+    print(f"F(4x2) n={n} hw={hw} cin={cin} cout={cout} pad={pad}: rel err {err:.2e}")
+    assert err < 1e-5, err
+
+
+def bank_check42():
+    groups = [[0, 1, 2, 3, 12, 13, 14, 15, 20, 21, 22, 23, 24, 25, 26, 27], [4, 5, 6, 7, 8, 9, 10, 11, 16, 17, 18, 19, 28, 29, 30, 31]]
+    for G, _, _, _, _, ROW, IMG in (W16_42, W8_42):
+        for grp in groups:
+            units = [(4 * (t >> 3) * ROW + (t & 7) * 9 if G == 1 else (t >> 3) * IMG + 4 * ((t >> 2) & 1) * ROW + (t & 3) * 9) % 16
+                     for t in grp]
+            assert len(set(units)) == 16, (G, grp, units)
+    print("F(4x2) patch reads: conflict-free")
+
+
 if __name__ == "__main__":
     bank_check()
     if "--windows-only" not in __import__("sys").argv:
@@ -259,4 +414,8 @@ if __name__ == "__main__":
     if "--all" in __import__("sys").argv:
         check(1, 20, 16, 128, 1)     # partial blocks, two channel blocks
         check(2, 12, 16, 64, 0)      # valid convolution
+    bank_check42()
+    check42(1, 16, 32, 64)           # F(4x2), one 16 x 16 block, two 16-channel slices
+    check42(5, 8, 16, 64)            # F(4x2), four-image blocks, a partial block of images
+    check42(1, 32, 16, 128)          # F(4x2), four blocks, two channel blocks
     print("emulation ok")

@@ -15,4 +15,7 @@ bool conv3x3_wino_serves(long nb, long h, long w, long cin, long cout, long pad_
 int conv3x3_wino_launch(const float* x, const float* u_packed, const float* bias, const float* residual, float* y, long nb, long h,
                         long w, long cin, long cout, long pad_top, long pad_left, long ho, long wo, int relu, hipStream_t stream);
 
+// Which Winograd form the fused resnet blocks take for a "same"-padded 3x3 / stride-1 layer (conv3x3_wino42.hip): 1 F(4x2), 0 F(2x2)
+int conv3x3_wino_form(long n, long h, long w, long cin, long cout, long pad);
+
 }  // namespace tia

@@ -15,6 +15,7 @@ there is no silent torch fallback.
 from __future__ import annotations
 
 import copy
+import functools
 
 import torch
 import torch.nn.functional as F  # noqa: N812
@@ -422,10 +423,39 @@ def pack_conv_weights_wino(conv: nn.Conv2d) -> torch.Tensor:
     return out
 
 
+def pack_conv_weights_wino42(conv: nn.Conv2d) -> torch.Tensor:
+    """OIHW 3x3 float32 -> the F(4x2, 3x3) Winograd-domain weights ``U = G4 g G2^T`` in the stage layout of
+    ``tia_conv3x3_wino42_nhwc_f32`` (``tia_conv_pack_weights_wino42_f32``: float64 transform, one rounding),
+    ``[24, cin/16, 2, cout/64, 2, 64, 4]`` (position 4 i + j, then as :func:`pack_conv_weights_wino`)."""
+    from tiatoolbox_amd import _lib
+
+    w = conv.weight.detach().to(torch.float32).contiguous()
+    cout, cin, kh, kw = w.shape
+    if (kh, kw) != (3, 3) or cin % 16 or cout % 64:
+        msg = f"Winograd F(4x2, 3x3) needs a 3x3 kernel, cin % 16 == 0 and cout % 64 == 0; got weight {tuple(w.shape)}."
+        raise ValueError(msg)
+    out = torch.empty((24, cin // 16, 2, cout // 64, 2, 64, 4), dtype=torch.float32, device=w.device)
+    with torch.cuda.device(w.device):
+        rc = _lib.load().tia_conv_pack_weights_wino42_f32(w.data_ptr(), cout, cin, out.data_ptr(), _lib.current_stream())
+    _lib.check(rc, "tia_conv_pack_weights_wino42_f32")
+    return out
+
+
+@functools.lru_cache(maxsize=256)
+def wino_form(n: int, h: int, w: int, cin: int, cout: int, pad: int) -> int:
+    """Which Winograd form the fused resnet blocks take for a "same"-padded 3x3 / stride-1 layer (``tia_conv3x3_wino_form``, a
+    host-only query): 1 F(4x2, 3x3), 0 F(2x2, 3x3); negative for shapes no Winograd form serves."""
+    from tiatoolbox_amd import _lib
+
+    return int(_lib.load().tia_conv3x3_wino_form(n, h, w, cin, cout, pad))
+
+
 def hip_conv3x3_wino(x: torch.Tensor, u_packed: torch.Tensor, bias: torch.Tensor | None, residual: torch.Tensor | None, *,
                      padding: int, relu: bool, pad_hi: int | None = None) -> torch.Tensor:
-    """``relu(conv3x3(x, w) + bias + residual)``, stride 1, through the Winograd F(2x2, 3x3) kernel (``tia_conv3x3_wino_nhwc_f32``):
-    float32 in / float32 accumulate like :func:`hip_conv2d`, 2.25 x fewer multiplies, results within ~1e-5 (relative) of it."""
+    """``relu(conv3x3(x, w) + bias + residual)``, stride 1, through a Winograd kernel: F(2x2, 3x3) (``tia_conv3x3_wino_nhwc_f32``) for
+    weights from :func:`pack_conv_weights_wino` (leading dimension 16), F(4x2, 3x3) (``tia_conv3x3_wino42_nhwc_f32``) for weights from
+    :func:`pack_conv_weights_wino42` (24).  float32 in / float32 accumulate like :func:`hip_conv2d`, 2.25 x / 3 x fewer multiplies,
+    results within ~1e-5 (relative) of it."""
     from tiatoolbox_amd import _lib
 
     if not (_nhwc_ptr_ok(x) and x.dtype == torch.float32):
@@ -435,10 +465,12 @@ def hip_conv3x3_wino(x: torch.Tensor, u_packed: torch.Tensor, bias: torch.Tensor
         msg = "hip_conv3x3_wino expects a float32 channels-last CUDA residual."
         raise ValueError(msg)
     n, cin, h, w = x.shape
-    if (u_packed.dim() != 7 or cin % 16 or tuple(u_packed.shape) != (16, cin // 16, 2, u_packed.shape[3], 2, 64, 4)  # noqa: PLR2004
+    npos = u_packed.shape[0] if u_packed.dim() == 7 else 0  # noqa: PLR2004
+    if (npos not in (16, 24) or cin % 16 or tuple(u_packed.shape) != (npos, cin // 16, 2, u_packed.shape[3], 2, 64, 4)
             or u_packed.dtype != torch.float32 or not u_packed.is_contiguous() or u_packed.device != x.device):
         msg = (f"hip_conv3x3_wino: packed weights {tuple(u_packed.shape)} {u_packed.dtype} on {u_packed.device} do not match an input with "
-               f"{cin} channels on {x.device} (expected pack_conv_weights_wino's [16, cin/16, 2, cout/64, 2, 64, 4] float32, contiguous).")
+               f"{cin} channels on {x.device} (expected pack_conv_weights_wino's [16, cin/16, 2, cout/64, 2, 64, 4] or "
+               f"pack_conv_weights_wino42's [24, ...] float32, contiguous).")
         raise ValueError(msg)
     cout = u_packed.shape[3] * 64
     behind = padding if pad_hi is None else pad_hi  # zero rows / columns behind the image (`padding` in front): "same", valid, TF-same
@@ -447,11 +479,12 @@ def hip_conv3x3_wino(x: torch.Tensor, u_packed: torch.Tensor, bias: torch.Tensor
     if residual is not None and residual.shape != y.shape:
         msg = f"residual shape {tuple(residual.shape)} != output shape {tuple(y.shape)}"
         raise ValueError(msg)
+    name = "tia_conv3x3_wino_nhwc_f32" if npos == 16 else "tia_conv3x3_wino42_nhwc_f32"  # noqa: PLR2004
     with torch.cuda.device(x.device):
-        rc = _lib.load().tia_conv3x3_wino_nhwc_f32(x.data_ptr(), u_packed.data_ptr(), bias.data_ptr() if bias is not None else 0,
-                                                   residual.data_ptr() if residual is not None else 0, y.data_ptr(), n, h, w, cin, cout,
-                                                   padding, padding, ho, wo, int(relu), _lib.current_stream())
-    _lib.check(rc, "tia_conv3x3_wino_nhwc_f32")
+        rc = getattr(_lib.load(), name)(x.data_ptr(), u_packed.data_ptr(), bias.data_ptr() if bias is not None else 0,
+                                        residual.data_ptr() if residual is not None else 0, y.data_ptr(), n, h, w, cin, cout,
+                                        padding, padding, ho, wo, int(relu), _lib.current_stream())
+    _lib.check(rc, name)
     return y
 
 
@@ -466,16 +499,20 @@ class _MfmaBlock(nn.Module):
         self._packed: dict[tuple[str, torch.dtype], torch.Tensor] = {}
         self._bias32: dict[str, torch.Tensor] = {}
 
-    def _wino(self, name: str) -> torch.Tensor | None:
-        """The layer's Winograd-domain weights if it is to run on that kernel (float32 3x3 / stride 1, cin % 16, cout % 64)."""
+    def _wino(self, name: str, x: torch.Tensor | None = None) -> torch.Tensor | None:
+        """The layer's Winograd-domain weights if it is to run on that kernel (float32 3x3 / stride 1, cin % 16, cout % 64): F(4x2, 3x3)
+        where the route query :func:`wino_form` takes it for the input ``x``, F(2x2, 3x3) otherwise (and without an input)."""
         conv = getattr(self, name)
         if (self.conv_algo != "winograd" or conv.kernel_size != (3, 3) or conv.stride != (1, 1) or conv.dilation != (1, 1)
                 or conv.groups != 1 or conv.in_channels % 16 or conv.out_channels % 64 or conv.padding[0] != conv.padding[1]
                 or conv.padding[0] > 2):  # noqa: PLR2004
             return None
-        cached = self._packed.get((name, "wino"))
+        key, pack = (name, "wino"), pack_conv_weights_wino
+        if x is not None and wino_form(x.shape[0], x.shape[2], x.shape[3], conv.in_channels, conv.out_channels, conv.padding[0]) == 1:
+            key, pack = (name, "wino42"), pack_conv_weights_wino42
+        cached = self._packed.get(key)
         if cached is None or cached.device != conv.weight.device:
-            cached = self._packed[(name, "wino")] = pack_conv_weights_wino(conv)
+            cached = self._packed[key] = pack(conv)
         return cached
 
     def _w(self, name: str, dtype: torch.dtype) -> torch.Tensor:
@@ -515,7 +552,7 @@ class _MfmaBlock(nn.Module):
         conv = getattr(self, name)
         k, st, pad = conv.kernel_size[0], conv.stride[0], conv.padding[0]
         if x.dtype == torch.float32:
-            u = self._wino(name)
+            u = self._wino(name, x)
             if u is not None:
                 return hip_conv3x3_wino(x, u, self._b(name), residual, padding=pad, relu=relu)
             return hip_conv2d(x, self._w(name, x.dtype), self._b(name), residual, kernel=k, stride=st, padding=pad, relu=relu)

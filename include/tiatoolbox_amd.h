@@ -38,7 +38,8 @@ extern "C" {
 /* Version 6 (round 6): + tia_gray_hist_u8 / tia_otsu_threshold_u32 / tia_otsu_fit_u8 / tia_threshold_lt_dev_u8 (one-pass, one-launch
  * Otsu fit whose threshold stays on the device), tia_morph_mask_u8 (the morphological masker in one launch), tia_reinhard_transform_u8 /
  * tia_reinhard_workspace_bytes / tia_lab_moments_u8 (one-launch Reinhard); tia_luminosity_mask_u8 and the float64 form of
- * tia_stain_augment_u8 (now a product of per-patch tables) take 16-byte accesses where the shape allows. */
+ * tia_stain_augment_u8 (now a product of per-patch tables) take 16-byte accesses where the shape allows.
+ * Additive, same version: tia_gather_area_patches_u8 (patch reads below the slide's resolution). */
 #define TIA_ABI_VERSION 6
 int tia_abi_version(void);
 
@@ -477,6 +478,16 @@ int tia_bias_relu_maxpool_nhwc(const void* d_x, const void* d_bias, int64_t n, i
  *   d_slide [sh,sw,c] u8   d_bounds [m,4] i32   d_out [m,ph,pw,c] u8 (ph*pw*c % 4 == 0, m <= 65535) */
 int tia_gather_patches_u8(const uint8_t* d_slide, int64_t sh, int64_t sw, int64_t c, const int32_t* d_bounds,
                           int64_t m, int64_t ph, int64_t pw, int32_t pad, uint8_t* d_out, void* stream);
+
+/* The same reads below the slide's resolution (VirtualWSIReader.read_bounds(..., resolution, units,
+ * coord_space="resolution", pad_constant_values=255), wsicore/wsireader.py): d_bounds[i] = (x0, y0, x1, y1) in baseline
+ * pixels with x1 - x0 == factor * pw and y1 - y0 == factor * ph; out[i] = the factor x factor box average of the region, `pad`
+ * standing in for every source byte outside the slide (padding before averaging).  Rounding is cv2.INTER_AREA's at an
+ * integer scale (resizeAreaFast): factor 2 -> (a + b + c + d + 2) >> 2, factor >= 3 -> integer box sum * (1.0f / factor^2)
+ * rounded half to even (as tia_box_downsample_u8), factor 1 -> tia_gather_patches_u8 byte for byte.
+ *   d_slide [sh,sw,c] u8, c in {1, 3}   d_bounds [m,4] i32   d_out [m,ph,pw,c] u8 (any ph*pw*c, any m)   1 <= factor <= 64 */
+int tia_gather_area_patches_u8(const uint8_t* d_slide, int64_t sh, int64_t sw, int64_t c, const int32_t* d_bounds,
+                               int64_t m, int64_t ph, int64_t pw, int64_t factor, int32_t pad, uint8_t* d_out, void* stream);
 
 /* =======================================================================================
  * ResNet convolutions on the matrix cores (models/architecture/vanilla.py:300-316 -> torchvision BasicBlock)

@@ -139,6 +139,115 @@ __global__ __launch_bounds__(CT) void gather_patches_kernel(const uint8_t* __res
     }
 }
 
+
+// ---- area-resampled patch reads (a slide read below its baseline resolution) ------------------------------------------
+// VirtualWSIReader.read_bounds(..., resolution, units, pad_constant_values=255) (wsicore/wsireader.py): the baseline region,
+// padded with `pad` outside the slide, shrunk by an integer factor k with imresize -> cv2.INTER_AREA, i.e. OpenCV's
+// resizeAreaFast for uint8 (modules/imgproc/src/resize.cpp): k == 2 is ResizeAreaFastVec, (a + b + c + d + 2) >> 2;
+// k >= 3 is saturate_cast<uchar>(float(sum) * (1.0f / (k * k))), rounded half to even.  The box sums stay integers.
+// One workgroup owns a tile of tile_h output rows x tile_w output pixels of one patch: the tile's k * tile_h source rows
+// are staged in LDS in aligned 16-byte chunks (one dwordx4 load per chunk that lies inside the slide row; only chunks that
+// cross the slide edge go byte by byte), then every thread reduces the boxes of 4 consecutive output bytes.  Row r of the
+// stage holds the aligned-down source run, so the run's first byte sits at (source address & 15).
+constexpr int kAreaStage = 16384;  // LDS bytes of source staged per workgroup (launcher sizes the tile to fit)
+constexpr int kAreaUnroll = 4;     // 16-byte chunks each thread has in flight before it writes them to LDS
+
+__device__ __forceinline__ uint32_t area_round(uint32_t sum, int k, float scale) {
+    if (k == 1) return sum;
+    if (k == 2) return (sum + 2u) >> 2;
+    const float v = rintf((float)sum * scale);
+    return (uint32_t)(v > 255.0f ? 255.0f : v);
+}
+
+__global__ __launch_bounds__(CT) void gather_area_patches_kernel(const uint8_t* __restrict__ slide, int sh, int sw, int c,
+                                                                  const int* __restrict__ bounds, int ph, int pw, int k,
+                                                                  int tile_w, int tile_h, int tiles_x, int pitch, int pad,
+                                                                  uint8_t* __restrict__ out) {
+    extern __shared__ uint4 stage4[];
+    uint8_t* stage = reinterpret_cast<uint8_t*>(stage4);
+    const int m = blockIdx.y;
+    const int ty = (int)blockIdx.x / tiles_x, tx = (int)blockIdx.x - ty * tiles_x;
+    const int oy0 = ty * tile_h, ox0 = tx * tile_w;
+    const int th = min(tile_h, ph - oy0), tw = min(tile_w, pw - ox0);
+    const long row_bytes = (long)sw * c;
+    const long span = (long)tw * k * c;                          // source bytes of one staged row
+    const long xs = ((long)bounds[m * 4 + 0] + (long)ox0 * k) * c;  // the run's byte offset in its slide row (may be < 0)
+    const long sy0 = (long)bounds[m * 4 + 1] + (long)oy0 * k;
+    const int rows = th * k;
+    const int nq = pitch >> 4;
+    const int total = rows * nq;
+    const uint32_t pad4 = 0x01010101u * (uint32_t)(pad & 255);
+    const uintptr_t base = reinterpret_cast<uintptr_t>(slide);
+    for (int i0 = threadIdx.x; i0 < total; i0 += CT * kAreaUnroll) {
+        uint4 v[kAreaUnroll];
+        long lo[kAreaUnroll], sy[kAreaUnroll];
+        int need[kAreaUnroll];  // 0: past the run, 1: all pad, 2: one aligned load, 3: byte by byte
+#pragma unroll
+        for (int u = 0; u < kAreaUnroll; ++u) {
+            const int i = i0 + u * CT;
+            const int r = i / nq, q = i - r * nq;
+            sy[u] = sy0 + r;
+            const int a = (int)((base + (uintptr_t)(sy[u] * row_bytes + xs)) & 15);
+            lo[u] = xs - a + 16L * q;  // the chunk's byte offset in the slide row; 16-byte aligned in memory
+            v[u] = make_uint4(pad4, pad4, pad4, pad4);
+            need[u] = 0;
+            if (i < total && 16L * q < a + span) {
+                need[u] = 1;
+                if (sy[u] >= 0 && sy[u] < sh && lo[u] + 16 > 0 && lo[u] < row_bytes)
+                    need[u] = (lo[u] >= 0 && lo[u] + 16 <= row_bytes) ? 2 : 3;
+            }
+            if (need[u] == 2) v[u] = *reinterpret_cast<const uint4*>(slide + sy[u] * row_bytes + lo[u]);
+        }
+#pragma unroll
+        for (int u = 0; u < kAreaUnroll; ++u) {
+            if (need[u] == 0) continue;
+            if (need[u] == 3) {  // the chunk crosses the left or right edge of the slide
+                const uint8_t* rp = slide + sy[u] * row_bytes;
+                uint32_t w[4] = {0u, 0u, 0u, 0u};
+#pragma unroll
+                for (int e = 0; e < 16; ++e) {
+                    const long o = lo[u] + e;
+                    const uint32_t b = (o >= 0 && o < row_bytes) ? (uint32_t)rp[o] : (uint32_t)(pad & 255);
+                    w[e >> 2] |= b << (8 * (e & 3));
+                }
+                v[u] = make_uint4(w[0], w[1], w[2], w[3]);
+            }
+            const int i = i0 + u * CT;
+            stage4[i] = v[u];  // row i / nq, chunk i % nq: the stage pitch is nq chunks
+        }
+    }
+    __syncthreads();
+    const int out_row = tw * c;            // output bytes of one tile row
+    const int groups = (out_row + 3) >> 2;  // 4-byte groups per tile row
+    const float scale = 1.0f / (float)(k * k);
+    for (int g = threadIdx.x; g < th * groups; g += CT) {
+        const int rr = g / groups, j0 = (g - rr * groups) * 4;
+        uint8_t* dst = out + (((size_t)m * ph + oy0 + rr) * pw + ox0) * c;
+        uint32_t sums[4] = {0u, 0u, 0u, 0u};
+        for (int dy = 0; dy < k; ++dy) {
+            const int r = rr * k + dy;
+            const int a = (int)((base + (uintptr_t)((sy0 + r) * row_bytes + xs)) & 15);
+            const uint8_t* sp = stage + r * pitch + a;
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                const int j = j0 + e;
+                if (j >= out_row) break;
+                const int ox = j / c, ch = j - ox * c;
+                const uint8_t* p = sp + ox * k * c + ch;
+                uint32_t s = 0;
+                for (int dx = 0; dx < k; ++dx) s += p[dx * c];
+                sums[e] += s;
+            }
+        }
+        if (j0 + 4 <= out_row && ((reinterpret_cast<uintptr_t>(dst + j0) & 3) == 0)) {
+            *reinterpret_cast<uint32_t*>(dst + j0) = area_round(sums[0], k, scale) | (area_round(sums[1], k, scale) << 8) |
+                                                     (area_round(sums[2], k, scale) << 16) | (area_round(sums[3], k, scale) << 24);
+        } else {
+            for (int e = 0; e < 4 && j0 + e < out_row; ++e) dst[j0 + e] = (uint8_t)area_round(sums[e], k, scale);
+        }
+    }
+}
+
 }  // namespace tia
 
 using namespace tia;
@@ -185,4 +294,33 @@ extern "C" int tia_gather_patches_u8(const uint8_t* d_slide, int64_t sh, int64_t
     hipLaunchKernelGGL(tia::gather_patches_kernel, dim3((unsigned)blocks, (unsigned)m), dim3(tia::CT), 0, (hipStream_t)stream,
                        d_slide, (int)sh, (int)sw, (int)c, d_bounds, (int)ph, (int)pw, pad, d_out);
     return hipGetLastError() == hipSuccess ? TIA_OK : TIA_ELAUNCH;
+}
+
+extern "C" int tia_gather_area_patches_u8(const uint8_t* d_slide, int64_t sh, int64_t sw, int64_t c, const int32_t* d_bounds,
+                                          int64_t m, int64_t ph, int64_t pw, int64_t factor, int32_t pad, uint8_t* d_out,
+                                          void* stream) {
+    if (!d_slide || !d_bounds || !d_out || sh <= 0 || sw <= 0 || (c != 1 && c != 3) || m < 0 || ph <= 0 || pw <= 0 || factor < 1)
+        return TIA_EINVAL;
+    if (m == 0) return TIA_OK;
+    if (factor > 64 || sh > 0x7fffffffL || sw * c > 0x7fffffffL || ph * factor > 0x7fffffffL || pw * factor * c > 0x7fffffffL)
+        return TIA_ESIZE;
+    // tile: as many output pixels per row as fit k staged rows in kAreaStage bytes, then as many output rows as fit
+    const long k = factor;
+    long tile_w = (tia::kAreaStage / k - 32) / (k * c);
+    tile_w = tile_w < 1 ? 1 : (tile_w > pw ? pw : tile_w);
+    const long pitch = ((tile_w * k * c + 15) & ~15L) + 16;  // the run plus up to 15 bytes of alignment in front
+    long tile_h = tia::kAreaStage / (k * pitch);
+    tile_h = tile_h < 1 ? 1 : (tile_h > ph ? ph : tile_h);
+    const long tiles_x = (pw + tile_w - 1) / tile_w, tiles_y = (ph + tile_h - 1) / tile_h;
+    if (tiles_x * tiles_y > 0x7fffffffL) return TIA_ESIZE;
+    const size_t lds = (size_t)(tile_h * k * pitch);
+    const long patch_bytes = ph * pw * c;
+    for (long s = 0; s < m; s += 65535) {
+        const long n = m - s < 65535 ? m - s : 65535;
+        hipLaunchKernelGGL(tia::gather_area_patches_kernel, dim3((unsigned)(tiles_x * tiles_y), (unsigned)n), dim3(tia::CT), lds,
+                           (hipStream_t)stream, d_slide, (int)sh, (int)sw, (int)c, d_bounds + s * 4, (int)ph, (int)pw, (int)k,
+                           (int)tile_w, (int)tile_h, (int)tiles_x, (int)pitch, pad, d_out + s * patch_bytes);
+        if (hipGetLastError() != hipSuccess) return TIA_ELAUNCH;
+    }
+    return TIA_OK;
 }

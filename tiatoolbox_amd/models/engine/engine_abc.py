@@ -748,6 +748,28 @@ class EngineABC:
                    "`input_resolutions`.")
             raise ValueError(msg)
 
+    def _reader_at_input_resolution(self, reader):
+        """A ``VirtualWSIReader`` whose native resolution is not the model's input resolution -> its view at that resolution
+        (``VirtualWSIReader.at_resolution``: patch reads area-resampled on the device), so that coordinates and outputs come
+        out in the pixel space of the model's resolution, as in the reference.  Any other reader is returned unchanged."""
+        from tiatoolbox_amd.wsicore import VirtualWSIReader, _close
+
+        if not isinstance(reader, VirtualWSIReader):
+            return reader
+        cfg = self._ioconfig
+        res = cfg.input_resolutions[0]
+        if reader.factor(res["resolution"], res["units"]) == 1:
+            return reader
+        others = [*cfg.input_resolutions[1:], *cfg.output_resolutions]
+        if getattr(cfg, "save_resolution", None) is not None:
+            others.append(cfg.save_resolution)
+        for o in others:
+            if o["units"] != res["units"] or not _close(float(o["resolution"]), float(res["resolution"])):
+                msg = (f"a resampled slide read needs every input / output / save resolution equal to the input resolution "
+                       f"{res['resolution']} {res['units']}; the ioconfig also has {o['resolution']} {o['units']}.")
+                raise ValueError(msg)
+        return reader.at_resolution(res["resolution"], res["units"])
+
     def get_wsi_coordinates(self, reader, mask_reader, *, min_mask_ratio: float = 0.0) -> np.ndarray:
         """Patch grid of one slide, filtered by the tissue mask (``WSIPatchDataset.__init__``, dataset_abc.py:309-345)."""
         from tiatoolbox_amd.tools.patchextraction import PatchExtractor
@@ -817,13 +839,15 @@ class EngineABC:
         out: dict = {}
         images = self.images if isinstance(self.images, (list, tuple)) else [self.images]
         for num, image in enumerate(images):
-            reader = self._open_slide(image)
-            self._check_read_resolution(reader, self._ioconfig)
+            base = self._open_slide(image)
+            reader = self._reader_at_input_resolution(base)
+            if reader is base:  # a resampled view is at the input resolution by construction
+                self._check_read_resolution(reader, self._ioconfig)
             mask_reader = None
             if self.masks is not None:
                 mask_reader = self._open_slide(self.masks[num], as_mask=True)
             elif kwargs.get("auto_get_mask", getattr(self, "auto_get_mask", True)):
-                mask_reader = reader.tissue_mask(resolution=1.25, units="power")
+                mask_reader = base.tissue_mask(resolution=1.25, units="power")
             coords = self.get_wsi_coordinates(reader, mask_reader, min_mask_ratio=float(kwargs.get("min_mask_ratio", 0.0)))
             raw = self.infer_wsi(reader, coords)
             processed = self.post_process_patches(raw_predictions=raw, **kwargs)

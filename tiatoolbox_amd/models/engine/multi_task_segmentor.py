@@ -716,12 +716,13 @@ class MultiTaskSegmentor(EngineABC):
     def process_wsi(self, image, mask=None, *, return_predictions=None, auto_get_mask: bool = True) -> dict:
         """One slide in memory: tissue mask -> patch inference stitched per head -> full-region or tile-mode post-processing;
         the dict ``run`` writes for it (single task: the task's table at the top level, ref. :1695-1704)."""
-        reader = self._open_slide(image)
+        base = self._open_slide(image)
         mask_reader = None
         if mask is not None:
             mask_reader = self._open_slide(mask, as_mask=True)
         elif auto_get_mask:
-            mask_reader = reader.tissue_mask(resolution=1.25, units="power")
+            mask_reader = base.tissue_mask(resolution=1.25, units="power")
+        reader = self._reader_at_input_resolution(base)
         raw = self.infer_wsi(reader, mask_reader)
         if raw["probabilities"] is None:
             return {"coordinates": raw["coordinates"]}

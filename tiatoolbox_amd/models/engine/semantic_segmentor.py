@@ -400,12 +400,13 @@ class SemanticSegmentor(PatchPredictor):
         save_dir = prepare_engines_save_dir(save_dir, patch_mode=False, overwrite=overwrite, distributed=self.distributed)
         paths: dict = {}
         for i, image in enumerate(self.images):
-            reader = self._open_slide(image)
+            base = self._open_slide(image)
             mask_reader = None
             if self.masks is not None:
                 mask_reader = self._open_slide(self.masks[i], as_mask=True)
             elif self.auto_get_mask:
-                mask_reader = reader.tissue_mask(resolution=1.25, units="power")
+                mask_reader = base.tissue_mask(resolution=1.25, units="power")
+            reader = self._reader_at_input_resolution(base)
             out = self.infer_wsi(reader, mask_reader, return_probabilities=bool(self.return_probabilities))
             arrays = {"predictions": out["predictions"].cpu().numpy(), "coordinates": out["coordinates"]}
             if "probabilities" in out:

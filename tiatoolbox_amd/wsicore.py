@@ -6,6 +6,12 @@ File-format readers (OpenSlide, TIFF, DICOM, ...) are out of scope (SURVEY 2.1 r
 GPU: the level-0 image lives in HBM (a 20k x 20k slide is 1.2 GB of the 288 GB) and a batch of patches is
 gathered by one kernel launch (``tia_gather_patches_u8``) that writes 255 wherever a region leaves the slide, exactly
 as ``WSIPatchDataset.__getitem__`` pads (``dataset_abc.py:430-436``).
+
+``ArrayWSIReader`` reads at the slide's own resolution only.  ``VirtualWSIReader`` (the reference's class name) also reads
+below it, by an integer factor ``k`` (:func:`resolution_factor`): ``read_bounds(..., resolution, units)`` and the light view
+``at_resolution(resolution, units)`` take the baseline region, pad it with 255 outside the slide and shrink it with
+``cv2.INTER_AREA``'s integer-scale rule in one launch (``tia_gather_area_patches_u8``), which is what the reference's
+``read_bounds`` -> ``imresize`` does.  Up-sampling, non-integer factors and multi-level pyramids are not supported.
 """
 
 from __future__ import annotations
@@ -144,3 +150,170 @@ class ArrayWSIReader:
         mask = masker.fit_transform(thumb[None])[0]
         return ArrayWSIReader(mask.to(torch.uint8) if isinstance(mask, torch.Tensor) else mask.astype(np.uint8),
                               mpp=None, power=resolution, mode="bool")
+
+
+# ------------------------------------------------------------------------------------------- reads below baseline
+_REL_TOL = 1e-6  # two resolutions are the same, and a ratio is an integer, within this relative tolerance
+
+
+def _close(a: float, b: float) -> bool:
+    return abs(a - b) <= _REL_TOL * max(1.0, abs(a), abs(b))
+
+
+def resolution_factor(resolution: float, units: str, *, mpp=None, power: float | None = None) -> int:
+    """Integer down-sampling factor ``k`` from a slide at (``mpp``, ``power``) to the requested ``(resolution, units)``.
+
+    ``units``: ``"mpp"`` (k = resolution / mpp), ``"power"`` (k = power / resolution), ``"baseline"`` (a scale of the
+    baseline: k = 1 / resolution) or ``"level"`` (only level 0, k = 1).  ``ValueError`` for up-sampling, a factor that is not an
+    integer, a native value of ``None``, ``mpp_x != mpp_y`` and ``level > 0``."""
+    if units == "level":
+        if not _close(float(resolution), 0.0):
+            msg = f"the in-memory slide holds one level (level 0); level {resolution} was requested."
+            raise ValueError(msg)
+        return 1
+    if units not in ("mpp", "power", "baseline"):
+        msg = f"Invalid resolution units `{units}`: expected 'mpp', 'power', 'baseline' or 'level'."
+        raise ValueError(msg)
+    resolution = float(resolution)
+    if not resolution > 0:
+        msg = f"the requested resolution must be positive, got {resolution} {units}."
+        raise ValueError(msg)
+    if units == "baseline":
+        ratio = 1.0 / resolution
+    else:
+        native = mpp if units == "mpp" else power
+        if native is None:
+            msg = f"the slide's native {units} is None: a read at {resolution} {units} cannot be placed."
+            raise ValueError(msg)
+        comps = [float(v) for v in np.asarray(native, dtype=np.float64).ravel()]
+        if not all(_close(v, comps[0]) for v in comps):
+            msg = f"the slide's mpp differs between x and y ({tuple(comps)}): anisotropic slides are not resampled."
+            raise ValueError(msg)
+        ratio = resolution / comps[0] if units == "mpp" else comps[0] / resolution
+    k = round(ratio)
+    if ratio < 1.0 and not _close(ratio, 1.0):
+        msg = (f"reading at {resolution} {units} up-samples the slide (factor {ratio:.6g} < 1); only down-sampling by an "
+               "integer factor is supported.")
+        raise ValueError(msg)
+    if not _close(ratio, float(k)):
+        msg = (f"reading at {resolution} {units} down-samples by {ratio:.6g}, not an integer factor; only integer factors "
+               "(cv2.INTER_AREA's box average) are supported.")
+        raise ValueError(msg)
+    return int(k)
+
+
+def _area_read(base: ArrayWSIReader, bounds, size: tuple[int, int], k: int, pad_value: int) -> torch.Tensor:
+    """``[M, ph, pw, C]`` area reads of baseline ``bounds`` (an int32 ``[M, 4]`` device tensor, ``size=(pw, ph)``, extents
+    ``k * size``): one ``tia_gather_area_patches_u8`` call."""
+    from tiatoolbox_amd import _lib
+
+    src = base.device_image if base.device_image.dim() == 3 else base.device_image[..., None]  # noqa: PLR2004
+    if src.dtype == torch.bool:
+        src = src.to(torch.uint8)
+    if src.dtype != torch.uint8:
+        msg = "device patch reads need a uint8 slide."
+        raise TypeError(msg)
+    src = src.contiguous()
+    sh, sw, c = src.shape
+    pw, ph = int(size[0]), int(size[1])
+    out = torch.empty((len(bounds), ph, pw, c), dtype=torch.uint8, device=src.device)
+    with torch.cuda.device(src.device):
+        rc = _lib.load().tia_gather_area_patches_u8(src.data_ptr(), sh, sw, c, bounds.data_ptr(), len(bounds), ph, pw, int(k),
+                                                    int(pad_value), out.data_ptr(), _lib.current_stream())
+    _lib.check(rc, "tia_gather_area_patches_u8")
+    return out if base.device_image.dim() == 3 else out[..., 0]  # noqa: PLR2004
+
+
+def _host_bounds(bounds) -> tuple[np.ndarray, tuple[int, int]]:
+    bounds = np.ascontiguousarray(np.asarray(bounds).reshape(-1, 4), dtype=np.int32)
+    sizes = np.unique(np.stack([bounds[:, 2] - bounds[:, 0], bounds[:, 3] - bounds[:, 1]], axis=1), axis=0)
+    if len(sizes) != 1:
+        msg = "read_bounds_batch expects regions of one size."
+        raise ValueError(msg)
+    pw, ph = int(sizes[0, 0]), int(sizes[0, 1])
+    if pw <= 0 or ph <= 0:
+        msg = f"empty region {pw} x {ph}."
+        raise ValueError(msg)
+    return bounds, (pw, ph)
+
+
+class VirtualWSIReader(ArrayWSIReader):
+    """ndarray-backed slide that also reads below its baseline resolution (reference ``VirtualWSIReader``, down-sampling by
+    an integer factor only).  Same constructor as :class:`ArrayWSIReader`; without a resolution every read is the
+    ``ArrayWSIReader`` read."""
+
+    def factor(self, resolution: float, units: str) -> int:
+        return resolution_factor(resolution, units, mpp=self.mpp, power=self.power)
+
+    def at_resolution(self, resolution: float, units: str) -> ResampledWSIView:
+        """The slide as seen at ``(resolution, units)``: a light view (no copy of the slide) whose reads take bounds in its
+        own pixel space."""
+        return ResampledWSIView(self, self.factor(resolution, units))
+
+    def read_bounds(self, bounds, resolution: float | None = None, units: str | None = None, coord_space: str = "baseline",
+                    pad_constant_values: int = 255) -> np.ndarray:
+        """One region ``[x0, y0, x1, y1]`` (the subset of the reference's signature users call).  With ``resolution``:
+        ``coord_space="resolution"`` takes the bounds at that resolution; ``"baseline"`` takes baseline bounds whose extents
+        are multiples of the factor.  The output is the padded baseline region box-averaged by the factor."""
+        if coord_space not in ("baseline", "resolution"):
+            msg = f"Invalid coord_space `{coord_space}`: expected 'baseline' or 'resolution'."
+            raise ValueError(msg)
+        if resolution is None:
+            return self.read_bounds_batch(np.asarray(bounds)[None], pad_constant_values)[0].cpu().numpy()
+        if units is None:
+            msg = "read_bounds with a resolution needs its units."
+            raise ValueError(msg)
+        view = self.at_resolution(resolution, units)
+        if coord_space == "resolution":
+            return view.read_bounds(bounds, pad_constant_values)
+        k = view.factor
+        b, (w, h) = _host_bounds(bounds)
+        if w % k or h % k:
+            msg = f"a {w} x {h} baseline region does not shrink by the integer factor {k}."
+            raise ValueError(msg)
+        bt = torch.from_numpy(b).to(self.device_image.device)
+        return _area_read(self, bt, (w // k, h // k), k, pad_constant_values)[0].cpu().numpy()
+
+
+class ResampledWSIView:
+    """A :class:`VirtualWSIReader` seen at ``1 / factor`` of its baseline resolution (``VirtualWSIReader.at_resolution``).
+
+    ``slide_dimensions`` follow the reference's ``np.round(baseline / factor)`` (``WSIReader._find_read_bounds_params``:
+    ``output_size = np.round(...)``, which rounds halves to even); ``mpp`` / ``power`` are scaled by the factor; reads take
+    bounds in this view's pixels and go through ``tia_gather_area_patches_u8``; the tissue mask comes from the base reader
+    (the reference computes it from baseline)."""
+
+    def __init__(self, base: VirtualWSIReader, factor: int) -> None:
+        self.base = base
+        self.factor = int(factor)
+        self.mode = base.mode
+        k = self.factor
+        self.mpp = None if base.mpp is None else (base.mpp * k if np.ndim(base.mpp) == 0 else tuple(float(v) * k for v in np.ravel(base.mpp)))
+        self.power = None if base.power is None else base.power / k
+
+    @property
+    def slide_dimensions(self) -> tuple[int, int]:
+        w, h = self.base.slide_dimensions
+        return int(np.round(w / self.factor)), int(np.round(h / self.factor))
+
+    def read_bounds_batch(self, bounds, pad_value: int = 255, *, size: tuple[int, int] | None = None) -> torch.Tensor:
+        """``[M, ph, pw, C]`` regions ``[x0, y0, x1, y1]`` in this view's pixels, ``pad_value`` outside the slide.  ``bounds`` may
+        be an int32 ``[M, 4]`` device tensor together with ``size=(pw, ph)``, as for ``ArrayWSIReader.read_bounds_batch``."""
+        k = self.factor
+        if isinstance(bounds, torch.Tensor) and bounds.is_cuda:
+            if size is None or bounds.dtype != torch.int32 or bounds.dim() != 2 or bounds.shape[1] != 4 or not bounds.is_contiguous():  # noqa: PLR2004
+                msg = "device bounds: a contiguous int32 [M, 4] tensor together with size=(pw, ph)."
+                raise ValueError(msg)
+            return _area_read(self.base, bounds * k if k != 1 else bounds, size, k, pad_value)
+        b, size = _host_bounds(bounds)
+        bt = torch.from_numpy(b * np.int32(k)).to(self.base.device_image.device)
+        return _area_read(self.base, bt, size, k, pad_value)
+
+    def read_bounds(self, bounds, pad_value: int = 255) -> np.ndarray:
+        return self.read_bounds_batch(np.asarray(bounds)[None], pad_value)[0].cpu().numpy()
+
+    def slide_thumbnail(self, resolution: float = 1.25, units: str = "power") -> torch.Tensor:
+        return self.base.slide_thumbnail(resolution, units)
+
+    def tissue_mask(self, method: str = "otsu", resolution: float = 1.25, units: str = "power", **masker_kwargs):
+        return self.base.tissue_mask(method, resolution, units, **masker_kwargs)

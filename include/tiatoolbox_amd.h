@@ -39,7 +39,8 @@ extern "C" {
  * Otsu fit whose threshold stays on the device), tia_morph_mask_u8 (the morphological masker in one launch), tia_reinhard_transform_u8 /
  * tia_reinhard_workspace_bytes / tia_lab_moments_u8 (one-launch Reinhard); tia_luminosity_mask_u8 and the float64 form of
  * tia_stain_augment_u8 (now a product of per-patch tables) take 16-byte accesses where the shape allows.
- * Additive, same version: tia_gather_area_patches_u8 (patch reads below the slide's resolution). */
+ * Additive, same version: tia_gather_area_patches_u8 (patch reads below the slide's resolution), tia_gather_area_resize_u8
+ * (the same at any down-sampling ratio). */
 #define TIA_ABI_VERSION 6
 int tia_abi_version(void);
 
@@ -488,6 +489,17 @@ int tia_gather_patches_u8(const uint8_t* d_slide, int64_t sh, int64_t sw, int64_
  *   d_slide [sh,sw,c] u8, c in {1, 3}   d_bounds [m,4] i32   d_out [m,ph,pw,c] u8 (any ph*pw*c, any m)   1 <= factor <= 64 */
 int tia_gather_area_patches_u8(const uint8_t* d_slide, int64_t sh, int64_t sw, int64_t c, const int32_t* d_bounds,
                                int64_t m, int64_t ph, int64_t pw, int64_t factor, int32_t pad, uint8_t* d_out, void* stream);
+
+/* The same reads at any down-sampling ratio: out[i] = cv::resize(region_i, (pw, ph), INTER_AREA) of the hb x wb baseline region
+ * whose top-left is (d_bounds[i][0], d_bounds[i][1]), `pad` standing in for every source byte outside the slide (padding before
+ * resampling); x1, y1 are not read (every region is wb x hb).  Per axis scale = 1.0 / ((double)p / b), as cv::resize.  Both
+ * scales integers within DBL_EPSILON (resizeAreaFast): equal -> tia_gather_area_patches_u8 byte for byte; unequal kx != ky ->
+ * rint(float(box sum) * (1.0f / (kx * ky))).  Otherwise computeResizeAreaTab's taps (double, weights rounded to float once)
+ * and ResizeArea_Invoker's float accumulation without fused multiply-add (horizontal per source row, then vertical), rint
+ * half to even, saturated.
+ *   d_slide [sh,sw,c] u8, c in {1, 3}   d_bounds [m,4] i32   d_out [m,ph,pw,c] u8 (any m)   1 <= wb / pw, hb / ph <= 64 */
+int tia_gather_area_resize_u8(const uint8_t* d_slide, int64_t sh, int64_t sw, int64_t c, const int32_t* d_bounds, int64_t m,
+                              int64_t hb, int64_t wb, int64_t ph, int64_t pw, int32_t pad, uint8_t* d_out, void* stream);
 
 /* =======================================================================================
  * ResNet convolutions on the matrix cores (models/architecture/vanilla.py:300-316 -> torchvision BasicBlock)

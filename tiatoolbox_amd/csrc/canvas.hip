@@ -3,6 +3,8 @@
 // :1398-1534 (merge_vertical_chunkwise), patch_predictor.py:382-446 (argmax).
 // Gather formulation: one thread owns one canvas element and sums its (<= a few) contributing blocks in
 // the reference's order, so results are deterministic and bit-identical to the NumPy path -- no float atomics.
+#include <float.h>
+
 #include "common.hpp"
 
 #pragma clang fp contract(off)
@@ -248,6 +250,170 @@ __global__ __launch_bounds__(CT) void gather_area_patches_kernel(const uint8_t* 
     }
 }
 
+
+// ---- area-resampled patch reads at any down-sampling ratio --------------------------------------------------------------
+// cv::resize(region, (pw, ph), INTER_AREA) of a wb x hb baseline region for uint8 (modules/imgproc/src/resize.cpp) where
+// the two scales are not one integer: computeResizeAreaTab's tap table per axis (double arithmetic, each weight rounded to
+// float once) and ResizeArea_Invoker's float accumulation (per source row, the x taps in order into a float; then the
+// rows, weighted by the y taps, in order), rint, saturate.  Every product is rounded before its add: the file is compiled
+// with fp contract(off).  Unequal integer scales kx != ky take resizeAreaFast's rule instead (kFast): the integer box sum
+// times 1.0f / (kx * ky), rinted.  The taps are the same for every patch; each workgroup builds those of its own tile.
+// One workgroup owns a tile of tile_h output rows x tile_w output pixels of one patch: it builds the tile's x and y taps in
+// LDS, stages the source rows they touch in aligned 16-byte chunks (the staging of gather_area_patches_kernel), then every
+// thread computes 4 consecutive output bytes of one output row from LDS and stores them as one dword.
+constexpr int kResizeStage = 24576;  // LDS bytes of source staged per workgroup (launcher sizes the tile to fit)
+
+// Taps of destination indices d0 .. d0 + cnt - 1 of an n_src -> n_dst axis: source indices first[i] .. first[i] + num[i] - 1
+// (contiguous), weights w[i * max_taps + t].  Fast mode: the k = n_src / n_dst indices of the box, no weights.
+__device__ void area_resize_taps(int n_src, int n_dst, int d0, int cnt, int max_taps, bool fast, int* first, int* num, float* w) {
+    const double scale = 1.0 / ((double)n_dst / (double)n_src);  // cv::resize: scale_x = 1. / inv_scale_x
+    for (int i = threadIdx.x; i < cnt; i += blockDim.x) {
+        const int d = d0 + i;
+        if (fast) {
+            const int k = n_src / n_dst;
+            first[i] = d * k;
+            num[i] = k;
+            continue;
+        }
+        const double f1 = d * scale, f2 = f1 + scale;
+        const double cell = fmin(scale, n_src - f1);
+        int s2 = min((int)floor(f2), n_src - 1);
+        const int s1 = min((int)ceil(f1), s2);
+        float* wd = w + (long)i * max_taps;
+        int n = 0;
+        const bool left = s1 - f1 > 1e-3;
+        if (left) wd[n++] = (float)((s1 - f1) / cell);
+        for (int s = s1; s < s2 && n < max_taps; ++s) wd[n++] = (float)(1.0 / cell);
+        if (f2 - s2 > 1e-3 && n < max_taps) wd[n++] = (float)(fmin(fmin(f2 - s2, 1.0), cell) / cell);
+        first[i] = left ? s1 - 1 : s1;
+        num[i] = n;
+    }
+}
+
+template <bool kFast>
+__global__ __launch_bounds__(CT) void gather_area_resize_kernel(const uint8_t* __restrict__ slide, int sh, int sw, int c,
+                                                                 const int* __restrict__ bounds, int hb, int wb, int ph, int pw,
+                                                                 int tile_w, int tile_h, int tiles_x, int span_cap, int rows_cap,
+                                                                 int pitch, int max_taps, int pad, uint8_t* __restrict__ out) {
+    extern __shared__ uint4 stage4[];
+    uint8_t* stage = reinterpret_cast<uint8_t*>(stage4);
+    int* xfirst = reinterpret_cast<int*>(stage + (long)rows_cap * pitch);
+    int* xnum = xfirst + tile_w;
+    int* yfirst = xnum + tile_w;
+    int* ynum = yfirst + tile_h;
+    float* xw = reinterpret_cast<float*>(ynum + tile_h);
+    float* yw = xw + (long)tile_w * max_taps;
+    const int m = blockIdx.y;
+    const int ty = (int)blockIdx.x / tiles_x, tx = (int)blockIdx.x - ty * tiles_x;
+    const int oy0 = ty * tile_h, ox0 = tx * tile_w;
+    const int th = min(tile_h, ph - oy0), tw = min(tile_w, pw - ox0);
+    area_resize_taps(wb, pw, ox0, tw, max_taps, kFast, xfirst, xnum, xw);
+    area_resize_taps(hb, ph, oy0, th, max_taps, kFast, yfirst, ynum, yw);
+    __syncthreads();
+    // the tile's source window: columns sxa .. sxa + span / c - 1 and rows sya .. sya + rows - 1 of the region (the launcher's
+    // caps bound both; the min() only keeps LDS accesses inside the allocation)
+    const int sxa = xfirst[0], sya = yfirst[0];
+    const long span = (long)min(xfirst[tw - 1] + xnum[tw - 1] - sxa, span_cap) * c;  // source bytes of one staged row
+    const int rows = min(yfirst[th - 1] + ynum[th - 1] - sya, rows_cap);
+    const long row_bytes = (long)sw * c;
+    const long xs = ((long)bounds[m * 4 + 0] + sxa) * c;  // the window's byte offset in its slide row (may be < 0)
+    const long sy0 = (long)bounds[m * 4 + 1] + sya;
+    const int nq = pitch >> 4;
+    const int total = rows * nq;
+    const uint32_t pad4 = 0x01010101u * (uint32_t)(pad & 255);
+    const uintptr_t base = reinterpret_cast<uintptr_t>(slide);
+    for (int i0 = threadIdx.x; i0 < total; i0 += CT * kAreaUnroll) {
+        uint4 v[kAreaUnroll];
+        long lo[kAreaUnroll], sy[kAreaUnroll];
+        int need[kAreaUnroll];  // 0: past the window, 1: all pad, 2: one aligned load, 3: byte by byte
+#pragma unroll
+        for (int u = 0; u < kAreaUnroll; ++u) {
+            const int i = i0 + u * CT;
+            const int r = i / nq, q = i - r * nq;
+            sy[u] = sy0 + r;
+            const int a = (int)((base + (uintptr_t)(sy[u] * row_bytes + xs)) & 15);
+            lo[u] = xs - a + 16L * q;  // the chunk's byte offset in the slide row; 16-byte aligned in memory
+            v[u] = make_uint4(pad4, pad4, pad4, pad4);
+            need[u] = 0;
+            if (i < total && 16L * q < a + span) {
+                need[u] = 1;
+                if (sy[u] >= 0 && sy[u] < sh && lo[u] + 16 > 0 && lo[u] < row_bytes)
+                    need[u] = (lo[u] >= 0 && lo[u] + 16 <= row_bytes) ? 2 : 3;
+            }
+            if (need[u] == 2) v[u] = *reinterpret_cast<const uint4*>(slide + sy[u] * row_bytes + lo[u]);
+        }
+#pragma unroll
+        for (int u = 0; u < kAreaUnroll; ++u) {
+            if (need[u] == 0) continue;
+            if (need[u] == 3) {  // the chunk crosses the left or right edge of the slide
+                const uint8_t* rp = slide + sy[u] * row_bytes;
+                uint32_t w[4] = {0u, 0u, 0u, 0u};
+#pragma unroll
+                for (int e = 0; e < 16; ++e) {
+                    const long o = lo[u] + e;
+                    const uint32_t b = (o >= 0 && o < row_bytes) ? (uint32_t)rp[o] : (uint32_t)(pad & 255);
+                    w[e >> 2] |= b << (8 * (e & 3));
+                }
+                v[u] = make_uint4(w[0], w[1], w[2], w[3]);
+            }
+            stage4[i0 + u * CT] = v[u];
+        }
+    }
+    __syncthreads();
+    const int out_row = tw * c;             // output bytes of one tile row
+    const int groups = (out_row + 3) >> 2;  // 4-byte groups per tile row
+    const float inv_area = kFast ? 1.0f / (float)((wb / pw) * (hb / ph)) : 0.0f;
+    for (int g = threadIdx.x; g < th * groups; g += CT) {
+        const int rr = g / groups, j0 = (g - rr * groups) * 4;
+        uint8_t* dst = out + (((size_t)m * ph + oy0 + rr) * pw + ox0) * c;
+        const int nj = min(4, out_row - j0);
+        int off[4], nx[4], px[4];  // per output byte: staged offset of its first x tap, tap count, tile pixel
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            const int j = min(j0 + e, out_row - 1);
+            px[e] = j / c;
+            off[e] = (xfirst[px[e]] - sxa) * c + (j - px[e] * c);
+            nx[e] = xnum[px[e]];
+        }
+        float acc[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+        uint32_t isum[4] = {0u, 0u, 0u, 0u};
+        const int yf = yfirst[rr] - sya, yn = ynum[rr];
+        for (int t = 0; t < yn; ++t) {
+            const int r = yf + t;
+            const int a = (int)((base + (uintptr_t)((sy0 + r) * row_bytes + xs)) & 15);
+            const uint8_t* sp = stage + r * pitch + a;
+            const float beta = kFast ? 0.0f : yw[rr * max_taps + t];
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                if (e >= nj) break;
+                const uint8_t* p = sp + off[e];
+                if (kFast) {
+                    uint32_t s = 0;
+                    for (int u = 0; u < nx[e]; ++u) s += p[u * c];
+                    isum[e] += s;
+                } else {
+                    const float* alpha = xw + px[e] * max_taps;
+                    float h = 0.0f;
+                    for (int u = 0; u < nx[e]; ++u) h += (float)p[u * c] * alpha[u];
+                    const float bh = beta * h;
+                    acc[e] = t == 0 ? bh : acc[e] + bh;
+                }
+            }
+        }
+        uint32_t b[4];
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            const float v = rintf(kFast ? (float)isum[e] * inv_area : acc[e]);
+            b[e] = (uint32_t)(v > 255.0f ? 255.0f : (v < 0.0f ? 0.0f : v));
+        }
+        if (nj == 4 && ((reinterpret_cast<uintptr_t>(dst + j0) & 3) == 0)) {
+            *reinterpret_cast<uint32_t*>(dst + j0) = b[0] | (b[1] << 8) | (b[2] << 16) | (b[3] << 24);
+        } else {
+            for (int e = 0; e < nj; ++e) dst[j0 + e] = (uint8_t)b[e];
+        }
+    }
+}
+
 }  // namespace tia
 
 using namespace tia;
@@ -320,6 +486,53 @@ extern "C" int tia_gather_area_patches_u8(const uint8_t* d_slide, int64_t sh, in
         hipLaunchKernelGGL(tia::gather_area_patches_kernel, dim3((unsigned)(tiles_x * tiles_y), (unsigned)n), dim3(tia::CT), lds,
                            (hipStream_t)stream, d_slide, (int)sh, (int)sw, (int)c, d_bounds + s * 4, (int)ph, (int)pw, (int)k,
                            (int)tile_w, (int)tile_h, (int)tiles_x, (int)pitch, pad, d_out + s * patch_bytes);
+        if (hipGetLastError() != hipSuccess) return TIA_ELAUNCH;
+    }
+    return TIA_OK;
+}
+
+extern "C" int tia_gather_area_resize_u8(const uint8_t* d_slide, int64_t sh, int64_t sw, int64_t c, const int32_t* d_bounds,
+                                         int64_t m, int64_t hb, int64_t wb, int64_t ph, int64_t pw, int32_t pad, uint8_t* d_out,
+                                         void* stream) {
+    if (!d_slide || !d_bounds || !d_out || sh <= 0 || sw <= 0 || (c != 1 && c != 3) || m < 0 || hb <= 0 || wb <= 0 || ph <= 0 ||
+        pw <= 0)
+        return TIA_EINVAL;
+    if (m == 0) return TIA_OK;
+    if (sh > 0x7fffffffL || sw * c > 0x7fffffffL || hb > 0x7fffffffL || wb * c > 0x7fffffffL || ph * pw * c > 0x7fffffffL)
+        return TIA_ESIZE;
+    // cv::resize's scales and its resizeAreaFast test (both scales integers within DBL_EPSILON)
+    const double scale_x = 1.0 / ((double)pw / (double)wb), scale_y = 1.0 / ((double)ph / (double)hb);
+    if (!(scale_x >= 1.0 && scale_y >= 1.0 && scale_x <= 64.0 && scale_y <= 64.0)) return TIA_ESIZE;
+    const long kx = lrint(scale_x), ky = lrint(scale_y);
+    const bool fast = fabs(scale_x - (double)kx) < DBL_EPSILON && fabs(scale_y - (double)ky) < DBL_EPSILON;
+    if (fast && kx == ky) return tia_gather_area_patches_u8(d_slide, sh, sw, c, d_bounds, m, ph, pw, kx, pad, d_out, stream);
+    // tile: the whole output row (at most 1024 bytes, one 4-byte group per thread) unless one tile row's staged source does
+    // not fit kResizeStage; then as many output rows as fit.  The caps bound every tile's source window (see the kernel).
+    const long max_taps = (long)floor(fmax(scale_x, scale_y)) + 3;
+    auto span_cap = [&](long tw) { return (long)floor((double)tw * scale_x) + 4; };
+    auto rows_cap = [&](long th) { return (long)floor((double)th * scale_y) + 4; };
+    auto pitch_of = [&](long tw) { return ((span_cap(tw) * c + 15) & ~15L) + 16; };  // plus up to 15 bytes of alignment
+    long tile_w = pw < 1024 / c ? pw : 1024 / c;
+    while (tile_w > 1 && rows_cap(1) * pitch_of(tile_w) > tia::kResizeStage) tile_w = (tile_w + 1) / 2;
+    const long tiles_x = (pw + tile_w - 1) / tile_w;
+    tile_w = (pw + tiles_x - 1) / tiles_x;
+    const long pitch = pitch_of(tile_w);
+    long tile_h = (long)((double)(tia::kResizeStage / pitch - 4) / scale_y);
+    tile_h = tile_h < 1 ? 1 : (tile_h > ph ? ph : tile_h);
+    while (tile_h > 1 && rows_cap(tile_h) * pitch > tia::kResizeStage) --tile_h;
+    const long tiles_y = (ph + tile_h - 1) / tile_h;
+    tile_h = (ph + tiles_y - 1) / tiles_y;
+    if (tiles_x * tiles_y > 0x7fffffffL) return TIA_ESIZE;
+    const long rows = rows_cap(tile_h);
+    const size_t lds = (size_t)(rows * pitch + (tile_w + tile_h) * (2 + max_taps) * 4);
+    if (lds > 65536) return TIA_ESIZE;
+    const long patch_bytes = ph * pw * c;
+    for (long s = 0; s < m; s += 65535) {
+        const long n = m - s < 65535 ? m - s : 65535;
+        auto kern = fast ? tia::gather_area_resize_kernel<true> : tia::gather_area_resize_kernel<false>;
+        hipLaunchKernelGGL(kern, dim3((unsigned)(tiles_x * tiles_y), (unsigned)n), dim3(tia::CT), lds, (hipStream_t)stream, d_slide,
+                           (int)sh, (int)sw, (int)c, d_bounds + s * 4, (int)hb, (int)wb, (int)ph, (int)pw, (int)tile_w, (int)tile_h,
+                           (int)tiles_x, (int)span_cap(tile_w), (int)rows, (int)pitch, (int)max_taps, pad, d_out + s * patch_bytes);
         if (hipGetLastError() != hipSuccess) return TIA_ELAUNCH;
     }
     return TIA_OK;

@@ -750,7 +750,8 @@ class EngineABC:
 
     def _reader_at_input_resolution(self, reader):
         """A ``VirtualWSIReader`` whose native resolution is not the model's input resolution -> its view at that resolution
-        (``VirtualWSIReader.at_resolution``: patch reads area-resampled on the device), so that coordinates and outputs come
+        (``VirtualWSIReader.at_resolution``: patch reads area-resampled on the device, by an integer factor or, for a
+        ``fractional`` reader, by its real scale), so that coordinates and outputs come
         out in the pixel space of the model's resolution, as in the reference.  Any other reader is returned unchanged."""
         from tiatoolbox_amd.wsicore import VirtualWSIReader, _close
 
@@ -758,7 +759,7 @@ class EngineABC:
             return reader
         cfg = self._ioconfig
         res = cfg.input_resolutions[0]
-        if reader.factor(res["resolution"], res["units"]) == 1:
+        if reader.scale(res["resolution"], res["units"]) == 1:
             return reader
         others = [*cfg.input_resolutions[1:], *cfg.output_resolutions]
         if getattr(cfg, "save_resolution", None) is not None:

@@ -8,10 +8,11 @@ gathered by one kernel launch (``tia_gather_patches_u8``) that writes 255 wherev
 as ``WSIPatchDataset.__getitem__`` pads (``dataset_abc.py:430-436``).
 
 ``ArrayWSIReader`` reads at the slide's own resolution only.  ``VirtualWSIReader`` (the reference's class name) also reads
-below it, by an integer factor ``k`` (:func:`resolution_factor`): ``read_bounds(..., resolution, units)`` and the light view
-``at_resolution(resolution, units)`` take the baseline region, pad it with 255 outside the slide and shrink it with
-``cv2.INTER_AREA``'s integer-scale rule in one launch (``tia_gather_area_patches_u8``), which is what the reference's
-``read_bounds`` -> ``imresize`` does.  Up-sampling, non-integer factors and multi-level pyramids are not supported.
+below it, by an integer factor ``k`` (:func:`resolution_factor`) or, with ``fractional=True``, by any ratio ``s >= 1``
+(:func:`resolution_scale`): ``read_bounds(..., resolution, units)`` and the light view ``at_resolution(resolution, units)``
+take the baseline region, pad it with 255 outside the slide and shrink it with ``cv2.INTER_AREA`` in one launch
+(``tia_gather_area_patches_u8`` at an integer scale, ``tia_gather_area_resize_u8`` at any other), which is what the
+reference's ``read_bounds`` -> ``imresize`` does.  Up-sampling, anisotropic mpp and multi-level pyramids are not supported.
 """
 
 from __future__ import annotations
@@ -160,17 +161,14 @@ def _close(a: float, b: float) -> bool:
     return abs(a - b) <= _REL_TOL * max(1.0, abs(a), abs(b))
 
 
-def resolution_factor(resolution: float, units: str, *, mpp=None, power: float | None = None) -> int:
-    """Integer down-sampling factor ``k`` from a slide at (``mpp``, ``power``) to the requested ``(resolution, units)``.
-
-    ``units``: ``"mpp"`` (k = resolution / mpp), ``"power"`` (k = power / resolution), ``"baseline"`` (a scale of the
-    baseline: k = 1 / resolution) or ``"level"`` (only level 0, k = 1).  ``ValueError`` for up-sampling, a factor that is not an
-    integer, a native value of ``None``, ``mpp_x != mpp_y`` and ``level > 0``."""
+def _resolution_ratio(resolution: float, units: str, mpp, power) -> float:
+    """Down-sampling ratio from a slide at (``mpp``, ``power``) to ``(resolution, units)``: every check of
+    :func:`resolution_factor` except the up-sampling and integer ones."""
     if units == "level":
         if not _close(float(resolution), 0.0):
             msg = f"the in-memory slide holds one level (level 0); level {resolution} was requested."
             raise ValueError(msg)
-        return 1
+        return 1.0
     if units not in ("mpp", "power", "baseline"):
         msg = f"Invalid resolution units `{units}`: expected 'mpp', 'power', 'baseline' or 'level'."
         raise ValueError(msg)
@@ -179,17 +177,26 @@ def resolution_factor(resolution: float, units: str, *, mpp=None, power: float |
         msg = f"the requested resolution must be positive, got {resolution} {units}."
         raise ValueError(msg)
     if units == "baseline":
-        ratio = 1.0 / resolution
-    else:
-        native = mpp if units == "mpp" else power
-        if native is None:
-            msg = f"the slide's native {units} is None: a read at {resolution} {units} cannot be placed."
-            raise ValueError(msg)
-        comps = [float(v) for v in np.asarray(native, dtype=np.float64).ravel()]
-        if not all(_close(v, comps[0]) for v in comps):
-            msg = f"the slide's mpp differs between x and y ({tuple(comps)}): anisotropic slides are not resampled."
-            raise ValueError(msg)
-        ratio = resolution / comps[0] if units == "mpp" else comps[0] / resolution
+        return 1.0 / resolution
+    native = mpp if units == "mpp" else power
+    if native is None:
+        msg = f"the slide's native {units} is None: a read at {resolution} {units} cannot be placed."
+        raise ValueError(msg)
+    comps = [float(v) for v in np.asarray(native, dtype=np.float64).ravel()]
+    if not all(_close(v, comps[0]) for v in comps):
+        msg = f"the slide's mpp differs between x and y ({tuple(comps)}): anisotropic slides are not resampled."
+        raise ValueError(msg)
+    return resolution / comps[0] if units == "mpp" else comps[0] / resolution
+
+
+def resolution_factor(resolution: float, units: str, *, mpp=None, power: float | None = None) -> int:
+    """Integer down-sampling factor ``k`` from a slide at (``mpp``, ``power``) to the requested ``(resolution, units)``.
+
+    ``units``: ``"mpp"`` (k = resolution / mpp), ``"power"`` (k = power / resolution), ``"baseline"`` (a scale of the
+    baseline: k = 1 / resolution) or ``"level"`` (only level 0, k = 1).  ``ValueError`` for up-sampling, a factor that is not an
+    integer, a native value of ``None``, ``mpp_x != mpp_y`` and ``level > 0``."""
+    ratio = _resolution_ratio(resolution, units, mpp, power)
+    resolution = float(resolution)
     k = round(ratio)
     if ratio < 1.0 and not _close(ratio, 1.0):
         msg = (f"reading at {resolution} {units} up-samples the slide (factor {ratio:.6g} < 1); only down-sampling by an "
@@ -202,18 +209,36 @@ def resolution_factor(resolution: float, units: str, *, mpp=None, power: float |
     return int(k)
 
 
-def _area_read(base: ArrayWSIReader, bounds, size: tuple[int, int], k: int, pad_value: int) -> torch.Tensor:
-    """``[M, ph, pw, C]`` area reads of baseline ``bounds`` (an int32 ``[M, 4]`` device tensor, ``size=(pw, ph)``, extents
-    ``k * size``): one ``tia_gather_area_patches_u8`` call."""
-    from tiatoolbox_amd import _lib
+def resolution_scale(resolution: float, units: str, *, mpp=None, power: float | None = None) -> float:
+    """Down-sampling scale ``s >= 1`` (baseline pixels per pixel at ``(resolution, units)``), integer or not.
 
+    The checks and messages of :func:`resolution_factor` except its integer check.  A ratio within ``_REL_TOL`` of an
+    integer is returned as that integer (a ``float``), so that integer scales keep the integer read."""
+    ratio = _resolution_ratio(resolution, units, mpp, power)
+    if ratio < 1.0 and not _close(ratio, 1.0):
+        msg = (f"reading at {float(resolution)} {units} up-samples the slide (factor {ratio:.6g} < 1); only down-sampling is "
+               "supported.")
+        raise ValueError(msg)
+    k = round(ratio)
+    return float(k) if _close(ratio, float(k)) else float(ratio)
+
+
+def _u8_source(base: ArrayWSIReader) -> torch.Tensor:
     src = base.device_image if base.device_image.dim() == 3 else base.device_image[..., None]  # noqa: PLR2004
     if src.dtype == torch.bool:
         src = src.to(torch.uint8)
     if src.dtype != torch.uint8:
         msg = "device patch reads need a uint8 slide."
         raise TypeError(msg)
-    src = src.contiguous()
+    return src.contiguous()
+
+
+def _area_read(base: ArrayWSIReader, bounds, size: tuple[int, int], k: int, pad_value: int) -> torch.Tensor:
+    """``[M, ph, pw, C]`` area reads of baseline ``bounds`` (an int32 ``[M, 4]`` device tensor, ``size=(pw, ph)``, extents
+    ``k * size``): one ``tia_gather_area_patches_u8`` call."""
+    from tiatoolbox_amd import _lib
+
+    src = _u8_source(base)
     sh, sw, c = src.shape
     pw, ph = int(size[0]), int(size[1])
     out = torch.empty((len(bounds), ph, pw, c), dtype=torch.uint8, device=src.device)
@@ -221,6 +246,24 @@ def _area_read(base: ArrayWSIReader, bounds, size: tuple[int, int], k: int, pad_
         rc = _lib.load().tia_gather_area_patches_u8(src.data_ptr(), sh, sw, c, bounds.data_ptr(), len(bounds), ph, pw, int(k),
                                                     int(pad_value), out.data_ptr(), _lib.current_stream())
     _lib.check(rc, "tia_gather_area_patches_u8")
+    return out if base.device_image.dim() == 3 else out[..., 0]  # noqa: PLR2004
+
+
+def _area_resize_read(base: ArrayWSIReader, bounds, extent: tuple[int, int], size: tuple[int, int], pad_value: int) -> torch.Tensor:
+    """``[M, ph, pw, C]`` reads of the ``extent=(wb, hb)`` baseline regions whose top-left corners are ``bounds[:, :2]`` (an
+    int32 ``[M, 4]`` device tensor), each resampled to ``size=(pw, ph)`` with ``cv2.INTER_AREA`` at any ratio: one
+    ``tia_gather_area_resize_u8`` call."""
+    from tiatoolbox_amd import _lib
+
+    src = _u8_source(base)
+    sh, sw, c = src.shape
+    wb, hb = int(extent[0]), int(extent[1])
+    pw, ph = int(size[0]), int(size[1])
+    out = torch.empty((len(bounds), ph, pw, c), dtype=torch.uint8, device=src.device)
+    with torch.cuda.device(src.device):
+        rc = _lib.load().tia_gather_area_resize_u8(src.data_ptr(), sh, sw, c, bounds.data_ptr(), len(bounds), hb, wb, ph, pw,
+                                                   int(pad_value), out.data_ptr(), _lib.current_stream())
+    _lib.check(rc, "tia_gather_area_resize_u8")
     return out if base.device_image.dim() == 3 else out[..., 0]  # noqa: PLR2004
 
 
@@ -238,23 +281,38 @@ def _host_bounds(bounds) -> tuple[np.ndarray, tuple[int, int]]:
 
 
 class VirtualWSIReader(ArrayWSIReader):
-    """ndarray-backed slide that also reads below its baseline resolution (reference ``VirtualWSIReader``, down-sampling by
-    an integer factor only).  Same constructor as :class:`ArrayWSIReader`; without a resolution every read is the
-    ``ArrayWSIReader`` read."""
+    """ndarray-backed slide that also reads below its baseline resolution (reference ``VirtualWSIReader``).  Same constructor
+    as :class:`ArrayWSIReader`, plus ``fractional``: ``False`` (the default) down-samples by an integer factor only,
+    ``True`` by any ratio >= 1 (:func:`resolution_scale`).  Without a resolution every read is the ``ArrayWSIReader`` read."""
+
+    fractional = False
+
+    def __init__(self, img, mpp: float | None = 0.25, power: float | None = 40.0, mode: str = "rgb", *,
+                 fractional: bool = False) -> None:
+        super().__init__(img, mpp=mpp, power=power, mode=mode)
+        self.fractional = bool(fractional)
 
     def factor(self, resolution: float, units: str) -> int:
         return resolution_factor(resolution, units, mpp=self.mpp, power=self.power)
 
+    def scale(self, resolution: float, units: str) -> float:
+        """Baseline pixels per pixel at ``(resolution, units)``: :func:`resolution_scale` for a fractional reader, else the
+        integer :meth:`factor`."""
+        if self.fractional:
+            return resolution_scale(resolution, units, mpp=self.mpp, power=self.power)
+        return self.factor(resolution, units)
+
     def at_resolution(self, resolution: float, units: str) -> ResampledWSIView:
         """The slide as seen at ``(resolution, units)``: a light view (no copy of the slide) whose reads take bounds in its
         own pixel space."""
-        return ResampledWSIView(self, self.factor(resolution, units))
+        return ResampledWSIView(self, self.scale(resolution, units))
 
     def read_bounds(self, bounds, resolution: float | None = None, units: str | None = None, coord_space: str = "baseline",
                     pad_constant_values: int = 255) -> np.ndarray:
         """One region ``[x0, y0, x1, y1]`` (the subset of the reference's signature users call).  With ``resolution``:
-        ``coord_space="resolution"`` takes the bounds at that resolution; ``"baseline"`` takes baseline bounds whose extents
-        are multiples of the factor.  The output is the padded baseline region box-averaged by the factor."""
+        ``coord_space="resolution"`` takes the bounds at that resolution; ``"baseline"`` takes baseline bounds, whose extents
+        must be multiples of the factor unless the reader is fractional (then the region is resampled to
+        ``np.round(extent / scale)``).  The output is the padded baseline region area-resampled to the resolution."""
         if coord_space not in ("baseline", "resolution"):
             msg = f"Invalid coord_space `{coord_space}`: expected 'baseline' or 'resolution'."
             raise ValueError(msg)
@@ -268,24 +326,34 @@ class VirtualWSIReader(ArrayWSIReader):
             return view.read_bounds(bounds, pad_constant_values)
         k = view.factor
         b, (w, h) = _host_bounds(bounds)
-        if w % k or h % k:
+        bt = torch.from_numpy(b).to(self.device_image.device)
+        if isinstance(k, int) and not (w % k or h % k):
+            return _area_read(self, bt, (w // k, h // k), k, pad_constant_values)[0].cpu().numpy()
+        if not self.fractional:
             msg = f"a {w} x {h} baseline region does not shrink by the integer factor {k}."
             raise ValueError(msg)
-        bt = torch.from_numpy(b).to(self.device_image.device)
-        return _area_read(self, bt, (w // k, h // k), k, pad_constant_values)[0].cpu().numpy()
+        pw, ph = int(np.round(w / k)), int(np.round(h / k))
+        if pw <= 0 or ph <= 0:
+            msg = f"a {w} x {h} baseline region is empty at 1 / {k:.6g} of the baseline resolution."
+            raise ValueError(msg)
+        return _area_resize_read(self, bt, (w, h), (pw, ph), pad_constant_values)[0].cpu().numpy()
 
 
 class ResampledWSIView:
     """A :class:`VirtualWSIReader` seen at ``1 / factor`` of its baseline resolution (``VirtualWSIReader.at_resolution``).
 
-    ``slide_dimensions`` follow the reference's ``np.round(baseline / factor)`` (``WSIReader._find_read_bounds_params``:
-    ``output_size = np.round(...)``, which rounds halves to even); ``mpp`` / ``power`` are scaled by the factor; reads take
-    bounds in this view's pixels and go through ``tia_gather_area_patches_u8``; the tissue mask comes from the base reader
-    (the reference computes it from baseline)."""
+    ``factor`` is the scale ``s`` (baseline pixels per view pixel): an ``int`` when it is an integer, else a ``float``.
+    ``slide_dimensions`` follow the reference's ``np.round(baseline / s)`` (``WSIReader._find_read_bounds_params``:
+    ``output_size = np.round(...)``, which rounds halves to even); ``mpp`` / ``power`` are scaled by ``s``; reads take
+    bounds in this view's pixels.  At an integer ``s`` they go through ``tia_gather_area_patches_u8``; otherwise the view
+    region ``[x0, y0, x0 + pw, y0 + ph]`` reads the baseline region at ``(np.round(x0 * s), np.round(y0 * s))`` of extent
+    ``(np.round(pw * s), np.round(ph * s))`` and resamples it to ``pw x ph`` (``tia_gather_area_resize_u8``).  The tissue
+    mask comes from the base reader (the reference computes it from baseline)."""
 
-    def __init__(self, base: VirtualWSIReader, factor: int) -> None:
+    def __init__(self, base: VirtualWSIReader, factor: float) -> None:
         self.base = base
-        self.factor = int(factor)
+        s = float(factor)
+        self.factor = round(s) if _close(s, round(s)) else s
         self.mode = base.mode
         k = self.factor
         self.mpp = None if base.mpp is None else (base.mpp * k if np.ndim(base.mpp) == 0 else tuple(float(v) * k for v in np.ravel(base.mpp)))
@@ -304,10 +372,19 @@ class ResampledWSIView:
             if size is None or bounds.dtype != torch.int32 or bounds.dim() != 2 or bounds.shape[1] != 4 or not bounds.is_contiguous():  # noqa: PLR2004
                 msg = "device bounds: a contiguous int32 [M, 4] tensor together with size=(pw, ph)."
                 raise ValueError(msg)
-            return _area_read(self.base, bounds * k if k != 1 else bounds, size, k, pad_value)
-        b, size = _host_bounds(bounds)
-        bt = torch.from_numpy(b * np.int32(k)).to(self.base.device_image.device)
-        return _area_read(self.base, bt, size, k, pad_value)
+            if isinstance(k, int):
+                return _area_read(self.base, bounds * k if k != 1 else bounds, size, k, pad_value)
+            top_left = torch.round(bounds[:, :2].double() * k).to(torch.int32)
+        else:
+            b, size = _host_bounds(bounds)
+            if isinstance(k, int):
+                bt = torch.from_numpy(b * np.int32(k)).to(self.base.device_image.device)
+                return _area_read(self.base, bt, size, k, pad_value)
+            top_left = torch.from_numpy(np.round(b[:, :2] * k).astype(np.int32)).to(self.base.device_image.device)
+        pw, ph = int(size[0]), int(size[1])
+        extent = (int(np.round(pw * k)), int(np.round(ph * k)))
+        bt = torch.cat([top_left, top_left + torch.tensor(extent, dtype=torch.int32, device=top_left.device)], dim=1).contiguous()
+        return _area_resize_read(self.base, bt, extent, (pw, ph), pad_value)
 
     def read_bounds(self, bounds, pad_value: int = 255) -> np.ndarray:
         return self.read_bounds_batch(np.asarray(bounds)[None], pad_value)[0].cpu().numpy()

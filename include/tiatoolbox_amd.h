@@ -40,7 +40,7 @@ extern "C" {
  * tia_reinhard_workspace_bytes / tia_lab_moments_u8 (one-launch Reinhard); tia_luminosity_mask_u8 and the float64 form of
  * tia_stain_augment_u8 (now a product of per-patch tables) take 16-byte accesses where the shape allows.
  * Additive, same version: tia_gather_area_patches_u8 (patch reads below the slide's resolution), tia_gather_area_resize_u8
- * (the same at any down-sampling ratio). */
+ * (the same at any down-sampling ratio), tia_gather_cubic_resize_u8 (patch reads above the slide's resolution). */
 #define TIA_ABI_VERSION 6
 int tia_abi_version(void);
 
@@ -500,6 +500,16 @@ int tia_gather_area_patches_u8(const uint8_t* d_slide, int64_t sh, int64_t sw, i
  *   d_slide [sh,sw,c] u8, c in {1, 3}   d_bounds [m,4] i32   d_out [m,ph,pw,c] u8 (any m)   1 <= wb / pw, hb / ph <= 64 */
 int tia_gather_area_resize_u8(const uint8_t* d_slide, int64_t sh, int64_t sw, int64_t c, const int32_t* d_bounds, int64_t m,
                               int64_t hb, int64_t wb, int64_t ph, int64_t pw, int32_t pad, uint8_t* d_out, void* stream);
+
+/* Reads above the slide's resolution: out[i] = cv::resize(region_i, (pw, ph), INTER_CUBIC) of the hb x wb baseline region whose
+ * top-left is (d_bounds[i][0], d_bounds[i][1]), `pad` standing in for every source byte outside the slide (padding before
+ * resampling); x1, y1 are not read.  resizeGeneric_'s fixed-point 8-bit path: per axis scale = 1.0 / ((double)p / b),
+ * fx = (float)((d + 0.5) * scale - 0.5), s = floor(fx), f = fx - s; interpolateCubic's float coefficients (A = -0.75, no fused
+ * multiply-add) each rounded half to even to a short of 2048 * coef; taps s - 1 .. s + 2 clamped to the region, not the slide;
+ * int32 horizontal then vertical sums, (v + (1 << 21)) >> 22 saturated to [0, 255].
+ *   d_slide [sh,sw,c] u8, c in {1, 3}   d_bounds [m,4] i32   d_out [m,ph,pw,c] u8 (any m, any pw * c)   pw >= wb, ph >= hb */
+int tia_gather_cubic_resize_u8(const uint8_t* d_slide, int64_t sh, int64_t sw, int64_t c, const int32_t* d_bounds, int64_t m,
+                               int64_t hb, int64_t wb, int64_t ph, int64_t pw, int32_t pad, uint8_t* d_out, void* stream);
 
 /* =======================================================================================
  * ResNet convolutions on the matrix cores (models/architecture/vanilla.py:300-316 -> torchvision BasicBlock)

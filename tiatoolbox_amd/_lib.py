@@ -94,6 +94,7 @@ _SIGNATURES = {
     "tia_gather_patches_u8": ([_P, _I64, _I64, _I64, _P, _I64, _I64, _I64, _I32, _P, _P], C.c_int),
     "tia_gather_area_patches_u8": ([_P, _I64, _I64, _I64, _P, _I64, _I64, _I64, _I64, _I32, _P, _P], C.c_int),
     "tia_gather_area_resize_u8": ([_P, _I64, _I64, _I64, _P, _I64, _I64, _I64, _I64, _I64, _I32, _P, _P], C.c_int),
+    "tia_gather_cubic_resize_u8": ([_P, _I64, _I64, _I64, _P, _I64, _I64, _I64, _I64, _I64, _I32, _P, _P], C.c_int),
     "tia_lab_hist_u8": ([_P, _I64, _I64, _I64, _P, _P, _P], C.c_int),
     "tia_reinhard_apply_u8": ([_P, _I64, _I64, _I64, _P, _P, _P, _P], C.c_int),
     "tia_reinhard_luts": ([_P, _I64, _P, _P, _P, _P, _P, _P, _P], C.c_int),

@@ -161,32 +161,21 @@ __device__ __forceinline__ uint32_t area_round(uint32_t sum, int k, float scale)
     return (uint32_t)(v > 255.0f ? 255.0f : v);
 }
 
-__global__ __launch_bounds__(CT) void gather_area_patches_kernel(const uint8_t* __restrict__ slide, int sh, int sw, int c,
-                                                                  const int* __restrict__ bounds, int ph, int pw, int k,
-                                                                  int tile_w, int tile_h, int tiles_x, int pitch, int pad,
-                                                                  uint8_t* __restrict__ out) {
-    extern __shared__ uint4 stage4[];
-    uint8_t* stage = reinterpret_cast<uint8_t*>(stage4);
-    const int m = blockIdx.y;
-    const int ty = (int)blockIdx.x / tiles_x, tx = (int)blockIdx.x - ty * tiles_x;
-    const int oy0 = ty * tile_h, ox0 = tx * tile_w;
-    const int th = min(tile_h, ph - oy0), tw = min(tile_w, pw - ox0);
-    const long row_bytes = (long)sw * c;
-    const long span = (long)tw * k * c;                          // source bytes of one staged row
-    const long xs = ((long)bounds[m * 4 + 0] + (long)ox0 * k) * c;  // the run's byte offset in its slide row (may be < 0)
-    const long sy0 = (long)bounds[m * 4 + 1] + (long)oy0 * k;
-    const int rows = th * k;
-    const int nq = pitch >> 4;
+// Stages bytes xs .. xs + span - 1 of slide rows sy0 .. sy0 + rows - 1 (either may reach outside the slide; those bytes read as
+// `pad`) into LDS rows of nq 16-byte chunks: row r holds the aligned-down run, so its first byte sits at (source address & 15).
+// The nt threads of the workgroup share the chunks, kAreaUnroll in flight per thread.
+__device__ __forceinline__ void stage_rows(const uint8_t* __restrict__ slide, int sh, long row_bytes, long xs, long sy0, long span,
+                                           int rows, int nq, int nt, int pad, uint4* stage4) {
     const int total = rows * nq;
     const uint32_t pad4 = 0x01010101u * (uint32_t)(pad & 255);
     const uintptr_t base = reinterpret_cast<uintptr_t>(slide);
-    for (int i0 = threadIdx.x; i0 < total; i0 += CT * kAreaUnroll) {
+    for (int i0 = threadIdx.x; i0 < total; i0 += nt * kAreaUnroll) {
         uint4 v[kAreaUnroll];
         long lo[kAreaUnroll], sy[kAreaUnroll];
-        int need[kAreaUnroll];  // 0: past the run, 1: all pad, 2: one aligned load, 3: byte by byte
+        int need[kAreaUnroll];  // 0: past the window, 1: all pad, 2: one aligned load, 3: byte by byte
 #pragma unroll
         for (int u = 0; u < kAreaUnroll; ++u) {
-            const int i = i0 + u * CT;
+            const int i = i0 + u * nt;
             const int r = i / nq, q = i - r * nq;
             sy[u] = sy0 + r;
             const int a = (int)((base + (uintptr_t)(sy[u] * row_bytes + xs)) & 15);
@@ -214,10 +203,28 @@ __global__ __launch_bounds__(CT) void gather_area_patches_kernel(const uint8_t* 
                 }
                 v[u] = make_uint4(w[0], w[1], w[2], w[3]);
             }
-            const int i = i0 + u * CT;
-            stage4[i] = v[u];  // row i / nq, chunk i % nq: the stage pitch is nq chunks
+            stage4[i0 + u * nt] = v[u];  // row i / nq, chunk i % nq: the stage pitch is nq chunks
         }
     }
+}
+
+__global__ __launch_bounds__(CT) void gather_area_patches_kernel(const uint8_t* __restrict__ slide, int sh, int sw, int c,
+                                                                  const int* __restrict__ bounds, int ph, int pw, int k,
+                                                                  int tile_w, int tile_h, int tiles_x, int pitch, int pad,
+                                                                  uint8_t* __restrict__ out) {
+    extern __shared__ uint4 stage4[];
+    uint8_t* stage = reinterpret_cast<uint8_t*>(stage4);
+    const int m = blockIdx.y;
+    const int ty = (int)blockIdx.x / tiles_x, tx = (int)blockIdx.x - ty * tiles_x;
+    const int oy0 = ty * tile_h, ox0 = tx * tile_w;
+    const int th = min(tile_h, ph - oy0), tw = min(tile_w, pw - ox0);
+    const long row_bytes = (long)sw * c;
+    const long span = (long)tw * k * c;                          // source bytes of one staged row
+    const long xs = ((long)bounds[m * 4 + 0] + (long)ox0 * k) * c;  // the run's byte offset in its slide row (may be < 0)
+    const long sy0 = (long)bounds[m * 4 + 1] + (long)oy0 * k;
+    const int rows = th * k;
+    const uintptr_t base = reinterpret_cast<uintptr_t>(slide);
+    stage_rows(slide, sh, row_bytes, xs, sy0, span, rows, pitch >> 4, CT, pad, stage4);
     __syncthreads();
     const int out_row = tw * c;            // output bytes of one tile row
     const int groups = (out_row + 3) >> 2;  // 4-byte groups per tile row
@@ -318,47 +325,8 @@ __global__ __launch_bounds__(CT) void gather_area_resize_kernel(const uint8_t* _
     const long row_bytes = (long)sw * c;
     const long xs = ((long)bounds[m * 4 + 0] + sxa) * c;  // the window's byte offset in its slide row (may be < 0)
     const long sy0 = (long)bounds[m * 4 + 1] + sya;
-    const int nq = pitch >> 4;
-    const int total = rows * nq;
-    const uint32_t pad4 = 0x01010101u * (uint32_t)(pad & 255);
     const uintptr_t base = reinterpret_cast<uintptr_t>(slide);
-    for (int i0 = threadIdx.x; i0 < total; i0 += CT * kAreaUnroll) {
-        uint4 v[kAreaUnroll];
-        long lo[kAreaUnroll], sy[kAreaUnroll];
-        int need[kAreaUnroll];  // 0: past the window, 1: all pad, 2: one aligned load, 3: byte by byte
-#pragma unroll
-        for (int u = 0; u < kAreaUnroll; ++u) {
-            const int i = i0 + u * CT;
-            const int r = i / nq, q = i - r * nq;
-            sy[u] = sy0 + r;
-            const int a = (int)((base + (uintptr_t)(sy[u] * row_bytes + xs)) & 15);
-            lo[u] = xs - a + 16L * q;  // the chunk's byte offset in the slide row; 16-byte aligned in memory
-            v[u] = make_uint4(pad4, pad4, pad4, pad4);
-            need[u] = 0;
-            if (i < total && 16L * q < a + span) {
-                need[u] = 1;
-                if (sy[u] >= 0 && sy[u] < sh && lo[u] + 16 > 0 && lo[u] < row_bytes)
-                    need[u] = (lo[u] >= 0 && lo[u] + 16 <= row_bytes) ? 2 : 3;
-            }
-            if (need[u] == 2) v[u] = *reinterpret_cast<const uint4*>(slide + sy[u] * row_bytes + lo[u]);
-        }
-#pragma unroll
-        for (int u = 0; u < kAreaUnroll; ++u) {
-            if (need[u] == 0) continue;
-            if (need[u] == 3) {  // the chunk crosses the left or right edge of the slide
-                const uint8_t* rp = slide + sy[u] * row_bytes;
-                uint32_t w[4] = {0u, 0u, 0u, 0u};
-#pragma unroll
-                for (int e = 0; e < 16; ++e) {
-                    const long o = lo[u] + e;
-                    const uint32_t b = (o >= 0 && o < row_bytes) ? (uint32_t)rp[o] : (uint32_t)(pad & 255);
-                    w[e >> 2] |= b << (8 * (e & 3));
-                }
-                v[u] = make_uint4(w[0], w[1], w[2], w[3]);
-            }
-            stage4[i0 + u * CT] = v[u];
-        }
-    }
+    stage_rows(slide, sh, row_bytes, xs, sy0, span, rows, pitch >> 4, CT, pad, stage4);
     __syncthreads();
     const int out_row = tw * c;             // output bytes of one tile row
     const int groups = (out_row + 3) >> 2;  // 4-byte groups per tile row
@@ -410,6 +378,141 @@ __global__ __launch_bounds__(CT) void gather_area_resize_kernel(const uint8_t* _
             *reinterpret_cast<uint32_t*>(dst + j0) = b[0] | (b[1] << 8) | (b[2] << 16) | (b[3] << 24);
         } else {
             for (int e = 0; e < nj; ++e) dst[j0 + e] = (uint8_t)b[e];
+        }
+    }
+}
+
+
+// ---- bicubic patch reads above the slide's resolution -----------------------------------------------------------------
+// cv::resize(region, (pw, ph), INTER_CUBIC) of a wb x hb baseline region for uint8 (resize.cpp: resizeGeneric_ with
+// HResizeCubic / VResizeCubic and interpolateCubic's A = -0.75): per axis fx = (float)((d + 0.5) * scale - 0.5), s = floor(fx),
+// f = fx - s, four float coefficients (no fused multiply-add: the file has fp contract(off)) each rounded half to even to a
+// short of 2048 * c; taps s - 1 .. s + 2 clamped to the REGION.  int32 horizontal sums src * alpha per source row, int32
+// vertical sums hsum * beta over 4 rows, (v + 2^21) >> 22 saturated.  Every sum is exact, so the order does not matter.
+// One workgroup owns a tile of tile_h output rows x tile_w output pixels of one patch: it builds the tile's x and y taps in
+// LDS, stages the region rows they touch (stage_rows), then each thread owns 4 consecutive output bytes of the tile row and
+// walks down a segment of the tile's rows keeping the horizontal sums of its 4-row source window in registers: each staged
+// row is summed once per column, not once per output row that reads it.
+constexpr int kCubicStage = 20480;  // LDS bytes of source staged per workgroup (launcher sizes the tile to fit)
+constexpr int kCubicRows = 64;      // output rows per tile at most
+
+// Source index s and the four taps' weights (2048 * c, rounded half to even) of output index d at scale = n_src / n_dst.
+__device__ __forceinline__ int cubic_taps(int d, double scale, short* w) {
+    const float fx = (float)((d + 0.5) * scale - 0.5);
+    const int s = (int)floorf(fx);
+    const float f = fx - (float)s;
+    const float A = -0.75f, x1 = f + 1.0f, g = 1.0f - f;
+    float cf[4];
+    cf[0] = ((A * x1 - 5.0f * A) * x1 + 8.0f * A) * x1 - 4.0f * A;
+    cf[1] = ((A + 2.0f) * f - (A + 3.0f)) * f * f + 1.0f;
+    cf[2] = ((A + 2.0f) * g - (A + 3.0f)) * g * g + 1.0f;
+    cf[3] = 1.0f - cf[0] - cf[1] - cf[2];
+#pragma unroll
+    for (int t = 0; t < 4; ++t) w[t] = (short)min(max((int)rintf(cf[t] * 2048.0f), -32768), 32767);
+    return s;
+}
+
+__global__ __launch_bounds__(CT) void gather_cubic_resize_kernel(const uint8_t* __restrict__ slide, int sh, int sw, int c,
+                                                                  const int* __restrict__ bounds, int hb, int wb, int ph, int pw,
+                                                                  int tile_w, int tile_h, int tiles_x, int nseg, int span_cap,
+                                                                  int rows_cap, int pitch, int pad, uint8_t* __restrict__ out) {
+    extern __shared__ uint4 stage4[];
+    uint8_t* stage = reinterpret_cast<uint8_t*>(stage4);
+    short* xoff = reinterpret_cast<short*>(stage + (long)rows_cap * pitch);  // [tile_w][4] staged byte offset of each x tap
+    short* xw = xoff + tile_w * 4;                                           // [tile_w][4] x weights
+    short* yw = xw + tile_w * 4;                                             // [tile_h][4] y weights
+    int* yq = reinterpret_cast<int*>(yw + tile_h * 4);                       // [tile_h] s - 1 of each output row
+    const int m = blockIdx.y;
+    const int ty = (int)blockIdx.x / tiles_x, tx = (int)blockIdx.x - ty * tiles_x;
+    const int oy0 = ty * tile_h, ox0 = tx * tile_w;
+    const int th = min(tile_h, ph - oy0), tw = min(tile_w, pw - ox0);
+    const double scale_x = 1.0 / ((double)pw / (double)wb), scale_y = 1.0 / ((double)ph / (double)hb);  // as cv::resize
+    // the tile's source window: region columns xlo .. xhi and rows ylo .. yhi (taps are monotone in d, clamped to the region;
+    // the launcher's caps bound both, the min() only keeps LDS accesses inside the allocation)
+    short tmp[4];
+    const int xlo = max(cubic_taps(ox0, scale_x, tmp) - 1, 0), xhi = min(cubic_taps(ox0 + tw - 1, scale_x, tmp) + 2, wb - 1);
+    const int ylo = max(cubic_taps(oy0, scale_y, tmp) - 1, 0), yhi = min(cubic_taps(oy0 + th - 1, scale_y, tmp) + 2, hb - 1);
+    const int cols = min(xhi - xlo + 1, span_cap);
+    const int rows = min(yhi - ylo + 1, rows_cap);
+    for (int i = threadIdx.x; i < tw + th; i += blockDim.x) {
+        if (i < tw) {
+            const int s = cubic_taps(ox0 + i, scale_x, xw + i * 4);
+#pragma unroll
+            for (int t = 0; t < 4; ++t) xoff[i * 4 + t] = (short)((min(max(s - 1 + t, 0), wb - 1) - xlo) * c);
+        } else {
+            const int r = i - tw;
+            yq[r] = cubic_taps(oy0 + r, scale_y, yw + r * 4) - 1;
+        }
+    }
+    const long row_bytes = (long)sw * c;
+    const long xs = ((long)bounds[m * 4 + 0] + xlo) * c;  // the window's byte offset in its slide row (may be < 0)
+    const long sy0 = (long)bounds[m * 4 + 1] + ylo;
+    const uintptr_t base = reinterpret_cast<uintptr_t>(slide);
+    stage_rows(slide, sh, row_bytes, xs, sy0, (long)cols * c, rows, pitch >> 4, blockDim.x, pad, stage4);
+    __syncthreads();
+    const int out_row = tw * c;             // output bytes of one tile row
+    const int groups = (out_row + 3) >> 2;  // 4-byte groups per tile row
+    const int seg = (int)threadIdx.x / groups;
+    if (seg >= nseg) return;
+    const int j0 = ((int)threadIdx.x - seg * groups) * 4;
+    const int nj = min(4, out_row - j0);
+    int off[4][4], alpha[4][4];  // per output byte e and x tap t: staged byte offset, weight
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        const int j = min(j0 + e, out_row - 1);
+        const int px = j / c, ch = j - px * c;
+#pragma unroll
+        for (int t = 0; t < 4; ++t) {
+            off[e][t] = xoff[px * 4 + t] + ch;
+            alpha[e][t] = xw[px * 4 + t];
+        }
+    }
+    // horizontal sums of region row q (clamped to the region) for the thread's 4 output bytes
+    auto hsum = [&](int q, int* h) {
+        const int r = min(max(min(max(q, 0), hb - 1) - ylo, 0), rows - 1);
+        const int a = (int)((base + (uintptr_t)((sy0 + r) * row_bytes + xs)) & 15);
+        const uint8_t* sp = stage + r * pitch + a;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            int v = 0;
+#pragma unroll
+            for (int t = 0; t < 4; ++t) v += (int)sp[off[e][t]] * alpha[e][t];
+            h[e] = v;
+        }
+    };
+    const int rb = seg * th / nseg, re = (seg + 1) * th / nseg;
+    int win[4][4];  // horizontal sums of region rows q0 .. q0 + 3 (unclamped indices)
+    int q0 = 0;
+    for (int rr = rb; rr < re; ++rr) {
+        const int q = yq[rr];
+        if (rr == rb || q >= q0 + 4) {
+#pragma unroll
+            for (int t = 0; t < 4; ++t) hsum(q + t, win[t]);
+            q0 = q;
+        }
+        for (; q0 < q; ++q0) {  // slide the window down by one row
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                win[0][e] = win[1][e];
+                win[1][e] = win[2][e];
+                win[2][e] = win[3][e];
+            }
+            hsum(q0 + 4, win[3]);
+        }
+        const short* beta = yw + rr * 4;
+        uint32_t b[4];
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            int v = 0;
+#pragma unroll
+            for (int t = 0; t < 4; ++t) v += win[t][e] * (int)beta[t];
+            b[e] = (uint32_t)min(max((v + (1 << 21)) >> 22, 0), 255);
+        }
+        uint8_t* dst = out + (((size_t)m * ph + oy0 + rr) * pw + ox0) * c + j0;
+        if (nj == 4 && ((reinterpret_cast<uintptr_t>(dst) & 3) == 0)) {
+            *reinterpret_cast<uint32_t*>(dst) = b[0] | (b[1] << 8) | (b[2] << 16) | (b[3] << 24);
+        } else {
+            for (int e = 0; e < nj; ++e) dst[e] = (uint8_t)b[e];
         }
     }
 }
@@ -533,6 +636,54 @@ extern "C" int tia_gather_area_resize_u8(const uint8_t* d_slide, int64_t sh, int
         hipLaunchKernelGGL(kern, dim3((unsigned)(tiles_x * tiles_y), (unsigned)n), dim3(tia::CT), lds, (hipStream_t)stream, d_slide,
                            (int)sh, (int)sw, (int)c, d_bounds + s * 4, (int)hb, (int)wb, (int)ph, (int)pw, (int)tile_w, (int)tile_h,
                            (int)tiles_x, (int)span_cap(tile_w), (int)rows, (int)pitch, (int)max_taps, pad, d_out + s * patch_bytes);
+        if (hipGetLastError() != hipSuccess) return TIA_ELAUNCH;
+    }
+    return TIA_OK;
+}
+
+extern "C" int tia_gather_cubic_resize_u8(const uint8_t* d_slide, int64_t sh, int64_t sw, int64_t c, const int32_t* d_bounds,
+                                          int64_t m, int64_t hb, int64_t wb, int64_t ph, int64_t pw, int32_t pad, uint8_t* d_out,
+                                          void* stream) {
+    if (!d_slide || !d_bounds || !d_out || sh <= 0 || sw <= 0 || (c != 1 && c != 3) || m < 0 || hb <= 0 || wb <= 0 || ph <= 0 ||
+        pw <= 0)
+        return TIA_EINVAL;
+    if (m == 0) return TIA_OK;
+    if (sh > 0x7fffffffL || sw * c > 0x7fffffffL || hb > 0x7fffffffL || wb * c > 0x7fffffffL || ph * pw * c > 0x7fffffffL)
+        return TIA_ESIZE;
+    if (pw < wb || ph < hb) return TIA_ESIZE;  // up-sampling (or the same size) on both axes
+    const double scale_x = 1.0 / ((double)pw / (double)wb), scale_y = 1.0 / ((double)ph / (double)hb);
+    // tile: the whole output row when it is at most 1024 bytes (one 4-byte group per thread), else column tiles of a multiple
+    // of 4 pixels (dword-aligned in the row); as many output rows as fit kCubicStage, at most kCubicRows.  The caps bound every
+    // tile's source window: the taps of tw consecutive outputs span at most floor((tw - 1) * scale) + 4 source indices.
+    long tile_w = pw;
+    if (pw * c > 1024) {
+        const long cap = (1024 / c) & ~3L;
+        const long tiles = (pw + cap - 1) / cap;
+        tile_w = (((pw + tiles - 1) / tiles) + 3) & ~3L;
+    }
+    const long tiles_x = (pw + tile_w - 1) / tile_w;
+    auto span_cap = [&](long tw) { return (long)floor((double)tw * scale_x) + 6; };
+    auto rows_cap = [&](long th) { return (long)floor((double)th * scale_y) + 6; };
+    const long pitch = ((span_cap(tile_w) * c + 15) & ~15L) + 16;  // plus up to 15 bytes of alignment
+    long tile_h = ph < tia::kCubicRows ? ph : tia::kCubicRows;
+    while (tile_h > 1 && rows_cap(tile_h) * pitch > tia::kCubicStage) --tile_h;
+    const long tiles_y = (ph + tile_h - 1) / tile_h;
+    tile_h = (ph + tiles_y - 1) / tiles_y;
+    if (tiles_x * tiles_y > 0x7fffffffL) return TIA_ESIZE;
+    const long groups = (tile_w * c + 3) / 4;  // 4-byte groups of one tile row: one thread each
+    long nseg = tia::CT / groups;              // the tile's rows split into segments when a row needs few threads
+    nseg = nseg < 1 ? 1 : (nseg > tile_h ? tile_h : nseg);
+    const long threads = ((groups * nseg + 63) / 64) * 64;
+    const long rows = rows_cap(tile_h);
+    const size_t lds = (size_t)(rows * pitch + tile_w * 16 + tile_h * 12);
+    if (threads > tia::CT || lds > 65536) return TIA_ESIZE;
+    const long patch_bytes = ph * pw * c;
+    for (long s = 0; s < m; s += 65535) {
+        const long n = m - s < 65535 ? m - s : 65535;
+        hipLaunchKernelGGL(tia::gather_cubic_resize_kernel, dim3((unsigned)(tiles_x * tiles_y), (unsigned)n), dim3((unsigned)threads),
+                           lds, (hipStream_t)stream, d_slide, (int)sh, (int)sw, (int)c, d_bounds + s * 4, (int)hb, (int)wb, (int)ph,
+                           (int)pw, (int)tile_w, (int)tile_h, (int)tiles_x, (int)nseg, (int)span_cap(tile_w), (int)rows, (int)pitch,
+                           pad, d_out + s * patch_bytes);
         if (hipGetLastError() != hipSuccess) return TIA_ELAUNCH;
     }
     return TIA_OK;

@@ -751,7 +751,8 @@ class EngineABC:
     def _reader_at_input_resolution(self, reader):
         """A ``VirtualWSIReader`` whose native resolution is not the model's input resolution -> its view at that resolution
         (``VirtualWSIReader.at_resolution``: patch reads area-resampled on the device, by an integer factor or, for a
-        ``fractional`` reader, by its real scale), so that coordinates and outputs come
+        ``fractional`` reader, by its real scale; enlarged bicubically for an ``upsample`` reader whose baseline is coarser
+        than the model's resolution), so that coordinates and outputs come
         out in the pixel space of the model's resolution, as in the reference.  Any other reader is returned unchanged."""
         from tiatoolbox_amd.wsicore import VirtualWSIReader, _close
 

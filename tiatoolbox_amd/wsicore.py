@@ -12,15 +12,22 @@ below it, by an integer factor ``k`` (:func:`resolution_factor`) or, with ``frac
 (:func:`resolution_scale`): ``read_bounds(..., resolution, units)`` and the light view ``at_resolution(resolution, units)``
 take the baseline region, pad it with 255 outside the slide and shrink it with ``cv2.INTER_AREA`` in one launch
 (``tia_gather_area_patches_u8`` at an integer scale, ``tia_gather_area_resize_u8`` at any other), which is what the
-reference's ``read_bounds`` -> ``imresize`` does.  Up-sampling, anisotropic mpp and multi-level pyramids are not supported.
+reference's ``read_bounds`` -> ``imresize`` does.  With ``upsample=True`` it also reads above the baseline resolution, by
+any ratio ``s`` in ``[1/64, 1)``: the region is padded the same way and enlarged with ``cv2.INTER_CUBIC``
+(``tia_gather_cubic_resize_u8``), as ``imresize(..., interpolation="optimise")`` does at a scale above 1.  Up-sampling is
+opt-in; anisotropic mpp and multi-level pyramids are not supported.
 """
 
 from __future__ import annotations
+
+import logging
 
 import numpy as np
 import torch
 
 from tiatoolbox_amd.utils import _tensors
+
+logger = logging.getLogger(__name__)
 
 
 class ArrayWSIReader:
@@ -155,6 +162,7 @@ class ArrayWSIReader:
 
 # ------------------------------------------------------------------------------------------- reads below baseline
 _REL_TOL = 1e-6  # two resolutions are the same, and a ratio is an integer, within this relative tolerance
+_MAX_UPSAMPLE = 64  # an up-sampling reader enlarges the slide by at most this ratio (scale >= 1 / 64)
 
 
 def _close(a: float, b: float) -> bool:
@@ -249,10 +257,10 @@ def _area_read(base: ArrayWSIReader, bounds, size: tuple[int, int], k: int, pad_
     return out if base.device_image.dim() == 3 else out[..., 0]  # noqa: PLR2004
 
 
-def _area_resize_read(base: ArrayWSIReader, bounds, extent: tuple[int, int], size: tuple[int, int], pad_value: int) -> torch.Tensor:
+def _resize_read(symbol: str, base: ArrayWSIReader, bounds, extent: tuple[int, int], size: tuple[int, int],
+                 pad_value: int) -> torch.Tensor:
     """``[M, ph, pw, C]`` reads of the ``extent=(wb, hb)`` baseline regions whose top-left corners are ``bounds[:, :2]`` (an
-    int32 ``[M, 4]`` device tensor), each resampled to ``size=(pw, ph)`` with ``cv2.INTER_AREA`` at any ratio: one
-    ``tia_gather_area_resize_u8`` call."""
+    int32 ``[M, 4]`` device tensor), each resampled to ``size=(pw, ph)``: one call of the entry point ``symbol``."""
     from tiatoolbox_amd import _lib
 
     src = _u8_source(base)
@@ -261,10 +269,20 @@ def _area_resize_read(base: ArrayWSIReader, bounds, extent: tuple[int, int], siz
     pw, ph = int(size[0]), int(size[1])
     out = torch.empty((len(bounds), ph, pw, c), dtype=torch.uint8, device=src.device)
     with torch.cuda.device(src.device):
-        rc = _lib.load().tia_gather_area_resize_u8(src.data_ptr(), sh, sw, c, bounds.data_ptr(), len(bounds), hb, wb, ph, pw,
-                                                   int(pad_value), out.data_ptr(), _lib.current_stream())
-    _lib.check(rc, "tia_gather_area_resize_u8")
+        rc = getattr(_lib.load(), symbol)(src.data_ptr(), sh, sw, c, bounds.data_ptr(), len(bounds), hb, wb, ph, pw,
+                                          int(pad_value), out.data_ptr(), _lib.current_stream())
+    _lib.check(rc, symbol)
     return out if base.device_image.dim() == 3 else out[..., 0]  # noqa: PLR2004
+
+
+def _area_resize_read(base: ArrayWSIReader, bounds, extent: tuple[int, int], size: tuple[int, int], pad_value: int) -> torch.Tensor:
+    """:func:`_resize_read` with ``cv2.INTER_AREA`` at any down-sampling ratio (``tia_gather_area_resize_u8``)."""
+    return _resize_read("tia_gather_area_resize_u8", base, bounds, extent, size, pad_value)
+
+
+def _cubic_resize_read(base: ArrayWSIReader, bounds, extent: tuple[int, int], size: tuple[int, int], pad_value: int) -> torch.Tensor:
+    """:func:`_resize_read` with ``cv2.INTER_CUBIC`` at an up-sampling ratio (``tia_gather_cubic_resize_u8``)."""
+    return _resize_read("tia_gather_cubic_resize_u8", base, bounds, extent, size, pad_value)
 
 
 def _host_bounds(bounds) -> tuple[np.ndarray, tuple[int, int]]:
@@ -283,36 +301,54 @@ def _host_bounds(bounds) -> tuple[np.ndarray, tuple[int, int]]:
 class VirtualWSIReader(ArrayWSIReader):
     """ndarray-backed slide that also reads below its baseline resolution (reference ``VirtualWSIReader``).  Same constructor
     as :class:`ArrayWSIReader`, plus ``fractional``: ``False`` (the default) down-samples by an integer factor only,
-    ``True`` by any ratio >= 1 (:func:`resolution_scale`).  Without a resolution every read is the ``ArrayWSIReader`` read."""
+    ``True`` by any ratio >= 1 (:func:`resolution_scale`); and ``upsample``: ``True`` also reads above the baseline
+    resolution, by any ratio in ``[1/64, 1)`` (``cv2.INTER_CUBIC``), ``False`` (the default) refuses it.  The two flags are
+    independent.  Without a resolution every read is the ``ArrayWSIReader`` read."""
 
     fractional = False
+    upsample = False
 
     def __init__(self, img, mpp: float | None = 0.25, power: float | None = 40.0, mode: str = "rgb", *,
-                 fractional: bool = False) -> None:
+                 fractional: bool = False, upsample: bool = False) -> None:
         super().__init__(img, mpp=mpp, power=power, mode=mode)
         self.fractional = bool(fractional)
+        self.upsample = bool(upsample)
 
     def factor(self, resolution: float, units: str) -> int:
         return resolution_factor(resolution, units, mpp=self.mpp, power=self.power)
 
     def scale(self, resolution: float, units: str) -> float:
         """Baseline pixels per pixel at ``(resolution, units)``: :func:`resolution_scale` for a fractional reader, else the
-        integer :meth:`factor`."""
+        integer :meth:`factor`.  An up-sampling reader returns a ratio ``s`` in ``[1/64, 1)`` where the others refuse to
+        up-sample."""
+        if self.upsample:
+            ratio = _resolution_ratio(resolution, units, self.mpp, self.power)
+            if ratio < 1.0 and not _close(ratio, 1.0):
+                if ratio < 1.0 / _MAX_UPSAMPLE and not _close(ratio, 1.0 / _MAX_UPSAMPLE):
+                    msg = (f"reading at {float(resolution)} {units} up-samples the slide by {1.0 / ratio:.6g}; at most "
+                           f"{_MAX_UPSAMPLE} is supported.")
+                    raise ValueError(msg)
+                return float(ratio)
         if self.fractional:
             return resolution_scale(resolution, units, mpp=self.mpp, power=self.power)
         return self.factor(resolution, units)
 
     def at_resolution(self, resolution: float, units: str) -> ResampledWSIView:
         """The slide as seen at ``(resolution, units)``: a light view (no copy of the slide) whose reads take bounds in its
-        own pixel space."""
-        return ResampledWSIView(self, self.scale(resolution, units))
+        own pixel space.  Logs a warning when the view up-samples the slide."""
+        s = self.scale(resolution, units)
+        if s < 1.0:
+            logger.warning("Read: the desired resolution %s %s is higher than the WSI baseline (maximum) resolution; the "
+                           "slide is up-sampled by %.6g.", resolution, units, 1.0 / s)
+        return ResampledWSIView(self, s)
 
     def read_bounds(self, bounds, resolution: float | None = None, units: str | None = None, coord_space: str = "baseline",
                     pad_constant_values: int = 255) -> np.ndarray:
         """One region ``[x0, y0, x1, y1]`` (the subset of the reference's signature users call).  With ``resolution``:
         ``coord_space="resolution"`` takes the bounds at that resolution; ``"baseline"`` takes baseline bounds, whose extents
-        must be multiples of the factor unless the reader is fractional (then the region is resampled to
-        ``np.round(extent / scale)``).  The output is the padded baseline region area-resampled to the resolution."""
+        must be multiples of the factor unless the reader is fractional or the read up-samples (then the region is resampled
+        to ``np.round(extent / scale)``).  The output is the padded baseline region area-resampled (bicubic when up-sampled)
+        to the resolution."""
         if coord_space not in ("baseline", "resolution"):
             msg = f"Invalid coord_space `{coord_space}`: expected 'baseline' or 'resolution'."
             raise ValueError(msg)
@@ -329,6 +365,9 @@ class VirtualWSIReader(ArrayWSIReader):
         bt = torch.from_numpy(b).to(self.device_image.device)
         if isinstance(k, int) and not (w % k or h % k):
             return _area_read(self, bt, (w // k, h // k), k, pad_constant_values)[0].cpu().numpy()
+        if k < 1:
+            return _cubic_resize_read(self, bt, (w, h), (int(np.round(w / k)), int(np.round(h / k))),
+                                      pad_constant_values)[0].cpu().numpy()
         if not self.fractional:
             msg = f"a {w} x {h} baseline region does not shrink by the integer factor {k}."
             raise ValueError(msg)
@@ -347,8 +386,9 @@ class ResampledWSIView:
     ``output_size = np.round(...)``, which rounds halves to even); ``mpp`` / ``power`` are scaled by ``s``; reads take
     bounds in this view's pixels.  At an integer ``s`` they go through ``tia_gather_area_patches_u8``; otherwise the view
     region ``[x0, y0, x0 + pw, y0 + ph]`` reads the baseline region at ``(np.round(x0 * s), np.round(y0 * s))`` of extent
-    ``(np.round(pw * s), np.round(ph * s))`` and resamples it to ``pw x ph`` (``tia_gather_area_resize_u8``).  The tissue
-    mask comes from the base reader (the reference computes it from baseline)."""
+    ``(np.round(pw * s), np.round(ph * s))`` and resamples it to ``pw x ph`` (``tia_gather_area_resize_u8``; at ``s < 1``,
+    an up-sampling reader's view, ``tia_gather_cubic_resize_u8``).  The tissue mask comes from the base reader (the
+    reference computes it from baseline)."""
 
     def __init__(self, base: VirtualWSIReader, factor: float) -> None:
         self.base = base
@@ -383,8 +423,12 @@ class ResampledWSIView:
             top_left = torch.from_numpy(np.round(b[:, :2] * k).astype(np.int32)).to(self.base.device_image.device)
         pw, ph = int(size[0]), int(size[1])
         extent = (int(np.round(pw * k)), int(np.round(ph * k)))
+        if extent[0] <= 0 or extent[1] <= 0:
+            msg = f"a {pw} x {ph} region is empty at the baseline: its extent rounds to {extent[0]} x {extent[1]} at scale {k:.6g}."
+            raise ValueError(msg)
         bt = torch.cat([top_left, top_left + torch.tensor(extent, dtype=torch.int32, device=top_left.device)], dim=1).contiguous()
-        return _area_resize_read(self.base, bt, extent, (pw, ph), pad_value)
+        read = _cubic_resize_read if k < 1 else _area_resize_read
+        return read(self.base, bt, extent, (pw, ph), pad_value)
 
     def read_bounds(self, bounds, pad_value: int = 255) -> np.ndarray:
         return self.read_bounds_batch(np.asarray(bounds)[None], pad_value)[0].cpu().numpy()

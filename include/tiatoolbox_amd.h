@@ -40,7 +40,8 @@ extern "C" {
  * tia_reinhard_workspace_bytes / tia_lab_moments_u8 (one-launch Reinhard); tia_luminosity_mask_u8 and the float64 form of
  * tia_stain_augment_u8 (now a product of per-patch tables) take 16-byte accesses where the shape allows.
  * Additive, same version: tia_gather_area_patches_u8 (patch reads below the slide's resolution), tia_gather_area_resize_u8
- * (the same at any down-sampling ratio), tia_gather_cubic_resize_u8 (patch reads above the slide's resolution). */
+ * (the same at any down-sampling ratio), tia_gather_cubic_resize_u8 (patch reads above the slide's resolution),
+ * tia_conv3x3_grouped_nhwc_f32 (the grouped 3x3 of ResNeXt). */
 #define TIA_ABI_VERSION 6
 int tia_abi_version(void);
 
@@ -678,6 +679,16 @@ int tia_scale_shift_act_view_nhwc_f32(const float* d_x, int64_t x_image_stride, 
 int tia_grouped_conv_valid_nhwc_f32(const float* d_x, const float* d_w_packed, float* d_y, int64_t y_image_stride,
                                     int64_t y_row_stride, int64_t y_pixel_stride, int64_t n, int64_t h, int64_t w,
                                     int64_t groups, int64_t cin_per_group, int64_t cout_per_group, int64_t k, void* stream);
+
+/* Grouped 3x3 convolution, padding 1, stride 1 or 2, with the bias and ReLU fused: the grouped conv2 of the ResNeXt Bottleneck
+ * (models/architecture/resnet.py: Conv2d(width, width, 3, stride, 1, groups=32)); float32 NHWC, on the vector ALU.
+ *   d_x [n,h,w,groups*cg] dense;  d_w_packed [groups][3][3][cg][cg] (in-group input channel, then output channel: from OIHW
+ *   [groups*cg, cg, 3, 3]);  d_bias [groups*cg] float32 or NULL;  d_y [n,ho,wo,groups*cg], ho = (h - 1) / stride + 1.
+ *   relu != 0: y = max(conv + bias, 0).  cg = channels per group in {4, 8, 16, 32, 64} (other widths -> TIA_ESIZE); 16-byte
+ *   aligned pointers.
+ * Additive, same version (6). */
+int tia_conv3x3_grouped_nhwc_f32(const float* d_x, const float* d_w_packed, const float* d_bias, float* d_y, int64_t n, int64_t h,
+                                 int64_t w, int64_t groups, int64_t channels_per_group, int64_t stride, int32_t relu, void* stream);
 
 /* out[b, Y, X, :] = x[b, Y/2, X/2, :] + y[b, Y, X, :] on NHWC float32: nearest x2 upsampling fused with the decoder's
  * skip-connection add (models/architecture/hovernet.py:447-449, utils.py:202-243).  x [n,h,w,c]; y a (possibly

@@ -83,6 +83,18 @@ PRETRAINED_INFO = {
             "save_resolution": {"units": "mpp", "resolution": 0.50}, "ignore_index": 0}),
     },
 }
+# the rest of the torchvision ResNet family of the kather100k zoo (pretrained_model.yaml): resnet18's ioconfig, 9 classes
+for _backbone in ("resnet101", "resnext50_32x4d", "resnext101_32x8d", "wide_resnet50_2", "wide_resnet101_2"):
+    PRETRAINED_INFO[f"{_backbone}-kather100k"] = {
+        "architecture": ("vanilla.CNNModel", {"backbone": _backbone, "num_classes": 9}),
+        "ioconfig": (IOPatchPredictorConfig, {
+            "patch_input_shape": [224, 224], "stride_shape": [224, 224],
+            "input_resolutions": [{"resolution": 0.5, "units": "mpp"}]}),
+        "dataset": "kather100k",
+    }
+# bare torchvision backbone names: feature extractors (CNNBackbone) without an ioconfig
+_BACKBONES = ("resnet18", "resnet34", "resnet50", "resnet101", "resnext50_32x4d", "resnext101_32x8d", "wide_resnet50_2",
+              "wide_resnet101_2")
 
 
 def local_pretrained_weights(model_name: str) -> Path | None:
@@ -117,7 +129,7 @@ def get_pretrained_model(pretrained_model: str | None = None, pretrained_weights
     if not isinstance(pretrained_model, str):
         msg = "pretrained_model must be a string."
         raise TypeError(msg)
-    if pretrained_model in ("resnet18", "resnet34", "resnet50", "resnet101"):
+    if pretrained_model in _BACKBONES:
         # a bare torchvision backbone name -> feature extractor without ioconfig (ref. :133-134); seeded weights here
         from tiatoolbox_amd.models.architecture.vanilla import CNNBackbone
 

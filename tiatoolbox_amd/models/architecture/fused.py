@@ -326,6 +326,46 @@ def hip_grouped_conv_valid(x: torch.Tensor, w_packed: torch.Tensor, *, groups: i
     return out
 
 
+def pack_grouped_conv_weights(conv: nn.Conv2d) -> torch.Tensor:
+    """Grouped OIHW 3x3 ``[groups * cg, cg, 3, 3]`` -> ``[groups, 3, 3, cg (input), cg (output)]`` float32, the layout of
+    ``tia_conv3x3_grouped_nhwc_f32`` (a group's weights of one tap and input channel are contiguous over its outputs)."""
+    w = conv.weight.detach().to(torch.float32)
+    cout, cg, kh, kw = w.shape
+    groups = conv.groups
+    if (kh, kw) != (3, 3) or cout != groups * cg or conv.in_channels != cout or cg not in (4, 8, 16, 32, 64):  # noqa: PLR2004
+        msg = f"the grouped 3x3 kernel takes cin == cout, 4 to 64 channels per group; got weight {tuple(w.shape)}, groups {groups}."
+        raise ValueError(msg)
+    return w.reshape(groups, cg, cg, 3, 3).permute(0, 3, 4, 2, 1).contiguous()
+
+
+def hip_conv3x3_grouped(x: torch.Tensor, w_packed: torch.Tensor, bias: torch.Tensor | None, *, stride: int,
+                        relu: bool) -> torch.Tensor:
+    """``relu(conv3x3(x, w, groups, stride, padding=1) + bias)`` on a float32 channels-last CUDA tensor
+    (``tia_conv3x3_grouped_nhwc_f32``, the ResNeXt conv2); ``w_packed`` from :func:`pack_grouped_conv_weights`."""
+    from tiatoolbox_amd import _lib
+
+    if not (_nhwc_ptr_ok(x) and x.dtype == torch.float32):
+        msg = "hip_conv3x3_grouped expects a float32 channels-last CUDA tensor."
+        raise ValueError(msg)
+    n, c, h, w = x.shape
+    groups, cg = w_packed.shape[0], w_packed.shape[-1]
+    if (tuple(w_packed.shape) != (groups, 3, 3, cg, cg) or groups * cg != c or w_packed.dtype != torch.float32
+            or not w_packed.is_contiguous() or w_packed.device != x.device):
+        msg = (f"hip_conv3x3_grouped: packed weights {tuple(w_packed.shape)} {w_packed.dtype} on {w_packed.device} do not match an "
+               f"input with {c} channels on {x.device} (expected pack_grouped_conv_weights' [groups, 3, 3, cg, cg] float32).")
+        raise ValueError(msg)
+    if bias is not None and not (bias.is_cuda and bias.dtype == torch.float32 and bias.numel() == c and bias.is_contiguous()):
+        msg = "hip_conv3x3_grouped takes a contiguous float32 CUDA bias of one value per channel."
+        raise ValueError(msg)
+    y = torch.empty((n, c, (h - 1) // stride + 1, (w - 1) // stride + 1), dtype=torch.float32, device=x.device,
+                    memory_format=torch.channels_last)
+    with torch.cuda.device(x.device):
+        rc = _lib.load().tia_conv3x3_grouped_nhwc_f32(x.data_ptr(), w_packed.data_ptr(), bias.data_ptr() if bias is not None else 0,
+                                                      y.data_ptr(), n, h, w, groups, cg, stride, int(relu), _lib.current_stream())
+    _lib.check(rc, "tia_conv3x3_grouped_nhwc_f32")
+    return y
+
+
 def hip_upsample2x_add(x: torch.Tensor, y: torch.Tensor, scale: torch.Tensor | None = None,
                        shift: torch.Tensor | None = None) -> torch.Tensor:
     """``x.repeat_interleave(2, 2).repeat_interleave(2, 3) + y`` in one pass (``tia_upsample2x_add_act_nhwc_f32``); ``y`` may be
@@ -519,7 +559,13 @@ class _MfmaBlock(nn.Module):
         conv = getattr(self, name)
         cached = self._packed.get((name, dtype))
         if cached is None or cached.device != conv.weight.device:
-            cached = pack_conv_weights(conv) if dtype == torch.float32 else pack_conv_weights_h(conv, dtype)
+            if conv.groups != 1 and dtype != torch.float32:
+                msg = f"grouped convolutions run in float32 only (tia_conv3x3_grouped_nhwc_f32); got {dtype}."
+                raise ValueError(msg)
+            if conv.groups != 1:
+                cached = pack_grouped_conv_weights(conv)
+            else:
+                cached = pack_conv_weights(conv) if dtype == torch.float32 else pack_conv_weights_h(conv, dtype)
             self._packed[(name, dtype)] = cached
         return cached
 
@@ -551,6 +597,14 @@ class _MfmaBlock(nn.Module):
     def _conv(self, name: str, x: torch.Tensor, residual: torch.Tensor | None, *, relu: bool) -> torch.Tensor:
         conv = getattr(self, name)
         k, st, pad = conv.kernel_size[0], conv.stride[0], conv.padding[0]
+        if conv.groups != 1:  # ResNeXt's grouped 3x3 (float32 only: _w refuses half); conv_algo does not apply
+            if x.dtype != torch.float32:
+                msg = f"grouped convolutions run in float32 only (tia_conv3x3_grouped_nhwc_f32); got {x.dtype}."
+                raise ValueError(msg)
+            if residual is not None or k != 3 or pad != 1:  # noqa: PLR2004
+                msg = "the grouped kernel is a 3x3 / padding 1 convolution without residual."
+                raise ValueError(msg)
+            return hip_conv3x3_grouped(x, self._w(name, x.dtype), self._b(name), stride=st, relu=relu)
         if x.dtype == torch.float32:
             u = self._wino(name, x)
             if u is not None:
@@ -575,7 +629,8 @@ class _MfmaBasic(_MfmaBlock):
 
 
 class _MfmaBottleneck(_MfmaBlock):
-    """Bottleneck as (downsample) / 1x1+bias+ReLU / 3x3+bias+ReLU / 1x1+bias+residual+ReLU launches."""
+    """Bottleneck as (downsample) / 1x1+bias+ReLU / 3x3+bias+ReLU / 1x1+bias+residual+ReLU launches; a grouped 3x3 (ResNeXt)
+    runs on ``tia_conv3x3_grouped_nhwc_f32``."""
 
     def __init__(self, blk: Bottleneck) -> None:
         super().__init__()
@@ -674,8 +729,9 @@ def hip_stem_conv_pool(x: torch.Tensor, w_packed: torch.Tensor, bias: torch.Tens
 
 class MfmaResNet(nn.Module):
     """ResNet trunk on hand-written kernels only: the stem (7x7 / 3 input channels + bias + ReLU + max-pool, one float32 MFMA
-    kernel reading uint8 or float32 patches) and every block convolution (BasicBlock: resnet18/34; Bottleneck: resnet50/101) as
-    an MFMA implicit GEMM with its epilogue fused (BN folded, channels-last) -- ``tia_conv2d_nhwc_f32`` for float32 (the
+    kernel reading uint8 or float32 patches) and every block convolution (BasicBlock: resnet18/34; Bottleneck: resnet50/101,
+    wide_resnet50_2/101_2, resnext50_32x4d/101_32x8d) as an MFMA implicit GEMM with its epilogue fused (BN folded, channels-last;
+    the grouped 3x3 of ResNeXt: ``tia_conv3x3_grouped_nhwc_f32``, float32 only) -- ``tia_conv2d_nhwc_f32`` for float32 (the
     reference's arithmetic), ``tia_conv2d_nhwc_h`` once the module has been cast to fp16 / bf16 (float32 accumulation; the stem
     is then ``tia_stem_conv7x7_pool_nhwc_h``: half inputs and weights on the half matrix cores, one rounding of the result).  A ``uint8`` input means ``ToTensor`` has been deferred into the stem: the
     kernel divides by 255 while it loads."""

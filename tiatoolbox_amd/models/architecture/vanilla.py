@@ -6,14 +6,15 @@ import numpy as np
 import torch
 from torch import nn
 
-from tiatoolbox_amd.models.architecture.resnet import resnet_trunk
+from tiatoolbox_amd.models.architecture.resnet import _CFG, resnet_trunk
 from tiatoolbox_amd.models.architecture.utils import argmax_last_axis
 from tiatoolbox_amd.models.models_abc import ModelABC
 
 
 def _get_architecture(arch_name: str, **_: dict) -> nn.Sequential:
-    """Backbone without the final pooling / FC (ref. :112-164); ResNet family only."""
-    if "resnet" not in arch_name:
+    """Backbone without the final pooling / FC (ref. :112-164); the torchvision ResNet family only (ResNet, ResNeXt,
+    Wide-ResNet)."""
+    if arch_name not in _CFG:
         msg = f"Backbone `{arch_name}` is not supported."
         raise ValueError(msg)
     return resnet_trunk(arch_name)

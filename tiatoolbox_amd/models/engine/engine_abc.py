@@ -431,6 +431,12 @@ class EngineABC:
                 # tia_conv2d_nhwc_h); every other trunk, and the CPU: BatchNorm folding only
                 resnet = any(isinstance(mod, (BasicBlock, Bottleneck)) for mod in m.modules())
                 use_mfma = on_gpu and resnet
+                grouped = any(isinstance(mod, torch.nn.Conv2d) and mod.groups != 1 for mod in m.modules())
+                if use_mfma and grouped and dtype != torch.float32:
+                    # the grouped 3x3 of ResNeXt has a float32 kernel only: fp16 / bf16 runs the BN-folded torch module
+                    logger.warning("%s: no %s kernel for grouped convolutions (ResNeXt); running the BatchNorm-folded torch "
+                                   "module in %s instead of the hand-written trunk.", type(self.model).__name__, dtype, dtype)
+                    use_mfma = False
                 m = fuse_cnn_model(m, epilogue_fusion="mfma" if use_mfma else False)
             elif on_gpu and dtype == torch.float32:
                 from tiatoolbox_amd.models.architecture.hovernet import HoVerNet

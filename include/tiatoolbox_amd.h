@@ -585,12 +585,20 @@ int tia_conv_pack_weights_wino_f32(const float* d_w_oihw, int64_t cout, int64_t 
 int tia_conv3x3_wino_nhwc_f32(const float* d_x, const float* d_u_packed, const float* d_bias, const float* d_residual, float* d_y,
                               int64_t n, int64_t h, int64_t w, int64_t cin, int64_t cout, int64_t pad_top, int64_t pad_left,
                               int64_t ho, int64_t wo, int32_t relu, void* stream);
+/* Which block geometry tia_conv3x3_wino_nhwc_f32 uses for ONE launch over n images of [ho, wo] outputs (host only, no launch;
+ * diagnostics for tests, like tia_conv3x3_geometry): 0 blocks of 16 x 16 outputs, 1 four images of at most 8 x 8 per block,
+ * 2 windows of wty x wtx tiles of 2 x 2 outputs, wg windows per block, blocks running across images (chosen by the MFMA rows
+ * kept busy over the whole batch, so it depends on n).  geom (may be NULL) = wg, wty, wtx, windows per image (zeros unless 2).
+ * TIA_EINVAL for non-positive arguments.  Additive, same version (6). */
+int tia_conv3x3_wino_geometry(int64_t n, int64_t ho, int64_t wo, int32_t geom[4]);
 
 /* Winograd F(4x2, 3x3) form of the same convolution (conv3x3_wino42.hip): F(4, 3) over rows x F(2, 3) over columns, 24 instead of
  * 36 multiplies per 4 x 2 outputs (3 per output against F(2x2)'s 4), same contract and fused epilogue as tia_conv3x3_wino_nhwc_f32,
  * within the same 1e-5 (relative) of a direct float32 convolution.  cin % 16 == 0, cout % 64 == 0.
  *   tia_conv_pack_weights_wino42_f32: OIHW [cout][cin][3][3] -> U = G4 g G2^T (float64, rounded once), 24 * cin * cout floats
  *   ([pos 24][cin/16][h8 2][cout/64][hi 2][64 cout][4 channels], pos = 4 i + j, i: F(4, 3) row, j: F(2, 3) column).
+ *   A batch beyond 2 GiB of input runs in equal groups like tia_conv2d_nhwc_f32's (ceil(n / k) images for the smallest k that fits),
+ *   rounded up to whole blocks of four images for maps of at most 8 x 8 outputs.
  *   tia_conv3x3_wino_form: host-only route query (no launch) -- which form the fused resnet blocks take for a 3x3 / stride-1
  *   layer of this shape ("same" padding `pad`): 1 F(4x2), 0 F(2x2); TIA_EINVAL / TIA_ESIZE for shapes no Winograd form serves. */
 int tia_conv_pack_weights_wino42_f32(const float* d_w_oihw, int64_t cout, int64_t cin, float* d_packed, void* stream);

@@ -182,6 +182,21 @@ def test_host_only_dispatch_queries():
     kind, (bw, br, pitch, strips) = geometry(40, 56, 40, 56, 1)
     assert kind == 4 and bw * strips == 56  # noqa: PLR2004
 
+    # the Winograd F(2x2) kernel's block geometry for one launch: four-image blocks up to 8 x 8, 16 x 16 blocks where they are >= 90 %
+    # busy, windows where they keep clearly more MFMA rows busy over the batch (a property of the batch: one 14 x 14 image has none)
+    def wino_geometry(n, ho, wo):
+        geom = (ctypes.c_int32 * 4)()
+        return lib.tia_conv3x3_wino_geometry(n, ho, wo, geom), list(geom)
+
+    assert wino_geometry(1024, 8, 8) == (1, [0, 0, 0, 0]) and wino_geometry(3, 8, 3)[0] == 1
+    assert wino_geometry(1024, 64, 64) == (0, [0, 0, 0, 0]) and wino_geometry(1, 32, 16)[0] == 0
+    for hw in (14, 56):
+        kind, (wg, wty, wtx, wins) = wino_geometry(1024, hw, hw)
+        assert kind == 2 and 1 <= wg <= 16 and wg * wty * wtx <= 64  # noqa: PLR2004
+        assert wins == -(-hw // (2 * wty)) * -(-hw // (2 * wtx))
+    assert lib.tia_conv3x3_wino_geometry(1024, 14, 14, None) == 2  # noqa: PLR2004
+    assert wino_geometry(0, 14, 14)[0] == -1 and wino_geometry(4, 0, 14)[0] == -1
+
     from tiatoolbox_amd.tools import _stain_device as dev
 
     for mode, expect in ((_lib.MODE_MACENKO, 1), (_lib.MODE_FIXED, 1), (_lib.MODE_VAHADANE, 0)):

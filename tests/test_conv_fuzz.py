@@ -3,7 +3,8 @@
 of ``tia_conv2d_nhwc_f32`` always runs on the register-staged slice kernel, whose raw output is the same convolution with the same
 float32 accumulation over (tap, 16-channel slice) -- what differs is the channel order inside a slice, i.e. rounding noise.  The band
 geometry's bookkeeping (strip / band / image-boundary arithmetic with host-computed reciprocals) is what this guards; the fixed cases
-against ``torch.nn.functional.conv2d`` on the CPU live in ``tests/test_engine.py``."""
+against ``torch.nn.functional.conv2d`` on the CPU live in ``tests/test_engine.py``; random and rectangular shapes of every convolution
+kernel against an independent float64 reference (and integer data bit for bit) in ``tests/test_conv_reference_sweep.py``."""
 import ctypes
 
 import numpy as np

@@ -114,6 +114,7 @@ _SIGNATURES = {
     "tia_conv2d_route_f32": ([_I64] * 12, C.c_int),
     "tia_conv_pack_weights_wino_f32": ([_P, _I64, _I64, _P, _P], C.c_int),
     "tia_conv3x3_wino_nhwc_f32": ([_P, _P, _P, _P, _P] + [_I64] * 9 + [_I32, _P], C.c_int),
+    "tia_conv3x3_wino_geometry": ([_I64] * 3 + [C.POINTER(C.c_int32)], C.c_int),
     "tia_conv_pack_weights_wino42_f32": ([_P, _I64, _I64, _P, _P], C.c_int),
     "tia_conv3x3_wino42_nhwc_f32": ([_P, _P, _P, _P, _P] + [_I64] * 9 + [_I32, _P], C.c_int),
     "tia_conv3x3_wino_form": ([_I64] * 6, C.c_int),

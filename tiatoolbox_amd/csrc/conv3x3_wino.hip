@@ -799,6 +799,18 @@ extern "C" int tia_conv_pack_weights_wino_f32(const float* d_w_oihw, int64_t cou
     return hipGetLastError() == hipSuccess ? TIA_OK : TIA_ELAUNCH;
 }
 
+extern "C" int tia_conv3x3_wino_geometry(int64_t n, int64_t ho, int64_t wo, int32_t geom[4]) {
+    if (n <= 0 || ho <= 0 || wo <= 0) return TIA_EINVAL;
+    const tia::WinoPlan plan = tia::wino_plan(n, ho, wo);
+    if (geom) {
+        geom[0] = plan.wg;
+        geom[1] = plan.wty;
+        geom[2] = plan.wtx;
+        geom[3] = plan.wins_x * plan.wins_y;
+    }
+    return plan.kind;
+}
+
 extern "C" int tia_conv3x3_wino_nhwc_f32(const float* d_x, const float* d_u_packed, const float* d_bias, const float* d_residual,
                                          float* d_y, int64_t n, int64_t h, int64_t w, int64_t cin, int64_t cout, int64_t pad_top,
                                          int64_t pad_left, int64_t ho, int64_t wo, int32_t relu, void* stream) {

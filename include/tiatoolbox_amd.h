@@ -41,7 +41,8 @@ extern "C" {
  * tia_stain_augment_u8 (now a product of per-patch tables) take 16-byte accesses where the shape allows.
  * Additive, same version: tia_gather_area_patches_u8 (patch reads below the slide's resolution), tia_gather_area_resize_u8
  * (the same at any down-sampling ratio), tia_gather_cubic_resize_u8 (patch reads above the slide's resolution),
- * tia_conv3x3_grouped_nhwc_f32 (the grouped 3x3 of ResNeXt). */
+ * tia_conv3x3_grouped_nhwc_f32 (the grouped 3x3 of ResNeXt), tia_stem_pack_weights_bf16x3 / tia_stem_conv7x7_pool_nhwc_u8x3 (the
+ * uint8 stem on the bf16 matrix cores with exactly split float32 weights). */
 #define TIA_ABI_VERSION 6
 int tia_abi_version(void);
 
@@ -651,6 +652,23 @@ int tia_stem_conv7x7_pool_nhwc_h(const void* d_x, int32_t x_is_u8, const void* d
                                  int32_t dtype, int64_t n, int64_t h, int64_t w, void* stream);
 /* OIHW [64,3,7,7] float32 -> [148,64]: rows (ky, kx, c), one zero row at the end. */
 int tia_stem_pack_weights_f32(const float* d_w_oihw, float* d_packed, void* stream);
+
+/* The uint8 stem on the bf16 matrix cores with EXACTLY SPLIT float32 weights (additive at version 6): float32 in, float32
+ * accumulate -- the arithmetic class of tia_stem_conv7x7_pool_nhwc, another summation order, several times less matrix time.
+ *   - a byte 0..255 is a bf16 number; a float32 weight is the sum of three bf16 numbers, w = hi + mid + lo (hi = bf16(w),
+ *     mid = bf16(w - hi), lo = bf16(w - hi - mid), round to nearest); every product byte * part has at most 16 significant
+ *     bits and is exact in the float32 accumulator of v_mfma_f32_32x32x16_bf16.  S = sum(byte * w) is therefore formed with no
+ *     rounding other than that of the float32 accumulation (order: k-steps of 16 with k = 24 ky + 3 kx + c, planes hi, mid, lo
+ *     within a step, one accumulator);
+ *   - y = maxpool3x3/2(relu(fl(S / 255) + bias)): the quotient correctly rounded, the bias a separate float32 addition.
+ * THE CALLER SPLITS AND CHECKS: d_parts_oihw is [3][64][3][7][7] float32 holding hi, mid, lo; the contract is that every part
+ * is a bf16 number (low 16 bits zero), that hi + mid + lo == w exactly and that every non-zero part is finite and normal.
+ * Weights without such a split (non-finite, next to overflow, |w| < ~1e-33) belong on tia_stem_conv7x7_pool_nhwc.
+ *   d_packed / d_w_packed3: [3][22][64][8] bf16 (the layout of tia_stem_pack_weights_h per plane), 16-byte aligned
+ *   d_x [n,h,w,3] uint8 (any byte alignment)   d_bias [64]   d_y [n,hp,wp,64] float32, 16-byte aligned. */
+int tia_stem_pack_weights_bf16x3(const float* d_parts_oihw, void* d_packed, void* stream);
+int tia_stem_conv7x7_pool_nhwc_u8x3(const uint8_t* d_x, const void* d_w_packed3, const float* d_bias, float* d_y, int64_t n,
+                                    int64_t h, int64_t w, void* stream);
 
 /* Half-precision sibling of tia_conv2d_nhwc_f32 for `compute_dtype="float16"|"bfloat16"` runs of the engines (an extension:
  * the reference computes in float32, vanilla.py:242; results are held to its own 1e-3 tolerance on the probabilities,

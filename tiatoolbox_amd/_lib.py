@@ -125,6 +125,8 @@ _SIGNATURES = {
     "tia_conv2d_nhwc_h": ([_P, _P, _P, _P, _P, _I64, _I64, _I64, _I64, _I64, _I64, _I64, _I64, _I64, _I32, _I32, _P], C.c_int),
     "tia_conv_pack_weights_h": ([_P, _I64, _I64, _I64, _I64, _I32, _P, _P], C.c_int),
     "tia_stem_pack_weights_f32": ([_P, _P, _P], C.c_int),
+    "tia_stem_pack_weights_bf16x3": ([_P, _P, _P], C.c_int),
+    "tia_stem_conv7x7_pool_nhwc_u8x3": ([_P, _P, _P, _P, _I64, _I64, _I64, _P], C.c_int),
     "tia_scale_shift_act_nhwc_f32": ([_P, _P, _P, _P, _I64, _I64, _I32, _P], C.c_int),
     "tia_scale_shift_act_view_nhwc_f32": ([_P, _I64, _I64, _I64, _P, _P, _P, _I64, _I64, _I64, _I64, _I32, _P], C.c_int),
     "tia_grouped_conv_valid_nhwc_f32": ([_P, _P, _P, _I64, _I64, _I64, _I64, _I64, _I64, _I64, _I64, _I64, _I64, _P], C.c_int),

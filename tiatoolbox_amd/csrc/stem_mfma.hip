@@ -23,6 +23,13 @@
 //   * LDS 70 KB -> two workgroups per CU: one converts / pools while the other multiplies
 // Wider images are cut into column strips of <= 128 conv columns (64 / 63 pooled columns), taller ones into row chunks
 // (one extra warm-up iteration per chunk supplies the carried row).
+//
+// Variants of the same kernel: MMA = 1 / 2, the half matrix cores for fp16 / bf16 trunks (inputs and weights rounded to half); MMA = 3,
+// the EXACTLY SPLIT form for uint8 patches and float32 trunks: a byte is a bf16 number, a float32 weight the exact sum
+// of three bf16 numbers (hi + mid + lo, split and checked by the caller), every product byte * part exact in the float32
+// accumulator of v_mfma_f32_32x32x16_bf16 -- S = sum(byte * w) with no rounding but that of the float32 accumulation, 33 MFMAs of 32
+// cycles per tile instead of 74 of 64; conv = fl(S / 255) + bias (quotient correctly rounded, bias a separate addition), ReLU, pool.
+// Its ring holds the bytes as bf16 integers (no table), its V tile one channel tile at a time: 79 KB of LDS, two workgroups per CU.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -50,6 +57,15 @@ constexpr int KH = 176;           // 7 * 24 = 168, padded to whole k-steps of 16
 constexpr int LUT16_OFF_B = REGION * 4;                 // byte offsets in the half variant's LDS
 constexpr int W16_OFF_B = LUT16_OFF_B + 512;
 constexpr int LDS_BYTES_H = W16_OFF_B + KH * COUT * 2;  // 55,808 B
+
+// exactly split variant (MMA = 3, uint8 input, float32 output; header comment): the staged rows hold the BYTES as bf16 integers, the
+// weights are three bf16 planes (hi, mid, lo) in the half variant's layout, of which only the 21 non-zero chunks of 8 k sit in
+// LDS; the V tile holds ONE channel tile at a time (two passes of bias / ReLU / maximum per iteration) so that two workgroups
+// still fit a CU: 16,384 + 3 * 21,504 = 80,896 B, 64 allocation granules of 1,280 B = half of the 160 KB
+constexpr int KCH3 = 21;                                // chunks of 8 k per plane in LDS: k < 168
+constexpr int PLANE16 = (KH / 8) * COUT * 8;            // halves per packed plane in global memory: [22][64][8]
+constexpr int REGION3_B = 128 * 32 * 4;                 // >= WROWS * RS16 * 2 = 14,256 (+ the zeroed reads of the last k-step)
+constexpr int LDS_BYTES_S = REGION3_B + 3 * KCH3 * COUT * 16;
 
 using f32x16 = __attribute__((ext_vector_type(16))) float;
 using h8v = __attribute__((ext_vector_type(8))) _Float16;
@@ -79,6 +95,18 @@ __device__ __forceinline__ void lds_barrier() {
     asm volatile("" ::: "memory");
 }
 
+// Split variant: the accumulator holds S = sum(byte * w); conv = S / 255 CORRECTLY ROUNDED (q = S r with r = fl(1 / 255), then one
+// Newton step on the exact remainder S - 255 q), the bias a separate float32 addition as in the unfused reference.  Contraction is
+// off: fused into the addition of the bias the quotient would not be rounded on its own.
+__device__ __forceinline__ float quot255_plus(float sacc, float bv) {
+#pragma clang fp contract(off)
+    constexpr float r = 1.0f / 255.0f;
+    const float q = sacc * r;
+    const float e = __builtin_fmaf(-255.0f, q, sacc);
+    const float q1 = __builtin_fmaf(e, r, q);
+    return q1 + bv;
+}
+
 // Phase timing (developer builds only: -DTIA_STEM_TIMING=1, build.build(defines=...)): thread 0 of two workgroups prints the mean
 // shader-clock cycles per loop iteration of: request + MFMA loop, barrier, V tile, horizontal maximum + stores, conversion.
 #ifndef TIA_STEM_TIMING
@@ -103,6 +131,10 @@ __global__ __launch_bounds__(NTH, 2) void stem7x7_pool_kernel(const void* __rest
                                                              const float* __restrict__ bias, void* __restrict__ yout, float* __restrict__ yconv, StemDims d) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     constexpr bool HALF = MMA != 0;
+    constexpr bool SPLIT = MMA == 3;
+    static_assert(!SPLIT || U8, "the split variant reads bytes");
+    constexpr int VJ = SPLIT ? 1 : 2;      // channel tiles of 32 in the V tile at a time
+    constexpr int VC = 32 * VJ;            // channels per V-tile pass
     constexpr int UPR = HALF ? 198 : 196;  // 4-element staging units per row
     constexpr int RSE = HALF ? RS16 : RS;  // elements per staged row
     const float* wpk = static_cast<const float*>(wpk_v);
@@ -111,7 +143,7 @@ __global__ __launch_bounds__(NTH, 2) void stem7x7_pool_kernel(const void* __rest
     float* lut = smem + LUT_OFF;
     unsigned short* lut16 = reinterpret_cast<unsigned short*>(reinterpret_cast<unsigned char*>(smem) + LUT16_OFF_B);
     float* Wl = smem + W_OFF;
-    const u32x4* Wh = reinterpret_cast<const u32x4*>(reinterpret_cast<unsigned char*>(smem) + W16_OFF_B);
+    const u32x4* Wh = reinterpret_cast<const u32x4*>(reinterpret_cast<unsigned char*>(smem) + (SPLIT ? REGION3_B : W16_OFF_B));
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int img = blockIdx.x / d.chunks, chunk = blockIdx.x - img * d.chunks;
@@ -131,7 +163,11 @@ __global__ __launch_bounds__(NTH, 2) void stem7x7_pool_kernel(const void* __rest
     constexpr int OOB = (int)0x80000000;
 
     // ---- weights and the /255 table into LDS (once) ----
-    if constexpr (HALF) {
+    if constexpr (SPLIT) {  // no table: a byte is a bf16 number as it stands
+        for (int pl = 0; pl < 3; ++pl)
+            for (int i = tid; i < KCH3 * COUT; i += NTH)
+                const_cast<u32x4*>(Wh)[pl * KCH3 * COUT + i] = static_cast<const u32x4*>(wpk_v)[pl * (PLANE16 / 8) + i];
+    } else if constexpr (HALF) {
         for (int i = tid; i < KH * COUT * 2 / 16; i += NTH) const_cast<u32x4*>(Wh)[i] = static_cast<const u32x4*>(wpk_v)[i];
         lut16[tid] = to_half_bits<MMA>(__fdiv_rn((float)tid, 255.0f));
     } else {
@@ -196,7 +232,9 @@ __global__ __launch_bounds__(NTH, 2) void stem7x7_pool_kernel(const void* __rest
                 const unsigned wbytes = __builtin_amdgcn_alignbyte(ld2[q], ld[q], (shv >> (2 * q)) & 3u) & cmask[q];
 #pragma unroll
                 for (int e = 0; e < 4; ++e) {
-                    if constexpr (HALF) hq[q][e] = lut16[(wbytes >> (8 * e)) & 255u];
+                    // split: the byte as a float32 integer (v_cvt_f32_ubyte) has its 8 significant bits in the upper half word
+                    if constexpr (SPLIT) hq[q][e] = (unsigned short)(__float_as_uint((float)((wbytes >> (8 * e)) & 255u)) >> 16);
+                    else if constexpr (HALF) hq[q][e] = lut16[(wbytes >> (8 * e)) & 255u];
                     else f[q][e] = lut[(wbytes >> (8 * e)) & 255u];
                 }
             }
@@ -271,6 +309,18 @@ __global__ __launch_bounds__(NTH, 2) void stem7x7_pool_kernel(const void* __rest
                     a0 = hh ? u32x4{0u, 0u, 0u, 0u} : a0;
                     a1 = hh ? u32x4{0u, 0u, 0u, 0u} : a1;
                 }
+                if constexpr (SPLIT) {
+                    // the last step's h = 1 half (k >= 168) is not in LDS: it re-reads chunk 20 against the zeroed A
+                    const u32x4* wp = (s == KH / 16 - 1 ? wv - hh * COUT : wv) + 2 * s * COUT;
+#pragma unroll
+                    for (int pl = 0; pl < 3; ++pl) {
+                        const u32x4 c0 = wp[pl * KCH3 * COUT], c1 = wp[pl * KCH3 * COUT + 32];
+                        acc[0][0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(*reinterpret_cast<b8v*>(&a0), *reinterpret_cast<const b8v*>(&c0), acc[0][0], 0, 0, 0);
+                        acc[0][1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(*reinterpret_cast<b8v*>(&a0), *reinterpret_cast<const b8v*>(&c1), acc[0][1], 0, 0, 0);
+                        acc[1][0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(*reinterpret_cast<b8v*>(&a1), *reinterpret_cast<const b8v*>(&c0), acc[1][0], 0, 0, 0);
+                        acc[1][1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(*reinterpret_cast<b8v*>(&a1), *reinterpret_cast<const b8v*>(&c1), acc[1][1], 0, 0, 0);
+                    }
+                } else {
                 const u32x4 b0 = wv[2 * s * COUT], b1 = wv[2 * s * COUT + 32];
                 if constexpr (MMA == 2) {
                     acc[0][0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(*reinterpret_cast<b8v*>(&a0), *reinterpret_cast<const b8v*>(&b0), acc[0][0], 0, 0, 0);
@@ -282,6 +332,7 @@ __global__ __launch_bounds__(NTH, 2) void stem7x7_pool_kernel(const void* __rest
                     acc[0][1] = __builtin_amdgcn_mfma_f32_32x32x16_f16(*reinterpret_cast<h8v*>(&a0), *reinterpret_cast<const h8v*>(&b1), acc[0][1], 0, 0, 0);
                     acc[1][0] = __builtin_amdgcn_mfma_f32_32x32x16_f16(*reinterpret_cast<h8v*>(&a1), *reinterpret_cast<const h8v*>(&b0), acc[1][0], 0, 0, 0);
                     acc[1][1] = __builtin_amdgcn_mfma_f32_32x32x16_f16(*reinterpret_cast<h8v*>(&a1), *reinterpret_cast<const h8v*>(&b1), acc[1][1], 0, 0, 0);
+                }
                 }
             }
         } else {
@@ -305,36 +356,46 @@ __global__ __launch_bounds__(NTH, 2) void stem7x7_pool_kernel(const void* __rest
 
         // ---- bias + ReLU, vertical maximum in registers (C/D layout: channel = lane & 31, pixel = (e&3) + 8 (e>>2) + 4 h) ----
         const bool row0 = 2 * py < d.ho, row1 = 2 * py + 1 < d.ho;
+        auto conv_bias = [](float sacc, float bv) {
+            if constexpr (SPLIT) return quot255_plus(sacc, bv);
+            else return sacc + bv;
+        };
+        // the V tile holds VJ channel tiles at a time: one pass (both tiles), or two passes of one tile each in the split variant
+#pragma unroll
+        for (int jp = 0; jp < 2 / VJ; ++jp) {
+        if (jp > 0) lds_barrier();  // the previous pass's horizontal maximum has read the V tile
         // both conv rows on the map, all 32 columns of the wave on the map, no pre-pool output wanted (wave-uniform, the common
         // case): 5 vector instructions per value instead of ~10 -- this phase competes for VALU issue with the MFMA stream of the
         // CU's other workgroup and ran 2.2 x slower beside it than alone (timing build)
-        if (row0 && row1 && ncols - 32 * wave >= 32 && yconv == nullptr) {
+        if (row0 && row1 && ncols - 32 * wave >= 32 && (SPLIT || yconv == nullptr)) {  // (the split variant has no pre-pool output)
 #pragma unroll
-            for (int j = 0; j < 2; ++j) {
+            for (int jj = 0; jj < VJ; ++jj) {
+                const int j = jp * VJ + jj;
                 const float bv = j == 0 ? bv0 : bv1;
-                float* vdst = ring + (32 * wave + 4 * hh) * COUT + j * 32 + (lane & 31);
+                float* vdst = ring + (32 * wave + 4 * hh) * VC + jj * 32 + (lane & 31);
 #pragma unroll
                 for (int e = 0; e < 16; ++e) {
-                    const float r0 = fmaxf(acc[0][j][e] + bv, 0.0f), r1 = fmaxf(acc[1][j][e] + bv, 0.0f);
-                    vdst[((e & 3) + 8 * (e >> 2)) * COUT] = fmaxf(carry[j][e], fmaxf(r0, r1));
+                    const float r0 = fmaxf(conv_bias(acc[0][j][e], bv), 0.0f), r1 = fmaxf(conv_bias(acc[1][j][e], bv), 0.0f);
+                    vdst[((e & 3) + 8 * (e >> 2)) * VC] = fmaxf(carry[j][e], fmaxf(r0, r1));
                     carry[j][e] = r1;
                 }
             }
         } else {
 #pragma unroll
-        for (int j = 0; j < 2; ++j) {
+        for (int jj = 0; jj < VJ; ++jj) {
+            const int j = jp * VJ + jj;
             const float bv = j == 0 ? bv0 : bv1;
 #pragma unroll
             for (int e = 0; e < 16; ++e) {
                 const int lcol = 32 * wave + (e & 3) + 8 * (e >> 2) + 4 * hh;
                 const bool colok = lcol < ncols;
-                float r0 = acc[0][j][e] + bv, r1 = acc[1][j][e] + bv;
+                float r0 = conv_bias(acc[0][j][e], bv), r1 = conv_bias(acc[1][j][e], bv);
                 r0 = (row0 && colok && r0 > 0.0f) ? r0 : 0.0f;
                 r1 = (row1 && colok && r1 > 0.0f) ? r1 : 0.0f;
                 const float v = fmaxf(carry[j][e], fmaxf(r0, r1));
                 carry[j][e] = r1;
-                ring[lcol * COUT + j * 32 + (lane & 31)] = v;
-                if (yconv != nullptr && py >= q0 && colok) {  // the pre-pool activation too (UNet's first skip connection)
+                ring[lcol * VC + jj * 32 + (lane & 31)] = v;
+                if (!SPLIT && yconv != nullptr && py >= q0 && colok) {  // the pre-pool activation too (UNet's first skip connection)
                     float* o = yconv + (((long)img * d.ho + 2 * py) * d.wo + c_start + lcol) * COUT + j * 32 + (lane & 31);
                     if (row0) o[0] = r0;
                     if (row1) o[(long)d.wo * COUT] = r1;
@@ -345,24 +406,25 @@ __global__ __launch_bounds__(NTH, 2) void stem7x7_pool_kernel(const void* __rest
         lds_barrier();
         SSTAMP(2)
 
-        // ---- horizontal maximum of three columns, one pooled row (<= 64 x 64 floats) written as float4 ----
+        // ---- horizontal maximum of three columns, one pooled row (<= 64 x VC floats) written as float4 ----
         if (py >= q0) {
-            const int c4 = tid & 15;
+            constexpr int C4 = VC / 4, PPP = NTH / C4;  // float4 per pixel, pixels per pass
+            const int c4 = tid & (C4 - 1);
 #pragma unroll
-            for (int pass = 0; pass < 4; ++pass) {
-                const int px = p0 + pass * 16 + (tid >> 4);
+            for (int pass = 0; pass < 64 / PPP; ++pass) {
+                const int px = p0 + pass * PPP + tid / C4;
                 if (px < p1) {
                     const int lcm = 2 * px - c_start;
                     const float4* vrow = reinterpret_cast<const float4*>(ring) + c4;
-                    float4 m = vrow[lcm * (COUT / 4)];
-                    const float4 r = vrow[(lcm + 1) * (COUT / 4)];  // lcm + 1 <= 127: zeros where the column does not exist
+                    float4 m = vrow[lcm * C4];
+                    const float4 r = vrow[(lcm + 1) * C4];  // lcm + 1 <= 127: zeros where the column does not exist
                     m.x = fmaxf(m.x, r.x), m.y = fmaxf(m.y, r.y), m.z = fmaxf(m.z, r.z), m.w = fmaxf(m.w, r.w);
                     if (lcm > 0) {
-                        const float4 l = vrow[(lcm - 1) * (COUT / 4)];
+                        const float4 l = vrow[(lcm - 1) * C4];
                         m.x = fmaxf(m.x, l.x), m.y = fmaxf(m.y, l.y), m.z = fmaxf(m.z, l.z), m.w = fmaxf(m.w, l.w);
                     }
-                    const long o = (((long)img * d.hp + py) * d.wp + px) * COUT + 4 * c4;
-                    if (d.out_dtype == TIA_DT_F32) {
+                    const long o = (((long)img * d.hp + py) * d.wp + px) * COUT + jp * VC + 4 * c4;
+                    if (SPLIT || d.out_dtype == TIA_DT_F32) {
                         *reinterpret_cast<float4*>(static_cast<float*>(yout) + o) = m;
                     } else {  // one rounding to half (round to nearest even) for the fp16 / bf16 trunk
                         unsigned short hv[4];
@@ -383,6 +445,7 @@ __global__ __launch_bounds__(NTH, 2) void stem7x7_pool_kernel(const void* __rest
                     }
                 }
             }
+        }
         }
         lds_barrier();
         SSTAMP(3)
@@ -446,6 +509,19 @@ extern "C" int tia_stem_pack_weights_h(const float* d_w_oihw, int32_t dtype, voi
     return hipGetLastError() == hipSuccess ? TIA_OK : TIA_ELAUNCH;
 }
 
+// Three bf16 planes (hi, mid, lo with hi + mid + lo == w exactly; split and checked by the caller: the header's contract), each in
+// the half variant's layout: [3][22][64][8].  The conversion below is exact for values that are bf16 numbers already.
+extern "C" int tia_stem_pack_weights_bf16x3(const float* d_parts_oihw, void* d_packed, void* stream) {
+    if (!d_parts_oihw || !d_packed) return TIA_EINVAL;
+    const dim3 grid((KH * COUT + 255) / 256);
+    for (int pl = 0; pl < 3; ++pl)
+        hipLaunchKernelGGL(stem_pack_h_kernel<2>, grid, dim3(256), 0, (hipStream_t)stream, d_parts_oihw + pl * (COUT * 147),
+                           (unsigned short*)d_packed + pl * PLANE16);
+    return hipGetLastError() == hipSuccess ? TIA_OK : TIA_ELAUNCH;
+}
+
+constexpr int32_t STEM_MMA_SPLIT = -3;  // stem_impl's `mma` for the exactly split variant (not a TIA_DT_* value)
+
 // mma: 0 = float32 matrix cores (weights [148][64] float32), TIA_DT_F16 / TIA_DT_BF16 = half matrix cores (weights packed by
 // tia_stem_pack_weights_h; the output type is then that half type)
 static int stem_impl(const void* d_x, int32_t x_is_u8, const void* d_w_packed, const float* d_bias, void* d_y, int32_t y_dtype,
@@ -464,21 +540,25 @@ static int stem_impl(const void* d_x, int32_t x_is_u8, const void* d_w_packed, c
     group = tia::even_group(n, group);
     const long strips = wp <= 64 ? 1 : 1 + (wp - 64 + 62) / 63;
     using Kernel = void (*)(const void*, const void*, const float*, void*, float*, StemDims);
-    const Kernel kernels[3][2] = {{stem7x7_pool_kernel<false, 0>, stem7x7_pool_kernel<true, 0>},
+    const Kernel kernels[4][2] = {{stem7x7_pool_kernel<false, 0>, stem7x7_pool_kernel<true, 0>},
                                   {stem7x7_pool_kernel<false, 1>, stem7x7_pool_kernel<true, 1>},
-                                  {stem7x7_pool_kernel<false, 2>, stem7x7_pool_kernel<true, 2>}};
+                                  {stem7x7_pool_kernel<false, 2>, stem7x7_pool_kernel<true, 2>},
+                                  {nullptr, stem7x7_pool_kernel<true, 3>}};  // split: uint8 input only
+    const int lds_bytes[4] = {(int)(LDS_FLOATS * sizeof(float)), LDS_BYTES_H, LDS_BYTES_H, LDS_BYTES_S};
     static tia::DeviceOnce attr_once;  // the dynamic-LDS attribute is per device
     if (!attr_once.ensure([&] {
-            for (int m = 0; m < 3; ++m)
+            for (int m = 0; m < 4; ++m)
                 for (int u = 0; u < 2; ++u)
-                    if (hipFuncSetAttribute(reinterpret_cast<const void*>(kernels[m][u]), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                            m == 0 ? (int)(LDS_FLOATS * sizeof(float)) : LDS_BYTES_H) != hipSuccess)
+                    if (kernels[m][u] != nullptr &&
+                        hipFuncSetAttribute(reinterpret_cast<const void*>(kernels[m][u]), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                            lds_bytes[m]) != hipSuccess)
                         return false;
             return true;
         }))
         return TIA_ELAUNCH;
-    const int mi = mma == TIA_DT_F16 ? 1 : (mma == TIA_DT_BF16 ? 2 : 0);
-    const size_t lds = mi == 0 ? (size_t)LDS_FLOATS * sizeof(float) : (size_t)LDS_BYTES_H;
+    const int mi = mma == TIA_DT_F16 ? 1 : (mma == TIA_DT_BF16 ? 2 : (mma == STEM_MMA_SPLIT ? 3 : 0));
+    if (kernels[mi][x_is_u8 ? 1 : 0] == nullptr) return TIA_EINVAL;
+    const size_t lds = (size_t)lds_bytes[mi];
     hipStream_t st = (hipStream_t)stream;
     for (long first = 0; first < n; first += group) {
         const long nb = n - first < group ? n - first : group;
@@ -512,4 +592,9 @@ extern "C" int tia_stem_conv7x7_pool_nhwc_h(const void* d_x, int32_t x_is_u8, co
                                             int32_t dtype, int64_t n, int64_t h, int64_t w, void* stream) {
     if (dtype != TIA_DT_F16 && dtype != TIA_DT_BF16) return TIA_EINVAL;
     return stem_impl(d_x, x_is_u8, d_w_packed_h, d_bias, d_y, dtype, nullptr, n, h, w, dtype, stream);
+}
+
+extern "C" int tia_stem_conv7x7_pool_nhwc_u8x3(const uint8_t* d_x, const void* d_w_packed3, const float* d_bias, float* d_y, int64_t n,
+                                               int64_t h, int64_t w, void* stream) {
+    return stem_impl(d_x, 1, d_w_packed3, d_bias, d_y, TIA_DT_F32, nullptr, n, h, w, STEM_MMA_SPLIT, stream);
 }

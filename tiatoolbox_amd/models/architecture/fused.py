@@ -6,6 +6,8 @@
   patches -> conv7x7 + bias + ReLU + max-pool, one kernel) and every block convolution (``csrc/conv_mfma.hip``: implicit GEMM
   on the matrix cores with bias / residual / ReLU in the epilogue).
   In fp16 / bf16 the same module runs on ``tia_stem_conv7x7_pool_nhwc_h`` / ``tia_conv2d_nhwc_h`` (no library convolution).
+  A float32 trunk in ``"winograd"`` mode given uint8 patches runs the stem on the bf16 matrix cores with exactly split weights
+  (``split_stem_weights`` / ``tia_stem_conv7x7_pool_nhwc_u8x3``: float32 in, float32 accumulate).
 
 State-dict compatibility is untouched: these are derived copies built from a loaded ``CNNModel`` (reference parameter
 names), never the object that loads weights.  Every wrapper raises on tensors it cannot take (host tensors, wrong layout):
@@ -22,6 +24,7 @@ import torch.nn.functional as F  # noqa: N812
 from torch import nn
 from torch.nn.utils.fusion import fuse_conv_bn_eval
 
+from tiatoolbox_amd import logger
 from tiatoolbox_amd.models.architecture.resnet import BasicBlock, Bottleneck
 
 
@@ -727,6 +730,71 @@ def hip_stem_conv_pool(x: torch.Tensor, w_packed: torch.Tensor, bias: torch.Tens
     return (y, conv) if return_conv else y
 
 
+def split_stem_weights(weight: torch.Tensor) -> tuple[torch.Tensor, bool]:
+    """Float32 weights as the sum of three bf16 numbers: ``parts[0] = bf16(w)``, ``parts[1] = bf16(w - parts[0])``,
+    ``parts[2] = bf16(w - parts[0] - parts[1])`` (round to nearest even; the subtractions are exact in float32), returned as a
+    float32 tensor ``[3, *w.shape]`` whose values are bf16 numbers, and whether the split is USABLE by the bf16 matrix cores:
+    ``parts.sum(0) == w`` exactly (compared in float64) and every non-zero part a finite, normal bf16 number.  Not usable:
+    non-finite weights, weights next to overflow (``bf16(w)`` rounds to infinity), weights so small that a part falls below
+    the normal range (``|w| < ~1e-33``, subnormals).  Device-agnostic: a few element-wise torch operations."""
+    w = weight.detach().to(torch.float32)
+    hi = w.to(torch.bfloat16).to(torch.float32)
+    r1 = w - hi
+    mid = r1.to(torch.bfloat16).to(torch.float32)
+    lo = (r1 - mid).to(torch.bfloat16).to(torch.float32)
+    parts = torch.stack((hi, mid, lo))
+    tiny = torch.finfo(torch.bfloat16).tiny  # 2^-126, the smallest normal bf16 (= float32) number
+    normal = (parts == 0) | (torch.isfinite(parts) & (parts.abs() >= tiny))
+    exact = parts.to(torch.float64).sum(0) == w.to(torch.float64)  # NaN compares unequal
+    return parts, bool(normal.all()) and bool(exact.all())
+
+
+def pack_stem_weights_split(conv) -> torch.Tensor | None:
+    """OIHW float32 ``[64, 3, 7, 7]`` -> ``[3, 22, 64, 8]`` bf16: the planes ``hi``, ``mid``, ``lo`` of
+    :func:`split_stem_weights`, each in the half stem's layout (``tia_stem_pack_weights_bf16x3``).  ``None`` when the weights
+    have no usable exact split: the caller then keeps the float32 stem."""
+    from tiatoolbox_amd import _lib
+
+    weight = conv.weight if isinstance(conv, nn.Module) else conv
+    w = weight.detach().to(torch.float32).contiguous()
+    geometry_ok = not isinstance(conv, nn.Conv2d) or (conv.stride == (2, 2) and conv.padding == (3, 3))
+    if tuple(w.shape) != (64, 3, 7, 7) or not geometry_ok or not w.is_cuda:
+        msg = f"the stem kernel is conv7x7 / stride 2 / pad 3, 3 -> 64 channels on a CUDA device; got weight {tuple(w.shape)} on {w.device}."
+        raise ValueError(msg)
+    parts, usable = split_stem_weights(w)
+    if not usable:
+        return None
+    parts = parts.contiguous()
+    out = torch.empty((3, 22, 64, 8), dtype=torch.bfloat16, device=w.device)
+    with torch.cuda.device(w.device):
+        rc = _lib.load().tia_stem_pack_weights_bf16x3(parts.data_ptr(), out.data_ptr(), _lib.current_stream())
+    _lib.check(rc, "tia_stem_pack_weights_bf16x3")
+    return out
+
+
+def hip_stem_conv_pool_split(x: torch.Tensor, w_packed3: torch.Tensor, bias: torch.Tensor) -> torch.Tensor:
+    """``maxpool3x3/2(relu(conv7x7/2(x / 255) + bias))`` of a uint8 NHWC batch on the bf16 matrix cores with exactly split
+    float32 weights (``tia_stem_conv7x7_pool_nhwc_u8x3``): bytes and weight parts are bf16 numbers, their products exact, the
+    accumulation float32; ``conv = fl(sum / 255) + bias``.  Float32 arithmetic in another summation order than
+    :func:`hip_stem_conv_pool`.  Returns ``[n, 64, hp, wp]`` float32, channels-last."""
+    from tiatoolbox_amd import _lib
+
+    if not (x.is_cuda and x.dim() == 4 and x.shape[-1] == 3 and x.is_contiguous() and x.dtype == torch.uint8):  # noqa: PLR2004
+        msg = f"hip_stem_conv_pool_split expects a contiguous NHWC uint8 CUDA batch with 3 channels, got {tuple(x.shape)} {x.dtype}."
+        raise ValueError(msg)
+    if w_packed3.dtype != torch.bfloat16 or tuple(w_packed3.shape) != (3, 22, 64, 8) or not w_packed3.is_contiguous():
+        msg = "hip_stem_conv_pool_split expects weights packed by pack_stem_weights_split."
+        raise ValueError(msg)
+    n, h, w, _ = x.shape
+    hp, wp = ((h - 1) // 2) // 2 + 1, ((w - 1) // 2) // 2 + 1
+    y = torch.empty((n, 64, hp, wp), dtype=torch.float32, device=x.device, memory_format=torch.channels_last)
+    with torch.cuda.device(x.device):
+        rc = _lib.load().tia_stem_conv7x7_pool_nhwc_u8x3(x.data_ptr(), w_packed3.data_ptr(), bias.data_ptr(), y.data_ptr(), n, h, w,
+                                                         _lib.current_stream())
+    _lib.check(rc, "tia_stem_conv7x7_pool_nhwc_u8x3")
+    return y
+
+
 class MfmaResNet(nn.Module):
     """ResNet trunk on hand-written kernels only: the stem (7x7 / 3 input channels + bias + ReLU + max-pool, one float32 MFMA
     kernel reading uint8 or float32 patches) and every block convolution (BasicBlock: resnet18/34; Bottleneck: resnet50/101,
@@ -734,7 +802,10 @@ class MfmaResNet(nn.Module):
     the grouped 3x3 of ResNeXt: ``tia_conv3x3_grouped_nhwc_f32``, float32 only) -- ``tia_conv2d_nhwc_f32`` for float32 (the
     reference's arithmetic), ``tia_conv2d_nhwc_h`` once the module has been cast to fp16 / bf16 (float32 accumulation; the stem
     is then ``tia_stem_conv7x7_pool_nhwc_h``: half inputs and weights on the half matrix cores, one rounding of the result).  A ``uint8`` input means ``ToTensor`` has been deferred into the stem: the
-    kernel divides by 255 while it loads."""
+    kernel divides by 255 while it loads.  In ``"winograd"`` mode (``set_conv_algo``; the engines' ``conv_algo="auto"``) a float32
+    trunk runs the stem of a uint8 batch on the bf16 matrix cores with exactly split weights (:func:`hip_stem_conv_pool_split`:
+    float32 arithmetic, another summation order); ``"direct"``, float32 input, half trunks and weights without an exact split
+    (one ``info`` line) keep the kernels above."""
 
     accepts_uint8 = True
 
@@ -744,6 +815,8 @@ class MfmaResNet(nn.Module):
         self.stem = folded[0]
         self._stem_packed: torch.Tensor | None = None
         self._stem_packed_dtype: torch.dtype | None = None
+        self._stem_split: torch.Tensor | None = None  # [3, 22, 64, 8] bf16 planes; None: not packed, or no exact split
+        self.conv_algo = "direct"
         blocks = []
         for layer in list(folded)[4:]:
             for blk in layer:
@@ -766,6 +839,8 @@ class MfmaResNet(nn.Module):
             self.prepare_stem(dtype)
             w = self._stem_packed
         if dtype == torch.float32:
+            if self.conv_algo == "winograd" and x.dtype == torch.uint8 and self._stem_split is not None:
+                return hip_stem_conv_pool_split(x, self._stem_split, self._stem_bias)
             return hip_stem_conv_pool(x, w, self._stem_bias)
         return hip_stem_conv_pool_h(x, w, self._stem_bias, dtype=dtype)  # half matrix cores, float32 accumulate
 
@@ -781,6 +856,7 @@ class MfmaResNet(nn.Module):
         if algo not in ("direct", "winograd"):
             msg = f"conv_algo must be 'direct' or 'winograd', got {algo!r}."
             raise ValueError(msg)
+        self.conv_algo = algo  # the stem of a uint8 batch: "winograd" = exactly split weights on the bf16 matrix cores
         for blk in self.blocks:
             blk.conv_algo = algo
 
@@ -796,6 +872,12 @@ class MfmaResNet(nn.Module):
         self._stem_packed = pack_stem_weights(weight) if dtype == torch.float32 else pack_stem_weights_h(weight, dtype)
         self._stem_packed_dtype = dtype
         self._stem_bias = self.stem.bias.detach().float().clone().contiguous()
+        self._stem_split = None
+        if dtype == torch.float32:  # both packings side by side (38 KB + 68 KB): set_conv_algo switches without repacking
+            self._stem_split = pack_stem_weights_split(weight)
+            if self._stem_split is None:
+                logger.info("MfmaResNet: the stem weights have no exact three-part bf16 split (non-finite or extreme "
+                            "exponents); uint8 batches keep the float32 stem kernel.")
 
 
 def fuse_cnn_model(model: nn.Module, *, epilogue_fusion: bool | str = False) -> nn.Module:

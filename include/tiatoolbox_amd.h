@@ -458,7 +458,8 @@ int tia_lut_apply_u8(const uint8_t* d_img, int64_t n, int64_t len, const uint8_t
 int tia_box_downsample_u8(const uint8_t* d_src, int64_t h, int64_t w, int64_t c, int64_t factor, uint8_t* d_out, void* stream);
 
 /* =======================================================================================
- * CNN epilogues (NHWC activations).  The convolutions themselves run in MIOpen; with BatchNorm
+ * CNN epilogues (NHWC activations).  The convolutions themselves run on the MFMA kernels below, which
+ * fuse this epilogue; these stand-alone passes serve a convolution output that has none.  With BatchNorm
  * folded into the weights every conv is followed by bias (+ residual) + ReLU, which PyTorch
  * executes as 2-3 separate full-tensor passes (models/architecture/vanilla.py:300-316 forward).
  * ===================================================================================== */

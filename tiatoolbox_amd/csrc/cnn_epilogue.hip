@@ -355,7 +355,10 @@ __global__ __launch_bounds__(256) void head1x1_kernel(const float4* __restrict__
             if (pre) {
 #pragma unroll
                 for (int i = 0; i < 4; ++i) {
-                    const float t = __fadd_rn(__fmul_rn(a[i], sc[i]), sh[i]);  // rounded like batch_norm, then relu
+                    // rounded like batch_norm, then relu: plain operators, which the contract(off) above covers (__fmul_rn /
+                    // __fadd_rn are inline `*` / `+` outside its scope and used to fuse into one v_pk_fma_f32)
+                    float t = a[i] * sc[i];
+                    t = t + sh[i];
                     a[i] = t > 0.0f ? t : 0.0f;
                 }
             }

@@ -124,7 +124,11 @@ __global__ __launch_bounds__(NTH, 2) void conv_mfma_f32_kernel(const float* __re
     // scale_shift_act kernel: the three forms are interchangeable bit for bit)
     auto pre_act = [](float v, float sc, float sh) {
         if constexpr (PRE) {
-            const float a = __fadd_rn(__fmul_rn(v, sc), sh);
+            // (plain operators under the pragma: __fmul_rn / __fadd_rn are inline `*` / `+` whose own scope allows contraction, so
+            // the pair used to fuse into one v_fma_f32 -- a single rounding)
+#pragma clang fp contract(off)
+            const float p = v * sc;
+            const float a = p + sh;
             return a > 0.0f ? a : 0.0f;
         } else {
             return v;
@@ -273,9 +277,10 @@ __global__ __launch_bounds__(NTH, 2) void conv_mfma_f32_kernel(const float* __re
                 if (relu) v = v > 0.0f ? v : 0.0f;
                 if constexpr (POST) {
                     if (m < m_total) {
+#pragma clang fp contract(off)
                         if (y) y[m * d.cout + n] = v;
-                        float a = __fmul_rn(v, ps);  // product and sum rounded separately, like batch_norm + relu
-                        a = __fadd_rn(a, pt);
+                        float a = v * ps;  // product and sum rounded separately, like batch_norm + relu (no v_fma_f32: see pre_act)
+                        a = a + pt;
                         post.y2[m * d.cout + n] = a > 0.0f ? a : 0.0f;
                     }
                 } else {

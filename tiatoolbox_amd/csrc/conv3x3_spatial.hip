@@ -23,19 +23,16 @@
 //   * epilogue through LDS in two column halves: float32 tile [256][BN/2] -> + bias + residual, ReLU, (one rounding), 16-byte stores
 //   * blockIdx remapped so that each XCD walks a contiguous range of pixel blocks
 #include "conv3x3_spatial.hpp"
-#include <atomic>
 
 #include <stdlib.h>
 
 #include "../../include/tiatoolbox_amd.h"
+#include "conv_device.hpp"
 
 namespace {
 
-using f32x16 = __attribute__((ext_vector_type(16))) float;
-using h8 = __attribute__((ext_vector_type(8))) _Float16;
-using b8 = __attribute__((ext_vector_type(8))) __bf16;
-using u32x4 = __attribute__((ext_vector_type(4))) unsigned;
-constexpr int OOB = (int)0x80000000;
+using namespace tia;
+
 constexpr int K_F32 = 0, K_F16 = 1, K_BF16 = 2;
 
 struct SpDims {
@@ -67,34 +64,6 @@ __device__ __forceinline__ f32x16 mma_h(const u32x4& a, const u32x4& b, const f3
     else
         return __builtin_amdgcn_mfma_f32_32x32x16_f16(*reinterpret_cast<const h8*>(&a), *reinterpret_cast<const h8*>(&b), c, 0, 0, 0);
 }
-template <int KIND>
-__device__ __forceinline__ float half_to_f32(unsigned short v) {
-    if constexpr (KIND == K_BF16) return __uint_as_float((unsigned)v << 16);
-    _Float16 h;
-    __builtin_memcpy(&h, &v, 2);
-    return (float)h;
-}
-template <int KIND>
-__device__ __forceinline__ unsigned short f32_to_half(float x) {  // round to nearest even
-    if constexpr (KIND == K_BF16) {
-        unsigned u = __float_as_uint(x);
-        if ((u & 0x7fffffffu) > 0x7f800000u) return (unsigned short)((u >> 16) | 0x40u);
-        u += 0x7fffu + ((u >> 16) & 1u);
-        return (unsigned short)(u >> 16);
-    } else {
-        const _Float16 h = (_Float16)x;
-        unsigned short v;
-        __builtin_memcpy(&v, &h, 2);
-        return v;
-    }
-}
-
-// 16 bytes per lane from a buffer straight into LDS: the wave's 64 lanes fill the 1 KB at `lds_wave_base` in lane order; an
-// out-of-range `voffset` writes zeros.  (A __device__ function: the builtin must not be seen by the host pass.)
-__device__ __forceinline__ void dma16(__amdgpu_buffer_rsrc_t rsrc, unsigned char* lds_wave_base, int voffset, int soffset) {
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (__attribute__((address_space(3))) void*)lds_wave_base, 16, voffset, soffset, 0, 0);
-}
-
 // Block geometries.  G16: one image, 16 x 16 output pixels, 8 waves (4 x 2).  G8 (maps of at most 8 x 8, e.g. resnet layer 4 at
 // 256^2 patches): TWO images of 8 x 8, 4 waves (2 x 2, wave row = image); an MFMA tile is four 8-pixel rows, and the row pitch is
 // 8 mod 16 units, which puts the four rows' lanes of a ds_read_b128 group ({0-3} {12-15} {20-23} {24-27}) on 16 different bank
@@ -138,13 +107,6 @@ struct GBN {
     static constexpr int NT = 256, G = 1, TH = 16, TW = 16, PH = 0, PWD = 0, ROW = 0, IMG = 1728, MROWS = 0, WAVES_M = 4, WN = 1;
     static constexpr bool BAND = true;
 };
-
-// s_waitcnt vmcnt(VM) lgkmcnt(0) (gfx9 encoding: vmcnt[3:0] | expcnt[6:4] = 7 (no wait) | lgkmcnt[11:8] | vmcnt[5:4] << 14)
-template <int VM>
-__device__ __forceinline__ void wait_vm_lgkm0() {
-    __builtin_amdgcn_s_waitcnt((VM & 15) | (7 << 4) | ((VM >> 4) << 14));
-    asm volatile("" ::: "memory");
-}
 
 // Phase timing (developer builds only: -DTIA_SP_TIMING=1, build.build(defines=...)): thread 0 of two workgroups prints the
 // shader-clock cycles of set-up, first-data wait, tap loop and epilogue, and the shader clock itself (against the constant 100 MHz
@@ -221,8 +183,8 @@ __global__ __launch_bounds__(GEO::NT, GEO::NT == 512 ? 4 : 2) void conv3x3_spati
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int wm = WN == 2 ? wave >> 1 : wave, wn = WN == 2 ? wave & 1 : 0;
 
-    const __amdgpu_buffer_rsrc_t rx = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(x), 0, (int)d.x_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rw = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(wk), 0, (int)d.w_bytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rx = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(x), 0, (int)d.x_bytes, kBufferRsrcFlags);
+    const __amdgpu_buffer_rsrc_t rw = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(wk), 0, (int)d.w_bytes, kBufferRsrcFlags);
 
     // patch staging: unit U = NT r + tid -> image U / IMG, row (U % IMG) / ROW, pixel (.. % ROW) / 5, unit-of-slice .. % 5 (4 = padding)
     int cen[NA];
@@ -528,8 +490,8 @@ __global__ __launch_bounds__(GEO::NT, GEO::NT == 512 ? 4 : 2) void conv3x3_spati
                     if (res) {
 #pragma unroll
                         for (int k = 0; k < 4; ++k) {
-                            v[2 * k] += half_to_f32<KIND>((unsigned short)(rq[it][0][k] & 0xffffu));
-                            v[2 * k + 1] += half_to_f32<KIND>((unsigned short)(rq[it][0][k] >> 16));
+                            v[2 * k] += half_to_f32<KIND == K_BF16>((unsigned short)(rq[it][0][k] & 0xffffu));
+                            v[2 * k + 1] += half_to_f32<KIND == K_BF16>((unsigned short)(rq[it][0][k] >> 16));
                         }
                     }
                     unsigned o[4];
@@ -540,7 +502,7 @@ __global__ __launch_bounds__(GEO::NT, GEO::NT == 512 ? 4 : 2) void conv3x3_spati
                             a0 = a0 > 0.0f ? a0 : 0.0f;
                             a1 = a1 > 0.0f ? a1 : 0.0f;
                         }
-                        o[k] = (unsigned)f32_to_half<KIND>(a0) | ((unsigned)f32_to_half<KIND>(a1) << 16);
+                        o[k] = (unsigned)f32_to_half<KIND == K_BF16>(a0) | ((unsigned)f32_to_half<KIND == K_BF16>(a1) << 16);
                     }
                     *reinterpret_cast<u32x4*>(yh + off) = u32x4{o[0], o[1], o[2], o[3]};
                 }
@@ -599,8 +561,8 @@ __global__ __launch_bounds__(512, 4) void conv1x1_ring_kernel(const float* __res
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int wm = wave >> 1, wn = wave & 1;
 
-    const __amdgpu_buffer_rsrc_t rx = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(x), 0, (int)d.x_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rw = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(wk), 0, (int)d.w_bytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rx = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(x), 0, (int)d.x_bytes, kBufferRsrcFlags);
+    const __amdgpu_buffer_rsrc_t rw = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(wk), 0, (int)d.w_bytes, kBufferRsrcFlags);
 
     // per DMA unit: byte offset of tap (0, 0) of its pixel (may lie before the buffer: only used when the tap is inside the image)
     // and one bit per kernel row / column saying whether that row / column of taps is inside (all set for a 1x1)
@@ -743,20 +705,6 @@ __global__ __launch_bounds__(512, 4) void conv1x1_ring_kernel(const float* __res
 }  // namespace
 
 namespace tia {
-
-// Compute units of the calling thread's CURRENT device, cached per device index (a process may drive several GPUs; the first caller
-// may be the host-only route query).  Without a usable device (build container): MI355X's 256.
-static long device_cu_count() {
-    static std::atomic<int> cached[64] = {};
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return 256;
-    int cus = cached[dev].load(std::memory_order_relaxed);
-    if (cus == 0) {
-        if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) return 256;
-        cached[dev].store(cus, std::memory_order_relaxed);
-    }
-    return cus;
-}
 
 bool conv3x3_spatial_serves(long nb, long h, long w, long cin, long cout, long pad_top, long pad_left, long ho, long wo, int dtype) {
     static const bool disabled = tia::dev_env("TIA_CONV_NO_SPATIAL") != nullptr;

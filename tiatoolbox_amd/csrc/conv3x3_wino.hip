@@ -34,18 +34,13 @@
 #include <stdint.h>
 #include <stdlib.h>
 
-#include <atomic>
-
 #include "../../include/tiatoolbox_amd.h"
 #include "conv3x3_wino.hpp"
 #include "dev_env.hpp"
 
 namespace {
 
-using f32x16 = __attribute__((ext_vector_type(16))) float;
-using u32x4 = __attribute__((ext_vector_type(4))) unsigned;
-using f32x2 = __attribute__((ext_vector_type(2))) float;
-constexpr int OOB = (int)0x80000000;
+using namespace tia;
 
 struct WinoDims {
     int n, h, w, cin, cout, ho, wo, pad_y, pad_x;
@@ -65,24 +60,6 @@ __device__ __forceinline__ int fdiv(int n, int d, float inv) {
     q += r >= d ? 1 : 0;
     q -= r < 0 ? 1 : 0;
     return q;
-}
-
-// Packed float32 add / subtract (two channels per instruction).  Inline assembly: the compiler splits a v2f32 subtraction into two
-// scalar v_sub_f32 (48 of the 56 vector instructions of a load phase), and it is the NUMBER of vector instructions issued beside the
-// SIMD partner's MFMA stream that stretches that phase.
-__device__ __forceinline__ f32x2 pk_add(f32x2 a, f32x2 b) {
-    f32x2 r;
-    asm("v_pk_add_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
-    return r;
-}
-__device__ __forceinline__ f32x2 pk_sub(f32x2 a, f32x2 b) {
-    f32x2 r;
-    asm("v_pk_add_f32 %0, %1, %2 neg_lo:[0,1] neg_hi:[0,1]" : "=v"(r) : "v"(a), "v"(b));
-    return r;
-}
-
-__device__ __forceinline__ void dma16(__amdgpu_buffer_rsrc_t rsrc, unsigned char* lds_wave_base, int voffset, int soffset) {
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (__attribute__((address_space(3))) void*)lds_wave_base, 16, voffset, soffset, 0, 0);
 }
 
 // LDS patch layout, in 16-byte units: a pixel is 4 units (16 float32 channels); pixels are stored in PAIRS of 9 units (two pixels +
@@ -111,15 +88,6 @@ struct W8 {
 struct WR {
     static constexpr int G = 0, TH = 16, TW = 16, PH = 0, PWD = 0, ROW = 0, IMG = 2560;  // IMG: the LDS patch allocation in units
 };
-// unit offset of pixel column px inside a row
-__device__ __forceinline__ constexpr int px_unit(int px) { return (px >> 1) * 9 + (px & 1) * 4; }
-
-// s_waitcnt vmcnt(VM) lgkmcnt(0) (gfx9 encoding: vmcnt[3:0] | expcnt[6:4] = 7 (no wait) | lgkmcnt[11:8] | vmcnt[5:4] << 14)
-template <int VM>
-__device__ __forceinline__ void wait_vm_lgkm0() {
-    __builtin_amdgcn_s_waitcnt((VM & 15) | (7 << 4) | ((VM >> 4) << 14));
-    asm volatile("" ::: "memory");
-}
 
 // Phase timing (developer builds only: -DTIA_WINO_TIMING=1): thread 0 of two workgroups prints shader-clock cycles of the prologue,
 // of the steps' compute and of their waits (vmcnt + barrier), of the epilogue, and the shader clock against the 100 MHz clock.
@@ -217,8 +185,8 @@ __global__ __launch_bounds__(512, 2) void conv3x3_wino_kernel(const float* __res
     const int irow = wave >> 1, wm = wave & 1, pg = wave >> 2;  // position row i, tile half; group = which half of the position grid (ping-pong)
     const int hi = lane >> 5;
 
-    const __amdgpu_buffer_rsrc_t rx = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(x), 0, (int)d.x_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t ru = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(u), 0, (int)d.u_bytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rx = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(x), 0, (int)d.x_bytes, kBufferRsrcFlags);
+    const __amdgpu_buffer_rsrc_t ru = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(u), 0, (int)d.u_bytes, kBufferRsrcFlags);
 
     // patch staging: unit U = NT r + tid -> image U / IMG, row (U % IMG) / ROW, pixel pair (.. % ROW) / 9, pixel and unit-of-slice from
     // the rest (layout above); outside the image / patch, padding units: an out-of-range offset (the DMA writes zeros)
@@ -650,17 +618,8 @@ __global__ void wino_pack_kernel(const float* __restrict__ w_oihw, int cout, int
         t[2][s] = 0.5 * (g[0][s] - g[1][s] + g[2][s]);
         t[3][s] = g[2][s];
     }
-    const int n_cs = cin >> 4, n_cb = cout >> 6;
-    const int cs = c >> 4, h8 = (c >> 3) & 1, hi = (c >> 2) & 1, c4 = c & 3, cb = o >> 6, col = o & 63;
 #pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const double uu[4] = {t[i][0], 0.5 * (t[i][0] + t[i][1] + t[i][2]), 0.5 * (t[i][0] - t[i][1] + t[i][2]), t[i][2]};
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const long block = (((long)(i * 4 + j) * n_cs + cs) * 2 + h8) * n_cb + cb;  // 2 KB = 512 floats
-            packed[block * 512 + (hi * 64 + col) * 4 + c4] = (float)uu[j];
-        }
-    }
+    for (int i = 0; i < 4; ++i) wino_pack_row(t[i], i, cout, cin, o, c, packed);
 }
 
 }  // namespace
@@ -678,18 +637,6 @@ static constexpr int wino_lds_bytes(int patch_units, int stages, bool persist) {
     }
     const int main_loop = 2 * a_bytes + stages * 32768 + 1024;
     return main_loop > tile ? main_loop : tile;
-}
-
-static long wino_cu_count() {  // compute units of the current device (MI355X: 256), cached per device index
-    static std::atomic<int> cached[64] = {};
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return 256;
-    int cus = cached[dev].load(std::memory_order_relaxed);
-    if (cus == 0) {
-        if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) return 256;
-        cached[dev].store(cus, std::memory_order_relaxed);
-    }
-    return cus;
 }
 
 bool conv3x3_wino_serves(long nb, long h, long w, long cin, long cout, long pad_top, long pad_left, long ho, long wo) {
@@ -752,51 +699,34 @@ int conv3x3_wino_launch(const float* x, const float* u_packed, const float* bias
         d.inv_wimg = 1.0f / (float)plan.wimg, d.inv_wrow = 1.0f / (float)plan.wrow, d.inv_wt = 1.0f / (float)(plan.wty * plan.wtx);
         d.inv_wtx = 1.0f / (float)plan.wtx, d.inv_wins = 1.0f / (float)(plan.wins_x * plan.wins_y), d.inv_wins_x = 1.0f / (float)plan.wins_x;
     }
-    // Persistent form (one workgroup per CU walks the items, the next item's first operands requested behind the current one's last
-    // steps): 16 x 16 blocks and the four-image blocks of small maps, an even number of 16-channel slices (the patch buffers alternate
-    // per slice and an item must end on buffer 1), at least two rounds of items -- everything else one block per workgroup.
-    static const bool no_persist = tia::dev_env("TIA_WINO_NO_PERSIST") != nullptr;  // developer switch (A/B measurements)
-    const long cus = wino_cu_count() / 8 * 8;
     // (the window geometry keeps one block per workgroup: measured on the 56^2 / 28^2 / 14^2 maps of 224^2 patches the persistent form
     // is -1 % / +1.6 % / +4 % there -- its per-item decode is all run-time divisions -- profiles/r06k_wino_persist_ab_224.txt)
-    const bool persist = !no_persist && plan.kind != 2 && (cin / 16) % 2 == 0 && cus >= 8 && tiles * (cout / 64) >= 2 * cus;
-    const dim3 grid = persist ? dim3((unsigned)cus) : dim3((unsigned)(((tiles + 7) / 8) * 8), (unsigned)(cout / 64));
-    static tia::DeviceOnce attr16, attr8, attrw, attr16p, attr8p;  // the dynamic-LDS attribute is per device
-#define TIA_WINO_LAUNCH(GEO_, NS_, PERSIST_, ONCE_)                                                                                  \
-    do {                                                                                                                             \
-        constexpr int lds = wino_lds_bytes((GEO_::G == 0 ? 1 : GEO_::G) * GEO_::IMG, NS_, PERSIST_);                                \
-        static_assert(lds <= 160 * 1024, "LDS");                                                                                     \
-        if (!ONCE_.ensure([] {                                                                                                       \
-                return hipFuncSetAttribute(reinterpret_cast<const void*>(&conv3x3_wino_kernel<GEO_, NS_, PERSIST_>),                  \
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, lds) == hipSuccess;                           \
-            }))                                                                                                                      \
-            return TIA_ELAUNCH;                                                                                                      \
-        hipLaunchKernelGGL((conv3x3_wino_kernel<GEO_, NS_, PERSIST_>), grid, dim3(512), lds, stream, x, u_packed, bias, residual, y,  \
-                           d, relu, (int)tiles, (int)tiles_x, (int)(tiles_y * tiles_x));                                             \
-    } while (0)
-    if (plan.kind == 1 && persist)
-        TIA_WINO_LAUNCH(W8, 2, true, attr8p);
+    const WinoGrid g = wino_grid(plan.kind != 2, tiles, cin, cout);
+    auto run = [&](auto geo, auto persist) {
+        using GEO = decltype(geo);
+        constexpr int lds = wino_lds_bytes((GEO::G == 0 ? 1 : GEO::G) * GEO::IMG, 2, decltype(persist)::value);
+        static_assert(lds <= 160 * 1024, "LDS");
+        return launch_dyn_lds<&conv3x3_wino_kernel<GEO, 2, decltype(persist)::value>>(g.grid, dim3(512), lds, stream, x, u_packed, bias, residual,
+                                                                                      y, d, relu, (int)tiles, (int)tiles_x, (int)(tiles_y * tiles_x));
+    };
+    bool ok;
+    if (plan.kind == 1 && g.persist)
+        ok = run(W8{}, std::true_type{});
     else if (plan.kind == 1)
-        TIA_WINO_LAUNCH(W8, 2, false, attr8);
+        ok = run(W8{}, std::false_type{});
     else if (plan.kind == 2)
-        TIA_WINO_LAUNCH(WR, 2, false, attrw);
-    else if (persist)
-        TIA_WINO_LAUNCH(W16, 2, true, attr16p);
+        ok = run(WR{}, std::false_type{});
+    else if (g.persist)
+        ok = run(W16{}, std::true_type{});
     else
-        TIA_WINO_LAUNCH(W16, 2, false, attr16);
-#undef TIA_WINO_LAUNCH
-    return hipGetLastError() == hipSuccess ? TIA_OK : TIA_ELAUNCH;
+        ok = run(W16{}, std::false_type{});
+    return ok ? TIA_OK : TIA_ELAUNCH;
 }
 
 }  // namespace tia
 
 extern "C" int tia_conv_pack_weights_wino_f32(const float* d_w_oihw, int64_t cout, int64_t cin, float* d_packed, void* stream) {
-    if (!d_w_oihw || !d_packed || cout <= 0 || cin <= 0) return TIA_EINVAL;
-    if (cin % 16 != 0 || cout % 64 != 0 || 16 * cin * cout * 4 > 0x7fffffffL) return TIA_ESIZE;
-    const long total = (long)cout * cin;
-    hipLaunchKernelGGL(wino_pack_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, d_w_oihw, (int)cout,
-                       (int)cin, d_packed);
-    return hipGetLastError() == hipSuccess ? TIA_OK : TIA_ELAUNCH;
+    return tia::wino_pack_run(16, wino_pack_kernel, d_w_oihw, cout, cin, d_packed, (hipStream_t)stream);
 }
 
 extern "C" int tia_conv3x3_wino_geometry(int64_t n, int64_t ho, int64_t wo, int32_t geom[4]) {
@@ -814,28 +744,6 @@ extern "C" int tia_conv3x3_wino_geometry(int64_t n, int64_t ho, int64_t wo, int3
 extern "C" int tia_conv3x3_wino_nhwc_f32(const float* d_x, const float* d_u_packed, const float* d_bias, const float* d_residual,
                                          float* d_y, int64_t n, int64_t h, int64_t w, int64_t cin, int64_t cout, int64_t pad_top,
                                          int64_t pad_left, int64_t ho, int64_t wo, int32_t relu, void* stream) {
-    if (!d_x || !d_u_packed || !d_y || n <= 0 || h <= 0 || w <= 0 || cin <= 0 || cout <= 0) return TIA_EINVAL;
-    if (ho <= 0 || wo <= 0 || pad_top < 0 || pad_left < 0 || pad_top > 2 || pad_left > 2) return TIA_EINVAL;
-    if (ho - 1 - pad_top >= h || wo - 1 - pad_left >= w) return TIA_EINVAL;  // every output sees at least its first tap row / column start on the map
-    if (((reinterpret_cast<uintptr_t>(d_x) | reinterpret_cast<uintptr_t>(d_u_packed) | reinterpret_cast<uintptr_t>(d_y) |
-          reinterpret_cast<uintptr_t>(d_residual) | reinterpret_cast<uintptr_t>(d_bias)) & 15) != 0)
-        return TIA_EINVAL;
-    if (cin % 16 != 0 || cout % 64 != 0) return TIA_ESIZE;
-    // 32-bit byte offsets into the input: images go in groups of < 2 GiB (and < 2^31 / 4 output pixels)
-    const long image_bytes = h * w * cin * 4;
-    if (image_bytes > 0x7fffffffL || ho * wo > 0x7fffffffL / 4) return TIA_ESIZE;
-    long group = 0x7fffffffL / image_bytes;
-    if (group * ho * wo > 0x7fffffffL / 2) group = 0x7fffffffL / 2 / (ho * wo);
-    if (group < 1) return TIA_ESIZE;
-    if (ho <= 8 && wo <= 8 && group > 4) group -= group % 4;  // whole blocks of four images
-    if (const long even = tia::even_group(n, group); even < group)
-        group = (ho <= 8 && wo <= 8 && even > 4) ? (even + 3) / 4 * 4 : even;  // equal groups (still whole blocks, still <= the limit)
-    for (long first = 0; first < n; first += group) {
-        const long nb = n - first < group ? n - first : group;
-        const int rc = tia::conv3x3_wino_launch(d_x + first * h * w * cin, d_u_packed, d_bias, d_residual ? d_residual + first * ho * wo * cout : nullptr,
-                                                d_y + first * ho * wo * cout, nb, h, w, cin, cout, pad_top, pad_left, ho, wo, relu,
-                                                (hipStream_t)stream);
-        if (rc != TIA_OK) return rc;
-    }
-    return TIA_OK;
+    return tia::conv3x3_wino_run(16, tia::conv3x3_wino_launch, d_x, d_u_packed, d_bias, d_residual, d_y, n, h, w, cin, cout, pad_top, pad_left,
+                                 ho, wo, relu, (hipStream_t)stream);
 }

@@ -31,36 +31,19 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include <atomic>
-
 #include "../../include/tiatoolbox_amd.h"
 #include "conv3x3_wino.hpp"
 #include "dev_env.hpp"
 
 namespace {
 
-using f32x16 = __attribute__((ext_vector_type(16))) float;
-using u32x4 = __attribute__((ext_vector_type(4))) unsigned;
-using f32x2 = __attribute__((ext_vector_type(2))) float;
-constexpr int OOB = (int)0x80000000;
+using namespace tia;
 
 struct Wino42Dims {
     int n, h, w, cin, cout, ho, wo, pad_y, pad_x;
     unsigned x_bytes, u_bytes;
     int pos_stride;  // bytes between consecutive positions of the packed weights: (cin / 16) * (cout / 64) * 4096
 };
-
-// packed float32 add / subtract (two channels per instruction; see conv3x3_wino.hip)
-__device__ __forceinline__ f32x2 pk_add(f32x2 a, f32x2 b) {
-    f32x2 r;
-    asm("v_pk_add_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
-    return r;
-}
-__device__ __forceinline__ f32x2 pk_sub(f32x2 a, f32x2 b) {
-    f32x2 r;
-    asm("v_pk_add_f32 %0, %1, %2 neg_lo:[0,1] neg_hi:[0,1]" : "=v"(r) : "v"(a), "v"(b));
-    return r;
-}
 
 // a * b + c / -(a * b) + c on a pair, the constant `a` from a scalar register pair
 __device__ __forceinline__ f32x2 pk_fma_s(f32x2 a, f32x2 b, f32x2 c) {
@@ -74,10 +57,6 @@ __device__ __forceinline__ f32x2 pk_fnma_s(f32x2 a, f32x2 b, f32x2 c) {
     return r;
 }
 
-__device__ __forceinline__ void dma16(__amdgpu_buffer_rsrc_t rsrc, unsigned char* lds_wave_base, int voffset, int soffset) {
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (__attribute__((address_space(3))) void*)lds_wave_base, 16, voffset, soffset, 0, 0);
-}
-
 // LDS patch images (16-byte units; pixel px of a row at (px >> 1) * 9 + (px & 1) * 4, see the bank analysis above)
 //   W16: one image, 16 x 16 output pixels = 4 x 8 tiles, patch 18 x 18
 //   W8:  four images of at most 8 x 8 = 4 x (2 x 4) tiles, patch 10 x 10 each
@@ -87,13 +66,6 @@ struct W16 {
 struct W8 {
     static constexpr int G = 4, TH = 8, TW = 8, PH = 10, PWD = 10, ROW = 48, IMG = 484;
 };
-__device__ __forceinline__ constexpr int px_unit(int px) { return (px >> 1) * 9 + (px & 1) * 4; }
-
-template <int VM>
-__device__ __forceinline__ void wait_vm_lgkm0() {
-    __builtin_amdgcn_s_waitcnt((VM & 15) | (7 << 4) | ((VM >> 4) << 14));
-    asm volatile("" ::: "memory");
-}
 
 // PERSIST: as in conv3x3_wino.hip (one workgroup per CU walks (pixel block, 64-channel tile) items; the next item's first patch slice
 // and weight stage are requested by the current item's last slice).  A weight stage of 48 KB makes every persistent map the LATE one:
@@ -155,8 +127,8 @@ __global__ __launch_bounds__(512, 2) void conv3x3_wino42_kernel(const float* __r
     const int pg = hrow;
     const int hi = lane >> 5;
 
-    const __amdgpu_buffer_rsrc_t rx = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(x), 0, (int)d.x_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t ru = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(u), 0, (int)d.u_bytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rx = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(x), 0, (int)d.x_bytes, kBufferRsrcFlags);
+    const __amdgpu_buffer_rsrc_t ru = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(u), 0, (int)d.u_bytes, kBufferRsrcFlags);
 
     int cen[NA];
     auto make_cen = [&] {
@@ -534,29 +506,8 @@ __global__ void wino42_pack_kernel(const float* __restrict__ w_oihw, int cout, i
         t[4][s] = g[0][s] / 24.0 - g[1][s] / 12.0 + g[2][s] / 6.0;
         t[5][s] = g[2][s];
     }
-    const int n_cs = cin >> 4, n_cb = cout >> 6;
-    const int cs = c >> 4, h8 = (c >> 3) & 1, hi = (c >> 2) & 1, c4 = c & 3, cb = o >> 6, col = o & 63;
 #pragma unroll
-    for (int i = 0; i < 6; ++i) {  // U = t G2^T
-        const double uu[4] = {t[i][0], 0.5 * (t[i][0] + t[i][1] + t[i][2]), 0.5 * (t[i][0] - t[i][1] + t[i][2]), t[i][2]};
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const long block = (((long)(i * 4 + j) * n_cs + cs) * 2 + h8) * n_cb + cb;  // 2 KB = 512 floats
-            packed[block * 512 + (hi * 64 + col) * 4 + c4] = (float)uu[j];
-        }
-    }
-}
-
-static long cu_count() {  // compute units of the current device (MI355X: 256), cached per device index
-    static std::atomic<int> cached[64] = {};
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return 256;
-    int cus = cached[dev].load(std::memory_order_relaxed);
-    if (cus == 0) {
-        if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) return 256;
-        cached[dev].store(cus, std::memory_order_relaxed);
-    }
-    return cus;
+    for (int i = 0; i < 6; ++i) wino_pack_row(t[i], i, cout, cin, o, c, packed);  // U = t G2^T
 }
 
 constexpr int wino42_lds_bytes(int patch_units) { return 2 * (((patch_units + 63) / 64 * 64) * 16) + 2 * 24 * 2048 + 1024; }
@@ -568,33 +519,24 @@ int conv3x3_wino42_launch(const float* x, const float* u_packed, const float* bi
     const long tiles = small ? (nb + 3) / 4 : nb * tiles_y * tiles_x;
     Wino42Dims d{(int)nb, (int)h, (int)w, (int)cin, (int)cout, (int)ho, (int)wo, (int)pad_top, (int)pad_left,
                  (unsigned)(nb * h * w * cin * 4), (unsigned)(24 * cin * cout * 4), (int)((cin / 16) * (cout / 64) * 4096)};
-    static const bool no_persist = tia::dev_env("TIA_WINO_NO_PERSIST") != nullptr;  // developer switch (A/B measurements)
-    const long cus = cu_count() / 8 * 8;
-    const bool persist = !no_persist && (cin / 16) % 2 == 0 && cus >= 8 && tiles * (cout / 64) >= 2 * cus;
-    const dim3 grid = persist ? dim3((unsigned)cus) : dim3((unsigned)(((tiles + 7) / 8) * 8), (unsigned)(cout / 64));
-    static tia::DeviceOnce attr16, attr8, attr16p, attr8p;  // the dynamic-LDS attribute is per device
-#define TIA_WINO42_LAUNCH(GEO_, PERSIST_, ONCE_)                                                                                     \
-    do {                                                                                                                             \
-        constexpr int lds = wino42_lds_bytes(GEO_::G * GEO_::IMG);                                                                   \
-        static_assert(lds <= 160 * 1024, "LDS");                                                                                     \
-        if (!ONCE_.ensure([] {                                                                                                       \
-                return hipFuncSetAttribute(reinterpret_cast<const void*>(&conv3x3_wino42_kernel<GEO_, PERSIST_>),                     \
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, lds) == hipSuccess;                           \
-            }))                                                                                                                      \
-            return TIA_ELAUNCH;                                                                                                      \
-        hipLaunchKernelGGL((conv3x3_wino42_kernel<GEO_, PERSIST_>), grid, dim3(512), lds, stream, x, u_packed, bias, residual, y, d,  \
-                           relu, (int)tiles, (int)tiles_x, (int)(tiles_y * tiles_x));                                                \
-    } while (0)
-    if (small && persist)
-        TIA_WINO42_LAUNCH(W8, true, attr8p);
+    const WinoGrid g = wino_grid(true, tiles, cin, cout);
+    auto run = [&](auto geo, auto persist) {
+        using GEO = decltype(geo);
+        constexpr int lds = wino42_lds_bytes(GEO::G * GEO::IMG);
+        static_assert(lds <= 160 * 1024, "LDS");
+        return launch_dyn_lds<&conv3x3_wino42_kernel<GEO, decltype(persist)::value>>(g.grid, dim3(512), lds, stream, x, u_packed, bias, residual, y,
+                                                                                    d, relu, (int)tiles, (int)tiles_x, (int)(tiles_y * tiles_x));
+    };
+    bool ok;
+    if (small && g.persist)
+        ok = run(W8{}, std::true_type{});
     else if (small)
-        TIA_WINO42_LAUNCH(W8, false, attr8);
-    else if (persist)
-        TIA_WINO42_LAUNCH(W16, true, attr16p);
+        ok = run(W8{}, std::false_type{});
+    else if (g.persist)
+        ok = run(W16{}, std::true_type{});
     else
-        TIA_WINO42_LAUNCH(W16, false, attr16);
-#undef TIA_WINO42_LAUNCH
-    return hipGetLastError() == hipSuccess ? TIA_OK : TIA_ELAUNCH;
+        ok = run(W16{}, std::false_type{});
+    return ok ? TIA_OK : TIA_ELAUNCH;
 }
 
 }  // namespace
@@ -618,39 +560,12 @@ extern "C" int tia_conv3x3_wino_form(int64_t n, int64_t h, int64_t w, int64_t ci
 }
 
 extern "C" int tia_conv_pack_weights_wino42_f32(const float* d_w_oihw, int64_t cout, int64_t cin, float* d_packed, void* stream) {
-    if (!d_w_oihw || !d_packed || cout <= 0 || cin <= 0) return TIA_EINVAL;
-    if (cin % 16 != 0 || cout % 64 != 0 || 24 * cin * cout * 4 > 0x7fffffffL) return TIA_ESIZE;
-    const long total = (long)cout * cin;
-    hipLaunchKernelGGL(wino42_pack_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, d_w_oihw, (int)cout,
-                       (int)cin, d_packed);
-    return hipGetLastError() == hipSuccess ? TIA_OK : TIA_ELAUNCH;
+    return tia::wino_pack_run(24, wino42_pack_kernel, d_w_oihw, cout, cin, d_packed, (hipStream_t)stream);
 }
 
 extern "C" int tia_conv3x3_wino42_nhwc_f32(const float* d_x, const float* d_u_packed, const float* d_bias, const float* d_residual,
                                            float* d_y, int64_t n, int64_t h, int64_t w, int64_t cin, int64_t cout, int64_t pad_top,
                                            int64_t pad_left, int64_t ho, int64_t wo, int32_t relu, void* stream) {
-    if (!d_x || !d_u_packed || !d_y || n <= 0 || h <= 0 || w <= 0 || cin <= 0 || cout <= 0) return TIA_EINVAL;
-    if (ho <= 0 || wo <= 0 || pad_top < 0 || pad_left < 0 || pad_top > 2 || pad_left > 2) return TIA_EINVAL;
-    if (ho - 1 - pad_top >= h || wo - 1 - pad_left >= w) return TIA_EINVAL;
-    if (((reinterpret_cast<uintptr_t>(d_x) | reinterpret_cast<uintptr_t>(d_u_packed) | reinterpret_cast<uintptr_t>(d_y) |
-          reinterpret_cast<uintptr_t>(d_residual) | reinterpret_cast<uintptr_t>(d_bias)) & 15) != 0)
-        return TIA_EINVAL;
-    if (cin % 16 != 0 || cout % 64 != 0 || 24 * cin * cout * 4 > 0x7fffffffL) return TIA_ESIZE;
-    // 32-bit byte offsets into the input: images go in groups of < 2 GiB (and < 2^31 / 4 output pixels)
-    const long image_bytes = h * w * cin * 4;
-    if (image_bytes > 0x7fffffffL || ho * wo > 0x7fffffffL / 4) return TIA_ESIZE;
-    long group = 0x7fffffffL / image_bytes;
-    if (group * ho * wo > 0x7fffffffL / 2) group = 0x7fffffffL / 2 / (ho * wo);
-    if (group < 1) return TIA_ESIZE;
-    if (ho <= 8 && wo <= 8 && group > 4) group -= group % 4;  // whole blocks of four images
-    if (const long even = tia::even_group(n, group); even < group)
-        group = (ho <= 8 && wo <= 8 && even > 4) ? (even + 3) / 4 * 4 : even;
-    for (long first = 0; first < n; first += group) {
-        const long nb = n - first < group ? n - first : group;
-        const int rc = conv3x3_wino42_launch(d_x + first * h * w * cin, d_u_packed, d_bias, d_residual ? d_residual + first * ho * wo * cout : nullptr,
-                                             d_y + first * ho * wo * cout, nb, h, w, cin, cout, pad_top, pad_left, ho, wo, relu,
-                                             (hipStream_t)stream);
-        if (rc != TIA_OK) return rc;
-    }
-    return TIA_OK;
+    return tia::conv3x3_wino_run(24, conv3x3_wino42_launch, d_x, d_u_packed, d_bias, d_residual, d_y, n, h, w, cin, cout, pad_top, pad_left, ho,
+                                 wo, relu, (hipStream_t)stream);
 }

@@ -1,0 +1,94 @@
+// Device and host leaves shared by the convolution kernels (conv3x3_wino.hip, conv3x3_wino42.hip, conv3x3_spatial.hip,
+// conv_mfma.hip, conv_mfma_h.hip, stem_mfma.hip); internal, not part of the C ABI.  Every device function here is a
+// __forceinline__ leaf: a kernel that uses one compiles to the instructions it had with a private copy.  The kernels keep their
+// own helpers in anonymous namespaces and say `using namespace tia;` inside them.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <atomic>
+
+namespace tia {
+
+using f32x16 = __attribute__((ext_vector_type(16))) float;
+using f32x2 = __attribute__((ext_vector_type(2))) float;
+using u32x4 = __attribute__((ext_vector_type(4))) unsigned;
+using h8 = __attribute__((ext_vector_type(8))) _Float16;
+using b8 = __attribute__((ext_vector_type(8))) __bf16;
+
+// Operands come through buffer descriptors (built from kernel arguments only, so they live in SGPRs): a 32-bit per-lane byte
+// offset is all the address arithmetic a load needs, and an out-of-range offset reads as zero -- which is exactly what a padding
+// tap must contribute, without a select after the load.
+constexpr int OOB = (int)0x80000000;           // voffset beyond every buffer extent: the load returns zeros (padding taps)
+constexpr int kBufferRsrcFlags = 0x00020000;   // descriptor word 3 of a raw buffer: DATA_FORMAT = 32 (bits 18:15 = 4), every other field zero
+
+// 16 bytes per lane from a buffer straight into LDS (buffer_load_dwordx4 ... lds): the wave's 64 lanes fill the 1 KB at
+// `lds_wave_base` in lane order; an out-of-range `voffset` writes zeros.  (A __device__ function: the builtin must not be seen by
+// the host pass, which otherwise drops the kernel's launch stub.)
+__device__ __forceinline__ void dma16(__amdgpu_buffer_rsrc_t rsrc, unsigned char* lds_wave_base, int voffset, int soffset) {
+    __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (__attribute__((address_space(3))) void*)lds_wave_base, 16, voffset, soffset, 0, 0);
+}
+
+// s_waitcnt vmcnt(VM) lgkmcnt(0) (gfx9 encoding: vmcnt[3:0] | expcnt[6:4] = 7 (no wait) | lgkmcnt[11:8] | vmcnt[5:4] << 14)
+template <int VM>
+__device__ __forceinline__ void wait_vm_lgkm0() {
+    __builtin_amdgcn_s_waitcnt((VM & 15) | (7 << 4) | ((VM >> 4) << 14));
+    asm volatile("" ::: "memory");
+}
+
+// Packed float32 add / subtract (two channels per instruction).  Inline assembly: the compiler splits a v2f32 subtraction into two
+// scalar v_sub_f32 (48 of the 56 vector instructions of a load phase of the F(2x2) Winograd kernel), and it is the NUMBER of vector
+// instructions issued beside the SIMD partner's MFMA stream that stretches that phase.
+__device__ __forceinline__ f32x2 pk_add(f32x2 a, f32x2 b) {
+    f32x2 r;
+    asm("v_pk_add_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
+    return r;
+}
+__device__ __forceinline__ f32x2 pk_sub(f32x2 a, f32x2 b) {
+    f32x2 r;
+    asm("v_pk_add_f32 %0, %1, %2 neg_lo:[0,1] neg_hi:[0,1]" : "=v"(r) : "v"(a), "v"(b));
+    return r;
+}
+
+// The Winograd kernels' LDS patch rows, in 16-byte units: pixels are stored in PAIRS of 9 units (two pixels of 4 units + one padding
+// unit; the bank analysis is in conv3x3_wino.hip).  Unit offset of pixel column px inside a row:
+__device__ __forceinline__ constexpr int px_unit(int px) { return (px >> 1) * 9 + (px & 1) * 4; }
+
+// float16 (BF = false) / bfloat16 (BF = true) bits <-> float32.  bfloat16 NaN rule: a NaN keeps its sign and upper payload and gets
+// the quiet bit -- the rounding increment would carry a NaN with a full low payload into infinity or the sign.
+template <bool BF>
+__device__ __forceinline__ float half_to_f32(unsigned short v) {
+    if constexpr (BF) return __uint_as_float((unsigned)v << 16);
+    _Float16 h;
+    __builtin_memcpy(&h, &v, 2);
+    return (float)h;
+}
+template <bool BF>
+__device__ __forceinline__ unsigned short f32_to_half(float x) {  // round to nearest even
+    if constexpr (BF) {
+        unsigned u = __float_as_uint(x);
+        if ((u & 0x7fffffffu) > 0x7f800000u) return (unsigned short)((u >> 16) | 0x40u);
+        u += 0x7fffu + ((u >> 16) & 1u);
+        return (unsigned short)(u >> 16);
+    } else {
+        const _Float16 h = (_Float16)x;
+        unsigned short v;
+        __builtin_memcpy(&v, &h, 2);
+        return v;
+    }
+}
+
+// Compute units of the calling thread's CURRENT device (MI355X: 256), cached per device index (a process may drive several GPUs;
+// the first caller may be a host-only route query).  Without a usable device (build container): MI355X's 256.
+inline long device_cu_count() {
+    static std::atomic<int> cached[64] = {};
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return 256;
+    int cus = cached[dev].load(std::memory_order_relaxed);
+    if (cus == 0) {
+        if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) return 256;
+        cached[dev].store(cus, std::memory_order_relaxed);
+    }
+    return cus;
+}
+
+}  // namespace tia

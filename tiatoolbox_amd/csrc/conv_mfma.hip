@@ -27,24 +27,22 @@
 #include "../../include/tiatoolbox_amd.h"
 #include "common.hpp"
 #include "conv3x3_spatial.hpp"
+#include "conv_device.hpp"
 
 namespace {
+
+using namespace tia;
 
 constexpr int BM = 128;
 constexpr int BK = 32;
 constexpr int NTH = 256;
 constexpr int LDA = BK + 1;
 
-using f32x16 = __attribute__((ext_vector_type(16))) float;
-
 struct ConvDims {
     int n, h, w, cin, cout, ho, wo, kh, kw, stride, pad_y, pad_x;  // pad_* = zero rows / columns in front (top, left)
     unsigned x_bytes, w_bytes;  // buffer extents of this launch (both < 2^31: the host splits the batch)
     int pstride;  // floats between horizontally adjacent input pixels: cin, except for the row-packed thin-input form below
 };
-
-using u32x4 = __attribute__((ext_vector_type(4))) unsigned;
-constexpr int OOB = (int)0x80000000;  // voffset beyond every buffer extent: the load returns zeros (padding taps)
 
 // second, "post-activated" output of the epilogue: y2 = relu(v * scale[c] + shift[c]) of the value v that goes to y -- the
 // BatchNorm + ReLU that FOLLOWS a residual sum in a pre-activation network (HoVer-Net: the next unit's "preact" or the
@@ -84,11 +82,9 @@ __global__ __launch_bounds__(NTH, 2) void conv_mfma_f32_kernel(const float* __re
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int wm = wave >> 1, wn = wave & 1;
 
-    // Both operands come through buffer descriptors (built from kernel arguments only, so they live in SGPRs): a 32-bit
-    // per-lane byte offset is all the address arithmetic a load needs, and an out-of-range offset reads as zero -- which
-    // is exactly what a padding tap must contribute, without a select after the load.
-    const __amdgpu_buffer_rsrc_t rx = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(x), 0, (int)d.x_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rw = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(wk), 0, (int)d.w_bytes, 0x00020000);
+    // both operands come through buffer descriptors (conv_device.hpp)
+    const __amdgpu_buffer_rsrc_t rx = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(x), 0, (int)d.x_bytes, kBufferRsrcFlags);
+    const __amdgpu_buffer_rsrc_t rw = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(wk), 0, (int)d.w_bytes, kBufferRsrcFlags);
 
     // ---- A staging: thread -> 4 (pixel, channel-quad) slots.  Per slot: the byte offset of tap (0, 0) of its pixel
     //      (may lie before the buffer: only used when the tap is inside the image) and one bit per kernel row / column

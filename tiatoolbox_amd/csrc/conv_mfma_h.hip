@@ -31,22 +31,19 @@
 #include "../../include/tiatoolbox_amd.h"
 #include "common.hpp"
 #include "conv3x3_spatial.hpp"
+#include "conv_device.hpp"
 
 namespace {
 
+using namespace tia;
+
 constexpr int BM = 128;
 constexpr int NTH = 256;
-
-using f32x16 = __attribute__((ext_vector_type(16))) float;
-using h8 = __attribute__((ext_vector_type(8))) _Float16;
-using b8 = __attribute__((ext_vector_type(8))) __bf16;
-using u32x4 = __attribute__((ext_vector_type(4))) unsigned;
 
 struct ConvDimsH {
     int n, h, w, cin, cout, ho, wo, kh, kw, stride, pad_y, pad_x;
     unsigned x_bytes, w_bytes;
 };
-constexpr int OOB = (int)0x80000000;
 
 template <bool BF>
 __device__ __forceinline__ f32x16 mma(const u32x4& a, const u32x4& b, const f32x16& c) {
@@ -55,35 +52,6 @@ __device__ __forceinline__ f32x16 mma(const u32x4& a, const u32x4& b, const f32x
     else
         return __builtin_amdgcn_mfma_f32_32x32x16_f16(*reinterpret_cast<const h8*>(&a), *reinterpret_cast<const h8*>(&b), c, 0, 0, 0);
 }
-template <bool BF>
-__device__ __forceinline__ float half_to_f32(unsigned short v) {
-    if constexpr (BF) return __uint_as_float((unsigned)v << 16);
-    _Float16 h;
-    __builtin_memcpy(&h, &v, 2);
-    return (float)h;
-}
-template <bool BF>
-__device__ __forceinline__ unsigned short f32_to_half(float x) {  // round to nearest even
-    if constexpr (BF) {
-        unsigned u = __float_as_uint(x);
-        if ((u & 0x7fffffffu) > 0x7f800000u) return (unsigned short)((u >> 16) | 0x40u);
-        u += 0x7fffu + ((u >> 16) & 1u);
-        return (unsigned short)(u >> 16);
-    } else {
-        const _Float16 h = (_Float16)x;
-        unsigned short v;
-        __builtin_memcpy(&v, &h, 2);
-        return v;
-    }
-}
-
-// 16 bytes per lane from a buffer straight into LDS (buffer_load_dwordx4 ... lds): the wave's 64 lanes fill the 1 KB at
-// `lds_wave_base` in lane order; an out-of-range `voffset` writes zeros.  (A __device__ function: the builtin must not be seen by
-// the host pass, which otherwise drops the kernel's launch stub.)
-__device__ __forceinline__ void dma16(__amdgpu_buffer_rsrc_t rsrc, unsigned char* lds_wave_base, int voffset, int soffset) {
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (__attribute__((address_space(3))) void*)lds_wave_base, 16, voffset, soffset, 0, 0);
-}
-
 template <int BN, bool BF, int BK>
 __global__ __launch_bounds__(NTH, 2) void conv_mfma_h_kernel(const void* __restrict__ x, const void* __restrict__ wk,
                                                           const float* __restrict__ bias, const void* __restrict__ res,
@@ -113,8 +81,8 @@ __global__ __launch_bounds__(NTH, 2) void conv_mfma_h_kernel(const void* __restr
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int wm = wave >> 1, wn = wave & 1;
 
-    const __amdgpu_buffer_rsrc_t rx = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(x), 0, (int)d.x_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rw = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(wk), 0, (int)d.w_bytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rx = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(x), 0, (int)d.x_bytes, kBufferRsrcFlags);
+    const __amdgpu_buffer_rsrc_t rw = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(wk), 0, (int)d.w_bytes, kBufferRsrcFlags);
 
     // ---- A staging: thread -> LDS positions P = tid + 256 r (16-byte units, lane-linear as the DMA writes them):
     //      pixel = P / CH = tid / CH + (256 / CH) r, source chunk = (P % CH) ^ ((pixel >> SH) & (CH - 1)), the same for every r ----

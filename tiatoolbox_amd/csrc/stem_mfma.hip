@@ -35,8 +35,11 @@
 
 #include "../../include/tiatoolbox_amd.h"
 #include "common.hpp"
+#include "conv_device.hpp"
 
 namespace {
+
+using namespace tia;
 
 constexpr int NTH = 256;
 constexpr int RS = 784;          // floats per staged input row: (2 * 128 + 5) pixels * 3 = 783, + 1 (read by the zero k row)
@@ -66,11 +69,6 @@ constexpr int KCH3 = 21;                                // chunks of 8 k per pla
 constexpr int PLANE16 = (KH / 8) * COUT * 8;            // halves per packed plane in global memory: [22][64][8]
 constexpr int REGION3_B = 128 * 32 * 4;                 // >= WROWS * RS16 * 2 = 14,256 (+ the zeroed reads of the last k-step)
 constexpr int LDS_BYTES_S = REGION3_B + 3 * KCH3 * COUT * 16;
-
-using f32x16 = __attribute__((ext_vector_type(16))) float;
-using h8v = __attribute__((ext_vector_type(8))) _Float16;
-using b8v = __attribute__((ext_vector_type(8))) __bf16;
-using u32x4 = __attribute__((ext_vector_type(4))) unsigned;
 
 template <int MMA>
 __device__ __forceinline__ unsigned short to_half_bits(float x) {  // round to nearest even (finite inputs)
@@ -159,8 +157,7 @@ __global__ __launch_bounds__(NTH, 2) void stem7x7_pool_kernel(const void* __rest
     const int q0 = chunk * d.rows_per_chunk, q1 = min(d.hp, q0 + d.rows_per_chunk);
     if (q0 >= q1) return;
 
-    const __amdgpu_buffer_rsrc_t rx = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(xin), 0, (int)d.x_bytes, 0x00020000);
-    constexpr int OOB = (int)0x80000000;
+    const __amdgpu_buffer_rsrc_t rx = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(xin), 0, (int)d.x_bytes, kBufferRsrcFlags);
 
     // ---- weights and the /255 table into LDS (once) ----
     if constexpr (SPLIT) {  // no table: a byte is a bf16 number as it stands
@@ -315,23 +312,23 @@ __global__ __launch_bounds__(NTH, 2) void stem7x7_pool_kernel(const void* __rest
 #pragma unroll
                     for (int pl = 0; pl < 3; ++pl) {
                         const u32x4 c0 = wp[pl * KCH3 * COUT], c1 = wp[pl * KCH3 * COUT + 32];
-                        acc[0][0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(*reinterpret_cast<b8v*>(&a0), *reinterpret_cast<const b8v*>(&c0), acc[0][0], 0, 0, 0);
-                        acc[0][1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(*reinterpret_cast<b8v*>(&a0), *reinterpret_cast<const b8v*>(&c1), acc[0][1], 0, 0, 0);
-                        acc[1][0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(*reinterpret_cast<b8v*>(&a1), *reinterpret_cast<const b8v*>(&c0), acc[1][0], 0, 0, 0);
-                        acc[1][1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(*reinterpret_cast<b8v*>(&a1), *reinterpret_cast<const b8v*>(&c1), acc[1][1], 0, 0, 0);
+                        acc[0][0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(*reinterpret_cast<b8*>(&a0), *reinterpret_cast<const b8*>(&c0), acc[0][0], 0, 0, 0);
+                        acc[0][1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(*reinterpret_cast<b8*>(&a0), *reinterpret_cast<const b8*>(&c1), acc[0][1], 0, 0, 0);
+                        acc[1][0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(*reinterpret_cast<b8*>(&a1), *reinterpret_cast<const b8*>(&c0), acc[1][0], 0, 0, 0);
+                        acc[1][1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(*reinterpret_cast<b8*>(&a1), *reinterpret_cast<const b8*>(&c1), acc[1][1], 0, 0, 0);
                     }
                 } else {
                 const u32x4 b0 = wv[2 * s * COUT], b1 = wv[2 * s * COUT + 32];
                 if constexpr (MMA == 2) {
-                    acc[0][0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(*reinterpret_cast<b8v*>(&a0), *reinterpret_cast<const b8v*>(&b0), acc[0][0], 0, 0, 0);
-                    acc[0][1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(*reinterpret_cast<b8v*>(&a0), *reinterpret_cast<const b8v*>(&b1), acc[0][1], 0, 0, 0);
-                    acc[1][0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(*reinterpret_cast<b8v*>(&a1), *reinterpret_cast<const b8v*>(&b0), acc[1][0], 0, 0, 0);
-                    acc[1][1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(*reinterpret_cast<b8v*>(&a1), *reinterpret_cast<const b8v*>(&b1), acc[1][1], 0, 0, 0);
+                    acc[0][0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(*reinterpret_cast<b8*>(&a0), *reinterpret_cast<const b8*>(&b0), acc[0][0], 0, 0, 0);
+                    acc[0][1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(*reinterpret_cast<b8*>(&a0), *reinterpret_cast<const b8*>(&b1), acc[0][1], 0, 0, 0);
+                    acc[1][0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(*reinterpret_cast<b8*>(&a1), *reinterpret_cast<const b8*>(&b0), acc[1][0], 0, 0, 0);
+                    acc[1][1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(*reinterpret_cast<b8*>(&a1), *reinterpret_cast<const b8*>(&b1), acc[1][1], 0, 0, 0);
                 } else {
-                    acc[0][0] = __builtin_amdgcn_mfma_f32_32x32x16_f16(*reinterpret_cast<h8v*>(&a0), *reinterpret_cast<const h8v*>(&b0), acc[0][0], 0, 0, 0);
-                    acc[0][1] = __builtin_amdgcn_mfma_f32_32x32x16_f16(*reinterpret_cast<h8v*>(&a0), *reinterpret_cast<const h8v*>(&b1), acc[0][1], 0, 0, 0);
-                    acc[1][0] = __builtin_amdgcn_mfma_f32_32x32x16_f16(*reinterpret_cast<h8v*>(&a1), *reinterpret_cast<const h8v*>(&b0), acc[1][0], 0, 0, 0);
-                    acc[1][1] = __builtin_amdgcn_mfma_f32_32x32x16_f16(*reinterpret_cast<h8v*>(&a1), *reinterpret_cast<const h8v*>(&b1), acc[1][1], 0, 0, 0);
+                    acc[0][0] = __builtin_amdgcn_mfma_f32_32x32x16_f16(*reinterpret_cast<h8*>(&a0), *reinterpret_cast<const h8*>(&b0), acc[0][0], 0, 0, 0);
+                    acc[0][1] = __builtin_amdgcn_mfma_f32_32x32x16_f16(*reinterpret_cast<h8*>(&a0), *reinterpret_cast<const h8*>(&b1), acc[0][1], 0, 0, 0);
+                    acc[1][0] = __builtin_amdgcn_mfma_f32_32x32x16_f16(*reinterpret_cast<h8*>(&a1), *reinterpret_cast<const h8*>(&b0), acc[1][0], 0, 0, 0);
+                    acc[1][1] = __builtin_amdgcn_mfma_f32_32x32x16_f16(*reinterpret_cast<h8*>(&a1), *reinterpret_cast<const h8*>(&b1), acc[1][1], 0, 0, 0);
                 }
                 }
             }

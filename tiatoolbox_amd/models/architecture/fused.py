@@ -448,40 +448,34 @@ def pack_conv_weights(conv: nn.Conv2d) -> torch.Tensor:
     return out
 
 
-def pack_conv_weights_wino(conv: nn.Conv2d) -> torch.Tensor:
-    """OIHW 3x3 float32 -> the Winograd-domain weights ``U = G g G^T`` in the stage layout of ``tia_conv3x3_wino_nhwc_f32``
-    (``tia_conv_pack_weights_wino_f32``: float64 transform, one rounding), ``[16, cin/16, 2, cout/64, 2, 64, 4]``
-    (position, 16-channel slice, 8-channel half, 64-column block, 4-channel group, column, channel)."""
+def _pack_conv_weights_wino(conv: nn.Conv2d, positions: int, entry: str, form: str) -> torch.Tensor:
+    """The Winograd-domain weights of a 3x3 convolution, ``[positions, cin/16, 2, cout/64, 2, 64, 4]``, packed by `entry`."""
     from tiatoolbox_amd import _lib
 
     w = conv.weight.detach().to(torch.float32).contiguous()
     cout, cin, kh, kw = w.shape
     if (kh, kw) != (3, 3) or cin % 16 or cout % 64:
-        msg = f"Winograd F(2x2, 3x3) needs a 3x3 kernel, cin % 16 == 0 and cout % 64 == 0; got weight {tuple(w.shape)}."
+        msg = f"Winograd {form} needs a 3x3 kernel, cin % 16 == 0 and cout % 64 == 0; got weight {tuple(w.shape)}."
         raise ValueError(msg)
-    out = torch.empty((16, cin // 16, 2, cout // 64, 2, 64, 4), dtype=torch.float32, device=w.device)
+    out = torch.empty((positions, cin // 16, 2, cout // 64, 2, 64, 4), dtype=torch.float32, device=w.device)
     with torch.cuda.device(w.device):
-        rc = _lib.load().tia_conv_pack_weights_wino_f32(w.data_ptr(), cout, cin, out.data_ptr(), _lib.current_stream())
-    _lib.check(rc, "tia_conv_pack_weights_wino_f32")
+        rc = getattr(_lib.load(), entry)(w.data_ptr(), cout, cin, out.data_ptr(), _lib.current_stream())
+    _lib.check(rc, entry)
     return out
+
+
+def pack_conv_weights_wino(conv: nn.Conv2d) -> torch.Tensor:
+    """OIHW 3x3 float32 -> the Winograd-domain weights ``U = G g G^T`` in the stage layout of ``tia_conv3x3_wino_nhwc_f32``
+    (``tia_conv_pack_weights_wino_f32``: float64 transform, one rounding), ``[16, cin/16, 2, cout/64, 2, 64, 4]``
+    (position, 16-channel slice, 8-channel half, 64-column block, 4-channel group, column, channel)."""
+    return _pack_conv_weights_wino(conv, 16, "tia_conv_pack_weights_wino_f32", "F(2x2, 3x3)")
 
 
 def pack_conv_weights_wino42(conv: nn.Conv2d) -> torch.Tensor:
     """OIHW 3x3 float32 -> the F(4x2, 3x3) Winograd-domain weights ``U = G4 g G2^T`` in the stage layout of
     ``tia_conv3x3_wino42_nhwc_f32`` (``tia_conv_pack_weights_wino42_f32``: float64 transform, one rounding),
     ``[24, cin/16, 2, cout/64, 2, 64, 4]`` (position 4 i + j, then as :func:`pack_conv_weights_wino`)."""
-    from tiatoolbox_amd import _lib
-
-    w = conv.weight.detach().to(torch.float32).contiguous()
-    cout, cin, kh, kw = w.shape
-    if (kh, kw) != (3, 3) or cin % 16 or cout % 64:
-        msg = f"Winograd F(4x2, 3x3) needs a 3x3 kernel, cin % 16 == 0 and cout % 64 == 0; got weight {tuple(w.shape)}."
-        raise ValueError(msg)
-    out = torch.empty((24, cin // 16, 2, cout // 64, 2, 64, 4), dtype=torch.float32, device=w.device)
-    with torch.cuda.device(w.device):
-        rc = _lib.load().tia_conv_pack_weights_wino42_f32(w.data_ptr(), cout, cin, out.data_ptr(), _lib.current_stream())
-    _lib.check(rc, "tia_conv_pack_weights_wino42_f32")
-    return out
+    return _pack_conv_weights_wino(conv, 24, "tia_conv_pack_weights_wino42_f32", "F(4x2, 3x3)")
 
 
 @functools.lru_cache(maxsize=256)

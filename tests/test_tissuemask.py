@@ -89,7 +89,8 @@ def test_hip_maskers_bit_exact(gold, images):
 @pytest.mark.gpu
 @pytest.mark.parametrize("conn", [4, 8])
 def test_ccl_matches_scipy_label(conn):
-    """Label numbering = raster order of first pixel, exactly scipy.ndimage.label; random + adversarial masks."""
+    """Label numbering = raster order of first pixel, exactly scipy.ndimage.label; random + adversarial masks.  (One shape, the LDS
+    form only: ``tests/test_imgops_reference.py`` covers both forms of labelling and hole filling and both loads of the area filter.)"""
     import torch
     from scipy import ndimage
 

@@ -160,6 +160,9 @@ def binary_morph(mask: torch.Tensor, offsets: torch.Tensor, op: str) -> torch.Te
 
 
 def fill_holes(mask: torch.Tensor) -> torch.Tensor:
+    """``scipy.ndimage.binary_fill_holes`` (4-connected background) of uint8 ``[n,h,w]`` planes as 0/1 bytes.  No caller inside the
+    package (HoVer-Net's post-processing fills its holes inside ``tia_hover_proc_np_hv_f32``): kept as the Python door to the
+    public ABI function ``tia_fill_holes_u8``, which ``tests/test_imgops_reference.py`` checks through it in both of its forms."""
     m, n, h, w = _planes(mask)
     out = torch.empty_like(m)
     ws = torch.empty(2 * n * h * w + n, dtype=torch.int32, device=m.device)

@@ -96,101 +96,12 @@ __device__ __forceinline__ void hist_add(unsigned* bins, int bin, bool valid, co
     }
 }
 
-// Visit every pixel of one HWC uint8 image with `f(idx, r, g, b)`; block-strided.
-// Fast path reads 12 contiguous bytes (4 pixels) per lane as three dwords: lanes of a wave
-// cover 768 contiguous bytes per iteration (coalesced), and pixels never straddle lanes.
-// The next group's dwords are requested before the current group is processed (software
-// prefetch), so the L2/HBM latency hides behind the per-pixel arithmetic even at 2-4 waves/SIMD.
-template <int NT, class F>
-__device__ __forceinline__ void for_each_pixel(const uint8_t* __restrict__ p, long hw, F&& f) {
-    if (((hw & 3) == 0) && ((reinterpret_cast<uintptr_t>(p) & 3) == 0)) {
-        const long ng = hw >> 2;
-        const uint32_t* __restrict__ q = reinterpret_cast<const uint32_t*>(p);
-        long g = threadIdx.x;
-        uint32_t a = 0, b = 0, c = 0;
-        if (g < ng) {
-            a = q[g * 3 + 0];
-            b = q[g * 3 + 1];
-            c = q[g * 3 + 2];
-        }
-        while (g < ng) {
-            const long gn = g + NT;
-            uint32_t na = 0, nb = 0, nc = 0;
-            if (gn < ng) {
-                na = q[gn * 3 + 0];
-                nb = q[gn * 3 + 1];
-                nc = q[gn * 3 + 2];
-            }
-            f(g * 4 + 0, a & 255u, (a >> 8) & 255u, (a >> 16) & 255u);
-            f(g * 4 + 1, a >> 24, b & 255u, (b >> 8) & 255u);
-            f(g * 4 + 2, (b >> 16) & 255u, b >> 24, c & 255u);
-            f(g * 4 + 3, (c >> 8) & 255u, (c >> 16) & 255u, c >> 24);
-            a = na;
-            b = nb;
-            c = nc;
-            g = gn;
-        }
-    } else {
-        for (long i = threadIdx.x; i < hw; i += NT) {
-            f(i, (uint32_t)p[3 * i], (uint32_t)p[3 * i + 1], (uint32_t)p[3 * i + 2]);
-        }
-    }
-}
-
-// Same sweep, additionally telling `f` whether the wave's lanes all hold identical pixels.
-template <int NT, class F>
-__device__ __forceinline__ void for_each_pixel_w(const uint8_t* __restrict__ p, long hw, F&& f) {
-    if (((hw & 3) == 0) && ((reinterpret_cast<uintptr_t>(p) & 3) == 0)) {
-        const long ng = hw >> 2;
-        const uint32_t* __restrict__ q = reinterpret_cast<const uint32_t*>(p);
-        long g = threadIdx.x;
-        uint32_t a = 0, b = 0, c = 0;
-        if (g < ng) {
-            a = q[g * 3 + 0];
-            b = q[g * 3 + 1];
-            c = q[g * 3 + 2];
-        }
-        while (g < ng) {
-            const long gn = g + NT;
-            uint32_t na = 0, nb = 0, nc = 0;
-            if (gn < ng) {
-                na = q[gn * 3 + 0];
-                nb = q[gn * 3 + 1];
-                nc = q[gn * 3 + 2];
-            }
-#ifndef TIA_UNIFORM
-#define TIA_UNIFORM 1
-#endif
-            WaveGroup wg{false, 0, 1u};
-            if (TIA_UNIFORM) {
-                const unsigned long long act = __ballot(1);
-                wg.leader = __ffsll((long long)act) - 1;
-                const uint32_t a0 = __builtin_amdgcn_readlane(a, wg.leader);
-                const uint32_t b0 = __builtin_amdgcn_readlane(b, wg.leader);
-                const uint32_t c0 = __builtin_amdgcn_readlane(c, wg.leader);
-                wg.uniform = __ballot(a == a0 && b == b0 && c == c0) == act;
-                wg.count = (unsigned)__popcll(act);
-            }
-            f(g * 4 + 0, a & 255u, (a >> 8) & 255u, (a >> 16) & 255u, wg);
-            f(g * 4 + 1, a >> 24, b & 255u, (b >> 8) & 255u, wg);
-            f(g * 4 + 2, (b >> 16) & 255u, b >> 24, c & 255u, wg);
-            f(g * 4 + 3, (c >> 8) & 255u, (c >> 16) & 255u, c >> 24, wg);
-            a = na;
-            b = nb;
-            c = nc;
-            g = gn;
-        }
-    } else {
-        WaveGroup wg{false, 0, 1u};
-        for (long i = threadIdx.x; i < hw; i += NT) {
-            f(i, (uint32_t)p[3 * i], (uint32_t)p[3 * i + 1], (uint32_t)p[3 * i + 2], wg);
-        }
-    }
-}
-
-// Group-level sweep for straight-line kernels: `f(g, a, b, c, wg)` receives the three dwords holding
-// pixels 4g..4g+3 (bytes r0 g0 b0 r1 | g1 b1 r2 g2 | b2 r3 g3 b3).  Requires hw % 4 == 0 and a
-// 4-byte aligned image (check with `groups_ok`).  Next group's dwords are prefetched.
+// Group-level sweep: `f(g, a, b, c, wg)` receives the three dwords holding pixels 4g..4g+3 (bytes r0 g0 b0 r1 | g1 b1 r2 g2 |
+// b2 r3 g3 b3) of one HWC uint8 image; block-strided.  Requires hw % 4 == 0 and a 4-byte aligned image (check with
+// `groups_ok`).  Lanes of a wave cover 768 contiguous bytes per iteration (coalesced), and pixels never straddle lanes.
+// The next group's dwords are requested before the current group is processed (software prefetch), so the L2/HBM latency
+// hides behind the per-pixel arithmetic even at 2-4 waves/SIMD.  This is the one copy of that loop and of the uniformity
+// ballot; a caller that ignores `wg` does not pay for the ballot (it has no side effect and is dropped).
 __device__ __forceinline__ bool groups_ok(const uint8_t* p, long hw) {
     return ((hw & 3) == 0) && ((reinterpret_cast<uintptr_t>(p) & 3) == 0);
 }
@@ -237,6 +148,30 @@ __device__ __forceinline__ void unpack_group(uint32_t a, uint32_t b, uint32_t c,
     r[1] = a >> 24;           g[1] = b & 255u;          bl[1] = (b >> 8) & 255u;
     r[2] = (b >> 16) & 255u;  g[2] = b >> 24;           bl[2] = c & 255u;
     r[3] = (c >> 8) & 255u;   g[3] = (c >> 16) & 255u;  bl[3] = c >> 24;
+}
+
+// Visit every pixel of one HWC uint8 image with `f(idx, r, g, b, wg)` in ascending order per lane, `wg` telling whether the
+// wave's lanes all hold identical pixels: the group sweep where the image allows it, pixel by pixel otherwise.
+template <int NT, class F>
+__device__ __forceinline__ void for_each_pixel_w(const uint8_t* __restrict__ p, long hw, F&& f) {
+    if (groups_ok(p, hw)) {
+        for_each_group<NT>(p, hw, [&](long g, uint32_t a, uint32_t b, uint32_t c, const WaveGroup& wg) {
+            f(g * 4 + 0, a & 255u, (a >> 8) & 255u, (a >> 16) & 255u, wg);
+            f(g * 4 + 1, a >> 24, b & 255u, (b >> 8) & 255u, wg);
+            f(g * 4 + 2, (b >> 16) & 255u, b >> 24, c & 255u, wg);
+            f(g * 4 + 3, (c >> 8) & 255u, (c >> 16) & 255u, c >> 24, wg);
+        });
+    } else {
+        const WaveGroup wg{false, 0, 1u};
+        for (long i = threadIdx.x; i < hw; i += NT) {
+            f(i, (uint32_t)p[3 * i], (uint32_t)p[3 * i + 1], (uint32_t)p[3 * i + 2], wg);
+        }
+    }
+}
+// The same sweep with `f(idx, r, g, b)`.
+template <int NT, class F>
+__device__ __forceinline__ void for_each_pixel(const uint8_t* __restrict__ p, long hw, F&& f) {
+    for_each_pixel_w<NT>(p, hw, [&](long idx, uint32_t r, uint32_t g, uint32_t b, const WaveGroup&) { f(idx, r, g, b); });
 }
 
 // ---- LDS-resident labelling of small planes (imgops.hip; internal interface shared with hover_post.hip) ---------------------

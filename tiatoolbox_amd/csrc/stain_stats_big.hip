@@ -63,26 +63,6 @@ struct BigState {
     double partial[kMaxBigGroups][10];
 };
 
-__device__ __forceinline__ void big_build_tables(double* od, int (*ty)[256], const tia_stain_tables* __restrict__ tab, double plow, double phigh,
-                                                 bool z1) {
-    for (int t = threadIdx.x; t < 256; t += blockDim.x) {
-        od[t] = tab->od_lut[t];
-        int v = t;
-        if (z1 && v == 0) v = 1;
-        int ce = v;
-        if (phigh > plow) {  // contrast_enhancer LUT (utils/misc.py:438-444 + skimage rescale_intensity), folded into the Y-row tables
-            double x = (double)v;
-            x = x < plow ? plow : (x > phigh ? phigh : x);
-            x = (x - plow) / (phigh - plow);
-            x = x * 255.0 + 0.0;
-            ce = (int)x;
-        }
-        ty[0][t] = tab->ty[0][ce];
-        ty[1][t] = tab->ty[1][ce];
-        ty[2][t] = tab->ty[2][ce];
-    }
-}
-
 // this workgroup's share of the image: pixels [lo, hi), a multiple of 4 apart from the image's end
 __device__ __forceinline__ void big_span(long hw, long& lo, long& hi) {
     const long per = (((hw + gridDim.x - 1) / gridDim.x) + 15) & ~15L;  // (16 pixels: whole 16-byte units of image bytes and of bin codes)
@@ -206,39 +186,9 @@ __device__ void big_p1_finish(long hw, const tia_stain_params& prm, BigState& st
     if (prm.mode == TIA_MODE_FIXED && tid < 6) st.S[tid] = prm.stain_fixed[tid];
     __syncthreads();
     if (tid < TIA_STATS_STRIDE) out[tid] = 0.0;
-    if (tid < 64) {
-        const unsigned h0 = big_ld(&st.hist[tid * 4]), h1 = big_ld(&st.hist[tid * 4 + 1]), h2 = big_ld(&st.hist[tid * 4 + 2]),
-                       h3 = big_ld(&st.hist[tid * 4 + 3]);
-        const unsigned incl = wave_incl_scan_u32(h0 + h1 + h2 + h3);
-        const unsigned base = incl - (h0 + h1 + h2 + h3);
-        cum[tid * 4] = base + h0;
-        cum[tid * 4 + 1] = base + h0 + h1;
-        cum[tid * 4 + 2] = base + h0 + h1 + h2;
-        cum[tid * 4 + 3] = incl;
-    }
-    __syncthreads();
-    const unsigned long long nbytes = (unsigned long long)hw * 3ull;
-    unsigned long long kp[2], kn[2];
-    double gm[2];
-    np_index(nbytes, prm.q_img_lo, kp[0], kn[0], gm[0]);
-    np_index(nbytes, prm.q_img_hi, kp[1], kn[1], gm[1]);
-    {
-        const unsigned long long c1 = cum[tid], c0 = tid ? cum[tid - 1] : 0;
-        if (c0 <= kp[0] && kp[0] < c1) ibc[0] = tid;
-        if (c0 <= kn[0] && kn[0] < c1) ibc[1] = tid;
-        if (c0 <= kp[1] && kp[1] < c1) ibc[2] = tid;
-        if (c0 <= kn[1] && kn[1] < c1) ibc[3] = tid;
-        if (c0 == 0 && c1 > 0) ibc[4] = tid;                                 // min byte
-        if (c1 == (unsigned)nbytes && c0 < (unsigned)nbytes) ibc[5] = tid;  // max byte
-    }
-    __syncthreads();
+    double plow, phigh;
+    ce_percentiles(st.hist, cum, ibc, hw, prm.q_img_lo, prm.q_img_hi, plow, phigh);
     if (tid == 0) {
-        double plow = np_lerp((double)ibc[0], (double)ibc[1], gm[0]);
-        double phigh = np_lerp((double)ibc[2], (double)ibc[3], gm[1]);
-        if (plow >= phigh) {
-            plow = (double)ibc[4];
-            phigh = (double)ibc[5];
-        }
         st.plow = plow;
         st.phigh = phigh;
         st.bmin = ibc[4];
@@ -261,7 +211,10 @@ __global__ __launch_bounds__(GT) void big_moments_kernel(const uint8_t* __restri
     __shared__ double red[GT / 64][10];
     BigState& st = states[blockIdx.y];
     const uint8_t* p = img + (size_t)blockIdx.y * (size_t)hw * 3u;
-    big_build_tables(od, ty, tab, st.plow, st.phigh, prm.zero_to_one != 0);
+    for (int t = threadIdx.x; t < 256; t += blockDim.x) {
+        od[t] = tab->od_lut[t];
+        ce_luminance_tables(tab, st.plow, st.phigh, prm.zero_to_one != 0, t, ty);
+    }
     __syncthreads();
     const int y_thr = prm.y_thr;
     double acc[10];
@@ -270,20 +223,7 @@ __global__ __launch_bounds__(GT) void big_moments_kernel(const uint8_t* __restri
     long lo, hi;
     big_span(hw, lo, hi);
     big_for_each_pixel(p, lo, hi, [&](uint32_t r, uint32_t g, uint32_t b) {
-        const int t = ty[0][r] + ty[1][g] + ty[2][b];
-        if (((t + (1 << 11)) >> 12) < y_thr) {
-            const double x = od[r], y = od[g], z = od[b];
-            acc[0] += 1.0;
-            acc[1] += x;
-            acc[2] += y;
-            acc[3] += z;
-            acc[4] = __builtin_fma(x, x, acc[4]);
-            acc[5] = __builtin_fma(x, y, acc[5]);
-            acc[6] = __builtin_fma(x, z, acc[6]);
-            acc[7] = __builtin_fma(y, y, acc[7]);
-            acc[8] = __builtin_fma(y, z, acc[8]);
-            acc[9] = __builtin_fma(z, z, acc[9]);
-        }
+        if (is_tissue(ty, r, g, b, y_thr)) od_moments_add(acc, od[r], od[g], od[b]);
     });
 #pragma unroll
     for (int i = 0; i < 10; ++i) {
@@ -372,26 +312,8 @@ __device__ void big_eigen(int groups, const tia_stain_params& prm, BigState& st,
         return;
     }
     if (n_tissue < 2) st.flags |= TIA_FLAG_DEGENERATE;
-    const double mx = acc[1] / nt, my = acc[2] / nt, mz = acc[3] / nt;
-    const double f = 1.0 / (nt - 1.0);
-    double cov[6];
-    cov[0] = (acc[4] - nt * mx * mx) * f;
-    cov[1] = (acc[5] - nt * mx * my) * f;
-    cov[2] = (acc[6] - nt * mx * mz) * f;
-    cov[3] = (acc[7] - nt * my * my) * f;
-    cov[4] = (acc[8] - nt * my * mz) * f;
-    cov[5] = (acc[9] - nt * mz * mz) * f;
-    double w[3], v[3][3];
-    jacobi3(cov, w, v);
-    // eigh: ascending eigenvalues; reference takes columns [2,1] = largest, 2nd largest
-    int i0 = 0, i1 = 1, i2 = 2;
-    if (w[i0] < w[i1]) { int t = i0; i0 = i1; i1 = t; }
-    if (w[i0] < w[i2]) { int t = i0; i0 = i2; i2 = t; }
-    if (w[i1] < w[i2]) { int t = i1; i1 = i2; i2 = t; }
-    double e1[3] = {v[0][i0], v[1][i0], v[2][i0]};
-    double e2[3] = {v[0][i1], v[1][i1], v[2][i1]};
-    if (e1[0] < 0) { e1[0] = -e1[0]; e1[1] = -e1[1]; e1[2] = -e1[2]; }
-    if (e2[0] < 0) { e2[0] = -e2[0]; e2[1] = -e2[1]; e2[2] = -e2[2]; }
+    double cov[6], e1[3], e2[3];
+    stats_eigen(acc, cov, e1, e2);
     for (int i = 0; i < 6; ++i) out[TIA_ST_COV + i] = cov[i];
     for (int i = 0; i < 3; ++i) {
         st.e1[i] = e1[i];
@@ -450,7 +372,10 @@ __global__ __launch_bounds__(GT) void big_lin_sweep_kernel(const uint8_t* __rest
     if (st.skip || st.fast != 1) return;  // (uniform)
     const uint8_t* p = img + (size_t)blockIdx.y * (size_t)hw * 3u;
     uint16_t* codes = codes_all + (size_t)blockIdx.y * 2u * (size_t)hw;
-    big_build_tables(od, ty, tab, st.plow, st.phigh, prm.zero_to_one != 0);
+    for (int t = threadIdx.x; t < 256; t += blockDim.x) {
+        od[t] = tab->od_lut[t];
+        ce_luminance_tables(tab, st.plow, st.phigh, prm.zero_to_one != 0, t, ty);
+    }
     double a[3], c[3];
 #pragma unroll
     for (int i = 0; i < 3; ++i) {
@@ -472,8 +397,7 @@ __global__ __launch_bounds__(GT) void big_lin_sweep_kernel(const uint8_t* __rest
         unsigned c0 = 0xffffu, c1 = 0xffffu;
         bool member = true;
         if (KIND == 0) {
-            const int t = ty[0][r] + ty[1][g] + ty[2][b];
-            member = ((t + (1 << 11)) >> 12) < y_thr;
+            member = is_tissue(ty, r, g, b, y_thr);
         }
         if (member) {
             double x[2];
@@ -874,7 +798,10 @@ __global__ __launch_bounds__(GT) void big_select_sweep_kernel(const uint8_t* __r
     BigState& st = states[blockIdx.y];
     if (st.skip || st.shift < 0) return;  // (uniform; the common case: no list overflowed, nothing to do)
     const uint8_t* p = img + (size_t)blockIdx.y * (size_t)hw * 3u;
-    big_build_tables(od, ty, tab, st.plow, st.phigh, prm.zero_to_one != 0);
+    for (int t = threadIdx.x; t < 256; t += blockDim.x) {
+        od[t] = tab->od_lut[t];
+        ce_luminance_tables(tab, st.plow, st.phigh, prm.zero_to_one != 0, t, ty);
+    }
     // ALL digit passes in this one launch (the host launches the fall-back unconditionally: six launches per selection that return at
     // once cost 4.5 us each).  Between passes the image's workgroups meet at a barrier built on `gen`: the workgroup that delivers last
     // runs the decision step, publishes it (release fence) and advances `gen`; the others sleep-spin on it.  The workgroups of an
@@ -906,8 +833,7 @@ __global__ __launch_bounds__(GT) void big_select_sweep_kernel(const uint8_t* __r
     big_span(hw, lo, hi);
     big_for_each_pixel(p, lo, hi, [&](uint32_t r, uint32_t g, uint32_t b) {
         if (KIND == 0) {
-            const int t = ty[0][r] + ty[1][g] + ty[2][b];
-            if (!(((t + (1 << 11)) >> 12) < y_thr)) return;
+            if (!is_tissue(ty, r, g, b, y_thr)) return;
         }
         const double ox = od[r], oy = od[g], oz = od[b];
         const double p0 = dot3(ox, oy, oz, a[0], a[1], a[2]);
@@ -1002,18 +928,6 @@ __device__ void big_select_step(BigState& st) {
 }
 
 // ---- after the angular selection: stain vectors, pseudo-inverse, start of the concentration selection ----------------------------
-__device__ __forceinline__ void big_pinv(const double (&S)[6], double (&P)[6]) {
-    const double a = S[0] * S[0] + S[1] * S[1] + S[2] * S[2];
-    const double bb = S[0] * S[3] + S[1] * S[4] + S[2] * S[5];
-    const double d = S[3] * S[3] + S[4] * S[4] + S[5] * S[5];
-    const double det = a * d - bb * bb;
-    const double g00 = d / det, g01 = -bb / det, g11 = a / det;
-    for (int j = 0; j < 3; ++j) {
-        P[j * 2 + 0] = S[j] * g00 + S[3 + j] * g01;
-        P[j * 2 + 1] = S[j] * g01 + S[3 + j] * g11;
-    }
-}
-
 __global__ __launch_bounds__(64) void big_vectors_kernel(long hw, tia_stain_params prm, const tia_stain_tables* __restrict__ tab,
                                                          BigState* __restrict__ states, double* __restrict__ stats) {
     const double* od_lut = tab->od_lut;
@@ -1022,30 +936,21 @@ __global__ __launch_bounds__(64) void big_vectors_kernel(long hw, tia_stain_para
     if (threadIdx.x != 0 || st.skip) return;
     double S[6];
     if (prm.mode == TIA_MODE_MACENKO) {
-        const double vp0 = key_f64(st.prefix[0]), vn0 = key_f64(st.prefix[1]), vp1 = key_f64(st.prefix[2]), vn1 = key_f64(st.prefix[3]);
-        const double min_phi = np_lerp(angle_of_key(vp0), angle_of_key(vn0), st.gm[0]);
-        const double max_phi = np_lerp(angle_of_key(vp1), angle_of_key(vn1), st.gm[1]);
-        out[TIA_ST_MINPHI] = min_phi;
-        out[TIA_ST_MAXPHI] = max_phi;
-        const double c1 = cos(min_phi), s1 = sin(min_phi), c2 = cos(max_phi), s2 = sin(max_phi);
-        const double* e1 = st.e1;
-        const double* e2 = st.e2;
-        double v1[3] = {e1[0] * c1 + e2[0] * s1, e1[1] * c1 + e2[1] * s1, e1[2] * c1 + e2[2] * s1};
-        double v2[3] = {e1[0] * c2 + e2[0] * s2, e1[1] * c2 + e2[1] * s2, e1[2] * c2 + e2[2] * s2};
-        const bool first = v1[0] > v2[0];
-        const double* h = first ? v1 : v2;
-        const double* e = first ? v2 : v1;
-        const double nh = sqrt(h[0] * h[0] + h[1] * h[1] + h[2] * h[2]);
-        const double ne = sqrt(e[0] * e[0] + e[1] * e[1] + e[2] * e[2]);
+        const double vp[2] = {key_f64(st.prefix[0]), key_f64(st.prefix[2])}, vn[2] = {key_f64(st.prefix[1]), key_f64(st.prefix[3])};
+        const double gm[2] = {st.gm[0], st.gm[1]}, e1[3] = {st.e1[0], st.e1[1], st.e1[2]}, e2[3] = {st.e2[0], st.e2[1], st.e2[2]};
+        double phi[2], hv[3], ev[3];
+        stats_stain_from_angles(vp, vn, gm, e1, e2, phi, hv, ev);
+        out[TIA_ST_MINPHI] = phi[0];
+        out[TIA_ST_MAXPHI] = phi[1];
         for (int i = 0; i < 3; ++i) {
-            S[i] = h[i] / nh;
-            S[3 + i] = e[i] / ne;
+            S[i] = hv[i];
+            S[3 + i] = ev[i];
         }
     } else {
         for (int i = 0; i < 6; ++i) S[i] = st.S[i];
     }
     double P[6];
-    big_pinv(S, P);
+    stats_pinv(S, P);
     for (int i = 0; i < 6; ++i) {
         st.S[i] = S[i];
         st.P[i] = P[i];
@@ -1056,20 +961,10 @@ __global__ __launch_bounds__(64) void big_vectors_kernel(long hw, tia_stain_para
     np_index((unsigned long long)hw, prm.q_conc, kp, kn, gm);
     st.gm[0] = st.gm[1] = gm;
     const unsigned long long ranks[kSelTargets] = {kp, kn, kp, kn};
-    // rigorous value bounds from the byte range: od in [od(bmax), od(bmin)] (the OD table is decreasing in the byte)
-    double lo[2] = {0.0, 0.0}, hi[2] = {0.0, 0.0};
-    const double oa = od_lut[st.bmax], ob = od_lut[st.bmin];
-    for (int t = 0; t < 2; ++t) {
-        for (int j = 0; j < 3; ++j) {
-            const double u = P[j * 2 + t] * oa, w = P[j * 2 + t] * ob;
-            lo[t] += u < w ? u : w;
-            hi[t] += u < w ? w : u;
-        }
-        const double pad = 1e-9 * (fabs(lo[t]) + fabs(hi[t])) + 1e-12;
-        lo[t] -= pad;
-        hi[t] += pad;
+    double lo[2], hi[2];
+    conc_bounds(P, od_lut[st.bmax], od_lut[st.bmin], lo, hi);
+    for (int t = 0; t < 2; ++t)
         if (!(hi[t] > lo[t])) hi[t] = lo[t] + 1.0;
-    }
     big_start_selection(st, ranks, 2, lo, hi);
 }
 
@@ -1080,29 +975,7 @@ __global__ __launch_bounds__(64) void big_final_kernel(tia_stain_params prm, Big
     double maxc[2];
     maxc[0] = np_lerp(key_f64(st.prefix[0]), key_f64(st.prefix[1]), st.gm[0]);
     maxc[1] = np_lerp(key_f64(st.prefix[2]), key_f64(st.prefix[3]), st.gm[1]);
-    unsigned flags = st.flags;
-    const double* S = st.S;
-    const double* P = st.P;
-    for (int i = 0; i < 6; ++i) {
-        out[TIA_ST_STAIN + i] = S[i];
-        out[TIA_ST_PINV + i] = P[i];
-    }
-    out[TIA_ST_MAXC + 0] = maxc[0];
-    out[TIA_ST_MAXC + 1] = maxc[1];
-    bool finite = true;
-    for (int i = 0; i < 6; ++i) finite = finite && isfinite(S[i]) && isfinite(P[i]);
-    finite = finite && isfinite(maxc[0]) && isfinite(maxc[1]);
-    if (!finite) flags |= TIA_FLAG_DEGENERATE;
-    if (prm.has_target) {
-        const double sc0 = prm.target_maxc[0] / maxc[0], sc1 = prm.target_maxc[1] / maxc[1];
-        if (!(isfinite(sc0) && isfinite(sc1))) flags |= TIA_FLAG_DEGENERATE;  // zero 99th-percentile concentration
-        out[TIA_ST_SCALE + 0] = sc0;
-        out[TIA_ST_SCALE + 1] = sc1;
-        for (int j = 0; j < 3; ++j)
-            for (int c = 0; c < 3; ++c)
-                out[TIA_ST_M + j * 3 + c] = P[j * 2 + 0] * sc0 * prm.target_stain[c] + P[j * 2 + 1] * sc1 * prm.target_stain[3 + c];
-    }
-    out[TIA_ST_FLAGS] = (double)flags;
+    stats_finish_record(out, prm, st.S, st.P, maxc, st.flags);
     // diagnostics of this path in the instrumentation slots: per selection, whether it fell back to the radix passes and the sizes
     // of its candidate lists
     for (int k = 0; k < 2; ++k)

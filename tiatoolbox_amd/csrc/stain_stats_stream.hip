@@ -159,74 +159,21 @@ __global__ __launch_bounds__(NT, DL ? TIA_STATS_WPE_DL : TIA_STATS_WPE) void sta
     }
     __syncthreads();
     }
-    if (tid < 64) {  // inclusive prefix over 256 bins: 4 consecutive bins per lane + one wave scan
-        const unsigned h0 = s.hist[tid * 4], h1 = s.hist[tid * 4 + 1], h2 = s.hist[tid * 4 + 2], h3 = s.hist[tid * 4 + 3];
-        const unsigned incl = wave_incl_scan_u32(h0 + h1 + h2 + h3);
-        const unsigned base = incl - (h0 + h1 + h2 + h3);
-        s.cum[tid * 4] = base + h0;
-        s.cum[tid * 4 + 1] = base + h0 + h1;
-        s.cum[tid * 4 + 2] = base + h0 + h1 + h2;
-        s.cum[tid * 4 + 3] = incl;
-    }
-    __syncthreads();
     {
-        const unsigned long long nbytes = (unsigned long long)hw * 3ull;
-        unsigned long long kp[2], kn[2];
-        double gm[2];
-        np_index(nbytes, prm.q_img_lo, kp[0], kn[0], gm[0]);
-        np_index(nbytes, prm.q_img_hi, kp[1], kn[1], gm[1]);
-        if (tid < 256) {
-            const unsigned long long c1 = s.cum[tid], c0 = tid ? s.cum[tid - 1] : 0;
-            if (c0 <= kp[0] && kp[0] < c1) s.ibc[0] = tid;
-            if (c0 <= kn[0] && kn[0] < c1) s.ibc[1] = tid;
-            if (c0 <= kp[1] && kp[1] < c1) s.ibc[2] = tid;
-            if (c0 <= kn[1] && kn[1] < c1) s.ibc[3] = tid;
-            if (c0 == 0 && c1 > 0) s.ibc[4] = tid;                                 // min byte
-            if (c1 == (unsigned)nbytes && c0 < (unsigned)nbytes) s.ibc[5] = tid;  // max byte
-        }
-        __syncthreads();
+        double plow, phigh;
+        ce_percentiles(s.hist, s.cum, s.ibc, hw, prm.q_img_lo, prm.q_img_hi, plow, phigh);
         if (tid == 0) {
-            // uint8 subtraction b-a is non-negative here (sorted), so no wrap-around to mimic
-            double plow = np_lerp((double)s.ibc[0], (double)s.ibc[1], gm[0]);
-            double phigh = np_lerp((double)s.ibc[2], (double)s.ibc[3], gm[1]);
-            if (plow >= phigh) {
-                plow = (double)s.ibc[4];
-                phigh = (double)s.ibc[5];
-            }
-            s.bc[0] = plow;
-            s.bc[1] = phigh;
             out[TIA_ST_PLOW] = plow;
             out[TIA_ST_PHIGH] = phigh;
         }
-        __syncthreads();
+        if (tid < 256) ce_luminance_tables(tab, plow, phigh, z1, tid, s.ty);
     }
     const int bmin = s.ibc[4], bmax = s.ibc[5];
-    if (tid < 256) {
-        // contrast_enhancer LUT (utils/misc.py:438-444 + skimage rescale_intensity), folded into
-        // the Y-row luminance tables: ty[c][v] = C[3+c]*sRGBGamma[ce(v)]
-        const double plow = s.bc[0], phigh = s.bc[1];
-        int v = tid;
-        if (z1 && v == 0) v = 1;
-        int ce = v;
-        if (phigh > plow) {
-            double x = (double)v;
-            x = x < plow ? plow : (x > phigh ? phigh : x);
-            x = (x - plow) / (phigh - plow);
-            x = x * 255.0 + 0.0;
-            ce = (int)x;
-        }
-        s.ty[0][tid] = tab->ty[0][ce];
-        s.ty[1][tid] = tab->ty[1][ce];
-        s.ty[2][tid] = tab->ty[2][ce];
-    }
     __syncthreads();
 
     stamp(s, TM_LUT);
     const int y_thr = prm.y_thr;
-    auto is_tissue = [&](uint32_t r, uint32_t g, uint32_t b) -> bool {
-        const int t = s.ty[0][r] + s.ty[1][g] + s.ty[2][b];
-        return ((t + (1 << 11)) >> 12) < y_thr;
-    };
+    auto is_tissue = [&](uint32_t r, uint32_t g, uint32_t b) -> bool { return tia::is_tissue(s.ty, r, g, b, y_thr); };
     // P2 records the mask as bits in LDS; later passes test a bit instead of three table look-ups
     const bool use_bits = hw <= (long)MASK_WORDS * 32;
     if (use_bits && !grp && !DL && prm.mode == TIA_MODE_MACENKO) {  // the per-pixel path ORs single bits
@@ -236,23 +183,6 @@ __global__ __launch_bounds__(NT, DL ? TIA_STATS_WPE_DL : TIA_STATS_WPE) void sta
     auto is_tissue_cached = [&](long idx, uint32_t r, uint32_t g, uint32_t b) -> bool {
         if (use_bits) return (s.mbits[idx >> 5] >> (idx & 31)) & 1u;
         return is_tissue(r, g, b);
-    };
-    // float32 optical density on the VALU (no table): -ln(max(v,1)/255) clamped at 1e-6 like rgb2od; |error| < 5e-7
-    // (v_log_f32 is accurate to 1 ulp).  Only ever used to CLASSIFY pixels against selection windows, with that error
-    // bound (and a wide margin) built into the comparison; every value that enters a result is float64 from the table.
-    auto od32 = [](uint32_t v) -> float {
-        const float f = (float)(v ? v : 1u) * (1.0f / 255.0f);
-        const float o = -0.69314718f * __log2f(f);
-        return o > 1e-6f ? o : 1e-6f;
-    };
-    // append one entry per lane that needs it to this wave's private list segment: position = wave count (uniform, in a
-    // register) + number of needing lanes below this one (v_mbcnt); no atomics, no cross-lane traffic
-    auto seg_push = [&](bool need, unsigned entry, unsigned* seg, unsigned cap, unsigned& count) {
-        const unsigned long long m = __ballot(need);
-        const unsigned before = __builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0u));
-        const unsigned pos = count + before;
-        if (need && pos < cap) seg[pos] = entry;
-        count += (unsigned)__popcll(m);
     };
 
     double S[6];  // source stain matrix rows H,E
@@ -281,22 +211,13 @@ __global__ __launch_bounds__(NT, DL ? TIA_STATS_WPE_DL : TIA_STATS_WPE) void sta
                     x[i] = OD(rr[i]);
                     y[i] = OD(gg[i]);
                     z[i] = OD(bb[i]);
-                    lum[i] = s.ty[0][rr[i]] + s.ty[1][gg[i]] + s.ty[2][bb[i]];
+                    lum[i] = tissue_lum(s.ty, rr[i], gg[i], bb[i]);
                 }
 #pragma unroll
                 for (int i = 0; i < 4; ++i) {
-                    if (((lum[i] + (1 << 11)) >> 12) < y_thr) {
+                    if (lum_is_tissue(lum[i], y_thr)) {
                         nib |= 1u << i;
-                        ac[0] += 1.0;
-                        ac[1] += x[i];
-                        ac[2] += y[i];
-                        ac[3] += z[i];
-                        ac[4] = __builtin_fma(x[i], x[i], ac[4]);
-                        ac[5] = __builtin_fma(x[i], y[i], ac[5]);
-                        ac[6] = __builtin_fma(x[i], z[i], ac[6]);
-                        ac[7] = __builtin_fma(y[i], y[i], ac[7]);
-                        ac[8] = __builtin_fma(y[i], z[i], ac[8]);
-                        ac[9] = __builtin_fma(z[i], z[i], ac[9]);
+                        od_moments_add(ac, x[i], y[i], z[i]);
                     }
                 }
                 if (use_bits) {  // 8 consecutive lanes hold 32 consecutive pixels: one mask word
@@ -340,16 +261,7 @@ __global__ __launch_bounds__(NT, DL ? TIA_STATS_WPE_DL : TIA_STATS_WPE) void sta
             const double x = OD(r), y = OD(g), z = OD(b);
             if (is_tissue(r, g, b)) {
                 if (use_bits) atomicOr(&s.mbits[idx >> 5], 1u << (idx & 31));
-                acc[0] += 1.0;
-                acc[1] += x;
-                acc[2] += y;
-                acc[3] += z;
-                acc[4] = __builtin_fma(x, x, acc[4]);
-                acc[5] = __builtin_fma(x, y, acc[5]);
-                acc[6] = __builtin_fma(x, z, acc[6]);
-                acc[7] = __builtin_fma(y, y, acc[7]);
-                acc[8] = __builtin_fma(y, z, acc[8]);
-                acc[9] = __builtin_fma(z, z, acc[9]);
+                od_moments_add(acc, x, y, z);
             }
         });
         block_sum(acc, s);
@@ -366,26 +278,8 @@ __global__ __launch_bounds__(NT, DL ? TIA_STATS_WPE_DL : TIA_STATS_WPE) void sta
         }
         if (n_tissue < 2) flags |= TIA_FLAG_DEGENERATE;
         if (tid == 0) {
-            const double mx = acc[1] / nt, my = acc[2] / nt, mz = acc[3] / nt;
-            const double f = 1.0 / (nt - 1.0);
-            double cov[6];
-            cov[0] = (acc[4] - nt * mx * mx) * f;
-            cov[1] = (acc[5] - nt * mx * my) * f;
-            cov[2] = (acc[6] - nt * mx * mz) * f;
-            cov[3] = (acc[7] - nt * my * my) * f;
-            cov[4] = (acc[8] - nt * my * mz) * f;
-            cov[5] = (acc[9] - nt * mz * mz) * f;
-            double w[3], v[3][3];
-            jacobi3(cov, w, v);
-            // eigh: ascending eigenvalues; reference takes columns [2,1] = largest, 2nd largest
-            int i0 = 0, i1 = 1, i2 = 2;
-            if (w[i0] < w[i1]) { int t = i0; i0 = i1; i1 = t; }
-            if (w[i0] < w[i2]) { int t = i0; i0 = i2; i2 = t; }
-            if (w[i1] < w[i2]) { int t = i1; i1 = i2; i2 = t; }
-            double e1[3] = {v[0][i0], v[1][i0], v[2][i0]};
-            double e2[3] = {v[0][i1], v[1][i1], v[2][i1]};
-            if (e1[0] < 0) { e1[0] = -e1[0]; e1[1] = -e1[1]; e1[2] = -e1[2]; }
-            if (e2[0] < 0) { e2[0] = -e2[0]; e2[1] = -e2[1]; e2[2] = -e2[2]; }
+            double cov[6], e1[3], e2[3];
+            stats_eigen(acc, cov, e1, e2);
             for (int i = 0; i < 6; ++i) out[TIA_ST_COV + i] = cov[i];
             for (int i = 0; i < 3; ++i) {
                 s.bc[2 + i] = e1[i];
@@ -410,30 +304,16 @@ __global__ __launch_bounds__(NT, DL ? TIA_STATS_WPE_DL : TIA_STATS_WPE) void sta
         double vp[2], vn[2];
         bool phi_done = false;
         if (prm.select_mode != 1) {
-            // float32 classification: with L_c = log2(max(v_c, 1)) the projections are x = Kx - sum_c ex_c L_c (ex = ln2 e1,
-            // Kx = log2(255) sum_c ex_c), likewise y; for window edges kb in [-1, 1] and x > 0, key < kb <=> y - kb (|x|+|y|) < 0.
-            // Error budget of s = y - kb d: |dL| <= 1 ulp(8) = 9.6e-7, constants rounded to float32 (6e-8 x 8), three FMA
-            // roundings (6e-8 x 10 each), the 1e-6 clamp of od(255): |dx|, |dy| <= 7e-6, |ds| <= 3 x 7e-6; four-fold margin.
-            const float ln2 = 0.6931471805599453f, l255 = 7.994353436858858f;
-            const float ex0 = ln2 * (float)e1x, ex1 = ln2 * (float)e1y, ex2 = ln2 * (float)e1z;
-            const float ey0 = ln2 * (float)e2x, ey1 = ln2 * (float)e2y, ey2 = ln2 * (float)e2z;
-            const float kx = l255 * (ex0 + ex1 + ex2), ky = l255 * (ey0 + ey1 + ey2);
-            const float tol = 8.0e-5f;
-            auto proj = [&](uint32_t r, uint32_t g, uint32_t b, float& x, float& y) {
-                const float lr = __log2f(fmaxf((float)r, 1.0f)), lg = __log2f(fmaxf((float)g, 1.0f)),
-                            lb = __log2f(fmaxf((float)b, 1.0f));
-                x = fmaf(-ex2, lb, fmaf(-ex1, lg, fmaf(-ex0, lr, kx)));
-                y = fmaf(-ey2, lb, fmaf(-ey1, lg, fmaf(-ey0, lr, ky)));
-            };
+            // float32 classification (Proj32, stain_stats_common.hpp): x, y = projections on the two eigenvectors
+            const Proj32<Log2Insn> proj(e1x, e1y, e1z, e2x, e2y, e2z, Log2Insn{});
+            const float tol = angle_tol;
             phi_done = window_select2(
                 p, hw,
                 [&](long idx, uint32_t r, uint32_t g, uint32_t b, float (&v)[2]) -> unsigned {
                     if (!is_tissue_cached(idx, r, g, b)) return 0u;
                     float x, y;
                     proj(r, g, b, x, y);
-                    const float d = fabsf(x) + fabsf(y);
-                    const float q = d > 0.0f ? y / d : 0.0f;
-                    v[0] = v[1] = x >= 0.0f ? q : (y >= 0.0f ? 2.0f - q : -2.0f - q);
+                    v[0] = v[1] = pseudo_angle32(y, x);
                     return 3u;
                 },
                 [&](long idx, uint32_t r, uint32_t g, uint32_t b, double (&x)[2]) -> unsigned {
@@ -447,7 +327,7 @@ __global__ __launch_bounds__(NT, DL ? TIA_STATS_WPE_DL : TIA_STATS_WPE) void sta
                 [&](unsigned* list, unsigned seg_cap) {
                     // window edges outside [-1, 1] (keys of the x < 0 half plane) are not handled by the cross-product
                     // test: every tissue pixel then becomes a candidate, the overflow check falls back to select2
-                    const double w[4] = {s.wlo[0], s.whi[0], s.wlo[1], s.whi[1]};
+                    const double w[4] = {s.ws.wlo[0], s.ws.whi[0], s.ws.wlo[1], s.ws.whi[1]};
                     bool edges_ok = true;
 #pragma unroll
                     for (int i = 0; i < 4; ++i) edges_ok = edges_ok && (!(fabs(w[i]) < 1e300) || fabs(w[i]) <= 1.0);
@@ -484,8 +364,8 @@ __global__ __launch_bounds__(NT, DL ? TIA_STATS_WPE_DL : TIA_STATS_WPE) void sta
                     });
                     if (lane_id() == 0) {
                         s.wcnt[wave_id()] = count;
-                        if (bl0) atomicAdd(&s.wbelow[0], (unsigned long long)bl0);
-                        if (bl1) atomicAdd(&s.wbelow[1], (unsigned long long)bl1);
+                        if (bl0) atomicAdd(&s.ws.wbelow[0], (unsigned long long)bl0);
+                        if (bl1) atomicAdd(&s.ws.wbelow[1], (unsigned long long)bl1);
                     }
                 },
                 s, kp, nn, vp, vn);
@@ -514,12 +394,12 @@ __global__ __launch_bounds__(NT, DL ? TIA_STATS_WPE_DL : TIA_STATS_WPE) void sta
                             ox[i] = OD(rr[i]);
                             oy[i] = OD(gg[i]);
                             oz[i] = OD(bb[i]);
-                            lum[i] = s.ty[0][rr[i]] + s.ty[1][gg[i]] + s.ty[2][bb[i]];
+                            lum[i] = tissue_lum(s.ty, rr[i], gg[i], bb[i]);
                         }
                         unsigned long long codes = 0ull;
 #pragma unroll
                         for (int i = 0; i < 4; ++i) {
-                            const bool tissue = ((lum[i] + (1 << 11)) >> 12) < y_thr;
+                            const bool tissue = lum_is_tissue(lum[i], y_thr);
                             const double p0 = dot3(ox[i], oy[i], oz[i], e1x, e1y, e1z);
                             const double p1 = dot3(ox[i], oy[i], oz[i], e2x, e2y, e2z);
                             const double d = (pseudo_angle(p1, p0) - lo) * sc;
@@ -544,21 +424,14 @@ __global__ __launch_bounds__(NT, DL ? TIA_STATS_WPE_DL : TIA_STATS_WPE) void sta
         }
 #endif
         if (tid == 0) {
-            const double min_phi = np_lerp(angle_of_key(vp[0]), angle_of_key(vn[0]), gm[0]);
-            const double max_phi = np_lerp(angle_of_key(vp[1]), angle_of_key(vn[1]), gm[1]);
-            out[TIA_ST_MINPHI] = min_phi;
-            out[TIA_ST_MAXPHI] = max_phi;
-            const double c1 = cos(min_phi), s1 = sin(min_phi), c2 = cos(max_phi), s2 = sin(max_phi);
-            double v1[3] = {e1x * c1 + e2x * s1, e1y * c1 + e2y * s1, e1z * c1 + e2z * s1};
-            double v2[3] = {e1x * c2 + e2x * s2, e1y * c2 + e2y * s2, e1z * c2 + e2z * s2};
-            const bool first = v1[0] > v2[0];
-            const double* h = first ? v1 : v2;
-            const double* e = first ? v2 : v1;
-            const double nh = sqrt(h[0] * h[0] + h[1] * h[1] + h[2] * h[2]);
-            const double ne = sqrt(e[0] * e[0] + e[1] * e[1] + e[2] * e[2]);
+            const double e1[3] = {e1x, e1y, e1z}, e2[3] = {e2x, e2y, e2z};
+            double phi[2], hv[3], ev[3];
+            stats_stain_from_angles(vp, vn, gm, e1, e2, phi, hv, ev);
+            out[TIA_ST_MINPHI] = phi[0];
+            out[TIA_ST_MAXPHI] = phi[1];
             for (int i = 0; i < 3; ++i) {
-                s.bc[8 + i] = h[i] / nh;
-                s.bc[11 + i] = e[i] / ne;
+                s.bc[8 + i] = hv[i];
+                s.bc[11 + i] = ev[i];
             }
         }
         __syncthreads();
@@ -578,16 +451,7 @@ __global__ __launch_bounds__(NT, DL ? TIA_STATS_WPE_DL : TIA_STATS_WPE) void sta
         for_each_pixel<NT>(p, hw, [&](long, uint32_t r, uint32_t g, uint32_t b) {
             if (is_tissue(r, g, b)) {
                 const double x = OD(r), y = OD(g), z = OD(b);
-                acc[0] += 1.0;
-                acc[1] += x;
-                acc[2] += y;
-                acc[3] += z;
-                acc[4] = __builtin_fma(x, x, acc[4]);
-                acc[5] = __builtin_fma(x, y, acc[5]);
-                acc[6] = __builtin_fma(x, z, acc[6]);
-                acc[7] = __builtin_fma(y, y, acc[7]);
-                acc[8] = __builtin_fma(y, z, acc[8]);
-                acc[9] = __builtin_fma(z, z, acc[9]);
+                od_moments_add(acc, x, y, z);
             }
         });
         block_sum(acc, s);
@@ -607,10 +471,8 @@ __global__ __launch_bounds__(NT, DL ? TIA_STATS_WPE_DL : TIA_STATS_WPE) void sta
             const double g6[6] = {acc[4], acc[5], acc[6], acc[7], acc[8], acc[9]};
             double w[3], v[3][3];
             jacobi3(g6, w, v);
-            int i0 = 0, i1 = 1, i2 = 2;
-            if (w[i0] < w[i1]) { int t = i0; i0 = i1; i1 = t; }
-            if (w[i0] < w[i2]) { int t = i0; i0 = i2; i2 = t; }
-            if (w[i1] < w[i2]) { int t = i1; i1 = i2; i2 = t; }
+            int i0, i1, i2;
+            eigen_descending(w, i0, i1, i2);
             const int order[2] = {i0, i1};
             for (int k = 0; k < 2; ++k) {
                 double u[3] = {v[0][order[k]], v[1][order[k]], v[2][order[k]]};
@@ -809,20 +671,9 @@ __global__ __launch_bounds__(NT, DL ? TIA_STATS_WPE_DL : TIA_STATS_WPE) void sta
         stamp(s, TM_P2);
     }
 
-    // ---- pseudo-inverse: C = OD . P,  P = S^T (S S^T)^-1  (lstsq of stainnorm.py:65) ----------
+    // ---- pseudo-inverse (lstsq of stainnorm.py:65) ----------
     double P[6];
-    {
-        const double a = S[0] * S[0] + S[1] * S[1] + S[2] * S[2];
-        const double bb = S[0] * S[3] + S[1] * S[4] + S[2] * S[5];
-        const double d = S[3] * S[3] + S[4] * S[4] + S[5] * S[5];
-        const double det = a * d - bb * bb;
-        const double g00 = d / det, g01 = -bb / det, g11 = a / det;
-#pragma unroll
-        for (int j = 0; j < 3; ++j) {
-            P[j * 2 + 0] = S[j] * g00 + S[3 + j] * g01;
-            P[j * 2 + 1] = S[j] * g01 + S[3 + j] * g11;
-        }
-    }
+    stats_pinv(S, P);
 
     // ---- P5/P6: exact percentile of both concentration channels over ALL pixels ----------------
     double maxc[2];
@@ -855,21 +706,16 @@ __global__ __launch_bounds__(NT, DL ? TIA_STATS_WPE_DL : TIA_STATS_WPE) void sta
                 if (tid < 6) s.chm[tid] = cm[tid];
                 __syncthreads();
             }
-            // rigorous value bounds from the byte range: od in [od(bmax), od(bmin)]
-            const double oa = OD(bmax), ob = OD(bmin);
+            conc_bounds(P, OD(bmax), OD(bmin), olo0, ohi0);
             const double inv_n = 1.0 / (double)hw;
     #pragma unroll
             for (int t = 0; t < 2; ++t) {
-                double lo = 0.0, hi = 0.0, mu = 0.0;
+                double mu = 0.0;
                 double mj[3];
     #pragma unroll
                 for (int j = 0; j < 3; ++j) {
-                    const double c = P[j * 2 + t];
-                    const double u = c * oa, w = c * ob;
-                    lo += u < w ? u : w;
-                    hi += u < w ? w : u;
                     mj[j] = s.chm[j] * inv_n;
-                    mu += c * mj[j];
+                    mu += P[j * 2 + t] * mj[j];
                 }
                 // sigma(C_t) <= sum_c |P[c][t]| sigma(od_c) (per-channel moments come from the byte histograms of P1)
                 const double cxx = s.chm[3] * inv_n - mj[0] * mj[0], cyy = s.chm[4] * inv_n - mj[1] * mj[1];
@@ -878,9 +724,6 @@ __global__ __launch_bounds__(NT, DL ? TIA_STATS_WPE_DL : TIA_STATS_WPE) void sta
                                     fabs(P[4 + t]) * sqrt(czz > 0.0 ? czz : 0.0);
                 const double var = sdev * sdev;
                 const double sg = sqrt(var) * 1.000001 + 1e-12 * (fabs(mu) + 1.0);
-                const double pad = 1e-9 * (fabs(lo) + fabs(hi)) + 1e-12;
-                olo0[t] = lo - pad;
-                ohi0[t] = hi + pad;
                 // histogram window: Chebyshev keeps the 99th percentile inside mu + 12 sigma
                 double wlo = mu - 8.0 * sg, whi = mu + 12.0 * sg;
                 wlo = wlo > olo0[t] ? wlo : olo0[t];
@@ -896,20 +739,9 @@ __global__ __launch_bounds__(NT, DL ? TIA_STATS_WPE_DL : TIA_STATS_WPE) void sta
         double vp[2], vn[2];
         bool conc_done = false;
         if (prm.select_mode != 1) {
-            // C_t = sum_c P[c][t] od_c = K_t - sum_c pt_c L_c with pt = ln2 P (see the angular sweep for the error budget):
-            // |dC_t| <= (9.6e-7 + 5e-7 + 1e-6 / ln2) |pt|_1 + 4 roundings of |C| <= ~4e-6 |P column|_1; eight-fold margin.
-            const float ln2 = 0.6931471805599453f, l255 = 7.994353436858858f;
-            const float a0 = ln2 * (float)P[0], a1 = ln2 * (float)P[2], a2 = ln2 * (float)P[4];
-            const float b0 = ln2 * (float)P[1], b1 = ln2 * (float)P[3], b2 = ln2 * (float)P[5];
-            const float ka = l255 * (a0 + a1 + a2), kb = l255 * (b0 + b1 + b2);
-            const float tol0 = 3.2e-5f * (fabsf((float)P[0]) + fabsf((float)P[2]) + fabsf((float)P[4])) + 1e-7f;
-            const float tol1 = 3.2e-5f * (fabsf((float)P[1]) + fabsf((float)P[3]) + fabsf((float)P[5])) + 1e-7f;
-            auto conc32 = [&](uint32_t r, uint32_t g, uint32_t b, float& c0, float& c1) {
-                const float lr = __log2f(fmaxf((float)r, 1.0f)), lg = __log2f(fmaxf((float)g, 1.0f)),
-                            lb = __log2f(fmaxf((float)b, 1.0f));
-                c0 = fmaf(-a2, lb, fmaf(-a1, lg, fmaf(-a0, lr, ka)));
-                c1 = fmaf(-b2, lb, fmaf(-b1, lg, fmaf(-b0, lr, kb)));
-            };
+            // float32 classification (Proj32, stain_stats_common.hpp): the two concentrations from the columns of P
+            const Proj32<Log2Insn> conc32(P[0], P[2], P[4], P[1], P[3], P[5], Log2Insn{});
+            const float tol0 = conc_tol(P[0], P[2], P[4]), tol1 = conc_tol(P[1], P[3], P[5]);
             conc_done = window_select2(
                 p, hw,
                 [&](long, uint32_t r, uint32_t g, uint32_t b, float (&v)[2]) -> unsigned {
@@ -923,10 +755,8 @@ __global__ __launch_bounds__(NT, DL ? TIA_STATS_WPE_DL : TIA_STATS_WPE) void sta
                     return 3u;
                 },
                 [&](unsigned* list, unsigned seg_cap) {
-                    const float lo0 = (float)s.wlo[0], hi0 = (float)s.whi[0], lo1 = (float)s.wlo[1], hi1 = (float)s.whi[1];
-                    // the float32 images of the window edges are themselves rounded: 1.2e-7 relative
-                    auto slack = [](float v) { return fabsf(v) < 3e38f ? 2.4e-7f * fabsf(v) : 0.0f; };
-                    const float t0 = tol0 + slack(lo0) + slack(hi0), t1 = tol1 + slack(lo1) + slack(hi1);
+                    const float lo0 = (float)s.ws.wlo[0], hi0 = (float)s.ws.whi[0], lo1 = (float)s.ws.wlo[1], hi1 = (float)s.ws.whi[1];
+                    const float t0 = tol0 + edge_slack(lo0) + edge_slack(hi0), t1 = tol1 + edge_slack(lo1) + edge_slack(hi1);
                     unsigned bl0 = 0, bl1 = 0, count = 0;
                     unsigned* seg = list + wave_id() * seg_cap;
                     for_each_group<NT>(p, hw, [&](long g, uint32_t a, uint32_t b, uint32_t c, const WaveGroup&) {
@@ -947,8 +777,8 @@ __global__ __launch_bounds__(NT, DL ? TIA_STATS_WPE_DL : TIA_STATS_WPE) void sta
                     });
                     if (lane_id() == 0) {
                         s.wcnt[wave_id()] = count;
-                        if (bl0) atomicAdd(&s.wbelow[0], (unsigned long long)bl0);
-                        if (bl1) atomicAdd(&s.wbelow[1], (unsigned long long)bl1);
+                        if (bl0) atomicAdd(&s.ws.wbelow[0], (unsigned long long)bl0);
+                        if (bl1) atomicAdd(&s.ws.wbelow[1], (unsigned long long)bl1);
                     }
                 },
                 s, kp, nn, vp, vn);
@@ -1015,6 +845,9 @@ __global__ __launch_bounds__(NT, DL ? TIA_STATS_WPE_DL : TIA_STATS_WPE) void sta
     }
 
     if (tid == 0) {
+        // The statements of stats_finish_record (stain_stats_common.hpp), kept in place: as a call, in every shape tried (parameter
+        // block by reference, by value, as its three fields), the <true> instantiation spilled 37 scalar registers instead of 21 and
+        // <false> up to 52 vector registers instead of 21.  A change to either copy goes to both.
         for (int i = 0; i < 6; ++i) {
             out[TIA_ST_STAIN + i] = S[i];
             out[TIA_ST_PINV + i] = P[i];

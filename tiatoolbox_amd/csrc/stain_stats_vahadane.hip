@@ -90,66 +90,14 @@ __global__ __launch_bounds__(NT, TIA_DL_WPE) void vahadane_dl_kernel(const uint8
         s.hist[tid] = tot;
     }
     __syncthreads();
-    if (tid < 64) {
-        const unsigned h0 = s.hist[tid * 4], h1 = s.hist[tid * 4 + 1], h2 = s.hist[tid * 4 + 2], h3 = s.hist[tid * 4 + 3];
-        const unsigned incl = wave_incl_scan_u32(h0 + h1 + h2 + h3);
-        const unsigned base = incl - (h0 + h1 + h2 + h3);
-        s.cum[tid * 4] = base + h0;
-        s.cum[tid * 4 + 1] = base + h0 + h1;
-        s.cum[tid * 4 + 2] = base + h0 + h1 + h2;
-        s.cum[tid * 4 + 3] = incl;
-    }
-    __syncthreads();
     {
-        const unsigned long long nbytes = (unsigned long long)hw * 3ull;
-        unsigned long long kp[2], kn[2];
-        double gm[2];
-        np_index(nbytes, prm.q_img_lo, kp[0], kn[0], gm[0]);
-        np_index(nbytes, prm.q_img_hi, kp[1], kn[1], gm[1]);
-        if (tid < 256) {
-            const unsigned long long c1 = s.cum[tid], c0 = tid ? s.cum[tid - 1] : 0;
-            if (c0 <= kp[0] && kp[0] < c1) s.ibc[0] = tid;
-            if (c0 <= kn[0] && kn[0] < c1) s.ibc[1] = tid;
-            if (c0 <= kp[1] && kp[1] < c1) s.ibc[2] = tid;
-            if (c0 <= kn[1] && kn[1] < c1) s.ibc[3] = tid;
-            if (c0 == 0 && c1 > 0) s.ibc[4] = tid;
-            if (c1 == (unsigned)nbytes && c0 < (unsigned)nbytes) s.ibc[5] = tid;
-        }
-        __syncthreads();
-        if (tid == 0) {
-            double plow = np_lerp((double)s.ibc[0], (double)s.ibc[1], gm[0]);
-            double phigh = np_lerp((double)s.ibc[2], (double)s.ibc[3], gm[1]);
-            if (plow >= phigh) {
-                plow = (double)s.ibc[4];
-                phigh = (double)s.ibc[5];
-            }
-            s.bc[0] = plow;
-            s.bc[1] = phigh;
-        }
-        __syncthreads();
-    }
-    if (tid < 256) {
-        const double plow = s.bc[0], phigh = s.bc[1];
-        int v = tid;
-        if (z1 && v == 0) v = 1;
-        int ce = v;
-        if (phigh > plow) {
-            double x = (double)v;
-            x = x < plow ? plow : (x > phigh ? phigh : x);
-            x = (x - plow) / (phigh - plow);
-            x = x * 255.0 + 0.0;
-            ce = (int)x;
-        }
-        s.ty[0][tid] = tab->ty[0][ce];
-        s.ty[1][tid] = tab->ty[1][ce];
-        s.ty[2][tid] = tab->ty[2][ce];
+        double plow, phigh;
+        ce_percentiles(s.hist, s.cum, s.ibc, hw, prm.q_img_lo, prm.q_img_hi, plow, phigh);
+        if (tid < 256) ce_luminance_tables(tab, plow, phigh, z1, tid, s.ty);
     }
     __syncthreads();
     const int y_thr = prm.y_thr;
-    auto is_tissue = [&](uint32_t r, uint32_t g, uint32_t b) -> bool {
-        const int t = s.ty[0][r] + s.ty[1][g] + s.ty[2][b];
-        return ((t + (1 << 11)) >> 12) < y_thr;
-    };
+    auto is_tissue = [&](uint32_t r, uint32_t g, uint32_t b) -> bool { return tia::is_tissue(s.ty, r, g, b, y_thr); };
 #define ODV(v) s.od[(v)]
     const double alpha = prm.dl_alpha;
     // ---- S0: uncentred second moments of the tissue OD (as the one-kernel form) ------------------------------------------------
@@ -159,16 +107,7 @@ __global__ __launch_bounds__(NT, TIA_DL_WPE) void vahadane_dl_kernel(const uint8
     for_each_pixel<NT>(p, hw, [&](long, uint32_t r, uint32_t g, uint32_t b) {
         if (is_tissue(r, g, b)) {
             const double x = ODV(r), y = ODV(g), z = ODV(b);
-            acc[0] += 1.0;
-            acc[1] += x;
-            acc[2] += y;
-            acc[3] += z;
-            acc[4] = __builtin_fma(x, x, acc[4]);
-            acc[5] = __builtin_fma(x, y, acc[5]);
-            acc[6] = __builtin_fma(x, z, acc[6]);
-            acc[7] = __builtin_fma(y, y, acc[7]);
-            acc[8] = __builtin_fma(y, z, acc[8]);
-            acc[9] = __builtin_fma(z, z, acc[9]);
+            od_moments_add(acc, x, y, z);
         }
     });
     block_sum(acc, s);
@@ -184,10 +123,8 @@ __global__ __launch_bounds__(NT, TIA_DL_WPE) void vahadane_dl_kernel(const uint8
         const double g6[6] = {acc[4], acc[5], acc[6], acc[7], acc[8], acc[9]};
         double w[3], v[3][3];
         jacobi3(g6, w, v);
-        int i0 = 0, i1 = 1, i2 = 2;
-        if (w[i0] < w[i1]) { int t = i0; i0 = i1; i1 = t; }
-        if (w[i0] < w[i2]) { int t = i0; i0 = i2; i2 = t; }
-        if (w[i1] < w[i2]) { int t = i1; i1 = i2; i2 = t; }
+        int i0, i1, i2;
+        eigen_descending(w, i0, i1, i2);
         const int order[2] = {i0, i1};
         for (int k = 0; k < 2; ++k) {
             double u[3] = {v[0][order[k]], v[1][order[k]], v[2][order[k]]};

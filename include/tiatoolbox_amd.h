@@ -563,6 +563,11 @@ int tia_conv2d_thin_nhwc_f32(const float* d_x, const float* d_w_packed, const fl
  * d_x [npix,64], d_w [cout][64] (the OIHW tensor), d_y [npix,cout], all float32; HBM-bound (one read of x). */
 int tia_conv1x1_head_nhwc_f32(const float* d_x, int64_t npix, const float* d_w, const float* d_bias, const float* d_pre_scale,
                               const float* d_pre_shift, int32_t cout, float* d_y, void* stream);
+/* The same head on HALF activations (additive at version 6): d_x [npix,64] of `dtype` (TIA_DT_F16 | TIA_DT_BF16), 16-byte
+ * aligned; weights, bias, pre_scale / pre_shift float32; pre(v) with product and sum rounded separately in float32; float32
+ * accumulation; d_y [npix,cout] FLOAT32 logits, cout <= 8.  HBM-bound: 2 * 64 + 4 * cout bytes per pixel. */
+int tia_conv1x1_head_nhwc_h(const void* d_x, int64_t npix, const float* d_w, const float* d_bias, const float* d_pre_scale,
+                            const float* d_pre_shift, int32_t cout, int32_t dtype, float* d_y, void* stream);
 
 /* tia_conv2d_nhwc_f32_ex with a second, post-activated output produced in the same epilogue:
  *   v  = act(conv(x, w) + bias [+ residual])      -> d_y   (may be NULL when only d_y2 is wanted)
@@ -642,6 +647,12 @@ int tia_conv1x1_pre_nhwc_f32(const float* d_x, const float* d_pre_scale, const f
  *   first skip connection of the UNet decoder (models/architecture/unet.py:356-372, ResNetEncoder features). */
 int tia_stem_conv7x7_pool_nhwc(const void* d_x, int32_t x_is_u8, const float* d_w_packed, const float* d_bias, void* d_y,
                                int32_t y_dtype, float* d_conv_out, int64_t n, int64_t h, int64_t w, void* stream);
+/* The same kernel and the same float32 arithmetic with the pre-pool output in y_dtype as well (additive at version 6):
+ *   d_conv_out (may be NULL) [n,ho,wo,64] of y_dtype, 16-byte aligned -- for TIA_DT_F16 / TIA_DT_BF16 the float32 value rounded
+ *   once (round to nearest even), i.e. exactly tia_stem_conv7x7_pool_nhwc's float32 output passed through one conversion: the
+ *   first skip connection of the half-precision UNet.  tia_stem_conv7x7_pool_nhwc is this entry point with a float32 d_conv_out. */
+int tia_stem_conv7x7_pool_conv_nhwc(const void* d_x, int32_t x_is_u8, const float* d_w_packed, const float* d_bias, void* d_y,
+                                    int32_t y_dtype, void* d_conv_out, int64_t n, int64_t h, int64_t w, void* stream);
 
 /* The same stem on the HALF matrix cores, for compute_dtype = float16 | bfloat16 of the engines (an extension: the reference runs
  * float32; `model.half()(ToTensor(x).half())` is what it mirrors): x / 255 and the weights rounded to `dtype`, float32
@@ -728,6 +739,14 @@ int tia_upsample2x_add_nhwc_f32(const float* d_x, const float* d_y, int64_t y_im
 int tia_upsample2x_add_act_nhwc_f32(const float* d_x, const float* d_y, int64_t y_image_stride, int64_t y_row_stride,
                                     const float* d_scale, const float* d_shift, float* d_out, int64_t n, int64_t h,
                                     int64_t w, int64_t c, void* stream);
+/* The half form (additive at version 6): x [n,h,w,c] and out [n,2h,2w,c] dense NHWC of `dtype` (TIA_DT_F16 | TIA_DT_BF16), y a
+ * (cropped) view of that type with y_image_stride / y_row_stride in elements; scale / shift float32 [c] (both NULL: plain sum).
+ * float32 arithmetic, every step rounded on its own: s = float(x) + float(y); p = s * scale; a = p + shift; max(a, 0); ONE
+ * rounding to half (nearest even).  Every x vector is read once for its 2 x 2 output block: 4.5 bytes per output element.
+ * c % 8 == 0 (else TIA_ESIZE); bases 16-byte aligned and strides multiples of 8 elements (else TIA_EINVAL); 64-bit offsets. */
+int tia_upsample2x_add_act_nhwc_h(const void* d_x, const void* d_y, int64_t y_image_stride, int64_t y_row_stride,
+                                  const float* d_scale, const float* d_shift, void* d_out, int64_t n, int64_t h, int64_t w,
+                                  int64_t c, int32_t dtype, void* stream);
 
 /* =======================================================================================
  * All borders of binary planes: cv2.findContours(layer, RETR_TREE, CHAIN_APPROX_NONE | _SIMPLE)

@@ -109,6 +109,7 @@ _SIGNATURES = {
     "tia_conv3x3_geometry": ([_I64, _I64, _I64, _I64, _I64, _I64, C.POINTER(C.c_int32)], C.c_int),
     "tia_conv2d_thin_nhwc_f32": ([_P, _P, _P, _P, _I64, _I64, _I64, _I64, _I64, _I64, _I64, _I64, _I64, _I64, _I64, _I32, _P], C.c_int),
     "tia_conv1x1_head_nhwc_f32": ([_P, _I64, _P, _P, _P, _P, _I32, _P, _P], C.c_int),
+    "tia_conv1x1_head_nhwc_h": ([_P, _I64, _P, _P, _P, _P, _I32, _I32, _P, _P], C.c_int),
     "tia_conv2d_post_nhwc_f32": ([_P, _P, _P, _P, _P, _I64, _I64, _I64, _I64, _I64, _I64, _I64, _I64, _I64, _I64, _I64, _I64, _I32,
                                   _P, _P, _P, _P], C.c_int),
     "tia_conv2d_route_f32": ([_I64] * 12, C.c_int),
@@ -122,6 +123,7 @@ _SIGNATURES = {
     "tia_stem_pack_weights_h": ([_P, _I32, _P, _P], C.c_int),
     "tia_stem_conv7x7_pool_nhwc_h": ([_P, _I32, _P, _P, _P, _I32, _I64, _I64, _I64, _P], C.c_int),
     "tia_stem_conv7x7_pool_nhwc": ([_P, _I32, _P, _P, _P, _I32, _P, _I64, _I64, _I64, _P], C.c_int),
+    "tia_stem_conv7x7_pool_conv_nhwc": ([_P, _I32, _P, _P, _P, _I32, _P, _I64, _I64, _I64, _P], C.c_int),
     "tia_conv2d_nhwc_h": ([_P, _P, _P, _P, _P, _I64, _I64, _I64, _I64, _I64, _I64, _I64, _I64, _I64, _I32, _I32, _P], C.c_int),
     "tia_conv_pack_weights_h": ([_P, _I64, _I64, _I64, _I64, _I32, _P, _P], C.c_int),
     "tia_stem_pack_weights_f32": ([_P, _P, _P], C.c_int),
@@ -133,6 +135,7 @@ _SIGNATURES = {
     "tia_conv3x3_grouped_nhwc_f32": ([_P, _P, _P, _P, _I64, _I64, _I64, _I64, _I64, _I64, _I32, _P], C.c_int),
     "tia_upsample2x_add_nhwc_f32": ([_P, _P, _I64, _I64, _P, _I64, _I64, _I64, _I64, _P], C.c_int),
     "tia_upsample2x_add_act_nhwc_f32": ([_P, _P, _I64, _I64, _P, _P, _P, _I64, _I64, _I64, _I64, _P], C.c_int),
+    "tia_upsample2x_add_act_nhwc_h": ([_P, _P, _I64, _I64, _P, _P, _P, _I64, _I64, _I64, _I64, _I32, _P], C.c_int),
     "tia_bias_act_nhwc": ([_P, _P, _P, _I64, _I64, _I32, _I32, _P], C.c_int),
     "tia_bias_relu_maxpool_nhwc": ([_P, _P, _I64, _I64, _I64, _I64, _I32, _P, _P], C.c_int),
     "tia_hover_instance_stats": ([_P, _P, _I64, _I64, _I64, _I32, _I32, _P, _P, _P], C.c_int),

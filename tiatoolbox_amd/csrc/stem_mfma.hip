@@ -124,13 +124,17 @@ struct StemDims {
     int out_dtype;               // TIA_DT_F32 | TIA_DT_F16 | TIA_DT_BF16: type of the pooled output (arithmetic is float32 either way)
 };
 
-template <bool U8, int MMA = 0>
-__global__ __launch_bounds__(NTH, 2) void stem7x7_pool_kernel(const void* __restrict__ xin, const void* __restrict__ wpk_v,
-                                                             const float* __restrict__ bias, void* __restrict__ yout, float* __restrict__ yconv, StemDims d) {
+// The kernel's body.  CDT: type of the pre-pool output `yconv` (0 float32; TIA_DT_F16 / TIA_DT_BF16: rounded once, the half UNet's first
+// skip).  A template parameter, not a field of StemDims, and two __global__ entries below (the body is inlined into each): the
+// float32 instantiations stay the code, and `stem7x7_pool_kernel<U8, MMA>` the name, they were.
+template <bool U8, int MMA, int CDT>
+__device__ __forceinline__ void stem7x7_pool_body(const void* __restrict__ xin, const void* __restrict__ wpk_v, const float* __restrict__ bias,
+                                                  void* __restrict__ yout, void* __restrict__ yconv, const StemDims& d) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     constexpr bool HALF = MMA != 0;
     constexpr bool SPLIT = MMA == 3;
     static_assert(!SPLIT || U8, "the split variant reads bytes");
+    static_assert(CDT == 0 || MMA == 0, "a half pre-pool output belongs to the float32-arithmetic stem");
     constexpr int VJ = SPLIT ? 1 : 2;      // channel tiles of 32 in the V tile at a time
     constexpr int VC = 32 * VJ;            // channels per V-tile pass
     constexpr int UPR = HALF ? 198 : 196;  // 4-element staging units per row
@@ -393,9 +397,23 @@ __global__ __launch_bounds__(NTH, 2) void stem7x7_pool_kernel(const void* __rest
                 carry[j][e] = r1;
                 ring[lcol * VC + jj * 32 + (lane & 31)] = v;
                 if (!SPLIT && yconv != nullptr && py >= q0 && colok) {  // the pre-pool activation too (UNet's first skip connection)
-                    float* o = yconv + (((long)img * d.ho + 2 * py) * d.wo + c_start + lcol) * COUT + j * 32 + (lane & 31);
-                    if (row0) o[0] = r0;
-                    if (row1) o[(long)d.wo * COUT] = r1;
+                    const long oi = (((long)img * d.ho + 2 * py) * d.wo + c_start + lcol) * COUT + j * 32 + (lane & 31);
+                    if constexpr (CDT == 0) {
+                        float* o = static_cast<float*>(yconv) + oi;
+                        if (row0) o[0] = r0;
+                        if (row1) o[(long)d.wo * COUT] = r1;
+                    } else {
+                        // the half UNet's first skip: the same float32 values, rounded once like the pooled map.  Lanes 2 k and 2 k + 1
+                        // hold neighbouring channels of the same pixel (every condition here is shared by the pair): they swap one
+                        // half each (DPP quad_perm [1, 0, 3, 2]), the even lane stores row 0's channel pair and the odd lane row 1's
+                        // -- one 4-byte store per lane instead of two 2-byte ones
+                        const bool odd = (lane & 1) != 0;
+                        const unsigned h0 = f32_to_half<CDT == TIA_DT_BF16>(r0), h1 = f32_to_half<CDT == TIA_DT_BF16>(r1);
+                        const unsigned got = (unsigned)__builtin_amdgcn_update_dpp(0, (int)(odd ? h0 : h1), 0xB1, 0xF, 0xF, true);
+                        const unsigned word = odd ? (got | (h1 << 16)) : (h0 | (got << 16));
+                        unsigned short* o = static_cast<unsigned short*>(yconv) + (odd ? oi - 1 + (long)d.wo * COUT : oi);
+                        if (odd ? row1 : row0) *reinterpret_cast<unsigned*>(o) = word;
+                    }
                 }
             }
         }
@@ -456,6 +474,19 @@ __global__ __launch_bounds__(NTH, 2) void stem7x7_pool_kernel(const void* __rest
                (int)blockIdx.x, q1 - it0, tm_[0] / (q1 - it0), tm_[1] / (q1 - it0), tm_[2] / (q1 - it0), tm_[3] / (q1 - it0),
                tm_[4] / (q1 - it0), tm_[5] / (q1 - it0), 100.0 * (double)(clock64() - t0c_) / (double)(wall_clock64() - t0w_));
 #endif
+}
+
+template <bool U8, int MMA = 0>
+__global__ __launch_bounds__(NTH, 2) void stem7x7_pool_kernel(const void* __restrict__ xin, const void* __restrict__ wpk_v,
+                                                             const float* __restrict__ bias, void* __restrict__ yout, float* __restrict__ yconv, StemDims d) {
+    stem7x7_pool_body<U8, MMA, 0>(xin, wpk_v, bias, yout, yconv, d);
+}
+
+// the float32-arithmetic stem writing its pre-pool output as halves of type CDT (tia_stem_conv7x7_pool_conv_nhwc)
+template <bool U8, int CDT>
+__global__ __launch_bounds__(NTH, 2) void stem7x7_pool_convh_kernel(const void* __restrict__ xin, const void* __restrict__ wpk_v,
+                                                                   const float* __restrict__ bias, void* __restrict__ yout, float* __restrict__ yconv, StemDims d) {
+    stem7x7_pool_body<U8, 0, CDT>(xin, wpk_v, bias, yout, yconv, d);
 }
 
 }  // namespace
@@ -522,7 +553,7 @@ constexpr int32_t STEM_MMA_SPLIT = -3;  // stem_impl's `mma` for the exactly spl
 // mma: 0 = float32 matrix cores (weights [148][64] float32), TIA_DT_F16 / TIA_DT_BF16 = half matrix cores (weights packed by
 // tia_stem_pack_weights_h; the output type is then that half type)
 static int stem_impl(const void* d_x, int32_t x_is_u8, const void* d_w_packed, const float* d_bias, void* d_y, int32_t y_dtype,
-                     float* d_conv_out, int64_t n, int64_t h, int64_t w, int32_t mma, void* stream) {
+                     void* d_conv_out, int32_t conv_dtype, int64_t n, int64_t h, int64_t w, int32_t mma, void* stream) {
     if (!d_x || !d_w_packed || !d_bias || !d_y || n <= 0 || h <= 0 || w <= 0) return TIA_EINVAL;
     if (y_dtype != TIA_DT_F32 && y_dtype != TIA_DT_F16 && y_dtype != TIA_DT_BF16) return TIA_EINVAL;
     if ((reinterpret_cast<uintptr_t>(d_w_packed) | reinterpret_cast<uintptr_t>(d_y)) & 15) return TIA_EINVAL;
@@ -541,9 +572,17 @@ static int stem_impl(const void* d_x, int32_t x_is_u8, const void* d_w_packed, c
                                   {stem7x7_pool_kernel<false, 1>, stem7x7_pool_kernel<true, 1>},
                                   {stem7x7_pool_kernel<false, 2>, stem7x7_pool_kernel<true, 2>},
                                   {nullptr, stem7x7_pool_kernel<true, 3>}};  // split: uint8 input only
+    // the float32-arithmetic stem with a half pre-pool output: [fp16 | bf16][float32 | uint8 input]
+    const Kernel kernels_ch[2][2] = {{stem7x7_pool_convh_kernel<false, TIA_DT_F16>, stem7x7_pool_convh_kernel<true, TIA_DT_F16>},
+                                     {stem7x7_pool_convh_kernel<false, TIA_DT_BF16>, stem7x7_pool_convh_kernel<true, TIA_DT_BF16>}};
     const int lds_bytes[4] = {(int)(LDS_FLOATS * sizeof(float)), LDS_BYTES_H, LDS_BYTES_H, LDS_BYTES_S};
     static tia::DeviceOnce attr_once;  // the dynamic-LDS attribute is per device
     if (!attr_once.ensure([&] {
+            for (int c = 0; c < 2; ++c)
+                for (int u = 0; u < 2; ++u)
+                    if (hipFuncSetAttribute(reinterpret_cast<const void*>(kernels_ch[c][u]), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                            lds_bytes[0]) != hipSuccess)
+                        return false;
             for (int m = 0; m < 4; ++m)
                 for (int u = 0; u < 2; ++u)
                     if (kernels[m][u] != nullptr &&
@@ -555,6 +594,9 @@ static int stem_impl(const void* d_x, int32_t x_is_u8, const void* d_w_packed, c
         return TIA_ELAUNCH;
     const int mi = mma == TIA_DT_F16 ? 1 : (mma == TIA_DT_BF16 ? 2 : (mma == STEM_MMA_SPLIT ? 3 : 0));
     if (kernels[mi][x_is_u8 ? 1 : 0] == nullptr) return TIA_EINVAL;
+    const bool conv_half = d_conv_out != nullptr && conv_dtype != TIA_DT_F32;
+    if (conv_half && (mi != 0 || (conv_dtype != TIA_DT_F16 && conv_dtype != TIA_DT_BF16))) return TIA_EINVAL;
+    const Kernel kernel = conv_half ? kernels_ch[conv_dtype == TIA_DT_BF16 ? 1 : 0][x_is_u8 ? 1 : 0] : kernels[mi][x_is_u8 ? 1 : 0];
     const size_t lds = (size_t)lds_bytes[mi];
     hipStream_t st = (hipStream_t)stream;
     for (long first = 0; first < n; first += group) {
@@ -572,26 +614,33 @@ static int stem_impl(const void* d_x, int32_t x_is_u8, const void* d_w_packed, c
         StemDims d{(int)nb, (int)h, (int)w, (int)ho, (int)wo, (int)hp, (int)wp, (int)chunks, (int)rows,
                    (unsigned)((nb * image_bytes + shift + 3) & ~3L), shift, (int)y_dtype};
         char* yg = static_cast<char*>(d_y) + first * hp * wp * COUT * (y_dtype == TIA_DT_F32 ? 4 : 2);
-        float* cg = d_conv_out ? d_conv_out + first * ho * wo * COUT : nullptr;
+        float* cg = d_conv_out ? reinterpret_cast<float*>(static_cast<char*>(d_conv_out) + first * ho * wo * COUT * (conv_dtype == TIA_DT_F32 ? 4 : 2))
+                               : nullptr;
         const dim3 grid((unsigned)(nb * chunks), (unsigned)strips);
-        hipLaunchKernelGGL(kernels[mi][x_is_u8 ? 1 : 0], grid, dim3(NTH), lds, st, static_cast<const void*>(xg), d_w_packed, d_bias,
+        hipLaunchKernelGGL(kernel, grid, dim3(NTH), lds, st, static_cast<const void*>(xg), d_w_packed, d_bias,
                            static_cast<void*>(yg), cg, d);
     }
     return hipGetLastError() == hipSuccess ? TIA_OK : TIA_ELAUNCH;
 }
 
+extern "C" int tia_stem_conv7x7_pool_conv_nhwc(const void* d_x, int32_t x_is_u8, const float* d_w_packed, const float* d_bias, void* d_y,
+                                               int32_t y_dtype, void* d_conv_out, int64_t n, int64_t h, int64_t w, void* stream) {
+    if (reinterpret_cast<uintptr_t>(d_conv_out) & 15) return TIA_EINVAL;
+    return stem_impl(d_x, x_is_u8, d_w_packed, d_bias, d_y, y_dtype, d_conv_out, y_dtype, n, h, w, 0, stream);
+}
+
 extern "C" int tia_stem_conv7x7_pool_nhwc(const void* d_x, int32_t x_is_u8, const float* d_w_packed, const float* d_bias, void* d_y,
                                           int32_t y_dtype, float* d_conv_out, int64_t n, int64_t h, int64_t w, void* stream) {
-    return stem_impl(d_x, x_is_u8, d_w_packed, d_bias, d_y, y_dtype, d_conv_out, n, h, w, 0, stream);
+    return stem_impl(d_x, x_is_u8, d_w_packed, d_bias, d_y, y_dtype, d_conv_out, TIA_DT_F32, n, h, w, 0, stream);
 }
 
 extern "C" int tia_stem_conv7x7_pool_nhwc_h(const void* d_x, int32_t x_is_u8, const void* d_w_packed_h, const float* d_bias, void* d_y,
                                             int32_t dtype, int64_t n, int64_t h, int64_t w, void* stream) {
     if (dtype != TIA_DT_F16 && dtype != TIA_DT_BF16) return TIA_EINVAL;
-    return stem_impl(d_x, x_is_u8, d_w_packed_h, d_bias, d_y, dtype, nullptr, n, h, w, dtype, stream);
+    return stem_impl(d_x, x_is_u8, d_w_packed_h, d_bias, d_y, dtype, nullptr, TIA_DT_F32, n, h, w, dtype, stream);
 }
 
 extern "C" int tia_stem_conv7x7_pool_nhwc_u8x3(const uint8_t* d_x, const void* d_w_packed3, const float* d_bias, float* d_y, int64_t n,
                                                int64_t h, int64_t w, void* stream) {
-    return stem_impl(d_x, 1, d_w_packed3, d_bias, d_y, TIA_DT_F32, nullptr, n, h, w, STEM_MMA_SPLIT, stream);
+    return stem_impl(d_x, 1, d_w_packed3, d_bias, d_y, TIA_DT_F32, nullptr, TIA_DT_F32, n, h, w, STEM_MMA_SPLIT, stream);
 }

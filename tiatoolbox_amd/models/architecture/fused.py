@@ -186,24 +186,32 @@ def hip_conv2d_thin(x: torch.Tensor, w_packed: torch.Tensor, bias: torch.Tensor 
 
 def hip_conv1x1_head(x: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor | None, *, pre_scale: torch.Tensor | None = None,
                      pre_shift: torch.Tensor | None = None) -> torch.Tensor:
-    """A class head: 1x1 convolution ``64 -> cout <= 8`` (``tia_conv1x1_head_nhwc_f32``), optionally of
-    ``relu(x * pre_scale[c] + pre_shift[c])`` (the BatchNorm + ReLU in front of HoVer-Net's ``u0/conv``) without writing
-    that intermediate.  ``x``: float32 channels-last ``[n, 64, h, w]``; ``weight``: ``[cout, 64]`` (or OIHW 1x1)."""
+    """A class head: 1x1 convolution ``64 -> cout <= 8`` (``tia_conv1x1_head_nhwc_f32``; fp16 / bf16 ``x``:
+    ``tia_conv1x1_head_nhwc_h``), optionally of ``relu(x * pre_scale[c] + pre_shift[c])`` (the BatchNorm + ReLU in front of
+    HoVer-Net's ``u0/conv``) without writing that intermediate.  ``x``: channels-last ``[n, 64, h, w]``; ``weight``: ``[cout, 64]``
+    (or OIHW 1x1).  Weights, bias and ``pre_*`` are float32 whatever ``x`` is, and so are the returned logits."""
     from tiatoolbox_amd import _lib
 
-    if not (_nhwc_ptr_ok(x) and x.dtype == torch.float32 and x.shape[1] == 64):  # noqa: PLR2004
-        msg = "hip_conv1x1_head expects a float32 channels-last CUDA tensor with 64 channels."
+    if not (_nhwc_ptr_ok(x) and x.shape[1] == 64):  # noqa: PLR2004
+        msg = "hip_conv1x1_head expects a float32 / fp16 / bf16 channels-last CUDA tensor with 64 channels."
+        raise ValueError(msg)
+    half = x.dtype != torch.float32
+    if half and any(t is not None and t.dtype != torch.float32 for t in (weight, bias, pre_scale, pre_shift)):
+        msg = f"hip_conv1x1_head takes weight, bias and pre_scale / pre_shift in float32 beside a {x.dtype} input."
         raise ValueError(msg)
     n, _, h, w = x.shape
     cout = weight.shape[0]
     wmat = weight.detach().reshape(cout, 64).to(torch.float32).contiguous()
     y = torch.empty((n, cout, h, w), dtype=torch.float32, device=x.device, memory_format=torch.channels_last)
+    ptrs = (wmat.data_ptr(), bias.data_ptr() if bias is not None else 0, pre_scale.data_ptr() if pre_scale is not None else 0,
+            pre_shift.data_ptr() if pre_shift is not None else 0)
+    name = "tia_conv1x1_head_nhwc_h" if half else "tia_conv1x1_head_nhwc_f32"
     with torch.cuda.device(x.device):
-        rc = _lib.load().tia_conv1x1_head_nhwc_f32(x.data_ptr(), n * h * w, wmat.data_ptr(), bias.data_ptr() if bias is not None else 0,
-                                                   pre_scale.data_ptr() if pre_scale is not None else 0,
-                                                   pre_shift.data_ptr() if pre_shift is not None else 0, cout, y.data_ptr(),
-                                                   _lib.current_stream())
-    _lib.check(rc, "tia_conv1x1_head_nhwc_f32")
+        if half:
+            rc = _lib.load().tia_conv1x1_head_nhwc_h(x.data_ptr(), n * h * w, *ptrs, cout, _DT[x.dtype], y.data_ptr(), _lib.current_stream())
+        else:
+            rc = _lib.load().tia_conv1x1_head_nhwc_f32(x.data_ptr(), n * h * w, *ptrs, cout, y.data_ptr(), _lib.current_stream())
+    _lib.check(rc, name)
     return y
 
 
@@ -371,27 +379,37 @@ def hip_conv3x3_grouped(x: torch.Tensor, w_packed: torch.Tensor, bias: torch.Ten
 
 def hip_upsample2x_add(x: torch.Tensor, y: torch.Tensor, scale: torch.Tensor | None = None,
                        shift: torch.Tensor | None = None) -> torch.Tensor:
-    """``x.repeat_interleave(2, 2).repeat_interleave(2, 3) + y`` in one pass (``tia_upsample2x_add_act_nhwc_f32``); ``y`` may be
-    a centre-cropped view of a channels-last tensor.  With ``scale`` / ``shift``: followed by ``relu(. * scale + shift)``."""
+    """``x.repeat_interleave(2, 2).repeat_interleave(2, 3) + y`` in one pass (``tia_upsample2x_add_act_nhwc_f32``; fp16 / bf16
+    ``x`` and ``y``: ``tia_upsample2x_add_act_nhwc_h``, float32 arithmetic and one rounding); ``y`` may be a centre-cropped view
+    of a channels-last tensor.  With ``scale`` / ``shift`` (float32): followed by ``relu(. * scale + shift)``."""
     from tiatoolbox_amd import _lib
 
     if not (x.is_cuda and y.is_cuda):
         msg = "hip_upsample2x_add expects CUDA tensors."
         raise ValueError(msg)
     n, c, h, w = x.shape
-    ok_y = (y.is_cuda and y.dtype == torch.float32 and y.shape == (n, c, 2 * h, 2 * w) and y.stride(1) == 1 and y.stride(3) == c
-            and y.stride(2) % 4 == 0 and y.stride(0) % 4 == 0 and y.data_ptr() % 16 == 0)
-    if not (_nhwc_ptr_ok(x) and x.dtype == torch.float32 and ok_y and c % 4 == 0):
-        msg = ("hip_upsample2x_add expects float32 channels-last tensors, `y` a (cropped) view with contiguous channels of shape "
-               f"[n, c, 2h, 2w], c % 4 == 0; got x {tuple(x.shape)} {x.dtype}, y {tuple(y.shape)} strides {tuple(y.stride())}.")
+    half = x.dtype in (torch.float16, torch.bfloat16)
+    vec = 8 if half else 4  # elements per 16-byte access
+    ok_y = (y.is_cuda and y.dtype == x.dtype and y.shape == (n, c, 2 * h, 2 * w) and y.stride(1) == 1 and y.stride(3) == c
+            and y.stride(2) % vec == 0 and y.stride(0) % vec == 0 and y.data_ptr() % 16 == 0)
+    if not (_nhwc_ptr_ok(x) and ok_y and c % vec == 0):
+        msg = ("hip_upsample2x_add expects channels-last tensors of one dtype (float32: c % 4 == 0; fp16 / bf16: c % 8 == 0), `y` a "
+               "(cropped) view with contiguous channels of shape [n, c, 2h, 2w] on a 16-byte aligned base and strides; "
+               f"got x {tuple(x.shape)} {x.dtype}, y {tuple(y.shape)} {y.dtype} strides {tuple(y.stride())}.")
         raise ValueError(msg)
-    out = torch.empty((n, c, 2 * h, 2 * w), dtype=torch.float32, device=x.device, memory_format=torch.channels_last)
+    if half and any(t is not None and t.dtype != torch.float32 for t in (scale, shift)):
+        msg = f"hip_upsample2x_add takes scale / shift in float32 beside {x.dtype} tensors."
+        raise ValueError(msg)
+    out = torch.empty((n, c, 2 * h, 2 * w), dtype=x.dtype, device=x.device, memory_format=torch.channels_last)
+    args = (x.data_ptr(), y.data_ptr(), y.stride(0), y.stride(2), scale.data_ptr() if scale is not None else 0,
+            shift.data_ptr() if shift is not None else 0, out.data_ptr(), n, h, w, c)
+    name = "tia_upsample2x_add_act_nhwc_h" if half else "tia_upsample2x_add_act_nhwc_f32"
     with torch.cuda.device(x.device):
-        rc = _lib.load().tia_upsample2x_add_act_nhwc_f32(x.data_ptr(), y.data_ptr(), y.stride(0), y.stride(2),
-                                                         scale.data_ptr() if scale is not None else 0,
-                                                         shift.data_ptr() if shift is not None else 0, out.data_ptr(), n, h, w, c,
-                                                         _lib.current_stream())
-    _lib.check(rc, "tia_upsample2x_add_act_nhwc_f32")
+        if half:
+            rc = _lib.load().tia_upsample2x_add_act_nhwc_h(*args, _DT[x.dtype], _lib.current_stream())
+        else:
+            rc = _lib.load().tia_upsample2x_add_act_nhwc_f32(*args, _lib.current_stream())
+    _lib.check(rc, name)
     return out
 
 
@@ -428,6 +446,9 @@ def pack_conv_weights_h(conv: nn.Conv2d, dtype: torch.dtype) -> torch.Tensor:
 
     w = conv.weight.detach().to(torch.float32).contiguous()
     cout, cin, kh, kw = w.shape
+    if not w.is_cuda or dtype not in (torch.float16, torch.bfloat16):
+        msg = f"pack_conv_weights_h packs CUDA weights for fp16 / bf16; got weights on {w.device} for {dtype}."
+        raise ValueError(msg)
     out = torch.empty((kh, kw, cin // 8, cout, 8), dtype=dtype, device=w.device)
     with torch.cuda.device(w.device):
         rc = _lib.load().tia_conv_pack_weights_h(w.data_ptr(), cout, cin, kh, kw, _DT[dtype], out.data_ptr(), _lib.current_stream())
@@ -652,6 +673,9 @@ def pack_stem_weights(conv) -> torch.Tensor:
     if tuple(w.shape) != (64, 3, 7, 7) or not geometry_ok:
         msg = f"the stem kernel is conv7x7 / stride 2 / pad 3, 3 -> 64 channels; got weight {tuple(w.shape)}."
         raise ValueError(msg)
+    if not w.is_cuda:
+        msg = f"pack_stem_weights packs on a CUDA device; got a weight on {w.device}."
+        raise ValueError(msg)
     out = torch.empty((148, 64), dtype=torch.float32, device=w.device)
     with torch.cuda.device(w.device):
         rc = _lib.load().tia_stem_pack_weights_f32(w.data_ptr(), out.data_ptr(), _lib.current_stream())
@@ -698,29 +722,33 @@ def hip_stem_conv_pool_h(x: torch.Tensor, w_packed: torch.Tensor, bias: torch.Te
 
 def hip_stem_conv_pool(x: torch.Tensor, w_packed: torch.Tensor, bias: torch.Tensor, *,
                        out_dtype: torch.dtype = torch.float32, return_conv: bool = False):
-    """``maxpool3x3/2(relu(conv7x7/2(x) + bias))`` in one kernel (``tia_stem_conv7x7_pool_nhwc``).
+    """``maxpool3x3/2(relu(conv7x7/2(x) + bias))`` in one kernel (``tia_stem_conv7x7_pool_conv_nhwc``).
 
     ``x``: NHWC ``[n, h, w, 3]`` contiguous CUDA tensor, ``uint8`` (scaled by 1/255 on load: ``ToTensor``) or ``float32`` (as is).
     Returns the pooled activations as an NCHW tensor stored channels-last (``[n, 64, hp, wp]``) of ``out_dtype`` (float32
     arithmetic; fp16 / bf16 = one rounding at the end, for the half-precision trunk).  ``return_conv=True``: ``(pooled, conv)``
-    with ``conv = relu(conv7x7(x) + bias)`` before the pooling (``[n, 64, ho, wo]`` float32, the UNet's first skip)."""
+    with ``conv = relu(conv7x7(x) + bias)`` before the pooling (``[n, 64, ho, wo]`` of ``out_dtype`` too, the UNet's first skip)."""
     from tiatoolbox_amd import _lib
 
     if not (x.is_cuda and x.dim() == 4 and x.shape[-1] == 3 and x.is_contiguous() and x.dtype in (torch.uint8, torch.float32)):
         msg = f"hip_stem_conv_pool expects a contiguous NHWC uint8 / float32 CUDA batch with 3 channels, got {tuple(x.shape)} {x.dtype}."
+        raise ValueError(msg)
+    if out_dtype not in _DT or w_packed.dtype != torch.float32 or bias.dtype != torch.float32:
+        msg = (f"hip_stem_conv_pool computes in float32 (weights from pack_stem_weights, float32 bias) and returns float32 / fp16 / bf16; "
+               f"got weights {w_packed.dtype}, bias {bias.dtype}, out_dtype {out_dtype}.")
         raise ValueError(msg)
     n, h, w, _ = x.shape
     hp, wp = ((h - 1) // 2) // 2 + 1, ((w - 1) // 2) // 2 + 1
     y = torch.empty((n, 64, hp, wp), dtype=out_dtype, device=x.device, memory_format=torch.channels_last)
     conv = None
     if return_conv:
-        conv = torch.empty((n, 64, (h - 1) // 2 + 1, (w - 1) // 2 + 1), dtype=torch.float32, device=x.device,
+        conv = torch.empty((n, 64, (h - 1) // 2 + 1, (w - 1) // 2 + 1), dtype=out_dtype, device=x.device,
                            memory_format=torch.channels_last)
     with torch.cuda.device(x.device):
-        rc = _lib.load().tia_stem_conv7x7_pool_nhwc(x.data_ptr(), int(x.dtype == torch.uint8), w_packed.data_ptr(), bias.data_ptr(),
-                                                    y.data_ptr(), _DT[out_dtype], conv.data_ptr() if conv is not None else 0, n, h, w,
-                                                    _lib.current_stream())
-    _lib.check(rc, "tia_stem_conv7x7_pool_nhwc")
+        rc = _lib.load().tia_stem_conv7x7_pool_conv_nhwc(x.data_ptr(), int(x.dtype == torch.uint8), w_packed.data_ptr(), bias.data_ptr(),
+                                                         y.data_ptr(), _DT[out_dtype], conv.data_ptr() if conv is not None else 0, n, h,
+                                                         w, _lib.current_stream())
+    _lib.check(rc, "tia_stem_conv7x7_pool_conv_nhwc")
     return (y, conv) if return_conv else y
 
 

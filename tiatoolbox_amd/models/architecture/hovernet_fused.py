@@ -30,8 +30,8 @@ import torch
 import torch.nn.functional as F  # noqa: N812
 from torch import nn
 
-from tiatoolbox_amd.models.architecture.fused import (hip_bias_act_, hip_conv1x1_head, hip_conv1x1_pre, hip_conv2d_ex, hip_conv2d_post,
-                                                      hip_conv3x3_wino, pack_conv_weights_wino,
+from tiatoolbox_amd.models.architecture.fused import (hip_bias_act_, hip_conv1x1_head, hip_conv1x1_pre, hip_conv2d_ex, hip_conv2d_h,
+                                                      hip_conv2d_post, hip_conv3x3_wino, pack_conv_weights_h, pack_conv_weights_wino,
                                                       hip_conv2d_thin, hip_grouped_conv_valid, hip_scale_shift_act,
                                                       hip_scale_shift_act_view, hip_upsample2x_add, pack_conv_weights,
                                                       pack_thin_conv_weights)
@@ -86,9 +86,51 @@ class _Conv(nn.Module):
         self.conv_algo = "direct"
         self.wino_ok = self.mfma_ok and conv.kernel_size == (3, 3) and conv.stride == (1, 1) and conv.dilation == (1, 1)
         self._wino: torch.Tensor | None = None
+        # half-precision form (`prepare`): plain attributes, so that casting the module leaves them as they are
+        self.half_dtype: torch.dtype | None = None
+        self._packed_h: torch.Tensor | None = None   # [kh, kw, cin/8, cout, 8] halves (MFMA layers)
+        self._weight32: torch.Tensor | None = None   # [cout, 64] float32 (class heads)
+        self._bias32: torch.Tensor | None = None
+
+    def prepare(self, dtype: torch.dtype) -> None:
+        """Switch this convolution to fp16 / bf16 activations (``tia_conv2d_nhwc_h``; a class head: ``tia_conv1x1_head_nhwc_h``) --
+        call it on the device BEFORE the module is cast: the weights are packed NOW from the float32, BN-folded parameters (one
+        rounding to half, after the folding), and the bias stays float32 in a plain attribute that ``module.to(dtype)`` does not
+        touch.  ``torch.float32`` switches back.  A layer neither kernel takes raises ``TypeError``: there is no library
+        fall-back in half precision (``conv_algo`` has no effect there either: no Winograd form in half)."""
+        if dtype == torch.float32:
+            self.half_dtype = self._packed_h = self._weight32 = self._bias32 = None
+            return
+        if dtype not in (torch.float16, torch.bfloat16) or self.weight.dtype != torch.float32:
+            msg = f"_Conv.prepare packs float32 parameters for fp16 / bf16; got {self.weight.dtype} parameters for {dtype}."
+            raise ValueError(msg)
+        if self.head_ok:
+            self._weight32 = self.weight.detach().reshape(self.weight.shape[0], 64).clone().contiguous()
+        elif self.mfma_ok:
+            self._packed_h = pack_conv_weights_h(self, dtype)  # reads `.weight` (OIHW, BN folded, float32)
+        else:
+            msg = (f"no {dtype} kernel for a convolution {tuple(self.weight.shape)} with groups = {self.groups}: tia_conv2d_nhwc_h takes "
+                   "cin % 32 == 0 and cout % 64 == 0, tia_conv1x1_head_nhwc_h 64 -> at most 8 channels.")
+            raise TypeError(msg)
+        self._bias32 = self.bias.detach().clone().contiguous() if self.bias is not None else None
+        self.half_dtype = dtype
+
+    def _forward_half(self, x: torch.Tensor, pads: tuple[int, int], relu: bool, residual: torch.Tensor | None,  # noqa: FBT001
+                      pre: "_BnAct | None") -> torch.Tensor:
+        if self.head_ok and pads == (0, 0) and not relu and residual is None:
+            sc, sh = pre.affine32() if pre is not None else (None, None)
+            return hip_conv1x1_head(_cl(x), self._weight32, self._bias32, pre_scale=sc, pre_shift=sh)
+        if pre is not None or self._packed_h is None or pads[0] != pads[1]:
+            msg = (f"half-precision _Conv {tuple(self.weight.shape)}: tia_conv2d_nhwc_h takes symmetric padding and no activation on "
+                   f"load (pads {pads}, pre {'given' if pre is not None else 'none'}).")
+            raise TypeError(msg)
+        return hip_conv2d_h(_cl(x), self._packed_h, self._bias32, residual, cout=self.weight.shape[0], kernel=self.kernel,
+                            stride=self.stride, padding=pads[0], relu=relu)
 
     def forward(self, x: torch.Tensor, *, pads: tuple[int, int] = (0, 0), relu: bool = False,
                 residual: torch.Tensor | None = None, out: torch.Tensor | None = None, pre: "_BnAct | None" = None) -> torch.Tensor:
+        if self.half_dtype is not None:
+            return self._forward_half(x, pads, relu, residual, pre)
         if self.head_ok and pads == (0, 0) and not relu and residual is None:
             # `pre`: the BatchNorm + ReLU in front of the head, applied on load
             return hip_conv1x1_head(_cl(x), self.weight, self.bias, pre_scale=pre.scale if pre is not None else None,
@@ -167,6 +209,15 @@ class _BnAct(nn.Module):
         scale, shift = _bn_affine(bn)
         self.register_buffer("scale", scale)
         self.register_buffer("shift", shift)
+        self._affine32: tuple[torch.Tensor, torch.Tensor] | None = None
+
+    def prepare(self, dtype: torch.dtype) -> None:
+        """Keep float32 copies of scale / shift in a plain attribute before the module is cast to ``dtype`` (the half kernels
+        take them in float32; the buffers would be rounded)."""
+        self._affine32 = None if dtype == torch.float32 else (self.scale.detach().float().clone(), self.shift.detach().float().clone())
+
+    def affine32(self) -> tuple[torch.Tensor, torch.Tensor]:
+        return self._affine32 if self._affine32 is not None else (self.scale, self.shift)
 
     def forward(self, x: torch.Tensor, *, inplace: bool = False) -> torch.Tensor:
         return hip_scale_shift_act(_cl(x), self.scale, self.shift, relu=True, inplace=inplace)

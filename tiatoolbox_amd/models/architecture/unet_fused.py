@@ -10,9 +10,11 @@ Same arithmetic graph as ``UNetModel.forward`` (reference ``models/architecture/
   convolution;
 * the stem -- ``x / 255`` (on load, from the uint8 patch), 7x7 / 2 convolution + BN + ReLU AND the 3x3 / 2 max-pool -- is ONE
   launch of the hand-written stem kernel, which also writes the pre-pool activation (the decoder's first skip connection);
-* only the final ``64 -> n_classes`` 1x1 stays on the library.
+* the final ``64 -> n_classes`` 1x1 is the class-head kernel.
 
-Built from a loaded model (reference parameter names); float32, CUDA, channels-last only.
+Built from a loaded model (reference parameter names); CUDA, channels-last only.  float32 by default; ``prepare(dtype)`` switches the
+same graph to fp16 / bf16 activations: ``tia_conv2d_nhwc_h`` for the 61 convolutions, the half forms of the up-sampling pass and
+of the head, the float32-arithmetic stem writing halves; float32 logits either way.
 """
 
 from __future__ import annotations
@@ -41,7 +43,8 @@ class _FusedBottleneckMfma(nn.Module):
 
 
 class FusedUNet(nn.Module):
-    """``forward(x)`` == ``UNetModel.forward(x)`` (class logits), float32 on a CUDA device; ResNet-50 encoder, pre-activation
+    """``forward(x)`` == ``UNetModel.forward(x)`` (class logits, float32) on a CUDA device, in float32 or -- after ``prepare(dtype)`` --
+    fp16 / bf16 activations; ResNet-50 encoder, pre-activation
     decoder, ``skip_type="add"`` (the layout of ``fcn-tissue_mask`` / ``fcn_resnet50_unet-bcss``)."""
 
     def __init__(self, model: nn.Module) -> None:
@@ -58,6 +61,8 @@ class FusedUNet(nn.Module):
             msg = "FusedUNet expects the torchvision ResNet stem (conv 7x7 / 2 / pad 3, 3 -> 64; max-pool 3 / 2 / 1)."
             raise TypeError(msg)
         self._stem_packed: torch.Tensor | None = None
+        self._stem_bias32: torch.Tensor | None = None
+        self.half_dtype: torch.dtype | None = None  # fp16 / bf16 once `prepare(dtype)` has packed the half form
         self.layers = nn.ModuleList(nn.Sequential(*[_FusedBottleneckMfma(b) for b in layer])
                                     for layer in (bb.layer1, bb.layer2, bb.layer3, bb.layer4))
         self.conv1x1 = _Conv(model.conv1x1)
@@ -78,12 +83,43 @@ class FusedUNet(nn.Module):
 
     accepts_uint8 = True  # `infer_batch` hands the uint8 batch over as it is: the stem kernel divides by 255 while it loads
 
+    def prepare(self, dtype: torch.dtype) -> None:
+        """fp16 / bf16 activations on the same graph (the engines' ``compute_dtype``): call this on the device, on the float32
+        copy, BEFORE ``.to(dtype)``.  Every convolution packs its BN-folded float32 weights for ``tia_conv2d_nhwc_h`` (rounded
+        once, after the folding) and keeps its bias in float32; the decoder's BN scale / shift, the head's weights and the stem's
+        packed weights and bias stay float32 in plain attributes that the cast does not reach.  The stem stays the float32-
+        arithmetic kernel writing both of its maps in ``dtype`` (< 2 % of the flops, and exactly one rounding of the float32
+        stem), the up-sampling passes and the head run on their half forms, the logits come back in float32.  A layer without
+        a half kernel raises ``TypeError``.  ``torch.float32`` switches back (on a module that has not been cast)."""
+        if dtype not in (torch.float32, torch.float16, torch.bfloat16):
+            msg = f"FusedUNet runs in float32, float16 or bfloat16; got {dtype}."
+            raise ValueError(msg)
+        if self.stem.weight.dtype != torch.float32:
+            msg = f"FusedUNet.prepare starts from the float32 parameters (call it before the cast); got {self.stem.weight.dtype}."
+            raise ValueError(msg)
+        for mod in self.modules():
+            if isinstance(mod, (_Conv, _BnAct)) and mod is not self.stem:
+                mod.prepare(dtype)
+        self._stem_packed = pack_stem_weights(self.stem.weight)
+        self._stem_bias32 = self.stem.bias.detach().clone().contiguous()
+        self.half_dtype = None if dtype == torch.float32 else dtype
+
     def forward(self, imgs: torch.Tensor, *args, **kwargs) -> torch.Tensor:  # noqa: ARG002
-        if self._stem_packed is None or self._stem_packed.device != self.stem.weight.device:
+        half = self.half_dtype
+        if half is None and (self._stem_packed is None or self._stem_packed.device != self.stem.weight.device):
             self._stem_packed = pack_stem_weights(self.stem.weight)
         x = imgs.permute(0, 2, 3, 1)  # the NHWC batch under the NCHW view
-        x = x.contiguous() if x.dtype == torch.uint8 else (x.to(torch.float32) / 255.0).contiguous()
-        x, conv = hip_stem_conv_pool(x, self._stem_packed, self.stem.bias, return_conv=True)
+        if x.dtype == torch.uint8:
+            x = x.contiguous()
+        elif half is None:
+            x = (x.to(torch.float32) / 255.0).contiguous()
+        else:
+            # the quotient through float64: correctly rounded for the integers 0 .. 255 (the device's `x / 255.0` multiplies by the
+            # rounded reciprocal), so a float batch and the same bytes give the same logits
+            x = (x.to(torch.float64) / 255.0).to(torch.float32).contiguous()
+        # (half: float32 arithmetic, both maps rounded once to `half`; the parameter `stem.bias` has been cast, its float32 copy has not)
+        x, conv = hip_stem_conv_pool(x, self._stem_packed, self.stem.bias if half is None else self._stem_bias32,
+                                     out_dtype=half or torch.float32, return_conv=True)
         feats = [conv]
         for layer in self.layers:
             x = layer(x)
@@ -91,7 +127,7 @@ class FusedUNet(nn.Module):
         x = self.conv1x1(feats[-1])
         skips = feats[:-1]
         for idx, stage in enumerate(self.up, start=1):
-            x = hip_upsample2x_add(_cl(x), _cl(skips[-idx]), stage[0].scale, stage[0].shift)  # + the block's pre-activation
+            x = hip_upsample2x_add(_cl(x), _cl(skips[-idx]), *stage[0].affine32())  # + the block's pre-activation
             for j, conv in enumerate(list(stage)[1:]):
                 last = j == len(stage) - 2
                 p = (conv.kernel - 1) // 2

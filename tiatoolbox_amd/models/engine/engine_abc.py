@@ -438,11 +438,11 @@ class EngineABC:
                                    "module in %s instead of the hand-written trunk.", type(self.model).__name__, dtype, dtype)
                     use_mfma = False
                 m = fuse_cnn_model(m, epilogue_fusion="mfma" if use_mfma else False)
-            elif on_gpu and dtype == torch.float32:
+            elif on_gpu:
                 from tiatoolbox_amd.models.architecture.hovernet import HoVerNet
                 from tiatoolbox_amd.models.architecture.unet import UNetModel
 
-                if isinstance(m, HoVerNet):
+                if isinstance(m, HoVerNet) and dtype == torch.float32:
                     # HoVer-Net / HoVerNet+ in float32: 104 of its 144 convolutions on the hand-written MFMA kernel,
                     # BN folded or fused with the ReLU, residual adds in the epilogues (architecture/hovernet_fused.py)
                     from tiatoolbox_amd.models.architecture.hovernet_fused import FusedHoVerNet
@@ -452,7 +452,9 @@ class EngineABC:
 
                     set_conv_algo(m, algo)
                 elif isinstance(m, UNetModel) and hasattr(m.backbone, "layer1") and m.skip_type == "add":
-                    # UNet with the ResNet-50 encoder in float32: 61 of its 63 convolutions on the MFMA kernel
+                    # UNet with the ResNet-50 encoder: 61 of its 63 convolutions on the MFMA kernel (float32: tia_conv2d_nhwc_f32_ex
+                    # / Winograd; fp16 / bf16: tia_conv2d_nhwc_h after `prepare(dtype)` below), stem and head on their own kernels.
+                    # HoVer-Net, the plain-encoder and the concat-skip UNet have no half kernels: fp16 / bf16 casts the torch module
                     from tiatoolbox_amd.models.architecture.unet_fused import FusedUNet
 
                     m = FusedUNet(m.to(device=self.device))
@@ -465,6 +467,8 @@ class EngineABC:
                     if type(mod).__name__ == "MfmaResNet":
                         mod.set_conv_algo(algo)  # run kwarg `conv_algo="winograd"`: opt-in float32 Winograd for the 3x3 / stride-1 layers
                         mod.prepare(dtype)
+                    elif type(mod).__name__ == "FusedUNet" and dtype != torch.float32:
+                        mod.prepare(dtype)  # half weights from the float32 BN-folded ones; float32 biases / BN affines kept aside
             m = m.to(dtype=dtype) if dtype != torch.float32 else m
             if on_gpu:
                 m = m.to(memory_format=torch.channels_last)
@@ -489,8 +493,9 @@ class EngineABC:
     def _use_miopen_find(self) -> bool:
         """Only an explicit ``miopen_find=True`` switches the library's solver search on.  The float32 inference copies (ResNet
         classifiers, ``FusedHoVerNet``, ``FusedUNet``) launch no library convolution at all since round 3; the switch matters
-        for what still runs as a plain torch module (half-precision segmentation networks, user-supplied architectures),
-        where MIOpen's immediate mode can pick a naive NHWC kernel."""
+        for what still runs as a plain torch module (HoVer-Net and the plain-encoder / concat-skip UNet in half precision,
+        user-supplied architectures), where MIOpen's immediate mode can pick a naive NHWC kernel.  (The ResNet-50 UNet in fp16 /
+        bf16 is ``FusedUNet`` too and launches no library convolution.)"""
         return bool(getattr(self, "miopen_find", None))
 
     def invalidate_inference_cache(self) -> None:

@@ -367,7 +367,10 @@ def test_stain_augmentor_f32_fast_path(gold, he_patches):
     odd = StainAugmentor(method="macenko", precision="f32")
     odd.fit(he_patches[0][:50, :50], threshold=0.85)      # 50*50*3 is not a chunk multiple: f64 kernel
     assert not odd._fast_path_ok()  # noqa: SLF001
-    assert odd.augment(alpha_beta=np.array([1.1, 0.9, 0.01, -0.01])).shape == (50, 50, 3)
+    res = odd.augment(alpha_beta=np.array([1.1, 0.9, 0.01, -0.01]))
+    assert res.shape == (50, 50, 3) and res.dtype == np.uint8
+    sm = ostain.MacenkoExtractor().get_stain_matrix(he_patches[0][:50, :50].copy())
+    _u8_close(res, ostain.stain_augment(he_patches[0][:50, :50], sm, np.array([1.1, 0.9]), np.array([0.01, -0.01])))
     with pytest.raises(ValueError, match="precision"):
         StainAugmentor(precision="f16")
     del torch

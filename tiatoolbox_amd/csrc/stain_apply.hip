@@ -106,6 +106,11 @@ struct Pack12 {
     alignas(16) T v[12];
 };
 
+// the alignment store12's accesses need: one dword, one qword or one 16-byte vector at a time
+template <class T>
+constexpr uintptr_t kStore12Align = sizeof(T) * 12 == 12 ? 4 : sizeof(T) * 12 == 24 ? 8 : 16;
+
+// `dst` is aligned to kStore12Align<T> (sweep12 checks)
 template <class T>
 __device__ __forceinline__ void store12(T* __restrict__ dst, const Pack12<T>& pk) {
     constexpr int bytes = sizeof(T) * 12;
@@ -261,7 +266,10 @@ __device__ __forceinline__ void sweep12(const Ctx& ctx, const uint8_t* __restric
                                         long hw) {
     using O = Out<OUT>;
     using T = typename O::T;
-    if ((hw & 3) == 0) {
+    // the 12-byte groups read dwords and store through store12: both need their alignment (a contiguous view may start at any
+    // element of a larger buffer); everything else takes the per-pixel loop, like the mask kernel and rgb2od_kernel
+    const bool vec_ok = (reinterpret_cast<uintptr_t>(src) & 3) == 0 && (reinterpret_cast<uintptr_t>(dst) & (kStore12Align<T> - 1)) == 0;
+    if ((hw & 3) == 0 && vec_ok) {
         const long ng = hw >> 2;
         const long stride = (long)gridDim.x * AT;
         for (long g0 = (long)blockIdx.x * AT + threadIdx.x; g0 < ng; g0 += stride * U) {

@@ -557,6 +557,14 @@ int tia_conv2d_thin_nhwc_f32(const float* d_x, const float* d_w_packed, const fl
                              int64_t w, int64_t c, int64_t cout, int64_t kh, int64_t kw, int64_t stride, int64_t pad_top,
                              int64_t ho, int64_t wo, int32_t relu, void* stream);
 
+/* The thin-input convolution with its output in y_dtype (additive at version 6): the same kernel and the same float32 arithmetic;
+ * d_y [n,ho,wo,cout] of y_dtype, 16-byte aligned -- for TIA_DT_F16 / TIA_DT_BF16 the float32 value rounded once (nearest even), i.e.
+ * exactly tia_conv2d_thin_nhwc_f32's output passed through one conversion: the 7x7 stem of the half-precision HoVer-Net.
+ * TIA_DT_F32 is tia_conv2d_thin_nhwc_f32 itself. */
+int tia_conv2d_thin_nhwc(const float* d_x, const float* d_w_packed, const float* d_bias, void* d_y, int32_t y_dtype, int64_t n,
+                         int64_t h, int64_t w, int64_t c, int64_t cout, int64_t kh, int64_t kw, int64_t stride, int64_t pad_top,
+                         int64_t ho, int64_t wo, int32_t relu, void* stream);
+
 /* 1x1 convolution with FEW output channels (the class heads: cin = 64 -> cout <= 8; hovernet.py:196-199 `u0/conv`,
  * unet.py:336 `clf`), optionally with the BatchNorm + ReLU that precedes it applied on load:
  *   y[p][o] = bias[o] + sum_c w[o][c] * pre(x[p][c]),  pre(v) = relu(v * pre_scale[c] + pre_shift[c]) or v (both NULL).
@@ -691,6 +699,21 @@ int tia_stem_conv7x7_pool_nhwc_u8x3(const uint8_t* d_x, const void* d_w_packed3,
 int tia_conv2d_nhwc_h(const void* d_x, const void* d_w_packed, const float* d_bias, const void* d_residual, void* d_y,
                       int64_t n, int64_t h, int64_t w, int64_t cin, int64_t cout, int64_t kh, int64_t kw, int64_t stride,
                       int64_t pad, int32_t dtype, int32_t relu, void* stream);
+/* The extended form (additive at version 6), the half sibling of tia_conv2d_nhwc_f32_ex + tia_conv2d_post_nhwc_f32:
+ *   - the zero border given explicitly: pad_top / pad_left rows / columns in front and as many behind as [ho, wo] reaches
+ *     (pad_top < kh, pad_left < kw, (ho - 1) * stride - pad_top < h, likewise for columns) -- TensorFlow "same" padding of
+ *     HoVer-Net's strided 3x3 layers (0 in front, 1 behind on even maps);
+ *   - an optional second output from the same epilogue: with v = act(conv + bias [+ residual]) in float32,
+ *       d_y  (may be NULL when d_y2 is given) = half(v)
+ *       d_y2 (may be NULL)                    = half(relu(v * post_scale[c] + post_shift[c]))
+ *     computed from v BEFORE it is rounded, product and sum rounded separately in float32, then ONE rounding to half.
+ *     post_scale / post_shift: float32 [cout], 16-byte aligned, required with d_y2 and refused (TIA_EINVAL) without it.
+ * tia_conv2d_nhwc_h is this entry point with symmetric pads and no second output (and may take the tap-reuse kernel for a
+ * 3x3 / stride-1 layer, which this one never does).  Channel counts as there (TIA_ESIZE); misaligned pointers TIA_EINVAL. */
+int tia_conv2d_nhwc_h_ex(const void* d_x, const void* d_w_packed, const float* d_bias, const void* d_residual, void* d_y,
+                         int64_t n, int64_t h, int64_t w, int64_t cin, int64_t cout, int64_t kh, int64_t kw, int64_t stride,
+                         int64_t pad_top, int64_t pad_left, int64_t ho, int64_t wo, int32_t dtype, int32_t relu,
+                         const float* d_post_scale, const float* d_post_shift, void* d_y2, void* stream);
 /* OIHW float32 weights -> [kh][kw][cin/8][cout][8] halves of `dtype` (a lane's 8 k-values of its column contiguous). */
 int tia_conv_pack_weights_h(const float* d_w_oihw, int64_t cout, int64_t cin, int64_t kh, int64_t kw, int32_t dtype,
                             void* d_packed, void* stream);
@@ -708,6 +731,14 @@ int tia_scale_shift_act_view_nhwc_f32(const float* d_x, int64_t x_image_stride, 
                                       const float* d_scale, const float* d_shift, float* d_y, int64_t n, int64_t h,
                                       int64_t w, int64_t c, int32_t relu, void* stream);
 
+/* The half form (additive at version 6): d_x a view of an NHWC buffer of `dtype` (TIA_DT_F16 | TIA_DT_BF16), strides in elements
+ * (multiples of 8, 16-byte aligned base, x_pixel_stride >= c, else TIA_EINVAL); c % 8 == 0 (else TIA_ESIZE); scale / shift
+ * float32 [c]; d_y [n,h,w,c] dense of `dtype`.  p = float(x) * scale; a = p + shift; max(a, 0) (relu != 0), each step rounded on
+ * its own in float32, ONE rounding to half.  The pre-activations and `blk_bna` of HoVer-Net's dense blocks in half. */
+int tia_scale_shift_act_view_nhwc_h(const void* d_x, int64_t x_image_stride, int64_t x_row_stride, int64_t x_pixel_stride,
+                                    const float* d_scale, const float* d_shift, void* d_y, int64_t n, int64_t h, int64_t w,
+                                    int64_t c, int32_t relu, int32_t dtype, void* stream);
+
 /* Grouped "valid" k x k convolution, stride 1, 32 input and 8 output channels per group (the second convolution of
  * HoVer-Net's dense units, hovernet.py:86-88: Conv2d(128, 32, k, groups=4)); float32 NHWC.
  *   d_x [n,h,w,groups*32] dense;  d_w_packed [groups][k][k][32][8] (from OIHW [groups*8, 32, k, k]);
@@ -717,6 +748,19 @@ int tia_scale_shift_act_view_nhwc_f32(const float* d_x, int64_t x_image_stride, 
 int tia_grouped_conv_valid_nhwc_f32(const float* d_x, const float* d_w_packed, float* d_y, int64_t y_image_stride,
                                     int64_t y_row_stride, int64_t y_pixel_stride, int64_t n, int64_t h, int64_t w,
                                     int64_t groups, int64_t cin_per_group, int64_t cout_per_group, int64_t k, void* stream);
+
+/* The half form (additive at version 6), on v_mfma_f32_16x16x32_f16 / _bf16 (one tap of one group is its K = 32):
+ *   d_x [n,h,w,groups*32] dense of `dtype` (TIA_DT_F16 | TIA_DT_BF16);
+ *   d_w_packed from tia_grouped_conv_pack_weights_h: OIHW float32 [groups*8, 32, k, k] rounded ONCE to `dtype`, laid out
+ *   [groups][k][k][4 chunks of 8 input channels][8 outputs][8 halves];
+ *   float32 accumulation, ONE rounding; y of `dtype` through y_image_stride / y_row_stride / y_pixel_stride in elements
+ *   (multiples of 8, base 16-byte aligned, else TIA_EINVAL), so the result lands in its 32-channel slice and window of a dense
+ *   block's feature buffer.  k in {3, 5} (HoVer-Net's two modes: the taps are unrolled); other k and other channel counts per
+ *   group -> TIA_ESIZE.  Nothing is launched on an error. */
+int tia_grouped_conv_pack_weights_h(const float* d_w_oihw, int64_t groups, int64_t k, int32_t dtype, void* d_packed, void* stream);
+int tia_grouped_conv_valid_nhwc_h(const void* d_x, const void* d_w_packed, void* d_y, int64_t y_image_stride, int64_t y_row_stride,
+                                  int64_t y_pixel_stride, int64_t n, int64_t h, int64_t w, int64_t groups, int64_t cin_per_group,
+                                  int64_t cout_per_group, int64_t k, int32_t dtype, void* stream);
 
 /* Grouped 3x3 convolution, padding 1, stride 1 or 2, with the bias and ReLU fused: the grouped conv2 of the ResNeXt Bottleneck
  * (models/architecture/resnet.py: Conv2d(width, width, 3, stride, 1, groups=32)); float32 NHWC, on the vector ALU.

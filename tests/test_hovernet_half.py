@@ -1,0 +1,187 @@
+"""Host-side checks of the half-precision ``FusedHoVerNet`` (no GPU): the new C entry points are declared, the references of
+``_hovernet_half_ref.py`` say what they claim, and ``prepare(dtype)`` keeps what the half kernels take in float32 through
+``module.to(dtype)`` -- with the HIP calls replaced by their plain-torch definitions (the fixture style of ``test_unet_half.py``) the
+half graph is then run on the CPU against the plain float32 module, for the three variants of the network."""
+
+from __future__ import annotations
+
+import copy
+import re
+import sys
+from pathlib import Path
+
+import pytest
+import torch
+
+sys.path.insert(0, str(Path(__file__).resolve().parent))
+import _hovernet_half_ref as R  # noqa: E402, N812
+
+ROOT = Path(__file__).resolve().parent.parent
+NEW_SYMBOLS = ("tia_conv2d_nhwc_h_ex", "tia_grouped_conv_valid_nhwc_h", "tia_grouped_conv_pack_weights_h",
+               "tia_scale_shift_act_view_nhwc_h", "tia_conv2d_thin_nhwc")
+halves = pytest.mark.parametrize("dtype", R.HALVES, ids=[R.IDS[d] for d in R.HALVES])
+
+
+def test_new_entry_points_are_declared_in_header_and_binding():
+    from tiatoolbox_amd import _lib
+
+    header = re.sub(r"/\*.*?\*/", "", (ROOT / "include" / "tiatoolbox_amd.h").read_text(), flags=re.S)
+    sig = _lib._SIGNATURES  # noqa: SLF001
+    for name in NEW_SYMBOLS:
+        assert re.search(rf"^\s*int\s+{name}\s*\(", header, flags=re.M), name
+        assert name in sig, name
+    # the ex form: two pads and the output size instead of one pad, and scale / shift / y2 in front of the stream
+    assert len(sig["tia_conv2d_nhwc_h_ex"][0]) == len(sig["tia_conv2d_nhwc_h"][0]) + 3 + 3
+    # the dtype travels as an int32 in front of the stream (view, grouped) / behind the output (thin)
+    assert len(sig["tia_scale_shift_act_view_nhwc_h"][0]) == len(sig["tia_scale_shift_act_view_nhwc_f32"][0]) + 1
+    assert len(sig["tia_grouped_conv_valid_nhwc_h"][0]) == len(sig["tia_grouped_conv_valid_nhwc_f32"][0]) + 1
+    assert len(sig["tia_conv2d_thin_nhwc"][0]) == len(sig["tia_conv2d_thin_nhwc_f32"][0]) + 1
+
+
+@halves
+def test_post_hand_example_tells_the_unrounded_sum_from_the_rounded_one(dtype):
+    x, w, res, sc, sh, want_y, want_y2 = R.post_hand_example(dtype)
+    v, y2 = R.conv_ex_ref(x, w, None, res, stride=1, pad_lo=0, pad_hi=0, relu=False, post_scale=sc, post_shift=sh)
+    u = 2.0 ** -(R.MANTISSA[dtype] + 2)
+    assert torch.equal(v.double(), torch.full_like(want_y, 1 + u))  # exact in float32 ...
+    assert torch.equal(v.to(dtype).double(), want_y) and torch.equal(y2.to(dtype).double(), want_y2)  # ... a tie in half; y2 = 1
+    late = torch.relu(v.to(dtype).float() * sc[None, :, None, None] + sh[None, :, None, None])  # the affine AFTER the rounding
+    assert not late.any()
+
+
+@halves
+def test_pack_references_invert_and_the_grouped_bound_is_far_below_the_range(dtype):
+    g = torch.Generator().manual_seed(6)
+    w = torch.randn((64, 32, 3, 3), generator=g)
+    assert torch.equal(R.unpack_h(R.pack_h(w, dtype)), w.to(dtype))
+    wg = torch.randn((32, 32, 5, 5), generator=g) * 0.05
+    packed = R.pack_grouped_h(wg, 4, dtype)
+    assert packed.shape == (4, 5, 5, 4, 8, 8) and torch.equal(R.unpack_grouped_h(packed), wg.to(dtype))
+    # [g][ky][kx][chunk][out][j] = w[8 g + out][8 chunk + j][ky][kx]
+    assert packed[2, 1, 4, 3, 5, 6] == wg.to(dtype)[2 * 8 + 5, 3 * 8 + 6, 1, 4]
+    x = torch.randn((2, 128, 7, 9), generator=g).to(dtype)
+    ref, bound = R.grouped_ref(x, wg.to(dtype), 4)
+    assert ref.shape == (2, 32, 3, 5) and float(bound.max()) * 20 <= float(ref.max() - ref.min())
+    x8 = torch.randn((1, 8, 2, 3), generator=g).to(dtype)
+    sc, sh = torch.rand(8, generator=g) + 0.5, torch.randn(8, generator=g)
+    want = torch.clamp_min(x8.float() * sc[None, :, None, None] + sh[None, :, None, None], 0).to(dtype)
+    assert torch.equal(R.view_act_ref(x8, sc, sh), want) and (want == 0).any() and (want > 0).any()
+
+
+# ---- the half graph on the CPU: HIP calls replaced by what the header says they compute --------------------------------------------
+@pytest.fixture
+def torch_half_kernels(monkeypatch):
+    return R.install_torch_kernels(monkeypatch)
+
+
+@halves
+@pytest.mark.parametrize("kind", ["fast", "original", "plus"])
+def test_prepare_keeps_float32_operands_through_the_cast_and_runs_the_same_graph(torch_half_kernels, dtype, kind):
+    from tiatoolbox_amd.models.architecture.hovernet_fused import _BnAct, _Conv, _FusedDenseBlock
+
+    hf, calls, probes = torch_half_kernels
+    model, x, ref = R.graph_case(kind)
+    x = x[:1]
+    heads = ["tp", "np", "hv", "ls"] if kind == "plus" else ["tp", "np", "hv"]
+    with torch.inference_mode():
+        fused = hf.FusedHoVerNet(copy.deepcopy(model))
+        stem32 = fused.stem(x / 255.0, pads=hf._same_pads(x.shape[2], 7, 1) if fused.stem_pad else (0, 0), relu=True)  # noqa: SLF001
+        for k in calls:
+            calls[k] = 0
+        want_bias = {n: m.bias.detach().clone() for n, m in fused.named_modules() if isinstance(m, _Conv) and m.bias is not None}
+        want_w = {n: m.weight.detach().clone() for n, m in fused.named_modules() if isinstance(m, _Conv)}
+        want_affine = {n: (m.scale.clone(), m.shift.clone()) for n, m in fused.named_modules() if isinstance(m, _BnAct)}
+        fused.prepare(dtype)
+        fused = fused.to(dtype)
+        assert fused.half_dtype == dtype and next(fused.parameters()).dtype == dtype  # the cast happened ...
+        grouped = {id(c2) for m in fused.modules() if isinstance(m, _FusedDenseBlock) for c2 in m.c2}
+        n_mfma = n_head = 0
+        for name, mod in fused.named_modules():  # ... and left the float32 operands alone, bit for bit
+            if isinstance(mod, _Conv) and mod is not fused.stem and id(mod) not in grouped:
+                assert mod.half_dtype == dtype and (mod.bias is None) == (mod._bias32 is None)  # noqa: SLF001
+                if mod.bias is not None:
+                    assert mod.bias.dtype == dtype and mod._bias32.dtype == torch.float32  # noqa: SLF001
+                    assert torch.equal(mod._bias32, want_bias[name])  # noqa: SLF001
+                if mod._weight32 is not None:  # noqa: SLF001  (a class head: float32 weights)
+                    n_head += 1
+                    assert mod._packed_h is None and torch.equal(mod._weight32, want_w[name].reshape(-1, 64))  # noqa: SLF001
+                else:
+                    n_mfma += 1
+                    assert mod._packed_h.dtype == dtype and torch.equal(R.unpack_h(mod._packed_h), want_w[name].to(dtype))  # noqa: SLF001
+            if isinstance(mod, _BnAct):
+                sc, sh = mod.affine32()
+                assert sc.dtype == sh.dtype == torch.float32 and mod.scale.dtype == dtype
+                assert torch.equal(sc, want_affine[name][0]) and torch.equal(sh, want_affine[name][1])
+            if isinstance(mod, _FusedDenseBlock):
+                assert mod.half_dtype == dtype and len(mod._grouped_h) == len(mod.c2)  # noqa: SLF001
+                for c2, wp in zip(mod.c2, mod._grouped_h):  # noqa: SLF001
+                    assert c2.half_dtype is None and wp.dtype == dtype  # the grouped convolutions are the block's, not `_Conv.prepare`'s
+        branches = len(heads)
+        assert n_mfma == 104 + (branches - 3) * 17 and n_head == branches and len(grouped) == 12 * branches
+        # the stem keeps its float32 packed weights and bias in plain attributes
+        assert fused._stem_packed32.dtype == torch.float32 and fused._stem_bias32.dtype == torch.float32  # noqa: SLF001
+        assert torch.equal(fused._stem_bias32, want_bias["stem"]) and fused.stem.half_dtype is None  # noqa: SLF001
+        got = fused(x.to(dtype))  # 0 .. 255 are numbers of both half types: what `infer_batch` hands over
+    # per forward: the 16 conv3 + shortcut of the encoder through the second output, the 3 strided 3x3 through explicit pads, every
+    # other MFMA layer through the plain wrapper; 12 grouped and 14 view passes (8 + 1 and 4 + 1) per branch; one shared up-sampling
+    assert calls == {"conv_h": n_mfma - 19, "conv_h_ex": 19, "post": 16, "grouped": 12 * branches, "thin": 1, "head": branches,
+                     "up": 1 + 2 * branches, "view": 14 * branches}
+    assert torch.equal(probes["stem"], stem32.to(dtype))  # the float32 copy's stem through one rounding
+    assert list(got) == list(ref) == heads
+    for name in heads:
+        assert got[name].dtype == torch.float32 and got[name].shape == ref[name][:1].shape
+        err = R.rel_err(got[name], ref[name][:1])
+        # every activation rounded to half once per layer over ~60 layers in a row: far above any wiring mistake's reach
+        assert err <= (0.02 if dtype == torch.float16 else 0.15), (name, err)
+
+
+def test_prepare_switches_back_to_float32_on_an_uncast_module(torch_half_kernels):
+    from tiatoolbox_amd.models.architecture.hovernet_fused import _Conv, _FusedDenseBlock
+
+    hf, _, _ = torch_half_kernels
+    model, _, _ = R.graph_case("fast")
+    fused = hf.FusedHoVerNet(copy.deepcopy(model))
+    fused.prepare(torch.bfloat16)
+    fused.prepare(torch.float32)
+    assert fused.half_dtype is None and fused._stem_packed32 is None  # noqa: SLF001
+    assert all(m.half_dtype is None for m in fused.modules() if isinstance(m, (_Conv, _FusedDenseBlock)))
+    with pytest.raises(ValueError, match="float32, float16 or bfloat16"):
+        fused.prepare(torch.float64)
+
+
+def test_prepare_refuses_cast_modules_and_layers_without_a_half_kernel(torch_half_kernels):
+    hf, _, _ = torch_half_kernels
+    model, _, _ = R.graph_case("fast")
+    with pytest.raises(ValueError, match="before the cast"):
+        hf.FusedHoVerNet(copy.deepcopy(model)).half().prepare(torch.float16)
+    # a decoder convolution narrower than the MFMA tile: float32 runs it as a torch convolution, half has no kernel for it
+    m = copy.deepcopy(model)
+    m.decoder["np"][2].conva = torch.nn.Conv2d(256, 48, 5, bias=False)
+    with pytest.raises(TypeError, match="no torch.float16 kernel"):
+        hf.FusedHoVerNet(m).prepare(torch.float16)
+    # a dense unit whose second convolution is not 32 -> 8 channels per group
+    m = copy.deepcopy(model)
+    unit = m.decoder["hv"][0].dense.units[0]
+    unit.conv2 = torch.nn.Conv2d(128, 32, 5, groups=2, bias=False)
+    with pytest.raises(TypeError, match="no torch.bfloat16 kernel for a dense unit"):
+        hf.FusedHoVerNet(m).prepare(torch.bfloat16)
+
+
+def test_wrappers_refuse_on_the_host_before_any_launch():
+    """Argument checks that need no device: the CUDA check comes first (no silent torch fall-back)."""
+    from tiatoolbox_amd.models.architecture import fused
+
+    x = torch.zeros((1, 32, 4, 4), dtype=torch.float16).contiguous(memory_format=torch.channels_last)
+    wp = torch.zeros((1, 1, 4, 64, 8), dtype=torch.float16)
+    with pytest.raises(ValueError, match="channels-last CUDA"):
+        fused.hip_conv2d_h_ex(x, wp, None, None, cout=64, kernel=1, stride=1, pad_lo=0, pad_hi=0, relu=False)
+    with pytest.raises(ValueError, match="channels-last CUDA"):
+        fused.hip_grouped_conv_valid_h(torch.zeros((1, 128, 5, 5), dtype=torch.float16).contiguous(memory_format=torch.channels_last),
+                                       torch.zeros((4, 3, 3, 4, 8, 8), dtype=torch.float16), groups=4, kernel=3)
+    with pytest.raises(ValueError, match="CUDA"):
+        fused.pack_grouped_conv_valid_weights_h(torch.zeros((32, 32, 3, 3)), 4, torch.float16)
+    with pytest.raises(ValueError, match="CUDA"):
+        fused.hip_scale_shift_act_view(x, torch.ones(32), torch.zeros(32))
+    with pytest.raises(ValueError, match="float32 CUDA tensor"):
+        fused.hip_conv2d_thin(torch.zeros((1, 3, 8, 8)), torch.zeros((7, 32, 64)), None, kernel=7, stride=1, pad_lo=3, pad_hi=3,
+                              relu=True, out_dtype=torch.float16)

@@ -108,6 +108,7 @@ _SIGNATURES = {
                                C.c_int),
     "tia_conv3x3_geometry": ([_I64, _I64, _I64, _I64, _I64, _I64, C.POINTER(C.c_int32)], C.c_int),
     "tia_conv2d_thin_nhwc_f32": ([_P, _P, _P, _P, _I64, _I64, _I64, _I64, _I64, _I64, _I64, _I64, _I64, _I64, _I64, _I32, _P], C.c_int),
+    "tia_conv2d_thin_nhwc": ([_P, _P, _P, _P, _I32, _I64, _I64, _I64, _I64, _I64, _I64, _I64, _I64, _I64, _I64, _I64, _I32, _P], C.c_int),
     "tia_conv1x1_head_nhwc_f32": ([_P, _I64, _P, _P, _P, _P, _I32, _P, _P], C.c_int),
     "tia_conv1x1_head_nhwc_h": ([_P, _I64, _P, _P, _P, _P, _I32, _I32, _P, _P], C.c_int),
     "tia_conv2d_post_nhwc_f32": ([_P, _P, _P, _P, _P, _I64, _I64, _I64, _I64, _I64, _I64, _I64, _I64, _I64, _I64, _I64, _I64, _I32,
@@ -125,6 +126,7 @@ _SIGNATURES = {
     "tia_stem_conv7x7_pool_nhwc": ([_P, _I32, _P, _P, _P, _I32, _P, _I64, _I64, _I64, _P], C.c_int),
     "tia_stem_conv7x7_pool_conv_nhwc": ([_P, _I32, _P, _P, _P, _I32, _P, _I64, _I64, _I64, _P], C.c_int),
     "tia_conv2d_nhwc_h": ([_P, _P, _P, _P, _P, _I64, _I64, _I64, _I64, _I64, _I64, _I64, _I64, _I64, _I32, _I32, _P], C.c_int),
+    "tia_conv2d_nhwc_h_ex": ([_P, _P, _P, _P, _P] + [_I64] * 12 + [_I32, _I32, _P, _P, _P, _P], C.c_int),
     "tia_conv_pack_weights_h": ([_P, _I64, _I64, _I64, _I64, _I32, _P, _P], C.c_int),
     "tia_stem_pack_weights_f32": ([_P, _P, _P], C.c_int),
     "tia_stem_pack_weights_bf16x3": ([_P, _P, _P], C.c_int),
@@ -132,6 +134,9 @@ _SIGNATURES = {
     "tia_scale_shift_act_nhwc_f32": ([_P, _P, _P, _P, _I64, _I64, _I32, _P], C.c_int),
     "tia_scale_shift_act_view_nhwc_f32": ([_P, _I64, _I64, _I64, _P, _P, _P, _I64, _I64, _I64, _I64, _I32, _P], C.c_int),
     "tia_grouped_conv_valid_nhwc_f32": ([_P, _P, _P, _I64, _I64, _I64, _I64, _I64, _I64, _I64, _I64, _I64, _I64, _P], C.c_int),
+    "tia_scale_shift_act_view_nhwc_h": ([_P, _I64, _I64, _I64, _P, _P, _P, _I64, _I64, _I64, _I64, _I32, _I32, _P], C.c_int),
+    "tia_grouped_conv_pack_weights_h": ([_P, _I64, _I64, _I32, _P, _P], C.c_int),
+    "tia_grouped_conv_valid_nhwc_h": ([_P, _P, _P, _I64, _I64, _I64, _I64, _I64, _I64, _I64, _I64, _I64, _I64, _I32, _P], C.c_int),
     "tia_conv3x3_grouped_nhwc_f32": ([_P, _P, _P, _P, _I64, _I64, _I64, _I64, _I64, _I64, _I32, _P], C.c_int),
     "tia_upsample2x_add_nhwc_f32": ([_P, _P, _I64, _I64, _P, _I64, _I64, _I64, _I64, _P], C.c_int),
     "tia_upsample2x_add_act_nhwc_f32": ([_P, _P, _I64, _I64, _P, _P, _P, _I64, _I64, _I64, _I64, _P], C.c_int),

@@ -60,7 +60,9 @@ struct ConvPost {
 
 using f32x4 = __attribute__((ext_vector_type(4))) float;
 
-template <int BN, bool POST = false, bool PRE = false>
+// YDT: the type of y (TIA_DT_F32; TIA_DT_F16 / TIA_DT_BF16: the same float32 value rounded once on the way out -- the thin stem of the
+// half-precision HoVer-Net; plain form only).  The float32 instantiations are what they were.
+template <int BN, bool POST = false, bool PRE = false, int YDT = TIA_DT_F32>
 __global__ __launch_bounds__(NTH, 2) void conv_mfma_f32_kernel(const float* __restrict__ x, const float* __restrict__ wk,
                                                             const float* __restrict__ bias, const float* __restrict__ res,
                                                             float* __restrict__ y, ConvDims d, int relu, int m_tiles,
@@ -279,6 +281,8 @@ __global__ __launch_bounds__(NTH, 2) void conv_mfma_f32_kernel(const float* __re
                         a = a + pt;
                         post.y2[m * d.cout + n] = a > 0.0f ? a : 0.0f;
                     }
+                } else if constexpr (YDT != TIA_DT_F32) {
+                    if (m < m_total) reinterpret_cast<unsigned short*>(y)[m * d.cout + n] = f32_to_half<YDT == TIA_DT_BF16>(v);
                 } else {
                     if (m < m_total) y[m * d.cout + n] = v;
                 }
@@ -357,10 +361,13 @@ static int conv2d_impl(const float* d_x, const float* d_w_packed, const float* d
                        int64_t h, int64_t w, int64_t cin, int64_t cout, int64_t kh, int64_t kw, int64_t stride, int64_t pad_top,
                        int64_t pad_left, int64_t ho, int64_t wo, int32_t relu, const float* d_post_scale, const float* d_post_shift,
                        float* d_y2, void* stream, int64_t pstride = 0, const float* d_pre_scale = nullptr,
-                       const float* d_pre_shift = nullptr) {
+                       const float* d_pre_shift = nullptr, int32_t y_dtype = TIA_DT_F32) {
     const bool with_post = d_y2 != nullptr;
     const bool with_pre = d_pre_scale != nullptr;
     if (pstride <= 0) pstride = cin;
+    // a half d_y (behind the float pointer): the thin form's plain epilogue only, on the slice kernel
+    const bool y_half = y_dtype != TIA_DT_F32;
+    if (y_half && ((y_dtype != TIA_DT_F16 && y_dtype != TIA_DT_BF16) || with_post || with_pre || d_residual || pstride == cin)) return TIA_EINVAL;
     // activation on load: 1x1 without padding only (a padding tap must contribute zero, not relu(shift))
     if (with_pre && (!d_pre_shift || with_post || kh != 1 || kw != 1 || pad_top != 0 || pad_left != 0 || pstride != cin ||
                      ((reinterpret_cast<uintptr_t>(d_pre_scale) | reinterpret_cast<uintptr_t>(d_pre_shift)) & 15) != 0))
@@ -383,7 +390,9 @@ static int conv2d_impl(const float* d_x, const float* d_w_packed, const float* d
                    (int)pad_left, (unsigned)(nb * image_bytes), (unsigned)w_bytes, (int)pstride};
         const float* xg = d_x + first * h * w * pstride;
         const float* rg = d_residual ? d_residual + first * ho * wo * cout : nullptr;
-        float* yg = d_y ? d_y + first * ho * wo * cout : nullptr;
+        float* yg = d_y ? (y_half ? reinterpret_cast<float*>(reinterpret_cast<unsigned short*>(d_y) + first * ho * wo * cout)
+                                  : d_y + first * ho * wo * cout)
+                        : nullptr;
         const ConvPost post{d_post_scale, d_post_shift, with_post ? d_y2 + first * ho * wo * cout : nullptr, d_pre_scale, d_pre_shift};
         const ConvRoute route = conv2d_route(plain, nb, h, w, cin, cout, kh, kw, stride, pad_top, pad_left, ho, wo);
         if (route == ROUTE_SPATIAL &&
@@ -399,7 +408,17 @@ static int conv2d_impl(const float* d_x, const float* d_w_packed, const float* d
         // 5 instead of 3 per CU) hides their prologue / epilogue better (+15-20 % on resnet18's down-sampling convolutions)
         const bool narrow = force64 || (!no_rule && kh == 1 && kw == 1 && cin <= 256);
         const ConvPost none{nullptr, nullptr, nullptr, nullptr, nullptr};
-        if (with_pre) {
+        if (y_half) {
+#define TIA_LAUNCH_YH(BN_, DT_)                                                                                                      \
+    hipLaunchKernelGGL((conv_mfma_f32_kernel<BN_, false, false, DT_>), dim3((unsigned)grid_x, (unsigned)(cout / BN_)), dim3(NTH), 0, st, \
+                       xg, d_w_packed, d_bias, rg, yg, d, relu, (int)m_tiles, none)
+            if (cout % 128 == 0 && !narrow) {
+                if (y_dtype == TIA_DT_BF16) TIA_LAUNCH_YH(128, TIA_DT_BF16); else TIA_LAUNCH_YH(128, TIA_DT_F16);
+            } else {
+                if (y_dtype == TIA_DT_BF16) TIA_LAUNCH_YH(64, TIA_DT_BF16); else TIA_LAUNCH_YH(64, TIA_DT_F16);
+            }
+#undef TIA_LAUNCH_YH
+        } else if (with_pre) {
             if (cout % 128 == 0 && !narrow)
                 hipLaunchKernelGGL((conv_mfma_f32_kernel<128, false, true>), dim3((unsigned)grid_x, (unsigned)(cout / 128)), dim3(NTH), 0,
                                    st, xg, d_w_packed, d_bias, rg, yg, d, relu, (int)m_tiles, post);
@@ -469,6 +488,18 @@ extern "C" int tia_conv2d_thin_nhwc_f32(const float* d_x, const float* d_w_packe
     if ((wo - 1) * stride + kw > w || (w - (wo - 1) * stride) * c < BK) return TIA_EINVAL;
     return conv2d_impl(d_x, d_w_packed, d_bias, nullptr, d_y, n, h, w, BK, cout, kh, 1, stride, pad_top, 0, ho, wo, relu, nullptr,
                        nullptr, nullptr, stream, c);
+}
+
+extern "C" int tia_conv2d_thin_nhwc(const float* d_x, const float* d_w_packed, const float* d_bias, void* d_y, int32_t y_dtype, int64_t n,
+                                    int64_t h, int64_t w, int64_t c, int64_t cout, int64_t kh, int64_t kw, int64_t stride, int64_t pad_top,
+                                    int64_t ho, int64_t wo, int32_t relu, void* stream) {
+    if (y_dtype == TIA_DT_F32)
+        return tia_conv2d_thin_nhwc_f32(d_x, d_w_packed, d_bias, static_cast<float*>(d_y), n, h, w, c, cout, kh, kw, stride, pad_top, ho, wo,
+                                        relu, stream);
+    if (!d_y || c <= 0 || kw <= 0 || c * kw > BK || c >= BK || stride <= 0 || wo <= 0 || (reinterpret_cast<uintptr_t>(d_y) & 15) != 0) return TIA_EINVAL;
+    if ((wo - 1) * stride + kw > w || (w - (wo - 1) * stride) * c < BK) return TIA_EINVAL;
+    return conv2d_impl(d_x, d_w_packed, d_bias, nullptr, static_cast<float*>(d_y), n, h, w, BK, cout, kh, 1, stride, pad_top, 0, ho, wo, relu,
+                       nullptr, nullptr, nullptr, stream, c, nullptr, nullptr, y_dtype);
 }
 
 extern "C" int tia_conv2d_post_nhwc_f32(const float* d_x, const float* d_w_packed, const float* d_bias, const float* d_residual,

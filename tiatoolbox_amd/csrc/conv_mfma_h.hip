@@ -52,10 +52,22 @@ __device__ __forceinline__ f32x16 mma(const u32x4& a, const u32x4& b, const f32x
     else
         return __builtin_amdgcn_mfma_f32_32x32x16_f16(*reinterpret_cast<const h8*>(&a), *reinterpret_cast<const h8*>(&b), c, 0, 0, 0);
 }
-template <int BN, bool BF, int BK>
+
+// second, post-activated output of the epilogue (POST kernels): y2 = relu(v * scale[c] + shift[c]) of the float32 value v BEFORE it is
+// rounded for y -- the BatchNorm + ReLU that follows a residual sum in a pre-activation network (conv_mfma.hip: ConvPost).  The LDS
+// of this kernel is filled by DMA straight from global memory, so there is no "activate on load" form: the half graph takes the
+// activated copy from here instead.  y may then be null.
+struct ConvPostH {
+    const float* scale;
+    const float* shift;
+    void* y2;
+};
+
+template <int BN, bool BF, int BK, bool POST = false>
 __global__ __launch_bounds__(NTH, 2) void conv_mfma_h_kernel(const void* __restrict__ x, const void* __restrict__ wk,
                                                           const float* __restrict__ bias, const void* __restrict__ res,
-                                                          void* __restrict__ y, ConvDimsH d, int relu, int m_tiles) {
+                                                          void* __restrict__ y, ConvDimsH d, int relu, int m_tiles,
+                                                          ConvPostH post = ConvPostH{nullptr, nullptr, nullptr}) {
     static_assert(BK == 32 || BK == 64, "slices of 32 or 64 input channels");
     constexpr int NTILE = BN / 64;
     constexpr int CH = BK / 8;                       // 16-byte chunks (8 halves) per pixel and slice
@@ -267,9 +279,32 @@ __global__ __launch_bounds__(NTH, 2) void conv_mfma_h_kernel(const void* __restr
                         a0 = a0 > 0.0f ? a0 : 0.0f;
                         a1 = a1 > 0.0f ? a1 : 0.0f;
                     }
+                    v[2 * k] = a0;
+                    v[2 * k + 1] = a1;
                     o[k] = (unsigned)f32_to_half<BF>(a0) | ((unsigned)f32_to_half<BF>(a1) << 16);
                 }
-                *reinterpret_cast<u32x4*>(yh + m * d.cout + col0) = u32x4{o[0], o[1], o[2], o[3]};
+                if constexpr (POST) {
+#pragma clang fp contract(off)
+                    // from the UNROUNDED v; product and sum rounded separately, like batch_norm + relu, then one rounding to half
+                    const float4 s0 = *reinterpret_cast<const float4*>(post.scale + col0), s1 = *reinterpret_cast<const float4*>(post.scale + col0 + 4);
+                    const float4 t0 = *reinterpret_cast<const float4*>(post.shift + col0), t1 = *reinterpret_cast<const float4*>(post.shift + col0 + 4);
+                    const float ps[8] = {s0.x, s0.y, s0.z, s0.w, s1.x, s1.y, s1.z, s1.w};
+                    const float pt[8] = {t0.x, t0.y, t0.z, t0.w, t1.x, t1.y, t1.z, t1.w};
+                    unsigned o2[4];
+#pragma unroll
+                    for (int k = 0; k < 4; ++k) {
+                        float a0 = v[2 * k] * ps[2 * k], a1 = v[2 * k + 1] * ps[2 * k + 1];
+                        a0 = a0 + pt[2 * k];
+                        a1 = a1 + pt[2 * k + 1];
+                        a0 = a0 > 0.0f ? a0 : 0.0f;
+                        a1 = a1 > 0.0f ? a1 : 0.0f;
+                        o2[k] = (unsigned)f32_to_half<BF>(a0) | ((unsigned)f32_to_half<BF>(a1) << 16);
+                    }
+                    *reinterpret_cast<u32x4*>(reinterpret_cast<unsigned short*>(post.y2) + m * d.cout + col0) = u32x4{o2[0], o2[1], o2[2], o2[3]};
+                    if (yh) *reinterpret_cast<u32x4*>(yh + m * d.cout + col0) = u32x4{o[0], o[1], o[2], o[3]};
+                } else {
+                    *reinterpret_cast<u32x4*>(yh + m * d.cout + col0) = u32x4{o[0], o[1], o[2], o[3]};
+                }
             }
         }
         __syncthreads();
@@ -314,18 +349,25 @@ extern "C" int tia_conv_pack_weights_h(const float* d_w_oihw, int64_t cout, int6
     return hipGetLastError() == hipSuccess ? TIA_OK : TIA_ELAUNCH;
 }
 
-extern "C" int tia_conv2d_nhwc_h(const void* d_x, const void* d_w_packed, const float* d_bias, const void* d_residual, void* d_y,
-                                 int64_t n, int64_t h, int64_t w, int64_t cin, int64_t cout, int64_t kh, int64_t kw, int64_t stride,
-                                 int64_t pad, int32_t dtype, int32_t relu, void* stream) {
-    if (!d_x || !d_w_packed || !d_y || n <= 0 || h <= 0 || w <= 0 || kh <= 0 || kw <= 0 || stride <= 0 || pad < 0) return TIA_EINVAL;
+// The one host path of both entry points.  `spatial`: the call may take the tap-reuse route (the plain entry point's 3x3 / stride 1).
+static int conv2d_h_impl(const void* d_x, const void* d_w_packed, const float* d_bias, const void* d_residual, void* d_y, int64_t n,
+                         int64_t h, int64_t w, int64_t cin, int64_t cout, int64_t kh, int64_t kw, int64_t stride, int64_t pad_top,
+                         int64_t pad_left, int64_t ho, int64_t wo, int32_t dtype, int32_t relu, const float* d_post_scale,
+                         const float* d_post_shift, void* d_y2, bool spatial, void* stream) {
+    const bool with_post = d_y2 != nullptr;
+    if (!d_x || !d_w_packed || (!d_y && !with_post) || n <= 0 || h <= 0 || w <= 0 || kh <= 0 || kw <= 0 || stride <= 0 || pad_top < 0 ||
+        pad_left < 0)
+        return TIA_EINVAL;
     if (dtype != TIA_DT_F16 && dtype != TIA_DT_BF16) return TIA_EINVAL;
+    if (with_post ? (!d_post_scale || !d_post_shift) : (d_post_scale || d_post_shift)) return TIA_EINVAL;
     if (cin % 32 != 0 || cout % 64 != 0) return TIA_ESIZE;
     if (((reinterpret_cast<uintptr_t>(d_x) | reinterpret_cast<uintptr_t>(d_w_packed) | reinterpret_cast<uintptr_t>(d_y) |
-          reinterpret_cast<uintptr_t>(d_residual) | reinterpret_cast<uintptr_t>(d_bias)) & 15) != 0)
+          reinterpret_cast<uintptr_t>(d_residual) | reinterpret_cast<uintptr_t>(d_bias) | reinterpret_cast<uintptr_t>(d_y2) |
+          reinterpret_cast<uintptr_t>(d_post_scale) | reinterpret_cast<uintptr_t>(d_post_shift)) & 15) != 0)
         return TIA_EINVAL;
-    if (kh > 16 || kw > 16 || pad >= kh || pad >= kw) return TIA_EINVAL;
-    const long ho = (h + 2 * pad - kh) / stride + 1, wo = (w + 2 * pad - kw) / stride + 1;
-    if (ho <= 0 || wo <= 0) return TIA_EINVAL;
+    if (kh > 16 || kw > 16 || pad_top >= kh || pad_left >= kw) return TIA_EINVAL;
+    // every output pixel's first tap row / column starts inside [-(k - 1), h): what lies beyond the image on either side reads as zeros
+    if (ho <= 0 || wo <= 0 || (ho - 1) * stride - pad_top >= h || (wo - 1) * stride - pad_left >= w) return TIA_EINVAL;
     const long image_bytes = h * w * cin * 2, w_bytes = kh * kw * cin * cout * 2;
     if (image_bytes > 0x7fffffffL || w_bytes > 0x7fffffffL || ho * wo > 0x7fffffffL / 4) return TIA_ESIZE;
     long group = 0x7fffffffL / image_bytes;
@@ -338,26 +380,34 @@ extern "C" int tia_conv2d_nhwc_h(const void* d_x, const void* d_w_packed, const 
         const long nb = n - first < group ? n - first : group;
         const long m_total = nb * ho * wo;
         const long m_tiles = (m_total + BM - 1) / BM;
-        ConvDimsH d{(int)nb, (int)h, (int)w, (int)cin, (int)cout, (int)ho, (int)wo, (int)kh, (int)kw, (int)stride, (int)pad, (int)pad,
-                    (unsigned)(nb * image_bytes), (unsigned)w_bytes};
+        ConvDimsH d{(int)nb, (int)h, (int)w, (int)cin, (int)cout, (int)ho, (int)wo, (int)kh, (int)kw, (int)stride, (int)pad_top,
+                    (int)pad_left, (unsigned)(nb * image_bytes), (unsigned)w_bytes};
         const char* xg = static_cast<const char*>(d_x) + first * image_bytes;
         const char* rg = d_residual ? static_cast<const char*>(d_residual) + first * ho * wo * cout * 2 : nullptr;
-        char* yg = static_cast<char*>(d_y) + first * ho * wo * cout * 2;
+        char* yg = d_y ? static_cast<char*>(d_y) + first * ho * wo * cout * 2 : nullptr;
+        const ConvPostH post{d_post_scale, d_post_shift, with_post ? static_cast<char*>(d_y2) + first * ho * wo * cout * 2 : nullptr};
         // 3x3 / stride 1 on maps that 16 x 16 pixel blocks cover with little waste: the tap-reuse form (conv3x3_spatial.hip)
-        if (tia::conv3x3_spatial_ok(kh, kw, stride, h, w, ho, wo, pad, pad, false) &&
-            tia::conv3x3_spatial_launch(xg, d_w_packed, d_bias, rg, yg, nb, h, w, cin, cout, pad, pad, ho, wo, dtype, relu, st))
+        if (spatial && !with_post && tia::conv3x3_spatial_ok(kh, kw, stride, h, w, ho, wo, pad_top, pad_left, false) &&
+            tia::conv3x3_spatial_launch(xg, d_w_packed, d_bias, rg, yg, nb, h, w, cin, cout, pad_top, pad_left, ho, wo, dtype, relu, st))
             continue;
         const long grid_x = ((m_tiles + 7) / 8) * 8;
         // 64-channel slices (two stages, 16 MFMAs per barrier, whole cache lines per pixel) measured no faster than 32-channel
         // slices in a three-stage ring (profiles/r03e_perf_conv_h*.txt: 527 vs 539 TF/s over the resnet18 trunk; slower on the
         // 1x1 convolutions): both sit on the global -> LDS byte rate, not on latency or barriers.  Kept as a developer switch.
         static const bool want64 = tia::dev_env("TIA_CONVH_BK64") != nullptr;
-        const bool bk64 = cin % 64 == 0 && want64;
+        const bool bk64 = cin % 64 == 0 && want64 && !with_post;
         const bool wide = cout % 128 == 0;
         const dim3 grid((unsigned)grid_x, (unsigned)(cout / (wide ? 128 : 64)));
 #define TIA_LAUNCH_H(BN_, BF_, BK_) \
-    hipLaunchKernelGGL((conv_mfma_h_kernel<BN_, BF_, BK_>), grid, dim3(NTH), 0, st, xg, d_w_packed, d_bias, rg, yg, d, relu, (int)m_tiles)
-        if (wide) {
+    hipLaunchKernelGGL((conv_mfma_h_kernel<BN_, BF_, BK_>), grid, dim3(NTH), 0, st, xg, d_w_packed, d_bias, rg, yg, d, relu, (int)m_tiles, \
+                       ConvPostH{nullptr, nullptr, nullptr})
+#define TIA_LAUNCH_H_POST(BN_, BF_) \
+    hipLaunchKernelGGL((conv_mfma_h_kernel<BN_, BF_, 32, true>), grid, dim3(NTH), 0, st, xg, d_w_packed, d_bias, rg, yg, d, relu, \
+                       (int)m_tiles, post)
+        if (with_post) {  // the second output is a template parameter: a run-time switch cost the plain instantiations 1.5-3.7 %
+            if (wide) { if (bf) TIA_LAUNCH_H_POST(128, true); else TIA_LAUNCH_H_POST(128, false); }
+            else { if (bf) TIA_LAUNCH_H_POST(64, true); else TIA_LAUNCH_H_POST(64, false); }
+        } else if (wide) {
             if (bf) { if (bk64) TIA_LAUNCH_H(128, true, 64); else TIA_LAUNCH_H(128, true, 32); }
             else { if (bk64) TIA_LAUNCH_H(128, false, 64); else TIA_LAUNCH_H(128, false, 32); }
         } else {
@@ -365,6 +415,24 @@ extern "C" int tia_conv2d_nhwc_h(const void* d_x, const void* d_w_packed, const 
             else { if (bk64) TIA_LAUNCH_H(64, false, 64); else TIA_LAUNCH_H(64, false, 32); }
         }
 #undef TIA_LAUNCH_H
+#undef TIA_LAUNCH_H_POST
     }
     return hipGetLastError() == hipSuccess ? TIA_OK : TIA_ELAUNCH;
+}
+
+extern "C" int tia_conv2d_nhwc_h(const void* d_x, const void* d_w_packed, const float* d_bias, const void* d_residual, void* d_y,
+                                 int64_t n, int64_t h, int64_t w, int64_t cin, int64_t cout, int64_t kh, int64_t kw, int64_t stride,
+                                 int64_t pad, int32_t dtype, int32_t relu, void* stream) {
+    if (!d_y || h <= 0 || w <= 0 || kh <= 0 || kw <= 0 || stride <= 0 || pad < 0) return TIA_EINVAL;
+    const long ho = (h + 2 * pad - kh) / stride + 1, wo = (w + 2 * pad - kw) / stride + 1;
+    return conv2d_h_impl(d_x, d_w_packed, d_bias, d_residual, d_y, n, h, w, cin, cout, kh, kw, stride, pad, pad, ho, wo, dtype, relu,
+                         nullptr, nullptr, nullptr, true, stream);
+}
+
+extern "C" int tia_conv2d_nhwc_h_ex(const void* d_x, const void* d_w_packed, const float* d_bias, const void* d_residual, void* d_y,
+                                    int64_t n, int64_t h, int64_t w, int64_t cin, int64_t cout, int64_t kh, int64_t kw, int64_t stride,
+                                    int64_t pad_top, int64_t pad_left, int64_t ho, int64_t wo, int32_t dtype, int32_t relu,
+                                    const float* d_post_scale, const float* d_post_shift, void* d_y2, void* stream) {
+    return conv2d_h_impl(d_x, d_w_packed, d_bias, d_residual, d_y, n, h, w, cin, cout, kh, kw, stride, pad_top, pad_left, ho, wo, dtype,
+                         relu, d_post_scale, d_post_shift, d_y2, false, stream);
 }

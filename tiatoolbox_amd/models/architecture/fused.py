@@ -155,15 +155,21 @@ def pack_thin_conv_weights(weight: torch.Tensor) -> torch.Tensor:
 
 
 def hip_conv2d_thin(x: torch.Tensor, w_packed: torch.Tensor, bias: torch.Tensor | None, *, kernel: int, stride: int, pad_lo: int,
-                    pad_hi: int, relu: bool) -> torch.Tensor:
+                    pad_hi: int, relu: bool, out_dtype: torch.dtype = torch.float32) -> torch.Tensor:
     """Convolution of a few-channel image (``c * kernel <= 32``: HoVer-Net's RGB 7x7 stem) on the MFMA kernel
     (``tia_conv2d_thin_nhwc_f32``): the ``kernel * c`` values under a row of taps are contiguous in NHWC, so they are read
     as one 32-wide slice.  ``x``: float32 channels-last ``[n, c, h, w]``; the horizontal padding (``pad_lo`` / ``pad_hi`` zero
-    columns, plus the few that keep the last slice inside its row) is materialised here, the vertical one is the kernel's."""
+    columns, plus the few that keep the last slice inside its row) is materialised here, the vertical one is the kernel's.
+    ``out_dtype`` fp16 / bf16 (``tia_conv2d_thin_nhwc``): the same float32 arithmetic on float32 inputs, weights and bias, the
+    result rounded once on the way out -- the stem of the half-precision HoVer-Net."""
     from tiatoolbox_amd import _lib
 
     if not (x.is_cuda and x.dtype == torch.float32 and x.dim() == 4):  # noqa: PLR2004
         msg = "hip_conv2d_thin expects a float32 CUDA tensor [n, c, h, w]."
+        raise ValueError(msg)
+    if out_dtype not in _DT or w_packed.dtype != torch.float32 or (bias is not None and bias.dtype != torch.float32):
+        msg = (f"hip_conv2d_thin computes in float32 (float32 packed weights and bias) and returns float32 / fp16 / bf16; got weights "
+               f"{w_packed.dtype}, bias {bias.dtype if bias is not None else None}, out_dtype {out_dtype}.")
         raise ValueError(msg)
     n, c, h, w = x.shape
     cout = w_packed.shape[-1]
@@ -175,12 +181,17 @@ def hip_conv2d_thin(x: torch.Tensor, w_packed: torch.Tensor, bias: torch.Tensor 
     wp = w + pad_lo + pad_hi + extra
     xp = torch.zeros((n, h, wp, c), dtype=torch.float32, device=x.device)
     xp[:, :, pad_lo:pad_lo + w] = rows
-    y = torch.empty((n, cout, ho, wo), dtype=torch.float32, device=x.device, memory_format=torch.channels_last)
+    y = torch.empty((n, cout, ho, wo), dtype=out_dtype, device=x.device, memory_format=torch.channels_last)
+    name = "tia_conv2d_thin_nhwc_f32" if out_dtype == torch.float32 else "tia_conv2d_thin_nhwc"
+    args = (n, h, wp, c, cout, kernel, kernel, stride, pad_lo, ho, wo, int(relu), _lib.current_stream())
     with torch.cuda.device(x.device):
-        rc = _lib.load().tia_conv2d_thin_nhwc_f32(xp.data_ptr(), w_packed.data_ptr(), bias.data_ptr() if bias is not None else 0,
-                                                  y.data_ptr(), n, h, wp, c, cout, kernel, kernel, stride, pad_lo, ho, wo, int(relu),
-                                                  _lib.current_stream())
-    _lib.check(rc, "tia_conv2d_thin_nhwc_f32")
+        if out_dtype == torch.float32:
+            rc = _lib.load().tia_conv2d_thin_nhwc_f32(xp.data_ptr(), w_packed.data_ptr(), bias.data_ptr() if bias is not None else 0,
+                                                      y.data_ptr(), *args)
+        else:
+            rc = _lib.load().tia_conv2d_thin_nhwc(xp.data_ptr(), w_packed.data_ptr(), bias.data_ptr() if bias is not None else 0,
+                                                  y.data_ptr(), _DT[out_dtype], *args)
+    _lib.check(rc, name)
     return y
 
 
@@ -289,26 +300,36 @@ def hip_scale_shift_act(x: torch.Tensor, scale: torch.Tensor, shift: torch.Tenso
 
 
 def hip_scale_shift_act_view(x: torch.Tensor, scale: torch.Tensor, shift: torch.Tensor, *, relu: bool = True) -> torch.Tensor:
-    """``relu(x * scale[c] + shift[c])`` of a channel-prefix / spatial-window VIEW of a channels-last float32 CUDA tensor,
-    written to a dense channels-last tensor (``tia_scale_shift_act_view_nhwc_f32``)."""
+    """``relu(x * scale[c] + shift[c])`` of a channel-prefix / spatial-window VIEW of a channels-last CUDA tensor, written to a
+    dense channels-last tensor (``tia_scale_shift_act_view_nhwc_f32``; an fp16 / bf16 ``x``: ``tia_scale_shift_act_view_nhwc_h``,
+    float32 ``scale`` / ``shift`` and arithmetic, one rounding)."""
     from tiatoolbox_amd import _lib
 
     if not x.is_cuda:
         msg = "hip_scale_shift_act_view expects a CUDA tensor."
         raise ValueError(msg)
     n, c, h, w = x.shape
-    ok = (x.is_cuda and x.dtype == torch.float32 and x.stride(1) == 1 and c % 4 == 0 and x.data_ptr() % 16 == 0
-          and all(x.stride(d) % 4 == 0 for d in (0, 2, 3)) and x.stride(3) >= c)
+    half = x.dtype in (torch.float16, torch.bfloat16)
+    vec = 8 if half else 4  # elements per 16-byte access
+    ok = (x.dtype in _DT and x.stride(1) == 1 and c % vec == 0 and x.data_ptr() % 16 == 0
+          and all(x.stride(d) % vec == 0 for d in (0, 2, 3)) and x.stride(3) >= c)
     if not ok:
-        msg = ("hip_scale_shift_act_view expects a float32 view with contiguous channels, c % 4 == 0, a 16-byte aligned base and "
-               f"strides that are multiples of 4 elements; got shape {tuple(x.shape)} strides {tuple(x.stride())} {x.dtype}.")
+        msg = ("hip_scale_shift_act_view expects a float32 / fp16 / bf16 view with contiguous channels, c % 4 == 0 (fp16 / bf16: c % 8 "
+               "== 0), a 16-byte aligned base and strides that are multiples of 4 (8) elements; "
+               f"got shape {tuple(x.shape)} strides {tuple(x.stride())} {x.dtype}.")
         raise ValueError(msg)
-    y = torch.empty((n, c, h, w), dtype=torch.float32, device=x.device, memory_format=torch.channels_last)
+    if any(not t.is_cuda or t.dtype != torch.float32 for t in (scale, shift)):
+        msg = f"hip_scale_shift_act_view takes scale / shift as float32 CUDA tensors; got {scale.dtype} / {shift.dtype} on {scale.device}."
+        raise ValueError(msg)
+    y = torch.empty((n, c, h, w), dtype=x.dtype, device=x.device, memory_format=torch.channels_last)
+    args = (x.data_ptr(), x.stride(0), x.stride(2), x.stride(3), scale.data_ptr(), shift.data_ptr(), y.data_ptr(), n, h, w, c, int(relu))
+    name = "tia_scale_shift_act_view_nhwc_h" if half else "tia_scale_shift_act_view_nhwc_f32"
     with torch.cuda.device(x.device):
-        rc = _lib.load().tia_scale_shift_act_view_nhwc_f32(x.data_ptr(), x.stride(0), x.stride(2), x.stride(3), scale.data_ptr(),
-                                                           shift.data_ptr(), y.data_ptr(), n, h, w, c, int(relu),
-                                                           _lib.current_stream())
-    _lib.check(rc, "tia_scale_shift_act_view_nhwc_f32")
+        if half:
+            rc = _lib.load().tia_scale_shift_act_view_nhwc_h(*args, _DT[x.dtype], _lib.current_stream())
+        else:
+            rc = _lib.load().tia_scale_shift_act_view_nhwc_f32(*args, _lib.current_stream())
+    _lib.check(rc, name)
     return y
 
 
@@ -334,6 +355,59 @@ def hip_grouped_conv_valid(x: torch.Tensor, w_packed: torch.Tensor, *, groups: i
                                                          out.stride(2), out.stride(3), n, h, w, groups, cin // groups, 8, kernel,
                                                          _lib.current_stream())
     _lib.check(rc, "tia_grouped_conv_valid_nhwc_f32")
+    return out
+
+
+def pack_grouped_conv_valid_weights_h(weight: torch.Tensor, groups: int, dtype: torch.dtype) -> torch.Tensor:
+    """Grouped OIHW float32 ``[groups * 8, 32, k, k]`` -> ``[groups, k, k, 4, 8, 8]`` halves of ``dtype`` (8-channel chunk, output,
+    channel within the chunk), rounded once: the operand layout of :func:`hip_grouped_conv_valid_h`
+    (``tia_grouped_conv_pack_weights_h``)."""
+    from tiatoolbox_amd import _lib
+
+    w = weight.detach()
+    if (not w.is_cuda or w.dtype != torch.float32 or dtype not in (torch.float16, torch.bfloat16) or w.dim() != 4  # noqa: PLR2004
+            or w.shape[0] != groups * 8 or w.shape[1] != 32 or w.shape[2] != w.shape[3]):  # noqa: PLR2004
+        msg = (f"pack_grouped_conv_valid_weights_h packs a float32 CUDA weight [groups * 8, 32, k, k] for fp16 / bf16; got "
+               f"{tuple(w.shape)} {w.dtype} on {w.device}, groups {groups}, {dtype}.")
+        raise ValueError(msg)
+    w = w.contiguous()
+    k = w.shape[2]
+    out = torch.empty((groups, k, k, 4, 8, 8), dtype=dtype, device=w.device)
+    with torch.cuda.device(w.device):
+        rc = _lib.load().tia_grouped_conv_pack_weights_h(w.data_ptr(), groups, k, _DT[dtype], out.data_ptr(), _lib.current_stream())
+    _lib.check(rc, "tia_grouped_conv_pack_weights_h")
+    return out
+
+
+def hip_grouped_conv_valid_h(x: torch.Tensor, w_packed: torch.Tensor, *, groups: int, kernel: int,
+                             out: torch.Tensor | None = None) -> torch.Tensor:
+    """:func:`hip_grouped_conv_valid` on fp16 / bf16 activations (``tia_grouped_conv_valid_nhwc_h``: the 16x16x32 MFMA, float32
+    accumulation, one rounding); ``w_packed`` from :func:`pack_grouped_conv_valid_weights_h` in ``x``'s dtype; ``out`` may be a
+    channel slice / window view of a wider channels-last buffer of that dtype."""
+    from tiatoolbox_amd import _lib
+
+    if not (_nhwc_ptr_ok(x) and x.dtype in (torch.float16, torch.bfloat16)):
+        msg = "hip_grouped_conv_valid_h expects an fp16 / bf16 channels-last CUDA tensor."
+        raise ValueError(msg)
+    n, cin, h, w = x.shape
+    if (w_packed.dtype != x.dtype or tuple(w_packed.shape) != (groups, kernel, kernel, 4, 8, 8) or not w_packed.is_contiguous()
+            or w_packed.device != x.device):
+        msg = (f"hip_grouped_conv_valid_h: packed weights {tuple(w_packed.shape)} {w_packed.dtype} on {w_packed.device} do not match "
+               f"{groups} groups, kernel {kernel}, {x.dtype} on {x.device} (expected pack_grouped_conv_valid_weights_h's layout).")
+        raise ValueError(msg)
+    ho, wo = h - kernel + 1, w - kernel + 1
+    if out is None:
+        out = torch.empty((n, groups * 8, ho, wo), dtype=x.dtype, device=x.device, memory_format=torch.channels_last)
+    if (out.shape != (n, groups * 8, ho, wo) or out.stride(1) != 1 or out.dtype != x.dtype or not out.is_cuda or out.data_ptr() % 16
+            or any(out.stride(d) % 8 for d in (0, 2, 3))):
+        msg = (f"hip_grouped_conv_valid_h: `out` must be a channels-last (view of a) {x.dtype} CUDA tensor of the output shape on a "
+               "16-byte aligned base with strides that are multiples of 8 elements.")
+        raise ValueError(msg)
+    with torch.cuda.device(x.device):
+        rc = _lib.load().tia_grouped_conv_valid_nhwc_h(x.data_ptr(), w_packed.data_ptr(), out.data_ptr(), out.stride(0), out.stride(2),
+                                                       out.stride(3), n, h, w, groups, cin // groups, 8, kernel, _DT[x.dtype],
+                                                       _lib.current_stream())
+    _lib.check(rc, "tia_grouped_conv_valid_nhwc_h")
     return out
 
 
@@ -438,6 +512,47 @@ def hip_conv2d_h(x: torch.Tensor, w_packed: torch.Tensor, bias: torch.Tensor | N
                                            kernel, kernel, stride, padding, _DT[x.dtype], int(relu), _lib.current_stream())
     _lib.check(rc, "tia_conv2d_nhwc_h")
     return y
+
+
+def hip_conv2d_h_ex(x: torch.Tensor, w_packed: torch.Tensor, bias: torch.Tensor | None, residual: torch.Tensor | None, *, cout: int,
+                    kernel: int, stride: int, pad_lo: int, pad_hi: int, relu: bool, post_scale: torch.Tensor | None = None,
+                    post_shift: torch.Tensor | None = None, want_raw: bool = True):
+    """:func:`hip_conv2d_h` with ``pad_lo`` zero rows / columns in front and ``pad_hi`` behind (``tia_conv2d_nhwc_h_ex``) and, with
+    ``post_scale`` / ``post_shift`` (float32), a second output ``relu(v * post_scale[c] + post_shift[c])`` of the float32 result
+    ``v`` BEFORE its rounding.  Returns ``y``, or ``(y or None, activated)`` with a second output (``want_raw=False``: no ``y``)."""
+    from tiatoolbox_amd import _lib
+
+    if not (_nhwc_ptr_ok(x) and x.dtype in (torch.float16, torch.bfloat16)):
+        msg = "hip_conv2d_h_ex expects an fp16 / bf16 channels-last CUDA tensor."
+        raise ValueError(msg)
+    with_post = post_scale is not None or post_shift is not None
+    if any(t is not None and (t.dtype != torch.float32 or not t.is_cuda) for t in (bias, post_scale, post_shift)) or (
+            with_post and (post_scale is None or post_shift is None)):
+        msg = "hip_conv2d_h_ex takes the bias and post_scale / post_shift (both or neither) as float32 CUDA tensors."
+        raise ValueError(msg)
+    if w_packed.dtype != x.dtype:
+        msg = f"hip_conv2d_h_ex: weights packed for {w_packed.dtype} beside a {x.dtype} input."
+        raise ValueError(msg)
+    if not with_post and not want_raw:
+        msg = "hip_conv2d_h_ex: want_raw=False needs a second output."
+        raise ValueError(msg)
+    n, cin, h, w = x.shape
+    ho = (h + pad_lo + pad_hi - kernel) // stride + 1
+    wo = (w + pad_lo + pad_hi - kernel) // stride + 1
+    shape = (n, cout, ho, wo)
+    if residual is not None and not (_nhwc_ptr_ok(residual) and residual.dtype == x.dtype and residual.shape == shape):
+        msg = "hip_conv2d_h_ex: residual must be a channels-last CUDA tensor of the output's dtype and shape."
+        raise ValueError(msg)
+    y = torch.empty(shape, dtype=x.dtype, device=x.device, memory_format=torch.channels_last) if want_raw else None
+    y2 = torch.empty(shape, dtype=x.dtype, device=x.device, memory_format=torch.channels_last) if with_post else None
+    with torch.cuda.device(x.device):
+        rc = _lib.load().tia_conv2d_nhwc_h_ex(x.data_ptr(), w_packed.data_ptr(), bias.data_ptr() if bias is not None else 0,
+                                              residual.data_ptr() if residual is not None else 0, y.data_ptr() if y is not None else 0,
+                                              n, h, w, cin, cout, kernel, kernel, stride, pad_lo, pad_lo, ho, wo, _DT[x.dtype], int(relu),
+                                              post_scale.data_ptr() if with_post else 0, post_shift.data_ptr() if with_post else 0,
+                                              y2.data_ptr() if with_post else 0, _lib.current_stream())
+    _lib.check(rc, "tia_conv2d_nhwc_h_ex")
+    return (y, y2) if with_post else y
 
 
 def pack_conv_weights_h(conv: nn.Conv2d, dtype: torch.dtype) -> torch.Tensor:

@@ -1,4 +1,5 @@
-"""Inference copy of :class:`HoVerNet` / :class:`HoVerNetPlus` on the hand-written float32 MFMA convolutions.
+"""Inference copy of :class:`HoVerNet` / :class:`HoVerNetPlus` on the hand-written MFMA convolutions (float32; fp16 / bf16 after
+``FusedHoVerNet.prepare(dtype)``, see there).
 
 Same arithmetic graph as ``HoVerNet.forward`` (reference ``models/architecture/hovernet.py:405-454``), re-expressed so
 that every convolution with ``cin % 32 == 0`` and ``cout % 64 == 0`` -- all 1x1 / 3x3 convolutions of the
@@ -31,9 +32,10 @@ import torch.nn.functional as F  # noqa: N812
 from torch import nn
 
 from tiatoolbox_amd.models.architecture.fused import (hip_bias_act_, hip_conv1x1_head, hip_conv1x1_pre, hip_conv2d_ex, hip_conv2d_h,
-                                                      hip_conv2d_post, hip_conv3x3_wino, pack_conv_weights_h, pack_conv_weights_wino,
-                                                      hip_conv2d_thin, hip_grouped_conv_valid, hip_scale_shift_act,
-                                                      hip_scale_shift_act_view, hip_upsample2x_add, pack_conv_weights,
+                                                      hip_conv2d_h_ex, hip_conv2d_post, hip_conv3x3_wino, pack_conv_weights_h,
+                                                      pack_conv_weights_wino, hip_conv2d_thin, hip_grouped_conv_valid,
+                                                      hip_grouped_conv_valid_h, hip_scale_shift_act, hip_scale_shift_act_view,
+                                                      hip_upsample2x_add, pack_conv_weights, pack_grouped_conv_valid_weights_h,
                                                       pack_thin_conv_weights)
 from tiatoolbox_amd.models.architecture.hovernet import centre_crop_to_shape
 from tiatoolbox_amd.models.architecture.utils import centre_crop
@@ -120,10 +122,13 @@ class _Conv(nn.Module):
         if self.head_ok and pads == (0, 0) and not relu and residual is None:
             sc, sh = pre.affine32() if pre is not None else (None, None)
             return hip_conv1x1_head(_cl(x), self._weight32, self._bias32, pre_scale=sc, pre_shift=sh)
-        if pre is not None or self._packed_h is None or pads[0] != pads[1]:
-            msg = (f"half-precision _Conv {tuple(self.weight.shape)}: tia_conv2d_nhwc_h takes symmetric padding and no activation on "
-                   f"load (pads {pads}, pre {'given' if pre is not None else 'none'}).")
+        if pre is not None or self._packed_h is None:
+            msg = (f"half-precision _Conv {tuple(self.weight.shape)}: tia_conv2d_nhwc_h takes no activation on load "
+                   f"(pads {pads}, pre {'given' if pre is not None else 'none'}).")
             raise TypeError(msg)
+        if pads[0] != pads[1]:  # TensorFlow "same" padding of a strided layer: the extended entry point
+            return hip_conv2d_h_ex(_cl(x), self._packed_h, self._bias32, residual, cout=self.weight.shape[0], kernel=self.kernel,
+                                   stride=self.stride, pad_lo=pads[0], pad_hi=pads[1], relu=relu)
         return hip_conv2d_h(_cl(x), self._packed_h, self._bias32, residual, cout=self.weight.shape[0], kernel=self.kernel,
                             stride=self.stride, padding=pads[0], relu=relu)
 
@@ -192,6 +197,16 @@ def _conv_with_post(conv: "_Conv", x: torch.Tensor, residual: torch.Tensor, bn: 
                            pad_hi=0, relu=False, post_scale=bn.scale, post_shift=bn.shift, want_raw=want_raw)
 
 
+def _conv_with_post_h(conv: "_Conv", x: torch.Tensor, residual: torch.Tensor, bn: "_BnAct", *, want_raw: bool):
+    """The half form of :func:`_conv_with_post` (``tia_conv2d_nhwc_h_ex``): the activated copy comes from the unrounded sum."""
+    if conv._packed_h is None:  # noqa: SLF001
+        msg = f"half-precision _Conv {tuple(conv.weight.shape)} has no packed half weights (prepare was not called)."
+        raise TypeError(msg)
+    scale, shift = bn.affine32()
+    return hip_conv2d_h_ex(_cl(x), conv._packed_h, conv._bias32, residual, cout=conv.weight.shape[0], kernel=conv.kernel,  # noqa: SLF001
+                           stride=conv.stride, pad_lo=0, pad_hi=0, relu=False, post_scale=scale, post_shift=shift, want_raw=want_raw)
+
+
 def _conv_pre_on_load(conv: "_Conv", x: torch.Tensor, bn: "_BnAct") -> torch.Tensor:
     """``relu(conv(relu(bn(x))) + bias)`` for a 1x1 MFMA convolution, the BN + ReLU applied to the operand on load."""
     if conv._packed is None or conv._packed.device != conv.weight.device:  # noqa: SLF001
@@ -223,8 +238,9 @@ class _BnAct(nn.Module):
         return hip_scale_shift_act(_cl(x), self.scale, self.shift, relu=True, inplace=inplace)
 
     def view(self, x: torch.Tensor) -> torch.Tensor:
-        """The same for a channel-prefix / window view of a wider channels-last buffer; dense result."""
-        return hip_scale_shift_act_view(x, self.scale, self.shift, relu=True)
+        """The same for a channel-prefix / window view of a wider channels-last buffer; dense result (half: the float32 affine)."""
+        scale, shift = self.affine32()
+        return hip_scale_shift_act_view(x, scale, shift, relu=True)
 
 
 class _FusedResidualBlock(nn.Module):
@@ -241,7 +257,23 @@ class _FusedResidualBlock(nn.Module):
         self.shortcut = _Conv(blk.shortcut) if blk.shortcut is not None else None
         self.out = _BnAct(blk.blk_bna.bn)
 
+    def _forward_half(self, x: torch.Tensor) -> torch.Tensor:
+        """fp16 / bf16: the half MFMA kernel fills its LDS by DMA and cannot activate on load, so EVERY unit takes the second
+        epilogue output -- conv3 + shortcut writes the raw half sum (the next unit's shortcut) and the activated half copy (the
+        next unit's input, taken from the unrounded sum); the last unit writes the activated copy only."""
+        shortcut = x if self.shortcut is None else self.shortcut(x)
+        units = len(self.c1)
+        a = x
+        for i, (c1, c2, c3) in enumerate(zip(self.c1, self.c2, self.c3)):
+            a = c1(a, relu=True)
+            a = c2(a, pads=_same_pads(a.shape[2], c2.kernel, c2.stride), relu=True)
+            last = i + 1 == units
+            shortcut, a = _conv_with_post_h(c3, a, _cl(shortcut), self.out if last else self.pre[i + 1], want_raw=not last)
+        return a
+
     def forward(self, x: torch.Tensor) -> torch.Tensor:
+        if self.c1[0].half_dtype is not None:
+            return self._forward_half(x)
         shortcut = x if self.shortcut is None else self.shortcut(x)
         units = len(self.c1)
         a = x  # the first unit has no pre-activation
@@ -276,6 +308,23 @@ class _FusedDenseBlock(nn.Module):
             self.c1.append(_Conv(mods["conv1"], mods["conv1/bn"]))
             self.c2.append(_Conv(mods["conv2"]))
         self.out = _BnAct(blk.blk_bna.bn)
+        # half-precision form (`prepare`): the grouped convolutions' packed half weights, one per unit; plain attributes
+        self.half_dtype: torch.dtype | None = None
+        self._grouped_h: list[torch.Tensor] | None = None
+
+    def prepare(self, dtype: torch.dtype) -> None:
+        """Pack the grouped convolutions for ``tia_grouped_conv_valid_nhwc_h`` from their float32 weights (one rounding); they
+        are this block's to prepare (``_Conv.prepare`` refuses them).  ``torch.float32`` switches back."""
+        if dtype == torch.float32:
+            self.half_dtype = self._grouped_h = None
+            return
+        for c2 in self.c2:
+            if not (c2.grouped_ok and c2.kernel in (3, 5)):
+                msg = (f"no {dtype} kernel for a dense unit's convolution {tuple(c2.weight.shape)} with groups = {c2.groups}: "
+                       "tia_grouped_conv_valid_nhwc_h takes 32 -> 8 channels per group, 3x3 or 5x5, stride 1, no bias.")
+                raise TypeError(msg)
+        self._grouped_h = [pack_grouped_conv_valid_weights_h(c2.weight, c2.groups, dtype) for c2 in self.c2]
+        self.half_dtype = dtype
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
         # x_{i+1} = cat(centre_crop(x_i), new_i): instead of re-concatenating the growing stack, one buffer holds all
@@ -291,7 +340,9 @@ class _FusedDenseBlock(nn.Module):
         for i, (pre, c1, c2) in enumerate(zip(self.pre, self.c1, self.c2)):
             view = buf[:, :c, i * r:h0 - i * r, i * r:w0 - i * r]
             dst = buf[:, c:c + grow, (i + 1) * r:h0 - (i + 1) * r, (i + 1) * r:w0 - (i + 1) * r]
-            if c2.grouped_ok:
+            if self.half_dtype is not None:
+                hip_grouped_conv_valid_h(c1(pre.view(view), relu=True), self._grouped_h[i], groups=c2.groups, kernel=c2.kernel, out=dst)
+            elif c2.grouped_ok:
                 c2(c1(pre.view(view), relu=True), out=dst)  # written straight into its slice
             else:
                 dst.copy_(c2(c1(pre.view(view), relu=True)))
@@ -312,7 +363,8 @@ class _FusedBranch(nn.Module):
 
 
 class FusedHoVerNet(nn.Module):
-    """``forward(x)`` == ``HoVerNet.forward(x)`` (``{branch: logits}``), float32 on a CUDA device."""
+    """``forward(x)`` == ``HoVerNet.forward(x)`` (``{branch: logits}``, float32) on a CUDA device, in float32 or -- after
+    ``prepare(dtype)`` -- with fp16 / bf16 activations."""
 
     def __init__(self, model: nn.Module) -> None:
         super().__init__()
@@ -325,11 +377,56 @@ class FusedHoVerNet(nn.Module):
         self.d2, self.d3 = _FusedResidualBlock(model.d2), _FusedResidualBlock(model.d3)
         self.conv_bot = _Conv(model.conv_bot)
         self.decoder = nn.ModuleDict(OrderedDict((name, _FusedBranch(branch)) for name, branch in model.decoder.items()))
+        # half-precision form (`prepare`): the stem stays the float32 thin kernel (its float32 operands in plain attributes)
+        self.half_dtype: torch.dtype | None = None
+        self._stem_packed32: torch.Tensor | None = None
+        self._stem_bias32: torch.Tensor | None = None
+
+    def prepare(self, dtype: torch.dtype) -> None:
+        """fp16 / bf16 activations on the same graph (the engines' ``compute_dtype``): call this on the device, on the float32
+        copy, BEFORE ``.to(dtype)``.  Every MFMA convolution packs its BN-folded float32 weights for ``tia_conv2d_nhwc_h(_ex)``
+        (rounded once, after the folding) and keeps its bias in float32; every BN scale / shift and the heads' weights stay
+        float32 in plain attributes that the cast does not reach; the dense blocks pack their grouped convolutions for
+        ``tia_grouped_conv_valid_nhwc_h``.  The stem stays the float32-arithmetic thin kernel writing its map in ``dtype`` (under
+        1 % of the forward; exactly one rounding of the float32 stem); residual units take their pre-activations from the second
+        epilogue output of conv3 (no activation on load in half); the logits come back in float32.  A layer without a half kernel
+        raises ``TypeError``: there is no library fall-back, and ``conv_algo`` has no effect in half.  ``torch.float32``
+        switches back (on a module that has not been cast)."""
+        if dtype not in (torch.float32, torch.float16, torch.bfloat16):
+            msg = f"FusedHoVerNet runs in float32, float16 or bfloat16; got {dtype}."
+            raise ValueError(msg)
+        if self.stem.weight.dtype != torch.float32:
+            msg = f"FusedHoVerNet.prepare starts from the float32 parameters (call it before the cast); got {self.stem.weight.dtype}."
+            raise ValueError(msg)
+        if dtype != torch.float32 and not (self.stem.thin_ok and self.stem.stride == 1):
+            msg = f"no {dtype} kernel for the stem {tuple(self.stem.weight.shape)}: tia_conv2d_thin_nhwc takes c * k <= 32, cout % 64 == 0."
+            raise TypeError(msg)
+        owned = {id(self.stem)}  # prepared by their owners: `_Conv.prepare` refuses a thin and a grouped convolution
+        for mod in self.modules():
+            if isinstance(mod, _FusedDenseBlock):
+                mod.prepare(dtype)
+                owned.update(id(c2) for c2 in mod.c2)
+        for mod in self.modules():
+            if isinstance(mod, (_Conv, _BnAct)) and id(mod) not in owned:
+                mod.prepare(dtype)
+        if dtype == torch.float32:
+            self.half_dtype = self._stem_packed32 = self._stem_bias32 = None
+            return
+        self._stem_packed32 = pack_thin_conv_weights(self.stem.weight)
+        self._stem_bias32 = self.stem.bias.detach().clone().contiguous() if self.stem.bias is not None else None
+        self.half_dtype = dtype
 
     def forward(self, input_tensor: torch.Tensor) -> dict:
-        x = _cl(input_tensor / 255.0)
+        half = self.half_dtype
+        # (half: the batch arrives in `half`, where 0 .. 255 are exact; the division is the float32 copy's)
+        x = _cl(input_tensor / 255.0) if half is None else _cl(input_tensor.float() / 255.0)
         pads = _same_pads(x.shape[2], self.stem.kernel, 1) if self.stem_pad else (0, 0)
-        d0 = self.d0(self.stem(x, pads=pads, relu=True))
+        if half is None:
+            stem = self.stem(x, pads=pads, relu=True)
+        else:  # the float32 stem rounded once
+            stem = hip_conv2d_thin(x, self._stem_packed32, self._stem_bias32, kernel=self.stem.kernel, stride=1, pad_lo=pads[0],
+                                   pad_hi=pads[1], relu=True, out_dtype=half)
+        d0 = self.d0(stem)
         d1 = self.d1(d0)
         d2 = self.d2(d1)
         d3 = self.conv_bot(self.d3(d2))

@@ -442,8 +442,9 @@ class EngineABC:
                 from tiatoolbox_amd.models.architecture.hovernet import HoVerNet
                 from tiatoolbox_amd.models.architecture.unet import UNetModel
 
-                if isinstance(m, HoVerNet) and dtype == torch.float32:
-                    # HoVer-Net / HoVerNet+ in float32: 104 of its 144 convolutions on the hand-written MFMA kernel,
+                if isinstance(m, HoVerNet):
+                    # HoVer-Net / HoVerNet+: 104 of its 144 convolutions on the hand-written MFMA kernel (float32:
+                    # tia_conv2d_nhwc_f32_ex / Winograd; fp16 / bf16: tia_conv2d_nhwc_h(_ex) after `prepare(dtype)` below),
                     # BN folded or fused with the ReLU, residual adds in the epilogues (architecture/hovernet_fused.py)
                     from tiatoolbox_amd.models.architecture.hovernet_fused import FusedHoVerNet
 
@@ -454,7 +455,7 @@ class EngineABC:
                 elif isinstance(m, UNetModel) and hasattr(m.backbone, "layer1") and m.skip_type == "add":
                     # UNet with the ResNet-50 encoder: 61 of its 63 convolutions on the MFMA kernel (float32: tia_conv2d_nhwc_f32_ex
                     # / Winograd; fp16 / bf16: tia_conv2d_nhwc_h after `prepare(dtype)` below), stem and head on their own kernels.
-                    # HoVer-Net, the plain-encoder and the concat-skip UNet have no half kernels: fp16 / bf16 casts the torch module
+                    # The plain-encoder and the concat-skip UNet have no half kernels: fp16 / bf16 casts the torch module
                     from tiatoolbox_amd.models.architecture.unet_fused import FusedUNet
 
                     m = FusedUNet(m.to(device=self.device))
@@ -467,7 +468,7 @@ class EngineABC:
                     if type(mod).__name__ == "MfmaResNet":
                         mod.set_conv_algo(algo)  # run kwarg `conv_algo="winograd"`: opt-in float32 Winograd for the 3x3 / stride-1 layers
                         mod.prepare(dtype)
-                    elif type(mod).__name__ == "FusedUNet" and dtype != torch.float32:
+                    elif type(mod).__name__ in ("FusedUNet", "FusedHoVerNet") and dtype != torch.float32:
                         mod.prepare(dtype)  # half weights from the float32 BN-folded ones; float32 biases / BN affines kept aside
             m = m.to(dtype=dtype) if dtype != torch.float32 else m
             if on_gpu:
@@ -493,9 +494,9 @@ class EngineABC:
     def _use_miopen_find(self) -> bool:
         """Only an explicit ``miopen_find=True`` switches the library's solver search on.  The float32 inference copies (ResNet
         classifiers, ``FusedHoVerNet``, ``FusedUNet``) launch no library convolution at all since round 3; the switch matters
-        for what still runs as a plain torch module (HoVer-Net and the plain-encoder / concat-skip UNet in half precision,
-        user-supplied architectures), where MIOpen's immediate mode can pick a naive NHWC kernel.  (The ResNet-50 UNet in fp16 /
-        bf16 is ``FusedUNet`` too and launches no library convolution.)"""
+        for what still runs as a plain torch module (the plain-encoder / concat-skip UNet in half precision, user-supplied
+        architectures), where MIOpen's immediate mode can pick a naive NHWC kernel.  (HoVer-Net and the ResNet-50 UNet in fp16 /
+        bf16 are ``FusedHoVerNet`` / ``FusedUNet`` too and launch no library convolution.)"""
         return bool(getattr(self, "miopen_find", None))
 
     def invalidate_inference_cache(self) -> None:

@@ -46,29 +46,24 @@ def conv_label(a, k, out):
     flops = 2.0 * n * ho * wo * co * (ci // self.groups) * self.kernel * self.kernel
     nbytes = 4.0 * (x.numel() + first.numel() + (k["residual"].numel() if k.get("residual") is not None else 0))
     return (f"conv {kind:7s} {self.kernel}x{self.kernel}/{self.stride} {ci:4d}->{co:4d} out {ho}x{wo}"
-            f"{' +res' if k.get('residual') is not None else ''}"), flops, nbytes
+            f"{' +res' if k.get('residual') is not None else ''}{' +pre' if k.get('pre') is not None else ''}"
+            f"{' +post' if k.get('post') is not None else ''}"), flops, nbytes
 
 
 hf._Conv.forward = timed(conv_label, orig_conv)
-for mod, name in ((hf, "hip_conv2d_post"), (hf, "hip_conv1x1_pre"), (hf, "hip_scale_shift_act"), (hf, "hip_scale_shift_act_view"), (hf, "hip_upsample2x_add"),
+for mod, name in ((hf, "hip_scale_shift_act"), (hf, "hip_scale_shift_act_view"), (hf, "hip_upsample2x_add"),
                   (uf, "hip_upsample2x_add"), (uf, "hip_stem_conv_pool")):
     def lab(a, k, out, name=name):
         first = out[1] if isinstance(out, tuple) else out
         x = a[0]
         flops = 0.0
-        if name == "hip_conv2d_post":
-            n, co, ho, wo = first.shape
-            flops = 2.0 * n * ho * wo * co * x.shape[1] * k["kernel"] ** 2
-        if name == "hip_conv1x1_pre":
-            n, co, ho, wo = first.shape
-            flops = 2.0 * n * ho * wo * co * x.shape[1]
         if name == "hip_stem_conv_pool":
             n, h, w, _ = x.shape
             flops = 2.0 * n * (h // 2) * (w // 2) * 64 * 147
         extra = sum(t.numel() * t.element_size() for t in (out if isinstance(out, tuple) else (out,)) if t is not None)
         return f"{name} {tuple(x.shape)} -> {tuple(first.shape)}", flops, float(x.numel() * x.element_size() + extra)
     setattr(mod, name, timed(lab, getattr(mod, name)))
-# conv_with_post goes through hip_conv2d_post directly, not _Conv.forward: both are wrapped above
+# (the second epilogue output and the activation on load are arguments of _Conv.forward: timed with their convolution above)
 
 if which == "hovernet":
     model, _ = get_pretrained_model("hovernet_fast-pannuke")

@@ -95,6 +95,7 @@ def test_prepare_keeps_float32_operands_through_the_cast_and_runs_the_same_graph
         fused = fused.to(dtype)
         assert fused.half_dtype == dtype and next(fused.parameters()).dtype == dtype  # the cast happened ...
         grouped = {id(c2) for m in fused.modules() if isinstance(m, _FusedDenseBlock) for c2 in m.c2}
+        n_grouped = 0
         n_mfma = n_head = 0
         for name, mod in fused.named_modules():  # ... and left the float32 operands alone, bit for bit
             if isinstance(mod, _Conv) and mod is not fused.stem and id(mod) not in grouped:
@@ -112,15 +113,17 @@ def test_prepare_keeps_float32_operands_through_the_cast_and_runs_the_same_graph
                 sc, sh = mod.affine32()
                 assert sc.dtype == sh.dtype == torch.float32 and mod.scale.dtype == dtype
                 assert torch.equal(sc, want_affine[name][0]) and torch.equal(sh, want_affine[name][1])
-            if isinstance(mod, _FusedDenseBlock):
-                assert mod.half_dtype == dtype and len(mod._grouped_h) == len(mod.c2)  # noqa: SLF001
-                for c2, wp in zip(mod.c2, mod._grouped_h):  # noqa: SLF001
-                    assert c2.half_dtype is None and wp.dtype == dtype  # the grouped convolutions are the block's, not `_Conv.prepare`'s
+            if isinstance(mod, _Conv) and id(mod) in grouped:  # a dense unit's grouped convolution: its own to prepare, like any layer
+                n_grouped += 1
+                assert mod.half_dtype == dtype and mod.bias is None and mod._bias32 is None and mod._weight32 is None  # noqa: SLF001
+                assert mod._packed_h.dtype == dtype  # noqa: SLF001
+                assert torch.equal(R.unpack_grouped_h(mod._packed_h), want_w[name].to(dtype))  # noqa: SLF001  (one rounding of the float32 weights)
         branches = len(heads)
-        assert n_mfma == 104 + (branches - 3) * 17 and n_head == branches and len(grouped) == 12 * branches
+        assert n_mfma == 104 + (branches - 3) * 17 and n_head == branches and len(grouped) == n_grouped == 12 * branches
         # the stem keeps its float32 packed weights and bias in plain attributes
-        assert fused._stem_packed32.dtype == torch.float32 and fused._stem_bias32.dtype == torch.float32  # noqa: SLF001
-        assert torch.equal(fused._stem_bias32, want_bias["stem"]) and fused.stem.half_dtype is None  # noqa: SLF001
+        assert fused.stem._packed.dtype == torch.float32 and fused.stem._bias32.dtype == torch.float32  # noqa: SLF001
+        assert fused.stem._packed_h is None and fused.stem._weight32 is None  # noqa: SLF001
+        assert torch.equal(fused.stem._bias32, want_bias["stem"]) and fused.stem.half_dtype == dtype  # noqa: SLF001
         got = fused(x.to(dtype))  # 0 .. 255 are numbers of both half types: what `infer_batch` hands over
     # per forward: the 16 conv3 + shortcut of the encoder through the second output, the 3 strided 3x3 through explicit pads, every
     # other MFMA layer through the plain wrapper; 12 grouped and 14 view passes (8 + 1 and 4 + 1) per branch; one shared up-sampling
@@ -136,15 +139,16 @@ def test_prepare_keeps_float32_operands_through_the_cast_and_runs_the_same_graph
 
 
 def test_prepare_switches_back_to_float32_on_an_uncast_module(torch_half_kernels):
-    from tiatoolbox_amd.models.architecture.hovernet_fused import _Conv, _FusedDenseBlock
+    from tiatoolbox_amd.models.architecture.hovernet_fused import _Conv
 
     hf, _, _ = torch_half_kernels
     model, _, _ = R.graph_case("fast")
     fused = hf.FusedHoVerNet(copy.deepcopy(model))
     fused.prepare(torch.bfloat16)
     fused.prepare(torch.float32)
-    assert fused.half_dtype is None and fused._stem_packed32 is None  # noqa: SLF001
-    assert all(m.half_dtype is None for m in fused.modules() if isinstance(m, (_Conv, _FusedDenseBlock)))
+    assert fused.half_dtype is None and fused.stem.half_dtype is None
+    convs = [m for m in fused.modules() if isinstance(m, _Conv)]  # the dense units' grouped convolutions among them
+    assert len(convs) == 144 and all(m.half_dtype is None and m._packed_h is None and m._bias32 is None for m in convs)  # noqa: SLF001
     with pytest.raises(ValueError, match="float32, float16 or bfloat16"):
         fused.prepare(torch.float64)
 
@@ -163,7 +167,7 @@ def test_prepare_refuses_cast_modules_and_layers_without_a_half_kernel(torch_hal
     m = copy.deepcopy(model)
     unit = m.decoder["hv"][0].dense.units[0]
     unit.conv2 = torch.nn.Conv2d(128, 32, 5, groups=2, bias=False)
-    with pytest.raises(TypeError, match="no torch.bfloat16 kernel for a dense unit"):
+    with pytest.raises(TypeError, match=r"no torch.bfloat16 kernel for a convolution \(32, 64, 5, 5\) with groups = 2,"):
         hf.FusedHoVerNet(m).prepare(torch.bfloat16)
 
 

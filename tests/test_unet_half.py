@@ -183,7 +183,7 @@ def test_prepare_refuses_layers_without_a_half_kernel_and_cast_modules():
     thin = _Conv(torch.nn.Conv2d(3, 64, 7, 2, 3))
     with pytest.raises(TypeError, match="no torch.float16 kernel"):
         thin.prepare(torch.float16)
-    grouped = _Conv(torch.nn.Conv2d(128, 32, 3, groups=4, bias=False))
+    grouped = _Conv(torch.nn.Conv2d(128, 32, 3, groups=2, bias=False))  # (32 -> 8 channels per group has a half kernel)
     with pytest.raises(TypeError, match="no torch.bfloat16 kernel"):
         grouped.prepare(torch.bfloat16)
     ok = _Conv(torch.nn.Conv2d(64, 5, 1))

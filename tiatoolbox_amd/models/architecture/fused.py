@@ -57,6 +57,24 @@ def _nhwc_ptr_ok(t: torch.Tensor) -> bool:
     return t.is_cuda and t.dim() == 4 and t.is_contiguous(memory_format=torch.channels_last) and t.dtype in _DT
 
 
+def _ptr(t: torch.Tensor | None) -> int:
+    """The address the C entry points take for an optional tensor: 0 stands for "none"."""
+    return t.data_ptr() if t is not None else 0
+
+
+def _conv_out_shape(name: str, x: torch.Tensor, cout: int, residual: torch.Tensor | None, *, kernel: int, stride: int, pad_lo: int,
+                    pad_hi: int) -> tuple[int, int, int, int]:
+    """``(n, cout, ho, wo)`` of a dense convolution of ``x`` with ``pad_lo`` zero rows / columns in front and ``pad_hi`` behind, for the
+    wrapper ``name``; a ``residual`` must be a channels-last CUDA tensor of ``x``'s dtype and exactly that shape."""
+    n, _, h, w = x.shape
+    shape = (n, cout, (h + pad_lo + pad_hi - kernel) // stride + 1, (w + pad_lo + pad_hi - kernel) // stride + 1)
+    if residual is not None and not (_nhwc_ptr_ok(residual) and residual.dtype == x.dtype and residual.shape == shape):
+        msg = (f"{name}: residual must be a channels-last CUDA tensor of the output's dtype and shape ({x.dtype}, {shape}); got "
+               f"{residual.dtype}, {tuple(residual.shape)}.")
+        raise ValueError(msg)
+    return shape
+
+
 def hip_bias_act_(x: torch.Tensor, bias: torch.Tensor, residual: torch.Tensor | None = None, *, relu: bool = True) -> torch.Tensor:
     """In place ``x = relu(x + bias[c] (+ residual))`` on an NCHW tensor stored channels-last."""
     from tiatoolbox_amd import _lib
@@ -66,8 +84,8 @@ def hip_bias_act_(x: torch.Tensor, bias: torch.Tensor, residual: torch.Tensor | 
         raise ValueError(msg)
     n, c, h, w = x.shape
     with torch.cuda.device(x.device):
-        rc = _lib.load().tia_bias_act_nhwc(x.data_ptr(), bias.data_ptr(), residual.data_ptr() if residual is not None else 0,
-                                           n * h * w, c, _DT[x.dtype], int(relu), _lib.current_stream())
+        rc = _lib.load().tia_bias_act_nhwc(x.data_ptr(), bias.data_ptr(), _ptr(residual), n * h * w, c, _DT[x.dtype], int(relu),
+                                           _lib.current_stream())
     _lib.check(rc, "tia_bias_act_nhwc")
     return x
 
@@ -101,12 +119,10 @@ def hip_conv2d(x: torch.Tensor, w_packed: torch.Tensor, bias: torch.Tensor | Non
         raise ValueError(msg)
     n, cin, h, w = x.shape
     cout = w_packed.shape[-1]
-    ho = (h + 2 * padding - kernel) // stride + 1
-    wo = (w + 2 * padding - kernel) // stride + 1
-    y = torch.empty((n, cout, ho, wo), dtype=torch.float32, device=x.device, memory_format=torch.channels_last)
+    shape = _conv_out_shape("hip_conv2d", x, cout, residual, kernel=kernel, stride=stride, pad_lo=padding, pad_hi=padding)
+    y = torch.empty(shape, dtype=torch.float32, device=x.device, memory_format=torch.channels_last)
     with torch.cuda.device(x.device):
-        rc = _lib.load().tia_conv2d_nhwc_f32(x.data_ptr(), w_packed.data_ptr(), bias.data_ptr() if bias is not None else 0,
-                                             residual.data_ptr() if residual is not None else 0, y.data_ptr(), n, h, w, cin,
+        rc = _lib.load().tia_conv2d_nhwc_f32(x.data_ptr(), w_packed.data_ptr(), _ptr(bias), _ptr(residual), y.data_ptr(), n, h, w, cin,
                                              cout, kernel, kernel, stride, padding, int(relu), _lib.current_stream())
     _lib.check(rc, "tia_conv2d_nhwc_f32")
     return y
@@ -121,21 +137,13 @@ def hip_conv2d_ex(x: torch.Tensor, w_packed: torch.Tensor, bias: torch.Tensor | 
     if not (_nhwc_ptr_ok(x) and x.dtype == torch.float32):
         msg = "hip_conv2d_ex expects a float32 channels-last CUDA tensor."
         raise ValueError(msg)
-    if residual is not None and not (_nhwc_ptr_ok(residual) and residual.dtype == torch.float32):
-        msg = "hip_conv2d_ex expects a float32 channels-last CUDA residual."
-        raise ValueError(msg)
     n, cin, h, w = x.shape
     cout = w_packed.shape[-1]
-    ho = (h + pad_lo + pad_hi - kernel) // stride + 1
-    wo = (w + pad_lo + pad_hi - kernel) // stride + 1
-    y = torch.empty((n, cout, ho, wo), dtype=torch.float32, device=x.device, memory_format=torch.channels_last)
-    if residual is not None and residual.shape != y.shape:
-        msg = f"residual shape {tuple(residual.shape)} != output shape {tuple(y.shape)}"
-        raise ValueError(msg)
+    shape = _conv_out_shape("hip_conv2d_ex", x, cout, residual, kernel=kernel, stride=stride, pad_lo=pad_lo, pad_hi=pad_hi)
+    y = torch.empty(shape, dtype=torch.float32, device=x.device, memory_format=torch.channels_last)
     with torch.cuda.device(x.device):
-        rc = _lib.load().tia_conv2d_nhwc_f32_ex(x.data_ptr(), w_packed.data_ptr(), bias.data_ptr() if bias is not None else 0,
-                                                residual.data_ptr() if residual is not None else 0, y.data_ptr(), n, h, w, cin,
-                                                cout, kernel, kernel, stride, pad_lo, pad_lo, ho, wo, int(relu),
+        rc = _lib.load().tia_conv2d_nhwc_f32_ex(x.data_ptr(), w_packed.data_ptr(), _ptr(bias), _ptr(residual), y.data_ptr(), n, h, w, cin,
+                                                cout, kernel, kernel, stride, pad_lo, pad_lo, shape[2], shape[3], int(relu),
                                                 _lib.current_stream())
     _lib.check(rc, "tia_conv2d_nhwc_f32_ex")
     return y
@@ -186,11 +194,9 @@ def hip_conv2d_thin(x: torch.Tensor, w_packed: torch.Tensor, bias: torch.Tensor 
     args = (n, h, wp, c, cout, kernel, kernel, stride, pad_lo, ho, wo, int(relu), _lib.current_stream())
     with torch.cuda.device(x.device):
         if out_dtype == torch.float32:
-            rc = _lib.load().tia_conv2d_thin_nhwc_f32(xp.data_ptr(), w_packed.data_ptr(), bias.data_ptr() if bias is not None else 0,
-                                                      y.data_ptr(), *args)
+            rc = _lib.load().tia_conv2d_thin_nhwc_f32(xp.data_ptr(), w_packed.data_ptr(), _ptr(bias), y.data_ptr(), *args)
         else:
-            rc = _lib.load().tia_conv2d_thin_nhwc(xp.data_ptr(), w_packed.data_ptr(), bias.data_ptr() if bias is not None else 0,
-                                                  y.data_ptr(), _DT[out_dtype], *args)
+            rc = _lib.load().tia_conv2d_thin_nhwc(xp.data_ptr(), w_packed.data_ptr(), _ptr(bias), y.data_ptr(), _DT[out_dtype], *args)
     _lib.check(rc, name)
     return y
 
@@ -214,8 +220,7 @@ def hip_conv1x1_head(x: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor |
     cout = weight.shape[0]
     wmat = weight.detach().reshape(cout, 64).to(torch.float32).contiguous()
     y = torch.empty((n, cout, h, w), dtype=torch.float32, device=x.device, memory_format=torch.channels_last)
-    ptrs = (wmat.data_ptr(), bias.data_ptr() if bias is not None else 0, pre_scale.data_ptr() if pre_scale is not None else 0,
-            pre_shift.data_ptr() if pre_shift is not None else 0)
+    ptrs = (wmat.data_ptr(), _ptr(bias), _ptr(pre_scale), _ptr(pre_shift))
     name = "tia_conv1x1_head_nhwc_h" if half else "tia_conv1x1_head_nhwc_f32"
     with torch.cuda.device(x.device):
         if half:
@@ -238,20 +243,13 @@ def hip_conv2d_post(x: torch.Tensor, w_packed: torch.Tensor, bias: torch.Tensor 
         raise ValueError(msg)
     n, cin, h, w = x.shape
     cout = w_packed.shape[-1]
-    ho = (h + pad_lo + pad_hi - kernel) // stride + 1
-    wo = (w + pad_lo + pad_hi - kernel) // stride + 1
-    shape = (n, cout, ho, wo)
-    if residual is not None and not (_nhwc_ptr_ok(residual) and residual.dtype == torch.float32 and residual.shape == shape):
-        msg = "hip_conv2d_post: residual must be a float32 channels-last CUDA tensor of the output shape."
-        raise ValueError(msg)
+    shape = _conv_out_shape("hip_conv2d_post", x, cout, residual, kernel=kernel, stride=stride, pad_lo=pad_lo, pad_hi=pad_hi)
     y = torch.empty(shape, dtype=torch.float32, device=x.device, memory_format=torch.channels_last) if want_raw else None
     y2 = torch.empty(shape, dtype=torch.float32, device=x.device, memory_format=torch.channels_last)
     with torch.cuda.device(x.device):
-        rc = _lib.load().tia_conv2d_post_nhwc_f32(x.data_ptr(), w_packed.data_ptr(), bias.data_ptr() if bias is not None else 0,
-                                                  residual.data_ptr() if residual is not None else 0,
-                                                  y.data_ptr() if y is not None else 0, n, h, w, cin, cout, kernel, kernel, stride,
-                                                  pad_lo, pad_lo, ho, wo, int(relu), post_scale.data_ptr(), post_shift.data_ptr(),
-                                                  y2.data_ptr(), _lib.current_stream())
+        rc = _lib.load().tia_conv2d_post_nhwc_f32(x.data_ptr(), w_packed.data_ptr(), _ptr(bias), _ptr(residual), _ptr(y), n, h, w, cin,
+                                                  cout, kernel, kernel, stride, pad_lo, pad_lo, shape[2], shape[3], int(relu),
+                                                  post_scale.data_ptr(), post_shift.data_ptr(), y2.data_ptr(), _lib.current_stream())
     _lib.check(rc, "tia_conv2d_post_nhwc_f32")
     return y, y2
 
@@ -268,16 +266,12 @@ def hip_conv1x1_pre(x: torch.Tensor, pre_scale: torch.Tensor, pre_shift: torch.T
         raise ValueError(msg)
     n, cin, h, w = x.shape
     cout = w_packed.shape[-1]
-    shape = (n, cout, (h - 1) // stride + 1, (w - 1) // stride + 1)
-    if residual is not None and not (_nhwc_ptr_ok(residual) and residual.dtype == torch.float32 and residual.shape == shape):
-        msg = "hip_conv1x1_pre: residual must be a float32 channels-last CUDA tensor of the output shape."
-        raise ValueError(msg)
+    shape = _conv_out_shape("hip_conv1x1_pre", x, cout, residual, kernel=1, stride=stride, pad_lo=0, pad_hi=0)
     y = torch.empty(shape, dtype=torch.float32, device=x.device, memory_format=torch.channels_last)
     with torch.cuda.device(x.device):
         rc = _lib.load().tia_conv1x1_pre_nhwc_f32(x.data_ptr(), pre_scale.data_ptr(), pre_shift.data_ptr(), w_packed.data_ptr(),
-                                                  bias.data_ptr() if bias is not None else 0,
-                                                  residual.data_ptr() if residual is not None else 0, y.data_ptr(), n, h, w, cin,
-                                                  cout, stride, int(relu), _lib.current_stream())
+                                                  _ptr(bias), _ptr(residual), y.data_ptr(), n, h, w, cin, cout, stride, int(relu),
+                                                  _lib.current_stream())
     _lib.check(rc, "tia_conv1x1_pre_nhwc_f32")
     return y
 
@@ -445,8 +439,8 @@ def hip_conv3x3_grouped(x: torch.Tensor, w_packed: torch.Tensor, bias: torch.Ten
     y = torch.empty((n, c, (h - 1) // stride + 1, (w - 1) // stride + 1), dtype=torch.float32, device=x.device,
                     memory_format=torch.channels_last)
     with torch.cuda.device(x.device):
-        rc = _lib.load().tia_conv3x3_grouped_nhwc_f32(x.data_ptr(), w_packed.data_ptr(), bias.data_ptr() if bias is not None else 0,
-                                                      y.data_ptr(), n, h, w, groups, cg, stride, int(relu), _lib.current_stream())
+        rc = _lib.load().tia_conv3x3_grouped_nhwc_f32(x.data_ptr(), w_packed.data_ptr(), _ptr(bias), y.data_ptr(), n, h, w, groups, cg, stride,
+                                                      int(relu), _lib.current_stream())
     _lib.check(rc, "tia_conv3x3_grouped_nhwc_f32")
     return y
 
@@ -475,8 +469,7 @@ def hip_upsample2x_add(x: torch.Tensor, y: torch.Tensor, scale: torch.Tensor | N
         msg = f"hip_upsample2x_add takes scale / shift in float32 beside {x.dtype} tensors."
         raise ValueError(msg)
     out = torch.empty((n, c, 2 * h, 2 * w), dtype=x.dtype, device=x.device, memory_format=torch.channels_last)
-    args = (x.data_ptr(), y.data_ptr(), y.stride(0), y.stride(2), scale.data_ptr() if scale is not None else 0,
-            shift.data_ptr() if shift is not None else 0, out.data_ptr(), n, h, w, c)
+    args = (x.data_ptr(), y.data_ptr(), y.stride(0), y.stride(2), _ptr(scale), _ptr(shift), out.data_ptr(), n, h, w, c)
     name = "tia_upsample2x_add_act_nhwc_h" if half else "tia_upsample2x_add_act_nhwc_f32"
     with torch.cuda.device(x.device):
         if half:
@@ -497,18 +490,13 @@ def hip_conv2d_h(x: torch.Tensor, w_packed: torch.Tensor, bias: torch.Tensor | N
         msg = "hip_conv2d_h expects an fp16 / bf16 channels-last CUDA tensor."
         raise ValueError(msg)
     n, cin, h, w = x.shape
-    ho = (h + 2 * padding - kernel) // stride + 1
-    wo = (w + 2 * padding - kernel) // stride + 1
-    y = torch.empty((n, cout, ho, wo), dtype=x.dtype, device=x.device, memory_format=torch.channels_last)
-    if residual is not None and not (_nhwc_ptr_ok(residual) and residual.dtype == x.dtype and residual.shape == y.shape):
-        msg = "hip_conv2d_h: residual must be a channels-last CUDA tensor of the output's dtype and shape."
-        raise ValueError(msg)
+    shape = _conv_out_shape("hip_conv2d_h", x, cout, residual, kernel=kernel, stride=stride, pad_lo=padding, pad_hi=padding)
     if bias is not None and bias.dtype != torch.float32:
         msg = "hip_conv2d_h takes the bias in float32."
         raise ValueError(msg)
+    y = torch.empty(shape, dtype=x.dtype, device=x.device, memory_format=torch.channels_last)
     with torch.cuda.device(x.device):
-        rc = _lib.load().tia_conv2d_nhwc_h(x.data_ptr(), w_packed.data_ptr(), bias.data_ptr() if bias is not None else 0,
-                                           residual.data_ptr() if residual is not None else 0, y.data_ptr(), n, h, w, cin, cout,
+        rc = _lib.load().tia_conv2d_nhwc_h(x.data_ptr(), w_packed.data_ptr(), _ptr(bias), _ptr(residual), y.data_ptr(), n, h, w, cin, cout,
                                            kernel, kernel, stride, padding, _DT[x.dtype], int(relu), _lib.current_stream())
     _lib.check(rc, "tia_conv2d_nhwc_h")
     return y
@@ -537,20 +525,13 @@ def hip_conv2d_h_ex(x: torch.Tensor, w_packed: torch.Tensor, bias: torch.Tensor 
         msg = "hip_conv2d_h_ex: want_raw=False needs a second output."
         raise ValueError(msg)
     n, cin, h, w = x.shape
-    ho = (h + pad_lo + pad_hi - kernel) // stride + 1
-    wo = (w + pad_lo + pad_hi - kernel) // stride + 1
-    shape = (n, cout, ho, wo)
-    if residual is not None and not (_nhwc_ptr_ok(residual) and residual.dtype == x.dtype and residual.shape == shape):
-        msg = "hip_conv2d_h_ex: residual must be a channels-last CUDA tensor of the output's dtype and shape."
-        raise ValueError(msg)
+    shape = _conv_out_shape("hip_conv2d_h_ex", x, cout, residual, kernel=kernel, stride=stride, pad_lo=pad_lo, pad_hi=pad_hi)
     y = torch.empty(shape, dtype=x.dtype, device=x.device, memory_format=torch.channels_last) if want_raw else None
     y2 = torch.empty(shape, dtype=x.dtype, device=x.device, memory_format=torch.channels_last) if with_post else None
     with torch.cuda.device(x.device):
-        rc = _lib.load().tia_conv2d_nhwc_h_ex(x.data_ptr(), w_packed.data_ptr(), bias.data_ptr() if bias is not None else 0,
-                                              residual.data_ptr() if residual is not None else 0, y.data_ptr() if y is not None else 0,
-                                              n, h, w, cin, cout, kernel, kernel, stride, pad_lo, pad_lo, ho, wo, _DT[x.dtype], int(relu),
-                                              post_scale.data_ptr() if with_post else 0, post_shift.data_ptr() if with_post else 0,
-                                              y2.data_ptr() if with_post else 0, _lib.current_stream())
+        rc = _lib.load().tia_conv2d_nhwc_h_ex(x.data_ptr(), w_packed.data_ptr(), _ptr(bias), _ptr(residual), _ptr(y), n, h, w, cin, cout,
+                                              kernel, kernel, stride, pad_lo, pad_lo, shape[2], shape[3], _DT[x.dtype], int(relu),
+                                              _ptr(post_scale), _ptr(post_shift), _ptr(y2), _lib.current_stream())
     _lib.check(rc, "tia_conv2d_nhwc_h_ex")
     return (y, y2) if with_post else y
 
@@ -654,8 +635,7 @@ def hip_conv3x3_wino(x: torch.Tensor, u_packed: torch.Tensor, bias: torch.Tensor
         raise ValueError(msg)
     name = "tia_conv3x3_wino_nhwc_f32" if npos == 16 else "tia_conv3x3_wino42_nhwc_f32"  # noqa: PLR2004
     with torch.cuda.device(x.device):
-        rc = getattr(_lib.load(), name)(x.data_ptr(), u_packed.data_ptr(), bias.data_ptr() if bias is not None else 0,
-                                        residual.data_ptr() if residual is not None else 0, y.data_ptr(), n, h, w, cin, cout,
+        rc = getattr(_lib.load(), name)(x.data_ptr(), u_packed.data_ptr(), _ptr(bias), _ptr(residual), y.data_ptr(), n, h, w, cin, cout,
                                         padding, padding, ho, wo, int(relu), _lib.current_stream())
     _lib.check(rc, name)
     return y
@@ -861,8 +841,7 @@ def hip_stem_conv_pool(x: torch.Tensor, w_packed: torch.Tensor, bias: torch.Tens
                            memory_format=torch.channels_last)
     with torch.cuda.device(x.device):
         rc = _lib.load().tia_stem_conv7x7_pool_conv_nhwc(x.data_ptr(), int(x.dtype == torch.uint8), w_packed.data_ptr(), bias.data_ptr(),
-                                                         y.data_ptr(), _DT[out_dtype], conv.data_ptr() if conv is not None else 0, n, h,
-                                                         w, _lib.current_stream())
+                                                         y.data_ptr(), _DT[out_dtype], _ptr(conv), n, h, w, _lib.current_stream())
     _lib.check(rc, "tia_stem_conv7x7_pool_conv_nhwc")
     return (y, conv) if return_conv else y
 

@@ -19,12 +19,11 @@ The other convolutions are hand-written too: the 3-channel 7x7 stem runs on the 
 thin-input form (``tia_conv2d_thin_nhwc_f32``), the dense units' grouped convolutions (32 -> 8 channels per group) on
 ``tia_grouped_conv_valid_nhwc_f32``, and the final ``BN -> ReLU -> 64 -> n_out`` 1x1 of every branch is one launch of
 ``tia_conv1x1_head_nhwc_f32``.  Built from a loaded model (reference parameter names), never the object that loads
-weights; float32, CUDA, channels-last only.
+weights; CUDA, channels-last only.  Which kernel a layer runs on, in float32 and in half, is `_Conv`'s to know and nobody else's.
 """
 
 from __future__ import annotations
 
-import os
 from collections import OrderedDict
 
 import torch
@@ -59,7 +58,22 @@ def _same_pads(size: int, ksize: int, stride: int) -> tuple[int, int]:
 
 
 class _Conv(nn.Module):
-    """One convolution of the graph: weights (optionally with a following BN folded in) packed for the MFMA kernel."""
+    """One convolution of the graph (optionally with a following BN folded in) and the one owner of every kernel form of it: which
+    kernel the layer runs on is fixed here, once (``route``), and so is which packed operands it holds in float32 and -- after
+    ``prepare(dtype)`` -- in fp16 / bf16.  ``forward`` is the only way in.
+
+    ===========  =========================================  ============================  =====================================
+    ``route``    layer                                      float32                       fp16 / bf16 (``prepare``)
+    ===========  =========================================  ============================  =====================================
+    ``head``     1x1, 64 -> at most 8 channels              ``.weight``                   ``_weight32`` (float32 ``[cout, 64]``)
+    ``thin``     cin * k <= 32 (the RGB stem)               ``_packed``                   ``_packed`` (float32; stride 1 only)
+    ``grouped``  32 -> 8 channels per group, no bias        ``_packed``                   ``_packed_h`` (3x3 / 5x5)
+    ``mfma``     cin % 32 == 0, cout % 64 == 0              ``_packed``, ``_wino``        ``_packed_h``
+    ``torch``    anything else                              library convolution           refused (``TypeError``)
+    ===========  =========================================  ============================  =====================================
+
+    A call outside its kernel's form (a head with a ReLU, a grouped layer with padding) takes the library convolution in float32 and
+    raises in half.  The bias is ``.bias`` in float32 and its float32 copy ``_bias32`` in half."""
 
     def __init__(self, conv: nn.Conv2d, bn: nn.BatchNorm2d | None = None) -> None:
         super().__init__()
@@ -80,9 +94,11 @@ class _Conv(nn.Module):
         # the dense units' grouped convolution: 32 -> 8 channels per group, stride 1, no bias
         self.grouped_ok = (conv.groups > 1 and conv.in_channels // conv.groups == 32 and conv.out_channels // conv.groups == 8
                            and conv.stride[0] == 1 and bias is None)
+        # the four flags exclude one another (groups; cin < 32, == 64, % 32 == 0; cout <= 8, % 64 == 0)
+        self.route = next((r for r in ("head", "thin", "grouped", "mfma") if getattr(self, r + "_ok")), "torch")
         self.weight = nn.Parameter(w.contiguous(), requires_grad=False)
         self.bias = nn.Parameter(bias.contiguous(), requires_grad=False) if bias is not None else None
-        self._packed: torch.Tensor | None = None
+        self._packed: torch.Tensor | None = None  # the route's float32 operand (`_operand`)
         # opt-in (`set_conv_algo(model, "winograd")`, engine kwarg `conv_algo`): plain 3x3 / stride-1 layers through the Winograd
         # F(2x2, 3x3) kernel (float32 in / float32 accumulate; csrc/conv3x3_wino.hip)
         self.conv_algo = "direct"
@@ -90,82 +106,118 @@ class _Conv(nn.Module):
         self._wino: torch.Tensor | None = None
         # half-precision form (`prepare`): plain attributes, so that casting the module leaves them as they are
         self.half_dtype: torch.dtype | None = None
-        self._packed_h: torch.Tensor | None = None   # [kh, kw, cin/8, cout, 8] halves (MFMA layers)
+        self._packed_h: torch.Tensor | None = None   # halves: [kh, kw, cin/8, cout, 8] (mfma), [groups, k, k, 4, 8, 8] (grouped)
         self._weight32: torch.Tensor | None = None   # [cout, 64] float32 (class heads)
         self._bias32: torch.Tensor | None = None
 
     def prepare(self, dtype: torch.dtype) -> None:
-        """Switch this convolution to fp16 / bf16 activations (``tia_conv2d_nhwc_h``; a class head: ``tia_conv1x1_head_nhwc_h``) --
-        call it on the device BEFORE the module is cast: the weights are packed NOW from the float32, BN-folded parameters (one
-        rounding to half, after the folding), and the bias stays float32 in a plain attribute that ``module.to(dtype)`` does not
-        touch.  ``torch.float32`` switches back.  A layer neither kernel takes raises ``TypeError``: there is no library
-        fall-back in half precision (``conv_algo`` has no effect there either: no Winograd form in half)."""
+        """Switch this convolution to fp16 / bf16 activations on the half form of its kernel (``tia_conv2d_nhwc_h(_ex)``,
+        ``tia_conv1x1_head_nhwc_h``, ``tia_grouped_conv_valid_nhwc_h``, ``tia_conv2d_thin_nhwc``) -- call it on the device BEFORE the
+        module is cast: the operands are packed NOW from the float32, BN-folded parameters (one rounding to half, after the folding;
+        the head's and the thin kernel's stay float32), never again from the cast ones, and the bias stays float32 in a plain
+        attribute that ``module.to(dtype)`` does not touch.  ``torch.float32`` switches back.  A layer without a half kernel raises
+        ``TypeError``: there is no library fall-back in half precision (``conv_algo`` has no effect there either: no Winograd form
+        in half)."""
         if dtype == torch.float32:
             self.half_dtype = self._packed_h = self._weight32 = self._bias32 = None
             return
         if dtype not in (torch.float16, torch.bfloat16) or self.weight.dtype != torch.float32:
             msg = f"_Conv.prepare packs float32 parameters for fp16 / bf16; got {self.weight.dtype} parameters for {dtype}."
             raise ValueError(msg)
-        if self.head_ok:
+        if self.route == "head":
             self._weight32 = self.weight.detach().reshape(self.weight.shape[0], 64).clone().contiguous()
-        elif self.mfma_ok:
+        elif self.route == "mfma":
             self._packed_h = pack_conv_weights_h(self, dtype)  # reads `.weight` (OIHW, BN folded, float32)
+        elif self.route == "grouped" and self.kernel in (3, 5):
+            self._packed_h = pack_grouped_conv_valid_weights_h(self.weight, self.groups, dtype)
+        elif self.route == "thin" and self.stride == 1:
+            self._packed = pack_thin_conv_weights(self.weight)  # float32 arithmetic; the output is written in `dtype`
         else:
-            msg = (f"no {dtype} kernel for a convolution {tuple(self.weight.shape)} with groups = {self.groups}: tia_conv2d_nhwc_h takes "
-                   "cin % 32 == 0 and cout % 64 == 0, tia_conv1x1_head_nhwc_h 64 -> at most 8 channels.")
+            msg = (f"no {dtype} kernel for a convolution {tuple(self.weight.shape)} with groups = {self.groups}, stride {self.stride}: "
+                   "tia_conv2d_nhwc_h takes cin % 32 == 0 and cout % 64 == 0, tia_conv1x1_head_nhwc_h 64 -> at most 8 channels, "
+                   "tia_grouped_conv_valid_nhwc_h 32 -> 8 channels per group, 3x3 or 5x5, stride 1, no bias, tia_conv2d_thin_nhwc "
+                   "c * k <= 32, cout % 64 == 0, stride 1.")
             raise TypeError(msg)
         self._bias32 = self.bias.detach().clone().contiguous() if self.bias is not None else None
         self.half_dtype = dtype
 
-    def _forward_half(self, x: torch.Tensor, pads: tuple[int, int], relu: bool, residual: torch.Tensor | None,  # noqa: FBT001
-                      pre: "_BnAct | None") -> torch.Tensor:
-        if self.head_ok and pads == (0, 0) and not relu and residual is None:
-            sc, sh = pre.affine32() if pre is not None else (None, None)
-            return hip_conv1x1_head(_cl(x), self._weight32, self._bias32, pre_scale=sc, pre_shift=sh)
-        if pre is not None or self._packed_h is None:
-            msg = (f"half-precision _Conv {tuple(self.weight.shape)}: tia_conv2d_nhwc_h takes no activation on load "
-                   f"(pads {pads}, pre {'given' if pre is not None else 'none'}).")
-            raise TypeError(msg)
-        if pads[0] != pads[1]:  # TensorFlow "same" padding of a strided layer: the extended entry point
-            return hip_conv2d_h_ex(_cl(x), self._packed_h, self._bias32, residual, cout=self.weight.shape[0], kernel=self.kernel,
-                                   stride=self.stride, pad_lo=pads[0], pad_hi=pads[1], relu=relu)
-        return hip_conv2d_h(_cl(x), self._packed_h, self._bias32, residual, cout=self.weight.shape[0], kernel=self.kernel,
-                            stride=self.stride, padding=pads[0], relu=relu)
+    @property
+    def activates_on_load(self) -> bool:
+        """Whether ``forward(pre=...)`` applies the BN + ReLU to the operand while the kernel loads it (``tia_conv1x1_pre_nhwc_f32``:
+        float32 1x1 MFMA layers; the half kernel fills its LDS by DMA and cannot)."""
+        return self.route == "mfma" and self.kernel == 1 and self.half_dtype is None
 
-    def forward(self, x: torch.Tensor, *, pads: tuple[int, int] = (0, 0), relu: bool = False,
-                residual: torch.Tensor | None = None, out: torch.Tensor | None = None, pre: "_BnAct | None" = None) -> torch.Tensor:
+    def _operand(self) -> torch.Tensor:
+        """The packed weights of this layer's kernel.  A prepared layer holds them since ``prepare`` (its parameters have been rounded
+        by the cast); an unprepared float32 one packs them on first use, and again after a move to another device."""
         if self.half_dtype is not None:
-            return self._forward_half(x, pads, relu, residual, pre)
-        if self.head_ok and pads == (0, 0) and not relu and residual is None:
-            # `pre`: the BatchNorm + ReLU in front of the head, applied on load
-            return hip_conv1x1_head(_cl(x), self.weight, self.bias, pre_scale=pre.scale if pre is not None else None,
-                                    pre_shift=pre.shift if pre is not None else None)
-        if pre is not None:
-            x = pre(x)
-        if self.thin_ok and residual is None:
-            if self._packed is None or self._packed.device != self.weight.device:
+            return self._packed if self.route == "thin" else self._packed_h
+        if self._packed is None or self._packed.device != self.weight.device:
+            if self.route == "thin":
                 self._packed = pack_thin_conv_weights(self.weight)
-            return hip_conv2d_thin(x, self._packed, self.bias, kernel=self.kernel, stride=self.stride, pad_lo=pads[0], pad_hi=pads[1],
-                                   relu=relu)
-        if self.grouped_ok and pads == (0, 0) and not relu and residual is None:
-            if self._packed is None or self._packed.device != self.weight.device:
+            elif self.route == "grouped":
                 g, k = self.groups, self.kernel
                 self._packed = self.weight.view(g, 8, 32, k, k).permute(0, 3, 4, 2, 1).contiguous()  # [g][ky][kx][c][j]
-            return hip_grouped_conv_valid(_cl(x), self._packed, groups=self.groups, kernel=self.kernel, out=out)
-        if self.wino_ok and self.conv_algo == "winograd" and max(pads) <= 2:  # noqa: PLR2004
-            if self._wino is None or self._wino.device != self.weight.device:
-                self._wino = pack_conv_weights_wino(self)  # reads `.weight` (OIHW, BN folded)
-            return hip_conv3x3_wino(_cl(x), self._wino, self.bias, residual, padding=pads[0], pad_hi=pads[1], relu=relu)
-        if self.mfma_ok:
-            if self._packed is None or self._packed.device != self.weight.device:
+            else:
                 self._packed = pack_conv_weights(self)  # reads `.weight` (OIHW)
-            return hip_conv2d_ex(_cl(x), self._packed, self.bias, residual, kernel=self.kernel, stride=self.stride,
+        return self._packed
+
+    def forward(self, x: torch.Tensor, *, pads: tuple[int, int] = (0, 0), relu: bool = False, residual: torch.Tensor | None = None,  # noqa: C901, PLR0911, PLR0912
+                out: torch.Tensor | None = None, pre: "_BnAct | None" = None, post: "_BnAct | None" = None, want_raw: bool = True):
+        """``v = act(conv(x) + bias + residual)``.  ``pre``: the convolution of ``relu(bn(x))`` instead, the BN + ReLU applied on load
+        where the kernel can (a head, ``activates_on_load``), as a pass of its own otherwise.  ``post``: returns ``(v, relu(bn(v)))``
+        -- ``(None, relu(bn(v)))`` with ``want_raw=False`` -- both from one epilogue on the MFMA kernels (half: the activated copy
+        comes from the unrounded sum).  ``out``: where a grouped layer writes (a channel slice / window of a wider buffer)."""
+        half = self.half_dtype
+        bias = self.bias if half is None else self._bias32
+        plain = pads == (0, 0) and not relu and residual is None
+        if post is not None and self.route != "mfma":  # no second epilogue output off the MFMA kernels: a pass of its own (float32)
+            v = self(x, pads=pads, relu=relu, residual=residual, pre=pre)
+            return (v if want_raw else None), post(v)
+        if self.route == "head" and plain:
+            sc, sh = pre.affine32() if pre is not None else (None, None)
+            return hip_conv1x1_head(_cl(x), self.weight if half is None else self._weight32, bias, pre_scale=sc, pre_shift=sh)
+        if pre is not None:
+            if self.activates_on_load and pads == (0, 0) and post is None:
+                return hip_conv1x1_pre(_cl(x), *pre.affine32(), self._operand(), bias, residual, stride=self.stride, relu=relu)
+            if half is not None:
+                msg = f"half-precision _Conv {tuple(self.weight.shape)}: the {self.route} kernel takes no activation on load."
+                raise TypeError(msg)
+            x = pre(x)
+        if self.route == "thin" and residual is None:
+            return hip_conv2d_thin(x, self._operand(), bias, kernel=self.kernel, stride=self.stride, pad_lo=pads[0], pad_hi=pads[1],
+                                   relu=relu, **({} if half is None else {"out_dtype": half}))
+        if self.route == "grouped" and plain:
+            conv = hip_grouped_conv_valid if half is None else hip_grouped_conv_valid_h
+            return conv(_cl(x), self._operand(), groups=self.groups, kernel=self.kernel, out=out)
+        if half is not None and self.route != "mfma":
+            msg = (f"half-precision _Conv {tuple(self.weight.shape)}: no {half} form of the {self.route} kernel for pads {pads}, "
+                   f"relu {relu}, residual {'given' if residual is not None else 'none'}.")
+            raise TypeError(msg)
+        if self.route == "mfma":
+            sc, sh = post.affine32() if post is not None else (None, None)
+            if half is not None:
+                geometry = {"cout": self.weight.shape[0], "kernel": self.kernel, "stride": self.stride}
+                if post is not None or pads[0] != pads[1]:
+                    # a second output, or TensorFlow "same" padding of a strided layer: the extended entry point (only the plain
+                    # one may take the tap-reuse route, so the two stay apart)
+                    return hip_conv2d_h_ex(_cl(x), self._packed_h, bias, residual, **geometry, pad_lo=pads[0], pad_hi=pads[1],
+                                           relu=relu, post_scale=sc, post_shift=sh, want_raw=want_raw)
+                return hip_conv2d_h(_cl(x), self._packed_h, bias, residual, **geometry, padding=pads[0], relu=relu)
+            if post is not None:
+                return hip_conv2d_post(_cl(x), self._operand(), bias, residual, kernel=self.kernel, stride=self.stride, pad_lo=pads[0],
+                                       pad_hi=pads[1], relu=relu, post_scale=sc, post_shift=sh, want_raw=want_raw)
+            if self.wino_ok and self.conv_algo == "winograd" and max(pads) <= 2:  # noqa: PLR2004
+                if self._wino is None or self._wino.device != self.weight.device:
+                    self._wino = pack_conv_weights_wino(self)  # reads `.weight` (OIHW, BN folded)
+                return hip_conv3x3_wino(_cl(x), self._wino, bias, residual, padding=pads[0], pad_hi=pads[1], relu=relu)
+            return hip_conv2d_ex(_cl(x), self._operand(), bias, residual, kernel=self.kernel, stride=self.stride,
                                  pad_lo=pads[0], pad_hi=pads[1], relu=relu)
         if pads != (0, 0):
             x = F.pad(x, (pads[0], pads[1], pads[0], pads[1]))
         y = _cl(F.conv2d(x, self.weight, None, self.stride, 0, 1, self.groups))
-        if self.bias is not None or relu or residual is not None:
-            bias = self.bias if self.bias is not None else torch.zeros(y.shape[1], device=y.device)
+        if bias is not None or relu or residual is not None:
+            bias = bias if bias is not None else torch.zeros(y.shape[1], device=y.device)
             if y.shape[1] % 4 == 0:
                 return hip_bias_act_(y, bias, residual, relu=relu)
             y = y + bias[None, :, None, None]
@@ -187,35 +239,6 @@ def set_conv_algo(model: nn.Module, algo: str) -> int:
             mod.conv_algo = algo
             count += int(mod.wino_ok)
     return count
-
-
-def _conv_with_post(conv: "_Conv", x: torch.Tensor, residual: torch.Tensor, bn: "_BnAct", *, want_raw: bool):
-    """``v = conv(x) + residual`` and ``relu(bn(v))`` from one launch (1x1 MFMA convolution); ``(v or None, activated)``."""
-    if conv._packed is None or conv._packed.device != conv.weight.device:  # noqa: SLF001
-        conv._packed = pack_conv_weights(conv)  # noqa: SLF001
-    return hip_conv2d_post(_cl(x), conv._packed, conv.bias, residual, kernel=conv.kernel, stride=conv.stride, pad_lo=0,  # noqa: SLF001
-                           pad_hi=0, relu=False, post_scale=bn.scale, post_shift=bn.shift, want_raw=want_raw)
-
-
-def _conv_with_post_h(conv: "_Conv", x: torch.Tensor, residual: torch.Tensor, bn: "_BnAct", *, want_raw: bool):
-    """The half form of :func:`_conv_with_post` (``tia_conv2d_nhwc_h_ex``): the activated copy comes from the unrounded sum."""
-    if conv._packed_h is None:  # noqa: SLF001
-        msg = f"half-precision _Conv {tuple(conv.weight.shape)} has no packed half weights (prepare was not called)."
-        raise TypeError(msg)
-    scale, shift = bn.affine32()
-    return hip_conv2d_h_ex(_cl(x), conv._packed_h, conv._bias32, residual, cout=conv.weight.shape[0], kernel=conv.kernel,  # noqa: SLF001
-                           stride=conv.stride, pad_lo=0, pad_hi=0, relu=False, post_scale=scale, post_shift=shift, want_raw=want_raw)
-
-
-def _conv_pre_on_load(conv: "_Conv", x: torch.Tensor, bn: "_BnAct") -> torch.Tensor:
-    """``relu(conv(relu(bn(x))) + bias)`` for a 1x1 MFMA convolution, the BN + ReLU applied to the operand on load."""
-    if conv._packed is None or conv._packed.device != conv.weight.device:  # noqa: SLF001
-        conv._packed = pack_conv_weights(conv)  # noqa: SLF001
-    return hip_conv1x1_pre(_cl(x), bn.scale, bn.shift, conv._packed, conv.bias, stride=conv.stride, relu=True)  # noqa: SLF001
-
-
-# developer switch for A/B measurements: TIA_HOVER_PRE_ON_LOAD=0 keeps the second (activated) epilogue output instead
-_PRE_ON_LOAD = os.environ.get("TIA_HOVER_PRE_ON_LOAD", "1") != "0"
 
 
 class _BnAct(nn.Module):
@@ -257,44 +280,24 @@ class _FusedResidualBlock(nn.Module):
         self.shortcut = _Conv(blk.shortcut) if blk.shortcut is not None else None
         self.out = _BnAct(blk.blk_bna.bn)
 
-    def _forward_half(self, x: torch.Tensor) -> torch.Tensor:
-        """fp16 / bf16: the half MFMA kernel fills its LDS by DMA and cannot activate on load, so EVERY unit takes the second
-        epilogue output -- conv3 + shortcut writes the raw half sum (the next unit's shortcut) and the activated half copy (the
-        next unit's input, taken from the unrounded sum); the last unit writes the activated copy only."""
-        shortcut = x if self.shortcut is None else self.shortcut(x)
-        units = len(self.c1)
-        a = x
-        for i, (c1, c2, c3) in enumerate(zip(self.c1, self.c2, self.c3)):
-            a = c1(a, relu=True)
-            a = c2(a, pads=_same_pads(a.shape[2], c2.kernel, c2.stride), relu=True)
-            last = i + 1 == units
-            shortcut, a = _conv_with_post_h(c3, a, _cl(shortcut), self.out if last else self.pre[i + 1], want_raw=not last)
-        return a
-
     def forward(self, x: torch.Tensor) -> torch.Tensor:
-        if self.c1[0].half_dtype is not None:
-            return self._forward_half(x)
         shortcut = x if self.shortcut is None else self.shortcut(x)
         units = len(self.c1)
         a = x  # the first unit has no pre-activation
         raw_in = False  # `a` is the raw residual sum: the unit's pre-activation is applied by conv1 on load
         for i, (c1, c2, c3) in enumerate(zip(self.c1, self.c2, self.c3)):
-            a = _conv_pre_on_load(c1, a, self.pre[i]) if raw_in else c1(a, relu=True)
+            a = c1(a, relu=True, pre=self.pre[i] if raw_in else None)
             a = c2(a, pads=_same_pads(a.shape[2], c2.kernel, c2.stride), relu=True)
             last = i + 1 == units
-            nxt = self.out if last else self.pre[i + 1]
-            raw_in = not last and _PRE_ON_LOAD and c3.mfma_ok and self.c1[i + 1].mfma_ok and self.c1[i + 1].kernel == 1
+            raw_in = not last and c3.mfma_ok and self.c1[i + 1].activates_on_load  # (never in half: no activation on load there)
             if raw_in:
                 # conv3 + shortcut only: the next unit reads this raw sum twice (conv1 activates it on load, conv3 adds it),
                 # so the activated copy is neither written nor read back -- 3 instead of 4 passes over the widest tensor
                 a = shortcut = c3(a, residual=_cl(shortcut))
-            elif c3.mfma_ok:
-                # conv3 + shortcut, and the BN + ReLU that follows the sum (the block's blk_bna, or the next unit's
-                # pre-activation when on-load activation is off), from one epilogue
-                shortcut, a = _conv_with_post(c3, a, _cl(shortcut), nxt, want_raw=not last)
             else:
-                shortcut = c3(a, residual=_cl(shortcut))
-                a = nxt(shortcut)
+                # conv3 + shortcut, and the BN + ReLU that follows the sum (the block's blk_bna; in half the next unit's
+                # pre-activation, taken from the unrounded sum), from one epilogue; the last unit writes the activated copy only
+                shortcut, a = c3(a, residual=_cl(shortcut), post=self.out if last else self.pre[i + 1], want_raw=not last)
         return a
 
 
@@ -308,23 +311,6 @@ class _FusedDenseBlock(nn.Module):
             self.c1.append(_Conv(mods["conv1"], mods["conv1/bn"]))
             self.c2.append(_Conv(mods["conv2"]))
         self.out = _BnAct(blk.blk_bna.bn)
-        # half-precision form (`prepare`): the grouped convolutions' packed half weights, one per unit; plain attributes
-        self.half_dtype: torch.dtype | None = None
-        self._grouped_h: list[torch.Tensor] | None = None
-
-    def prepare(self, dtype: torch.dtype) -> None:
-        """Pack the grouped convolutions for ``tia_grouped_conv_valid_nhwc_h`` from their float32 weights (one rounding); they
-        are this block's to prepare (``_Conv.prepare`` refuses them).  ``torch.float32`` switches back."""
-        if dtype == torch.float32:
-            self.half_dtype = self._grouped_h = None
-            return
-        for c2 in self.c2:
-            if not (c2.grouped_ok and c2.kernel in (3, 5)):
-                msg = (f"no {dtype} kernel for a dense unit's convolution {tuple(c2.weight.shape)} with groups = {c2.groups}: "
-                       "tia_grouped_conv_valid_nhwc_h takes 32 -> 8 channels per group, 3x3 or 5x5, stride 1, no bias.")
-                raise TypeError(msg)
-        self._grouped_h = [pack_grouped_conv_valid_weights_h(c2.weight, c2.groups, dtype) for c2 in self.c2]
-        self.half_dtype = dtype
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
         # x_{i+1} = cat(centre_crop(x_i), new_i): instead of re-concatenating the growing stack, one buffer holds all
@@ -340,12 +326,9 @@ class _FusedDenseBlock(nn.Module):
         for i, (pre, c1, c2) in enumerate(zip(self.pre, self.c1, self.c2)):
             view = buf[:, :c, i * r:h0 - i * r, i * r:w0 - i * r]
             dst = buf[:, c:c + grow, (i + 1) * r:h0 - (i + 1) * r, (i + 1) * r:w0 - (i + 1) * r]
-            if self.half_dtype is not None:
-                hip_grouped_conv_valid_h(c1(pre.view(view), relu=True), self._grouped_h[i], groups=c2.groups, kernel=c2.kernel, out=dst)
-            elif c2.grouped_ok:
-                c2(c1(pre.view(view), relu=True), out=dst)  # written straight into its slice
-            else:
-                dst.copy_(c2(c1(pre.view(view), relu=True)))
+            new = c2(c1(pre.view(view), relu=True), out=dst)  # the grouped kernel writes straight into its slice
+            if new is not dst:  # any other layer (float32 only: `prepare` refuses it)
+                dst.copy_(new)
             c += grow
         return self.out.view(buf[:, :, units * r:h0 - units * r, units * r:w0 - units * r])
 
@@ -377,17 +360,14 @@ class FusedHoVerNet(nn.Module):
         self.d2, self.d3 = _FusedResidualBlock(model.d2), _FusedResidualBlock(model.d3)
         self.conv_bot = _Conv(model.conv_bot)
         self.decoder = nn.ModuleDict(OrderedDict((name, _FusedBranch(branch)) for name, branch in model.decoder.items()))
-        # half-precision form (`prepare`): the stem stays the float32 thin kernel (its float32 operands in plain attributes)
-        self.half_dtype: torch.dtype | None = None
-        self._stem_packed32: torch.Tensor | None = None
-        self._stem_bias32: torch.Tensor | None = None
+        self.half_dtype: torch.dtype | None = None  # fp16 / bf16 once `prepare(dtype)` has switched every layer
 
     def prepare(self, dtype: torch.dtype) -> None:
         """fp16 / bf16 activations on the same graph (the engines' ``compute_dtype``): call this on the device, on the float32
         copy, BEFORE ``.to(dtype)``.  Every MFMA convolution packs its BN-folded float32 weights for ``tia_conv2d_nhwc_h(_ex)``
         (rounded once, after the folding) and keeps its bias in float32; every BN scale / shift and the heads' weights stay
-        float32 in plain attributes that the cast does not reach; the dense blocks pack their grouped convolutions for
-        ``tia_grouped_conv_valid_nhwc_h``.  The stem stays the float32-arithmetic thin kernel writing its map in ``dtype`` (under
+        float32 in plain attributes that the cast does not reach; the dense units' grouped convolutions are packed for
+        ``tia_grouped_conv_valid_nhwc_h``.  Each layer does this for itself (``_Conv.prepare``, ``_BnAct.prepare``).  The stem stays the float32-arithmetic thin kernel writing its map in ``dtype`` (under
         1 % of the forward; exactly one rounding of the float32 stem); residual units take their pre-activations from the second
         epilogue output of conv3 (no activation on load in half); the logits come back in float32.  A layer without a half kernel
         raises ``TypeError``: there is no library fall-back, and ``conv_algo`` has no effect in half.  ``torch.float32``
@@ -398,34 +378,17 @@ class FusedHoVerNet(nn.Module):
         if self.stem.weight.dtype != torch.float32:
             msg = f"FusedHoVerNet.prepare starts from the float32 parameters (call it before the cast); got {self.stem.weight.dtype}."
             raise ValueError(msg)
-        if dtype != torch.float32 and not (self.stem.thin_ok and self.stem.stride == 1):
-            msg = f"no {dtype} kernel for the stem {tuple(self.stem.weight.shape)}: tia_conv2d_thin_nhwc takes c * k <= 32, cout % 64 == 0."
-            raise TypeError(msg)
-        owned = {id(self.stem)}  # prepared by their owners: `_Conv.prepare` refuses a thin and a grouped convolution
         for mod in self.modules():
-            if isinstance(mod, _FusedDenseBlock):
+            if isinstance(mod, (_Conv, _BnAct)):
                 mod.prepare(dtype)
-                owned.update(id(c2) for c2 in mod.c2)
-        for mod in self.modules():
-            if isinstance(mod, (_Conv, _BnAct)) and id(mod) not in owned:
-                mod.prepare(dtype)
-        if dtype == torch.float32:
-            self.half_dtype = self._stem_packed32 = self._stem_bias32 = None
-            return
-        self._stem_packed32 = pack_thin_conv_weights(self.stem.weight)
-        self._stem_bias32 = self.stem.bias.detach().clone().contiguous() if self.stem.bias is not None else None
-        self.half_dtype = dtype
+        self.half_dtype = None if dtype == torch.float32 else dtype
 
     def forward(self, input_tensor: torch.Tensor) -> dict:
         half = self.half_dtype
         # (half: the batch arrives in `half`, where 0 .. 255 are exact; the division is the float32 copy's)
         x = _cl(input_tensor / 255.0) if half is None else _cl(input_tensor.float() / 255.0)
         pads = _same_pads(x.shape[2], self.stem.kernel, 1) if self.stem_pad else (0, 0)
-        if half is None:
-            stem = self.stem(x, pads=pads, relu=True)
-        else:  # the float32 stem rounded once
-            stem = hip_conv2d_thin(x, self._stem_packed32, self._stem_bias32, kernel=self.stem.kernel, stride=1, pad_lo=pads[0],
-                                   pad_hi=pads[1], relu=True, out_dtype=half)
+        stem = self.stem(x, pads=pads, relu=True)  # (half: the float32 stem rounded once)
         d0 = self.d0(stem)
         d1 = self.d1(d0)
         d2 = self.d2(d1)

@@ -1,4 +1,5 @@
-"""Inference copy of :class:`UNetModel` (ResNet-50 encoder) on the hand-written float32 MFMA convolutions.
+"""Inference copy of :class:`UNetModel` (ResNet-50 encoder) on the hand-written MFMA convolutions (float32; fp16 / bf16
+after ``FusedUNet.prepare(dtype)``).
 
 Same arithmetic graph as ``UNetModel.forward`` (reference ``models/architecture/unet.py:356-417``):
 

@@ -792,6 +792,32 @@ int tia_upsample2x_add_act_nhwc_h(const void* d_x, const void* d_y, int64_t y_im
                                   const float* d_scale, const float* d_shift, void* d_out, int64_t n, int64_t h, int64_t w,
                                   int64_t c, int32_t dtype, void* stream);
 
+/* y[b, oy, ox, :] = mean of the 2 x 2 window of x at rows 2 oy, 2 oy + 1 and columns 2 ox, 2 ox + 1 on NHWC float32: AvgPool2d(2,
+ * stride=2) of the plain UNet encoder (models/architecture/unet.py: UnetEncoder).  x [n,h,w,c] dense; y [n,h/2,w/2,c] dense (floor
+ * division: a last odd row or column is not read).  The arithmetic is fixed: s = ((x00 + x01) + x10) + x11 with xrc = row r, column c
+ * of the window, every sum rounded in float32, then y = s * 0.25f -- the order of torch's avg_pool2d, bit for bit.
+ * c % 4 == 0 (else TIA_ESIZE); h >= 2, w >= 2, n > 0, non-null 16-byte aligned pointers (else TIA_EINVAL); 64-bit offsets; nothing is
+ * launched on an error return.  Additive, same version (6). */
+int tia_avgpool2x2_nhwc_f32(const float* d_x, float* d_y, int64_t n, int64_t h, int64_t w, int64_t c, void* stream);
+/* The half form (additive at version 6): x and y of `dtype` (TIA_DT_F16 | TIA_DT_BF16); the four inputs widened to float32, the same
+ * three sums and product, ONE rounding to half (nearest even).  c % 8 == 0 (else TIA_ESIZE); otherwise as above. */
+int tia_avgpool2x2_nhwc_h(const void* d_x, void* d_y, int64_t n, int64_t h, int64_t w, int64_t c, int32_t dtype, void* stream);
+
+/* out[b, Y, X, 0:cx] = act(x[b, Y/2, X/2, :]), out[b, Y, X, cx:cx+cy] = act(y[b, Y, X, :]) on NHWC float32: nearest x2 upsampling
+ * fused with the channel concatenation of a UNet decoder's skip connection (models/architecture/unet.py: skip_type="concat") and,
+ * with scale / shift, the BatchNorm + ReLU of a pre-activation decoder block.  x [n,h,w,cx], y [n,2h,2w,cy], out [n,2h,2w,cx+cy], all
+ * dense; scale / shift float32 [cx+cy], both given or both NULL.  NULL: act is the identity and the pass is a pure copy (bit-equal
+ * outputs).  Given: p = v * scale[ch]; a = p + shift[ch]; max(a, 0), product and sum rounded separately (no fused multiply-add).
+ * Every x vector is read once for its 2 x 2 outputs.  cx % 4 == 0 and cy % 4 == 0 (else TIA_ESIZE); positive sizes, non-null 16-byte
+ * aligned pointers (else TIA_EINVAL); 64-bit offsets; nothing is launched on an error return.  Additive, same version (6). */
+int tia_upsample2x_concat_act_nhwc_f32(const float* d_x, const float* d_y, const float* d_scale, const float* d_shift, float* d_out,
+                                       int64_t n, int64_t h, int64_t w, int64_t cx, int64_t cy, void* stream);
+/* The half form (additive at version 6): x, y and out of `dtype` (TIA_DT_F16 | TIA_DT_BF16), scale / shift float32.  With an affine
+ * v is widened to float32 first and the result rounded ONCE to half (nearest even); without, the halves are copied as they are.
+ * cx % 8 == 0 and cy % 8 == 0 (else TIA_ESIZE); otherwise as above. */
+int tia_upsample2x_concat_act_nhwc_h(const void* d_x, const void* d_y, const float* d_scale, const float* d_shift, void* d_out,
+                                     int64_t n, int64_t h, int64_t w, int64_t cx, int64_t cy, int32_t dtype, void* stream);
+
 /* =======================================================================================
  * All borders of binary planes: cv2.findContours(layer, RETR_TREE, CHAIN_APPROX_NONE | _SIMPLE)
  * (models/architecture/hovernetplus.py:222-226, HoVerNetPlus._get_layer_info)

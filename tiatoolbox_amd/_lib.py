@@ -141,6 +141,10 @@ _SIGNATURES = {
     "tia_upsample2x_add_nhwc_f32": ([_P, _P, _I64, _I64, _P, _I64, _I64, _I64, _I64, _P], C.c_int),
     "tia_upsample2x_add_act_nhwc_f32": ([_P, _P, _I64, _I64, _P, _P, _P, _I64, _I64, _I64, _I64, _P], C.c_int),
     "tia_upsample2x_add_act_nhwc_h": ([_P, _P, _I64, _I64, _P, _P, _P, _I64, _I64, _I64, _I64, _I32, _P], C.c_int),
+    "tia_avgpool2x2_nhwc_f32": ([_P, _P, _I64, _I64, _I64, _I64, _P], C.c_int),
+    "tia_avgpool2x2_nhwc_h": ([_P, _P, _I64, _I64, _I64, _I64, _I32, _P], C.c_int),
+    "tia_upsample2x_concat_act_nhwc_f32": ([_P, _P, _P, _P, _P, _I64, _I64, _I64, _I64, _I64, _P], C.c_int),
+    "tia_upsample2x_concat_act_nhwc_h": ([_P, _P, _P, _P, _P, _I64, _I64, _I64, _I64, _I64, _I32, _P], C.c_int),
     "tia_bias_act_nhwc": ([_P, _P, _P, _I64, _I64, _I32, _I32, _P], C.c_int),
     "tia_bias_relu_maxpool_nhwc": ([_P, _P, _I64, _I64, _I64, _I64, _I32, _P, _P], C.c_int),
     "tia_hover_instance_stats": ([_P, _P, _I64, _I64, _I64, _I32, _I32, _P, _P, _P], C.c_int),

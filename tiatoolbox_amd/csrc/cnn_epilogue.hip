@@ -1,6 +1,7 @@
 // Fused CNN epilogues on gfx950 for NHWC activations (fp32 / fp16 / bf16), HBM-bound:
 //   bias_act      : x = relu(x + bias[c] (+ residual))           1 read (+1) + 1 write, in place
 //   stem epilogue : out = maxpool3x3s2p1(relu(x + bias[c]))      reads the conv1 output once
+//   avgpool2x2 / upsample2x_concat (float32 forms; kernels in stream_glue.hpp): the plain UNet encoder's pooling, the concat skip
 // 16 bytes per lane per access (8 halves / 4 floats); consecutive lanes walk the channel axis so a
 // wave covers 1 KiB of contiguous NHWC memory per instruction.  Arithmetic in fp32, same order as
 // the unfused torch ops ((x + b) + r, then max(.,0)).
@@ -8,6 +9,7 @@
 #include <hip/hip_fp16.h>
 
 #include "common.hpp"
+#include "stream_glue.hpp"
 
 #pragma clang fp contract(off)
 
@@ -508,4 +510,13 @@ extern "C" int tia_conv1x1_head_nhwc_f32(const float* d_x, int64_t npix, const f
         default: launch_head<8>(d_x, npix, d_w, d_bias, d_pre_scale, d_pre_shift, d_y, st); break;
     }
     return hipGetLastError() == hipSuccess ? TIA_OK : TIA_ELAUNCH;
+}
+
+extern "C" int tia_avgpool2x2_nhwc_f32(const float* d_x, float* d_y, int64_t n, int64_t h, int64_t w, int64_t c, void* stream) {
+    return launch_avgpool2x2<Vec<float>>(d_x, d_y, n, h, w, c, (hipStream_t)stream);
+}
+
+extern "C" int tia_upsample2x_concat_act_nhwc_f32(const float* d_x, const float* d_y, const float* d_scale, const float* d_shift,
+                                                   float* d_out, int64_t n, int64_t h, int64_t w, int64_t cx, int64_t cy, void* stream) {
+    return launch_upsample2x_concat<Vec<float>>(d_x, d_y, d_scale, d_shift, d_out, n, h, w, cx, cy, (hipStream_t)stream);
 }

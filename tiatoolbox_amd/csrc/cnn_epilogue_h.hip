@@ -3,11 +3,13 @@
 //   head 1x1             : y[p][o] = bias[o] + sum_c w[o][c] * pre(x[p][c])            half in, float32 logits out
 //   scale_shift_act_view : y = act(x * scale[c] + shift[c]) of a view of a wider buffer  half in, half out
 //   grouped_conv_valid   : HoVer-Net's dense-unit Conv2d(128, 32, k, groups=4)           half in, half out, on the 16x16x32 MFMA
+//   avgpool2x2 / upsample2x_concat_act : the plain UNet encoder's pooling and the concat skip (kernels in stream_glue.hpp)
 // The half forms of tia_upsample2x_add_act_nhwc_f32 / tia_conv1x1_head_nhwc_f32 / tia_scale_shift_act_view_nhwc_f32 /
 // tia_grouped_conv_valid_nhwc_f32 (cnn_epilogue.hip).  16 bytes per lane and
 // access (8 halves), float32 arithmetic with every step rounded on its own (contraction off: the order of the unfused torch
 // ops), ONE round-to-nearest-even to half at the end, 64-bit element offsets (a tensor may exceed 2^31 bytes).
 #include "conv_device.hpp"
+#include "stream_glue.hpp"
 #include "wide_io.hpp"
 
 #pragma clang fp contract(off)
@@ -36,6 +38,14 @@ __device__ __forceinline__ v4u pack8(const float (&f)[8]) {
     v.x = w[0], v.y = w[1], v.z = w[2], v.w = w[3];
     return v;
 }
+
+// the 16-byte vector of 8 halves as stream_glue.hpp's kernels take it
+template <bool BF>
+struct HalfVec {
+    static constexpr int N = 8;
+    static __device__ __forceinline__ void unpack(const v4u& v, float (&f)[8]) { unpack8<BF>(v, f); }
+    static __device__ __forceinline__ v4u pack(const float (&f)[8]) { return pack8<BF>(f); }
+};
 
 // One thread per 8 channels of an INPUT pixel: it reads that vector once and produces the 2 x 2 output block above it (four
 // reads of the skip view, four stores).  blockIdx.x = input row b * h + yy (so the two output rows are 2 * row and 2 * row + 1),
@@ -383,4 +393,18 @@ extern "C" int tia_grouped_conv_valid_nhwc_h(const void* d_x, const void* d_w_pa
                        (hipStream_t)stream, (const unsigned short*)d_x, (const v4u*)d_w_packed, (unsigned short*)d_y, (int)n, (int)h, (int)w,
                        (int)groups, (long)y_image_stride, (long)y_row_stride, (long)y_pixel_stride);
     return hipGetLastError() == hipSuccess ? TIA_OK : TIA_ELAUNCH;
+}
+
+extern "C" int tia_avgpool2x2_nhwc_h(const void* d_x, void* d_y, int64_t n, int64_t h, int64_t w, int64_t c, int32_t dtype, void* stream) {
+    if (dtype != TIA_DT_F16 && dtype != TIA_DT_BF16) return TIA_EINVAL;
+    if (dtype == TIA_DT_BF16) return launch_avgpool2x2<HalfVec<true>>(d_x, d_y, n, h, w, c, (hipStream_t)stream);
+    return launch_avgpool2x2<HalfVec<false>>(d_x, d_y, n, h, w, c, (hipStream_t)stream);
+}
+
+extern "C" int tia_upsample2x_concat_act_nhwc_h(const void* d_x, const void* d_y, const float* d_scale, const float* d_shift, void* d_out,
+                                                int64_t n, int64_t h, int64_t w, int64_t cx, int64_t cy, int32_t dtype, void* stream) {
+    if (dtype != TIA_DT_F16 && dtype != TIA_DT_BF16) return TIA_EINVAL;
+    if (dtype == TIA_DT_BF16)
+        return launch_upsample2x_concat<HalfVec<true>>(d_x, d_y, d_scale, d_shift, d_out, n, h, w, cx, cy, (hipStream_t)stream);
+    return launch_upsample2x_concat<HalfVec<false>>(d_x, d_y, d_scale, d_shift, d_out, n, h, w, cx, cy, (hipStream_t)stream);
 }

@@ -480,6 +480,75 @@ def hip_upsample2x_add(x: torch.Tensor, y: torch.Tensor, scale: torch.Tensor | N
     return out
 
 
+def hip_avgpool2x2(x: torch.Tensor) -> torch.Tensor:
+    """``F.avg_pool2d(x, 2, 2)`` in one pass (``tia_avgpool2x2_nhwc_f32``; fp16 / bf16 ``x``: ``tia_avgpool2x2_nhwc_h``, float32
+    arithmetic and one rounding): the sums in torch's order, ``((x00 + x01) + x10) + x11``, times 0.25; a last odd row or column
+    is dropped."""
+    from tiatoolbox_amd import _lib
+
+    if not x.is_cuda:
+        msg = "hip_avgpool2x2 expects a CUDA tensor."
+        raise ValueError(msg)
+    half = x.dtype in (torch.float16, torch.bfloat16)
+    vec = 8 if half else 4  # elements per 16-byte access
+    if not (_nhwc_ptr_ok(x) and x.shape[1] % vec == 0 and x.shape[2] >= 2 and x.shape[3] >= 2 and x.data_ptr() % 16 == 0):  # noqa: PLR2004
+        msg = ("hip_avgpool2x2 expects a channels-last tensor [n, c, h, w] with h >= 2, w >= 2 (float32: c % 4 == 0; fp16 / bf16: "
+               f"c % 8 == 0) on a 16-byte aligned base; got x {tuple(x.shape)} {x.dtype} strides {tuple(x.stride())}.")
+        raise ValueError(msg)
+    n, c, h, w = x.shape
+    out = torch.empty((n, c, h // 2, w // 2), dtype=x.dtype, device=x.device, memory_format=torch.channels_last)
+    name = "tia_avgpool2x2_nhwc_h" if half else "tia_avgpool2x2_nhwc_f32"
+    with torch.cuda.device(x.device):
+        if half:
+            rc = _lib.load().tia_avgpool2x2_nhwc_h(x.data_ptr(), out.data_ptr(), n, h, w, c, _DT[x.dtype], _lib.current_stream())
+        else:
+            rc = _lib.load().tia_avgpool2x2_nhwc_f32(x.data_ptr(), out.data_ptr(), n, h, w, c, _lib.current_stream())
+    _lib.check(rc, name)
+    return out
+
+
+def hip_upsample2x_concat(x: torch.Tensor, y: torch.Tensor, scale: torch.Tensor | None = None,
+                          shift: torch.Tensor | None = None) -> torch.Tensor:
+    """``torch.cat([x.repeat_interleave(2, 2).repeat_interleave(2, 3), y], 1)`` in one pass (``tia_upsample2x_concat_act_nhwc_f32``;
+    fp16 / bf16 ``x`` and ``y``: ``tia_upsample2x_concat_act_nhwc_h``): a pure copy, bit for bit.  With ``scale`` / ``shift``
+    (float32, ``cx + cy`` channels): followed by ``relu(. * scale + shift)``, product and sum rounded separately in float32 and --
+    for halves -- one rounding at the end."""
+    from tiatoolbox_amd import _lib
+
+    if not (x.is_cuda and y.is_cuda):
+        msg = "hip_upsample2x_concat expects CUDA tensors."
+        raise ValueError(msg)
+    half = x.dtype in (torch.float16, torch.bfloat16)
+    vec = 8 if half else 4  # elements per 16-byte access
+    ok = (_nhwc_ptr_ok(x) and _nhwc_ptr_ok(y) and y.dtype == x.dtype and y.shape[0] == x.shape[0]
+          and tuple(y.shape[2:]) == (2 * x.shape[2], 2 * x.shape[3]) and x.shape[1] % vec == 0 and y.shape[1] % vec == 0
+          and x.data_ptr() % 16 == 0 and y.data_ptr() % 16 == 0)
+    if not ok:
+        msg = ("hip_upsample2x_concat expects channels-last tensors of one dtype, x [n, cx, h, w] and y [n, cy, 2h, 2w] (float32: "
+               "cx % 4 == 0 and cy % 4 == 0; fp16 / bf16: cx % 8 == 0 and cy % 8 == 0), dense on 16-byte aligned bases; "
+               f"got x {tuple(x.shape)} {x.dtype} strides {tuple(x.stride())}, y {tuple(y.shape)} {y.dtype} strides {tuple(y.stride())}.")
+        raise ValueError(msg)
+    n, cx, h, w = x.shape
+    cy = y.shape[1]
+    if (scale is None) != (shift is None) or any(
+            t is not None and not (t.is_cuda and t.dtype == torch.float32 and t.shape == (cx + cy,) and t.is_contiguous())
+            for t in (scale, shift)):
+        msg = (f"hip_upsample2x_concat takes scale / shift in float32 ([cx + cy] = [{cx + cy}] each, both or neither) beside {x.dtype} "
+               f"tensors; got {None if scale is None else (tuple(scale.shape), scale.dtype)}, "
+               f"{None if shift is None else (tuple(shift.shape), shift.dtype)}.")
+        raise ValueError(msg)
+    out = torch.empty((n, cx + cy, 2 * h, 2 * w), dtype=x.dtype, device=x.device, memory_format=torch.channels_last)
+    args = (x.data_ptr(), y.data_ptr(), _ptr(scale), _ptr(shift), out.data_ptr(), n, h, w, cx, cy)
+    name = "tia_upsample2x_concat_act_nhwc_h" if half else "tia_upsample2x_concat_act_nhwc_f32"
+    with torch.cuda.device(x.device):
+        if half:
+            rc = _lib.load().tia_upsample2x_concat_act_nhwc_h(*args, _DT[x.dtype], _lib.current_stream())
+        else:
+            rc = _lib.load().tia_upsample2x_concat_act_nhwc_f32(*args, _lib.current_stream())
+    _lib.check(rc, name)
+    return out
+
+
 def hip_conv2d_h(x: torch.Tensor, w_packed: torch.Tensor, bias: torch.Tensor | None, residual: torch.Tensor | None, *,
                  cout: int, kernel: int, stride: int, padding: int, relu: bool) -> torch.Tensor:
     """``relu(conv2d(x, w) + bias + residual)`` on an fp16 / bf16 channels-last CUDA tensor (``tia_conv2d_nhwc_h``: MFMA with

@@ -452,23 +452,37 @@ class EngineABC:
                     from tiatoolbox_amd.models.architecture.hovernet_fused import set_conv_algo
 
                     set_conv_algo(m, algo)
-                elif isinstance(m, UNetModel) and hasattr(m.backbone, "layer1") and m.skip_type == "add":
-                    # UNet with the ResNet-50 encoder: 61 of its 63 convolutions on the MFMA kernel (float32: tia_conv2d_nhwc_f32_ex
-                    # / Winograd; fp16 / bf16: tia_conv2d_nhwc_h after `prepare(dtype)` below), stem and head on their own kernels.
-                    # The plain-encoder and the concat-skip UNet have no half kernels: fp16 / bf16 casts the torch module
-                    from tiatoolbox_amd.models.architecture.unet_fused import FusedUNet
-
-                    m = FusedUNet(m.to(device=self.device))
+                elif isinstance(m, UNetModel):
+                    # UNet, either skip type.  ResNet-50 encoder (FusedUNet): 61 of its 63 convolutions on the MFMA kernel (float32:
+                    # tia_conv2d_nhwc_f32_ex / Winograd; fp16 / bf16: tia_conv2d_nhwc_h after `prepare(dtype)` below), stem and head
+                    # on their own kernels.  Plain encoder (FusedPlainUNet): every convolution on those kernels, the first on the
+                    # thin-input form, pooling and concatenation on tia_avgpool2x2_nhwc_* / tia_upsample2x_concat_act_nhwc_*.
+                    # A model with a layer that none of the kernels takes stays the torch module (cast in half), with a warning
                     from tiatoolbox_amd.models.architecture.hovernet_fused import set_conv_algo
+                    from tiatoolbox_amd.models.architecture.unet_fused import (FusedPlainUNet, FusedUNet, UnsupportedLayerError,
+                                                                               library_convolutions)
 
-                    set_conv_algo(m, algo)
+                    fused_cls = FusedUNet if hasattr(m.backbone, "layer1") else FusedPlainUNet
+                    try:
+                        m = fused_cls(m.to(device=self.device))
+                    except UnsupportedLayerError as exc:  # (the constructors' own refusal; any other error is a bug and propagates)
+                        logger.warning("%s: %s  Running the torch module in %s instead: its convolutions are library (MIOpen) "
+                                       "convolutions.", type(self.model).__name__, exc, dtype)
+                    else:
+                        set_conv_algo(m, algo)
+                        # FusedUNet builds around a layer off the kernels' shapes: in float32 that layer alone goes to the library
+                        # -- never silently; in half `prepare` below refuses it with its own message
+                        library = library_convolutions(m) if dtype == torch.float32 else []
+                        if library:
+                            logger.warning("%s: no hand-written kernel for the convolution(s) %s of the fused graph: they run as "
+                                           "library (MIOpen) convolutions.", type(self.model).__name__, ", ".join(library))
             m = m.to(device=self.device)
             if on_gpu:  # hand-written trunks pack their weights (and keep float32 biases) from the float32 parameters
                 for mod in m.modules():
                     if type(mod).__name__ == "MfmaResNet":
                         mod.set_conv_algo(algo)  # run kwarg `conv_algo="winograd"`: opt-in float32 Winograd for the 3x3 / stride-1 layers
                         mod.prepare(dtype)
-                    elif type(mod).__name__ in ("FusedUNet", "FusedHoVerNet") and dtype != torch.float32:
+                    elif type(mod).__name__ in ("FusedUNet", "FusedPlainUNet", "FusedHoVerNet") and dtype != torch.float32:
                         mod.prepare(dtype)  # half weights from the float32 BN-folded ones; float32 biases / BN affines kept aside
             m = m.to(dtype=dtype) if dtype != torch.float32 else m
             if on_gpu:
@@ -493,10 +507,10 @@ class EngineABC:
 
     def _use_miopen_find(self) -> bool:
         """Only an explicit ``miopen_find=True`` switches the library's solver search on.  The float32 inference copies (ResNet
-        classifiers, ``FusedHoVerNet``, ``FusedUNet``) launch no library convolution at all since round 3; the switch matters
-        for what still runs as a plain torch module (the plain-encoder / concat-skip UNet in half precision, user-supplied
-        architectures), where MIOpen's immediate mode can pick a naive NHWC kernel.  (HoVer-Net and the ResNet-50 UNet in fp16 /
-        bf16 are ``FusedHoVerNet`` / ``FusedUNet`` too and launch no library convolution.)"""
+        classifiers, ``FusedHoVerNet``, ``FusedUNet``, ``FusedPlainUNet``) launch no library convolution at all; the switch matters
+        for what still runs as a plain torch module (a UNet with a layer that no kernel takes -- the engine warns when it builds
+        one --, user-supplied architectures), where MIOpen's immediate mode can pick a naive NHWC kernel.  (HoVer-Net and every
+        UNet the fused classes accept are the same classes in fp16 / bf16 and launch no library convolution there either.)"""
         return bool(getattr(self, "miopen_find", None))
 
     def invalidate_inference_cache(self) -> None:

@@ -387,6 +387,24 @@ int tia_canvas_finalize_f32(const float* d_row_a, const uint8_t* d_cnt_a, int64_
                             const uint8_t* d_cnt_b, int64_t ys_b, int64_t oh, int64_t width, int64_t c,
                             int64_t y_begin, int64_t y_end, float* d_probs, uint8_t* d_pred, void* stream);
 
+/*
+ * Patch predictions painted into a whole-slide map (PatchPredictor.merge_predictions; additive at version 6): for every map
+ * pixel (Y, X) of the h x w canvas, sum[Y,X,k] = the float32 sum of d_values[i,k] over the patches i whose rectangle
+ * d_rects[i] = (x0, y0, x1, y1) (map pixels, half-open, clipped to the canvas; x1 <= x0 or y1 <= y0 covers nothing) holds the
+ * pixel, added one at a time in ascending i -- `out[y0:y1, x0:x1] += values[i]` in a loop over i, bit for bit; count[Y,X] = the
+ * number of such patches; raw = float32(float64(sum) / (float64(count) + 1e-8)); label = 1 + the first maximum over k of
+ * sum[Y,X,:] where count > 0, else 0.  Gather by tiles, no atomics: the map is cut into tiles of tile_h x tile_w pixels (row-major,
+ * tiles_x = ceil(w / tile_w)); d_tile_items[d_tile_offsets[t] .. d_tile_offsets[t + 1]) lists every patch whose rectangle meets tile
+ * t, in ASCENDING order (the caller's contract; an item outside [0, n) is skipped).  Any of the four outputs may be NULL, not all.
+ *   d_rects [n,4] i32   d_values [n,c] f32   d_tile_offsets [tiles_y*tiles_x+1] i32   d_tile_items [d_tile_offsets[last]] i32
+ *   d_sum, d_raw [h,w,c] f32   d_count [h,w] i32   d_labels [h,w] u8 (label_bytes 1, c <= 254) or i32 (label_bytes 4)
+ * TIA_EINVAL: a null input or list pointer, all outputs NULL, n / c / h / w / tile_h / tile_w <= 0, label_bytes not 1 or 4, or
+ * label_bytes 1 with c > 254.  TIA_ESIZE: h * w >= 2^31, n >= 2^31, or 2^24 tiles or more.  Nothing is launched on an error.
+ */
+int tia_merge_patch_rects_f32(const int32_t* d_rects, const float* d_values, int64_t n, int64_t c, int64_t h, int64_t w,
+                              const int32_t* d_tile_offsets, const int32_t* d_tile_items, int64_t tile_h, int64_t tile_w,
+                              float* d_sum, float* d_raw, int32_t* d_count, void* d_labels, int32_t label_bytes, void* stream);
+
 
 /* =======================================================================================
  * Reinhard colour normalisation (tools/stainnorm.py:222-367): OpenCV 8-bit RGB<->Lab

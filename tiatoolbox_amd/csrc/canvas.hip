@@ -3,6 +3,10 @@
 // :1398-1534 (merge_vertical_chunkwise), patch_predictor.py:382-446 (argmax).
 // Gather formulation: one thread owns one canvas element and sums its (<= a few) contributing blocks in
 // the reference's order, so results are deterministic and bit-identical to the NumPy path -- no float atomics.
+// Also here: merge_patch_rects_kernel, the patch classifier's merge_predictions (models/engine/patch_predictor.py:merge_predictions
+// of the reference: `out[y0:y1, x0:x1] += p[i]` in a loop over patches, then a divide by the coverage count and an argmax): one
+// workgroup per map tile walks the tile's ascending list of patch rectangles, so every pixel adds its patches in patch order;
+// and the batched patch reads of the WSI engines (plain, area-resampled, bicubic) further down.
 #include <float.h>
 
 #include "common.hpp"
@@ -71,6 +75,75 @@ __global__ __launch_bounds__(CT) void finalize_kernel(const float* __restrict__ 
             }
         }
         pred[(size_t)y * width + x] = (uint8_t)best;
+    }
+}
+
+
+// ---- merge_predictions: per-patch class rows painted into a whole-slide map ---------------------------------------------
+// sum[Y, X, k] = the float32 sum of values[i, k] over the patches i whose map-space rectangle (x0, y0, x1, y1; half-open)
+// holds (Y, X), added one at a time in ascending i; count[Y, X] = how many.  A workgroup owns one tile_h x tile_w tile of the
+// map and walks the tile's list (every patch whose rectangle meets the tile, ascending: the order is the contract); the list
+// item, its rectangle and its row of values are the same for every lane of a wave, so they come through scalar loads and
+// the per-pixel work is a coverage test and up to kMergeChunk adds into registers.  More classes than kMergeChunk take further
+// passes over the list, the order within a class unchanged.  raw = float32(float64(sum) / (float64(count) + 1e-8)) (the
+// reference's divisor); label = 1 + the first maximum of the SUMS where count > 0 (one positive divisor per pixel: the argmax
+// of the exact quotient, whatever the quotient's rounding), 0 elsewhere.  A tile larger than the workgroup takes several
+// pixels per thread.  List items outside [0, n) are skipped, so a bad list cannot read outside `values`.
+constexpr int kMergeChunk = 16;
+
+template <typename L>
+__global__ __launch_bounds__(CT) void merge_patch_rects_kernel(const int* __restrict__ rects, const float* __restrict__ values, int n,
+                                                                int c, int h, int w, const int* __restrict__ tile_offsets,
+                                                                const int* __restrict__ tile_items, int tile_h, int tile_w,
+                                                                int tiles_x, float* __restrict__ sum, float* __restrict__ raw,
+                                                                int* __restrict__ count, L* __restrict__ labels) {
+    const int tile = (int)blockIdx.x;
+    const int ty = tile / tiles_x, tx = tile - ty * tiles_x;
+    const int y0 = ty * tile_h, x0 = tx * tile_w;
+    const int th = min(tile_h, h - y0), tw = min(tile_w, w - x0);
+    const int lb = tile_offsets[tile], le = tile_offsets[tile + 1];
+    for (int p = threadIdx.x; p < th * tw; p += CT) {
+        const int py = p / tw;
+        const int X = x0 + (p - py * tw), Y = y0 + py;
+        const size_t pix = (size_t)Y * w + X;
+        int best = 0, cnt = 0;
+        float bestv = 0.0f;
+        for (int c0 = 0; c0 < c; c0 += kMergeChunk) {
+            const int cc = min(kMergeChunk, c - c0);
+            float acc[kMergeChunk];
+#pragma unroll
+            for (int k = 0; k < kMergeChunk; ++k) acc[k] = 0.0f;
+            cnt = 0;
+            for (int j = lb; j < le; ++j) {
+                const int i = tile_items[j];
+                if ((unsigned)i >= (unsigned)n) continue;
+                const int* r = rects + (size_t)i * 4;
+                const bool in = X >= r[0] && X < r[2] && Y >= r[1] && Y < r[3];
+                const float* v = values + (size_t)i * c + c0;
+#pragma unroll
+                for (int k = 0; k < kMergeChunk; ++k) {
+                    if (k < cc) {
+                        const float s = acc[k] + v[k];
+                        acc[k] = in ? s : acc[k];
+                    }
+                }
+                cnt += in ? 1 : 0;
+            }
+            const double den = (double)cnt + 1e-8;
+#pragma unroll
+            for (int k = 0; k < kMergeChunk; ++k) {
+                if (k < cc) {
+                    if (sum) sum[pix * c + c0 + k] = acc[k];
+                    if (raw) raw[pix * c + c0 + k] = (float)((double)acc[k] / den);
+                    if ((c0 == 0 && k == 0) || acc[k] > bestv) {
+                        bestv = acc[k];
+                        best = c0 + k;
+                    }
+                }
+            }
+        }
+        if (count) count[pix] = cnt;
+        if (labels) labels[pix] = (L)(cnt > 0 ? best + 1 : 0);
     }
 }
 
@@ -548,6 +621,32 @@ extern "C" int tia_canvas_finalize_f32(const float* d_row_a, const uint8_t* d_cn
     if (nb > 16384) nb = 16384;
     hipLaunchKernelGGL(finalize_kernel, dim3((unsigned)nb), dim3(CT), 0, (hipStream_t)stream, d_row_a, d_cnt_a, (long)ys_a, d_row_b,
                        d_cnt_b, (long)ys_b, (int)oh, (int)width, (int)c, (long)y_begin, (long)y_end, d_probs, d_pred);
+    return hipGetLastError() == hipSuccess ? TIA_OK : TIA_ELAUNCH;
+}
+
+extern "C" int tia_merge_patch_rects_f32(const int32_t* d_rects, const float* d_values, int64_t n, int64_t c, int64_t h, int64_t w,
+                                         const int32_t* d_tile_offsets, const int32_t* d_tile_items, int64_t tile_h, int64_t tile_w,
+                                         float* d_sum, float* d_raw, int32_t* d_count, void* d_labels, int32_t label_bytes,
+                                         void* stream) {
+    if (!d_rects || !d_values || !d_tile_offsets || !d_tile_items) return TIA_EINVAL;
+    if (!d_sum && !d_raw && !d_count && !d_labels) return TIA_EINVAL;
+    if (n <= 0 || c <= 0 || h <= 0 || w <= 0 || tile_h <= 0 || tile_w <= 0) return TIA_EINVAL;
+    if ((label_bytes != 1 && label_bytes != 4) || (label_bytes == 1 && c > 254)) return TIA_EINVAL;
+    if (h > 0x7fffffffL || w > 0x7fffffffL || h * w > 0x7fffffffL || n > 0x7fffffffL || c > 0x7fffffffL) return TIA_ESIZE;
+    // a tile never reaches past the map (the tile counts do not change): pixels per tile <= h * w < 2^31
+    const long th = tile_h < h ? tile_h : h, tw = tile_w < w ? tile_w : w;
+    const long tiles_x = (w + tw - 1) / tw, tiles_y = (h + th - 1) / th;
+    if (tiles_x * tiles_y * tia::CT > 0xffffffffL) return TIA_ESIZE;  // (a launch holds fewer than 2^32 threads: tiles this small on a map this large)
+    hipStream_t st = (hipStream_t)stream;
+    if (label_bytes == 1) {
+        hipLaunchKernelGGL(tia::merge_patch_rects_kernel<uint8_t>, dim3((unsigned)(tiles_x * tiles_y)), dim3(tia::CT), 0, st, d_rects,
+                           d_values, (int)n, (int)c, (int)h, (int)w, d_tile_offsets, d_tile_items, (int)th, (int)tw, (int)tiles_x, d_sum,
+                           d_raw, d_count, (uint8_t*)d_labels);
+    } else {
+        hipLaunchKernelGGL(tia::merge_patch_rects_kernel<int32_t>, dim3((unsigned)(tiles_x * tiles_y)), dim3(tia::CT), 0, st, d_rects,
+                           d_values, (int)n, (int)c, (int)h, (int)w, d_tile_offsets, d_tile_items, (int)th, (int)tw, (int)tiles_x, d_sum,
+                           d_raw, d_count, (int32_t*)d_labels);
+    }
     return hipGetLastError() == hipSuccess ? TIA_OK : TIA_ELAUNCH;
 }
 

@@ -25,6 +25,9 @@ class DeepFeatureExtractor(PatchPredictor):
 
     def _update_run_params(self, images, **kwargs):
         kwargs["return_probabilities"] = True  # the features ARE the output (ref. :262-290 ignores the flag)
+        if kwargs.get("merge_predictions"):
+            msg = "merge_predictions merges class probabilities into a tissue-type map; feature vectors have no such map."
+            raise ValueError(msg)
         return super()._update_run_params(images, **kwargs)
 
     def post_process_patches(self, raw_predictions: dict, **_) -> dict:

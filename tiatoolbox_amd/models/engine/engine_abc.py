@@ -223,6 +223,26 @@ def iter_row_outputs(infer, row_sels: list[np.ndarray], batch_size: int):
         yield k, (row if is_tuple else row[0])
 
 
+def open_slide(image, *, as_mask: bool = False):
+    """In-memory slide: an ``ArrayWSIReader``, an ``H x W (x 3)`` array / tensor, or a ``.npy`` path.  File-format
+    readers (OpenSlide, TIFF, ...) are out of scope."""
+    from tiatoolbox_amd.wsicore import ArrayWSIReader
+
+    if isinstance(image, ArrayWSIReader):
+        return image
+    if isinstance(image, (str, Path)):
+        path = Path(image)
+        if path.suffix != ".npy":
+            msg = (f"cannot open `{path}`: whole-slide file formats are outside the accelerated hot path; pass an "
+                   "ArrayWSIReader, an array, or a .npy file.")
+            raise NotImplementedError(msg)
+        image = np.load(path)
+    kw = {"mpp": None, "power": None, "mode": "bool"} if as_mask else {}
+    if as_mask and not isinstance(image, torch.Tensor):
+        image = (np.asarray(image) > 0).astype(np.uint8)
+    return ArrayWSIReader(image, **kw)
+
+
 class EngineABC:
     """Abstract engine: model + ioconfig + ``run()`` (ref. :136-1885)."""
 
@@ -740,23 +760,8 @@ class EngineABC:
 
     # ------------------------------------------------------------------------------ WSI mode
     def _open_slide(self, image, *, as_mask: bool = False):
-        """In-memory slide: an ``ArrayWSIReader``, an ``H x W (x 3)`` array / tensor, or a ``.npy`` path.  File-format
-        readers (OpenSlide, TIFF, ...) are out of scope."""
-        from tiatoolbox_amd.wsicore import ArrayWSIReader
-
-        if isinstance(image, ArrayWSIReader):
-            return image
-        if isinstance(image, (str, Path)):
-            path = Path(image)
-            if path.suffix != ".npy":
-                msg = (f"cannot open `{path}`: whole-slide file formats are outside the accelerated hot path; pass an "
-                       "ArrayWSIReader, an array, or a .npy file.")
-                raise NotImplementedError(msg)
-            image = np.load(path)
-        kw = {"mpp": None, "power": None, "mode": "bool"} if as_mask else {}
-        if as_mask and not isinstance(image, torch.Tensor):
-            image = (np.asarray(image) > 0).astype(np.uint8)
-        return ArrayWSIReader(image, **kw)
+        """:func:`open_slide`."""
+        return open_slide(image, as_mask=as_mask)
 
     @staticmethod
     def _check_read_resolution(reader, ioconfig) -> None:
@@ -858,6 +863,11 @@ class EngineABC:
             local = tdist.all_gather_rows(local.to(dev), n)
         return {"probabilities": local, "coordinates": coords}
 
+    def post_process_wsi(self, processed: dict, *, base, reader) -> dict:  # noqa: ARG002
+        """Slide-level step of WSI mode after ``post_process_patches``: ``base`` is the slide as opened, ``reader`` the reader
+        the patch grid was made on (``base`` or its view at the input resolution).  Nothing by default."""
+        return processed
+
     def _run_wsi_mode(self, save_dir, **kwargs) -> dict:
         """Per slide: tissue mask -> patch grid -> ``infer_wsi`` -> ``post_process_patches`` -> ``<stem>.npz`` under
         ``save_dir`` (ref. ``_run_wsi_mode`` :1540-1682; arrays ``predictions``, ``coordinates`` and, on request,
@@ -879,6 +889,7 @@ class EngineABC:
             coords = self.get_wsi_coordinates(reader, mask_reader, min_mask_ratio=float(kwargs.get("min_mask_ratio", 0.0)))
             raw = self.infer_wsi(reader, coords)
             processed = self.post_process_patches(raw_predictions=raw, **kwargs)
+            processed = self.post_process_wsi(processed, base=base, reader=reader)
             arrays = self.save_predictions(processed_predictions=processed, output_type="dict", **kwargs)
             key = image if isinstance(image, (str, Path)) else num
             stem = Path(image).stem if isinstance(image, (str, Path)) else str(num)

@@ -2,9 +2,13 @@
 
 from __future__ import annotations
 
+from pathlib import Path
+
+import numpy as np
 import torch
 
-from tiatoolbox_amd.models.engine.engine_abc import EngineABC
+from tiatoolbox_amd.models.engine import _patch_merge
+from tiatoolbox_amd.models.engine.engine_abc import EngineABC, open_slide
 from tiatoolbox_amd.utils.misc import cast_to_min_dtype
 
 
@@ -14,6 +18,13 @@ class PatchPredictor(EngineABC):
     Extra run-time kwargs on MI355X: ``compute_dtype`` ("float32" | "float16" | "bfloat16") and
     ``stain_normalizer`` (a fitted :class:`~tiatoolbox_amd.tools.stainnorm.StainNormalizer`; shorthand
     for ``model.preproc_func = StainNormPreproc(normalizer, default_preproc)``).
+
+    WSI mode (``patch_mode=False``) also takes ``merge_predictions=True`` with ``merge_resolution`` (default 1.25) and
+    ``merge_units`` (default ``"power"``): every slide's ``.npz`` then also holds ``merged_predictions``, the tissue-type map of
+    :meth:`merge_predictions` at that resolution, and -- with ``return_probabilities=True`` -- ``merged_probabilities``, its raw
+    map.  The per-patch probabilities are merged where ``infer_wsi`` left them, in HBM.  The three options are decided per
+    call, like ``return_probabilities``; without the flag the files hold ``predictions``, ``coordinates`` and, on request,
+    ``probabilities`` only.
     """
 
     def __init__(self, model, batch_size: int = 8, num_workers: int = 0, weights=None, *,
@@ -27,6 +38,10 @@ class PatchPredictor(EngineABC):
     def _update_run_params(self, images, **kwargs):
         """ref. :448-549: ``probabilities`` are dropped unless THIS call passes ``return_probabilities=True`` (ref. :535-537:
         ``kwargs.get("return_probabilities")`` -- per call, not sticky)."""
+        # the merge options are this call's alone and never become attributes (``self.merge_predictions`` is the static method)
+        self._merge_on = bool(kwargs.pop("merge_predictions", False))
+        self._merge_resolution = kwargs.pop("merge_resolution", 1.25)
+        self._merge_units = kwargs.pop("merge_units", "power")
         out = super()._update_run_params(images, **kwargs)
         if not self.return_probabilities:
             self.drop_keys.append("probabilities")
@@ -52,3 +67,103 @@ class PatchPredictor(EngineABC):
         else:
             raw_predictions["predictions"] = cast_to_min_dtype(predictions)
         return raw_predictions
+
+    def post_process_wsi(self, processed: dict, *, base, reader) -> dict:
+        """``merge_predictions=True``: the slide's patch rows merged into ``merged_predictions`` (and ``merged_probabilities``
+        with ``return_probabilities``) at ``merge_resolution`` / ``merge_units``.  The patch space is that of ``reader``, the
+        reader the grid was made on; the canvas is the slide ``base`` at the merge resolution.  Under ``torch.distributed``
+        every rank holds all rows after the all-gather and merges them; rank 0 writes."""
+        if not getattr(self, "_merge_on", False):
+            return processed
+        from tiatoolbox_amd.wsicore import _resolution_ratio
+
+        ratio = _resolution_ratio(self._merge_resolution, self._merge_units, base.mpp, base.power)
+        canvas_wh = _patch_merge.canvas_size(base.slide_dimensions, ratio)
+        merged = _merge_output(processed, reader.slide_dimensions, canvas_wh, want_raw=bool(self.return_probabilities))
+        processed["merged_predictions"] = merged["labels"]
+        if self.return_probabilities:
+            processed["merged_probabilities"] = merged["raw"]
+        return processed
+
+    @staticmethod
+    def merge_predictions(img, output, resolution: float = 1.25, units: str = "power", postproc_func=None,
+                          return_raw: bool = False):  # noqa: FBT001, FBT002  (the reference's signature)
+        """Merge the per-patch results of a WSI-mode run into a 2-D tissue-type map of the slide at ``(resolution, units)``
+        (the reference's ``PatchPredictor.merge_predictions``).
+
+        ``img``: the slide -- an ``ArrayWSIReader`` / ``VirtualWSIReader``, an array / tensor or a ``.npy`` path, as ``run()``
+        takes them.  ``output``: a ``dict`` or the path of a WSI-mode ``.npz`` with ``coordinates`` ``[N, 4]`` and
+        ``probabilities`` ``[N, C]`` and / or ``predictions`` ``[N]``, plus ``resolution`` and ``units``: the resolution the
+        patches were read at (their coordinates' pixel space), which the files do not record themselves.
+
+        Canvas and patch space measure ``np.round(slide_dimensions / s)`` pixels, ``s`` the down-sampling ratio from the slide's
+        baseline (any positive ratio, up-sampling included).  Patch ``i`` covers the map rectangle ``ceil((x0, x1) * fx)`` x
+        ``ceil((y0, y1) * fy)`` clipped to the canvas, ``fx = W / Ws``, ``fy = H / Hs`` (the reference multiplies the (x, y)
+        bounds by a (y, x) factor; the two differ on non-proportional canvases only, and this method uses ``fx`` for x and
+        ``fy`` for y).  Overlapping patches are averaged: the probabilities are summed in float32 in patch order and divided by
+        the coverage count (``+ 1e-8``, in float64).
+
+        Returns ``[H, W]`` labels: ``1 + argmax`` of the summed probabilities where a patch covers the pixel, 0 elsewhere
+        (``uint8`` up to 254 classes, else ``int32``).  ``postproc_func`` replaces the argmax: it gets the raw map ``[H, W, C]``
+        (a tensor or an array, as ``probabilities`` is) and returns ``[H, W]`` integers; 1 is added where a patch covers the pixel.
+        ``return_raw=True`` returns the raw ``[H, W, C]`` float32 map instead (0 where nothing covers).  Without
+        ``probabilities`` the map is the float32 sum of ``predictions + 1`` over the covering patches -- overlapping patches ADD,
+        as in the reference, so pass probabilities for overlapping strides -- and ``return_raw=True`` is a ``ValueError``.
+        CUDA probabilities are merged on their device by ``tia_merge_patch_rects_f32``; the result is of their kind."""
+        if isinstance(output, (str, Path)):
+            with np.load(output) as data:
+                output = {k: data[k] for k in data.files}
+        missing = [k for k in ("resolution", "units") if k not in output]
+        if missing:
+            msg = (f"`output` lacks {missing}: merge_predictions needs output['resolution'] and output['units'], the resolution "
+                   "the patch coordinates are in (ioconfig.input_resolutions[0]).")
+            raise ValueError(msg)
+        if "coordinates" not in output or not ("probabilities" in output or "predictions" in output):
+            msg = "`output` needs 'coordinates' and 'probabilities' and / or 'predictions'."
+            raise ValueError(msg)
+        from tiatoolbox_amd.wsicore import _resolution_ratio
+
+        reader = img if hasattr(img, "slide_dimensions") else open_slide(img)
+        dims = reader.slide_dimensions
+        patch_units = output["units"]
+        patch_units = patch_units.item() if isinstance(patch_units, np.ndarray) else patch_units
+        patch_wh = _patch_merge.canvas_size(dims, _resolution_ratio(float(np.asarray(output["resolution"])), str(patch_units),
+                                                                    reader.mpp, reader.power))
+        canvas_wh = _patch_merge.canvas_size(dims, _resolution_ratio(resolution, units, reader.mpp, reader.power))
+        if "probabilities" not in output and return_raw:
+            msg = "return_raw=True needs output['probabilities']; this output holds predictions only."
+            raise ValueError(msg)
+        merged = _merge_output(output, patch_wh, canvas_wh, want_raw=return_raw or postproc_func is not None,
+                               want_count=postproc_func is not None)
+        if "probabilities" not in output:
+            return merged["sum"][..., 0]
+        if return_raw:
+            return merged["raw"]
+        if postproc_func is None:
+            return merged["labels"]
+        labels, covered = postproc_func(merged["raw"]), merged["count"] > 0
+        if isinstance(labels, torch.Tensor):
+            return labels + covered.to(labels.dtype)
+        return np.asarray(labels) + np.asarray(covered.cpu() if isinstance(covered, torch.Tensor) else covered).astype(np.asarray(labels).dtype)
+
+
+def _merge_output(output: dict, patch_wh, canvas_wh, *, want_raw: bool = False, want_count: bool = False) -> dict:
+    """The outputs of :func:`_patch_merge.merge_patch_rects` for one slide's ``coordinates`` + ``probabilities`` (``labels``,
+    ``raw`` / ``count`` on request) or, without probabilities, ``predictions`` (``sum`` of ``predictions + 1``, one channel)."""
+    w, h = int(canvas_wh[0]), int(canvas_wh[1])
+    if min(w, h, int(patch_wh[0]), int(patch_wh[1])) <= 0:
+        msg = (f"the merged map ({w} x {h}) or the patch space ({patch_wh[0]} x {patch_wh[1]}) has a zero dimension at the "
+               "requested resolution.")
+        raise ValueError(msg)
+    rects = _patch_merge.patch_rects(output["coordinates"], patch_wh, (h, w))
+    if "probabilities" in output:
+        values = output["probabilities"]
+        values = values if isinstance(values, torch.Tensor) else np.asarray(values, dtype=np.float32)
+        want = ("labels", *(("raw",) if want_raw else ()), *(("count",) if want_count else ()))
+        return _patch_merge.merge_patch_rects(rects, values.reshape(len(rects), -1), (h, w), want=want)
+    preds = output["predictions"]
+    if isinstance(preds, torch.Tensor):
+        values = (preds.reshape(-1, 1) + 1).to(torch.float32)
+    else:
+        values = (np.asarray(preds).reshape(-1, 1).astype(np.int64) + 1).astype(np.float32)
+    return _patch_merge.merge_patch_rects(rects, values, (h, w), want=("sum",))

@@ -651,6 +651,31 @@ int tia_conv3x3_wino_form(int64_t n, int64_t h, int64_t w, int64_t cin, int64_t 
 int tia_conv2d_route_f32(int64_t n, int64_t h, int64_t w, int64_t cin, int64_t cout, int64_t kh, int64_t kw, int64_t stride,
                          int64_t pad_top, int64_t pad_left, int64_t ho, int64_t wo);
 
+/* kh x kw float32 convolution on the BF16 matrix cores with BOTH operands split into three bf16 numbers (additive at version 6):
+ * float32 in, float32 accumulate -- the arithmetic class of tia_conv2d_nhwc_f32 in another summation order.  a = hi + mid + lo
+ * and w = hi + mid + lo exactly (round to nearest), every bf16 x bf16 product is exact in the float32 accumulator, and six of
+ * the nine products (all but mid * lo, lo * mid, lo * lo: below 2^-23 |a w|) are accumulated per 16-channel step in the order
+ * lo * hi, hi * lo, mid * mid, mid * hi, hi * mid, hi * hi (activation part x weight part).  The activations are split by the
+ * kernel, the weights by the caller:
+ *   tia_conv_pack_weights_bf16x3: d_parts_oihw [3][cout][cin][kh][kw] float32 holding hi, mid, lo -- the contract is that every
+ *     part is a bf16 number (low 16 bits zero), that hi + mid + lo == w exactly and that every non-zero part is finite and
+ *     normal (fused.split_stem_weights checks it) -> d_packed [kh][kw][cin/16][cout/128][3][2][128][8] bf16 (plane, 8-channel
+ *     k-chunk, column, channel): cin % 16 == 0, cout % 128 == 0 (TIA_ESIZE otherwise).
+ *   tia_conv2d_bf16x3_nhwc_f32: the arguments, checks and return codes of tia_conv2d_nhwc_f32 with cin % 16 == 0 and
+ *     cout % 128 == 0, padding (pad_top, pad_left) on both sides, every pointer 16-byte aligned; batches beyond 2 GiB of input run
+ *     in equal groups.  It runs at ANY batch size: routing is the caller's decision.  Non-finite activations, and activations
+ *     with |a| >= 2^127 (2 - 2^-8) = 3.3961e38 (bf16(a) is infinite), make every output that reads them non-finite; parts below 2^-126 may be flushed to zero.
+ *   tia_conv2d_bf16x3_serves (host only, no device needed): 1 where the engines' conv_algo="auto" takes this kernel -- the shape
+ *     is one tia_conv2d_route_f32 puts on the LDS-DMA ring (2) AND its layer class measured faster than the float32 ring kernel
+ *     (stride 2 and kh * kw * cin >= 64: DESIGN 4.27); 0 otherwise, and 0 under the developer switch TIA_CONV_NO_SPLIT (with TIA_DEV=1). */
+int tia_conv_pack_weights_bf16x3(const float* d_parts_oihw, int64_t cout, int64_t cin, int64_t kh, int64_t kw, void* d_packed,
+                                 void* stream);
+int tia_conv2d_bf16x3_nhwc_f32(const float* d_x, const void* d_w_packed3, const float* d_bias, const float* d_residual, float* d_y,
+                               int64_t n, int64_t h, int64_t w, int64_t cin, int64_t cout, int64_t kh, int64_t kw, int64_t stride,
+                               int64_t pad_top, int64_t pad_left, int32_t relu, void* stream);
+int tia_conv2d_bf16x3_serves(int64_t n, int64_t h, int64_t w, int64_t cin, int64_t cout, int64_t kh, int64_t kw, int64_t stride,
+                             int64_t pad_top, int64_t pad_left, int64_t ho, int64_t wo);
+
 /* 1x1 convolution (any stride, no padding) whose INPUT is activated on load:
  *   y = act(conv1x1(relu(x * pre_scale[c] + pre_shift[c]), w) + bias [+ residual])
  * -- the "preact/bn" + ReLU in front of conv1 of HoVer-Net's residual units 2..n (models/architecture/hovernet.py:100-147),

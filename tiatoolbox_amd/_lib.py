@@ -115,6 +115,9 @@ _SIGNATURES = {
     "tia_conv2d_post_nhwc_f32": ([_P, _P, _P, _P, _P, _I64, _I64, _I64, _I64, _I64, _I64, _I64, _I64, _I64, _I64, _I64, _I64, _I32,
                                   _P, _P, _P, _P], C.c_int),
     "tia_conv2d_route_f32": ([_I64] * 12, C.c_int),
+    "tia_conv_pack_weights_bf16x3": ([_P, _I64, _I64, _I64, _I64, _P, _P], C.c_int),
+    "tia_conv2d_bf16x3_nhwc_f32": ([_P, _P, _P, _P, _P] + [_I64] * 10 + [_I32, _P], C.c_int),
+    "tia_conv2d_bf16x3_serves": ([_I64] * 12, C.c_int),
     "tia_conv_pack_weights_wino_f32": ([_P, _I64, _I64, _P, _P], C.c_int),
     "tia_conv3x3_wino_nhwc_f32": ([_P, _P, _P, _P, _P] + [_I64] * 9 + [_I32, _P], C.c_int),
     "tia_conv3x3_wino_geometry": ([_I64] * 3 + [C.POINTER(C.c_int32)], C.c_int),

@@ -714,7 +714,9 @@ class _MfmaBlock(nn.Module):
     """Shared machinery of the hand-written blocks: per-convolution packed weights (float32: ``[kh, kw, cin, cout]``; fp16 /
     bf16: ``[kh, kw, cin/8, cout, 8]``), float32 biases, and one launch per convolution with its epilogue fused."""
 
-    conv_algo = "direct"  # "winograd": float32 3x3 / stride-1 layers through tia_conv3x3_wino_nhwc_f32 (MfmaResNet.set_conv_algo)
+    # "winograd": float32 3x3 / stride-1 layers through tia_conv3x3_wino_nhwc_f32, large stride-2 launches through
+    # tia_conv2d_bf16x3_nhwc_f32 (MfmaResNet.set_conv_algo)
+    conv_algo = "direct"
 
     def __init__(self) -> None:
         super().__init__()
@@ -751,6 +753,23 @@ class _MfmaBlock(nn.Module):
             self._packed[(name, dtype)] = cached
         return cached
 
+    def _split(self, name: str, x: torch.Tensor | None = None) -> torch.Tensor | None:
+        """The layer's three-plane bf16 weights if it is to run on the split-operand kernel (``conv_algo="winograd"``, i.e. the engines'
+        ``"auto"``; float32, ``groups == 1``, square kernel and stride, symmetric padding, cin % 16, cout % 128, a usable exact split)
+        and, for an input ``x``, the route query :func:`conv_split_serves` takes it; ``None`` otherwise."""
+        conv = getattr(self, name)
+        if (self.conv_algo != "winograd" or conv.groups != 1 or conv.dilation != (1, 1) or conv.in_channels % 16 or conv.out_channels % 128
+                or conv.kernel_size[0] != conv.kernel_size[1] or conv.stride[0] != conv.stride[1] or conv.padding[0] != conv.padding[1]
+                or conv.padding[0] >= conv.kernel_size[0] or conv.kernel_size[0] > 16 or conv.padding_mode != "zeros"):  # noqa: PLR2004
+            return None
+        if x is not None and not conv_split_serves(x.shape[0], x.shape[2], x.shape[3], conv.in_channels, conv.out_channels,
+                                                   conv.kernel_size[0], conv.stride[0], conv.padding[0]):
+            return None
+        key = (name, "split")
+        if key not in self._packed or (self._packed[key] is not None and self._packed[key].device != conv.weight.device):
+            self._packed[key] = pack_conv_weights_split(conv)  # None: no usable split (remembered: asked once per device)
+        return self._packed[key]
+
     def _b(self, name: str) -> torch.Tensor | None:
         conv = getattr(self, name)
         if conv.bias is None:
@@ -771,8 +790,10 @@ class _MfmaBlock(nn.Module):
             if conv is None:
                 continue
             self._w(name, dtype)
-            if dtype == torch.float32:
-                self._wino(name)
+            if dtype == torch.float32 and self._wino(name) is None:
+                # the split-operand kernel's weights, if conv_algo is already "winograd" (the engines set it before they prepare);
+                # otherwise, as with _wino, the layer packs them in its first forward after set_conv_algo
+                self._split(name)
             if conv.bias is not None:
                 self._bias32[name] = conv.bias.detach().float().clone().contiguous()
 
@@ -791,6 +812,9 @@ class _MfmaBlock(nn.Module):
             u = self._wino(name, x)
             if u is not None:
                 return hip_conv3x3_wino(x, u, self._b(name), residual, padding=pad, relu=relu)
+            w3 = self._split(name, x)
+            if w3 is not None:
+                return hip_conv2d_split(x, w3, self._b(name), residual, kernel=k, stride=st, padding=pad, relu=relu)
             return hip_conv2d(x, self._w(name, x.dtype), self._b(name), residual, kernel=k, stride=st, padding=pad, relu=relu)
         return hip_conv2d_h(x, self._w(name, x.dtype), self._b(name), residual, cout=conv.out_channels, kernel=k, stride=st,
                             padding=pad, relu=relu)
@@ -977,6 +1001,67 @@ def hip_stem_conv_pool_split(x: torch.Tensor, w_packed3: torch.Tensor, bias: tor
         rc = _lib.load().tia_stem_conv7x7_pool_nhwc_u8x3(x.data_ptr(), w_packed3.data_ptr(), bias.data_ptr(), y.data_ptr(), n, h, w,
                                                          _lib.current_stream())
     _lib.check(rc, "tia_stem_conv7x7_pool_nhwc_u8x3")
+    return y
+
+
+def pack_conv_weights_split(conv: nn.Conv2d) -> torch.Tensor | None:
+    """OIHW float32 -> ``[kh, kw, cin/16, cout/128, 3, 2, 128, 8]`` bf16: the planes ``hi``, ``mid``, ``lo`` of
+    :func:`split_stem_weights` in the stage layout of ``tia_conv2d_bf16x3_nhwc_f32`` (``tia_conv_pack_weights_bf16x3``).  ``None``
+    when the weights have no usable exact split (one ``info`` line): the layer then keeps the float32 kernel."""
+    from tiatoolbox_amd import _lib
+
+    w = conv.weight.detach().to(torch.float32).contiguous()
+    cout, cin, kh, kw = w.shape
+    if cin % 16 or cout % 128 or conv.groups != 1:
+        msg = f"the split-operand kernel needs cin % 16 == 0, cout % 128 == 0 and groups == 1; got weight {tuple(w.shape)}."
+        raise ValueError(msg)
+    parts, usable = split_stem_weights(w)
+    if not usable:
+        logger.info("a %s convolution's weights have no exact three-part bf16 split (non-finite or extreme exponents); the "
+                    "layer keeps the float32 kernel.", tuple(w.shape))
+        return None
+    parts = parts.contiguous()
+    out = torch.empty((kh, kw, cin // 16, cout // 128, 3, 2, 128, 8), dtype=torch.bfloat16, device=w.device)
+    with torch.cuda.device(w.device):
+        rc = _lib.load().tia_conv_pack_weights_bf16x3(parts.data_ptr(), cout, cin, kh, kw, out.data_ptr(), _lib.current_stream())
+    _lib.check(rc, "tia_conv_pack_weights_bf16x3")
+    return out
+
+
+@functools.lru_cache(maxsize=256)
+def conv_split_serves(n: int, h: int, w: int, cin: int, cout: int, kernel: int, stride: int, padding: int) -> bool:
+    """Whether the fused resnet blocks run this symmetric-padded convolution on the split-operand kernel under ``conv_algo="auto"``
+    (``tia_conv2d_bf16x3_serves``, a host-only query)."""
+    from tiatoolbox_amd import _lib
+
+    ho, wo = (h + 2 * padding - kernel) // stride + 1, (w + 2 * padding - kernel) // stride + 1
+    return _lib.load().tia_conv2d_bf16x3_serves(n, h, w, cin, cout, kernel, kernel, stride, padding, padding, ho, wo) == 1
+
+
+def hip_conv2d_split(x: torch.Tensor, w_packed3: torch.Tensor, bias: torch.Tensor | None, residual: torch.Tensor | None, *,
+                     kernel: int, stride: int, padding: int, relu: bool) -> torch.Tensor:
+    """``relu(conv2d(x, w) + bias + residual)`` on a float32 channels-last CUDA tensor on the bf16 matrix cores with both operands
+    split into three bf16 numbers (``tia_conv2d_bf16x3_nhwc_f32``; weights from :func:`pack_conv_weights_split`): float32 in,
+    float32 accumulate, another summation order than :func:`hip_conv2d`."""
+    from tiatoolbox_amd import _lib
+
+    if not (_nhwc_ptr_ok(x) and x.dtype == torch.float32):
+        msg = "hip_conv2d_split expects a float32 channels-last CUDA tensor."
+        raise ValueError(msg)
+    n, cin, h, w = x.shape
+    if (w_packed3.dim() != 8 or w_packed3.dtype != torch.bfloat16 or not w_packed3.is_contiguous() or w_packed3.device != x.device  # noqa: PLR2004
+            or tuple(w_packed3.shape) != (kernel, kernel, cin // 16, w_packed3.shape[3], 3, 2, 128, 8) or cin % 16):
+        msg = (f"hip_conv2d_split: weights {tuple(w_packed3.shape)} {w_packed3.dtype} on {w_packed3.device} are not "
+               f"pack_conv_weights_split's [k, k, cin/16, cout/128, 3, 2, 128, 8] bf16 for a {kernel}x{kernel} kernel over {cin} channels on {x.device}.")
+        raise ValueError(msg)
+    cout = w_packed3.shape[3] * 128
+    shape = _conv_out_shape("hip_conv2d_split", x, cout, residual, kernel=kernel, stride=stride, pad_lo=padding, pad_hi=padding)
+    y = torch.empty(shape, dtype=torch.float32, device=x.device, memory_format=torch.channels_last)
+    with torch.cuda.device(x.device):
+        rc = _lib.load().tia_conv2d_bf16x3_nhwc_f32(x.data_ptr(), w_packed3.data_ptr(), _ptr(bias), _ptr(residual), y.data_ptr(), n, h, w,
+                                                    cin, cout, kernel, kernel, stride, padding, padding, int(relu),
+                                                    _lib.current_stream())
+    _lib.check(rc, "tia_conv2d_bf16x3_nhwc_f32")
     return y
 
 

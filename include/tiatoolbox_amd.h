@@ -738,7 +738,11 @@ int tia_stem_conv7x7_pool_nhwc_u8x3(const uint8_t* d_x, const void* d_w_packed3,
  * tests/engines/test_patch_predictor.py:712-722): implicit GEMM on v_mfma_f32_32x32x16_f16 / _bf16, float32 accumulate;
  * bias + residual + ReLU in float32, ONE rounding to half on the way out.
  *   d_x [n,h,w,cin] half   d_w_packed from tia_conv_pack_weights_h   d_bias [cout] float32 or NULL
- *   d_residual [n,ho,wo,cout] half or NULL   d_y [n,ho,wo,cout] half.   cin % 32 == 0, cout % 64 == 0, 16-byte aligned. */
+ *   d_residual [n,ho,wo,cout] half or NULL   d_y [n,ho,wo,cout] half.   cin % 32 == 0, cout % 64 == 0, 16-byte aligned.
+ * Argument codes: null pointers, a dtype that is not a half type and scale / shift without d_y2 are TIA_EINVAL; then the shape
+ * checks of tia_conv2d_nhwc_f32 in its order -- a non-positive size (cin and cout included), stride or a negative pad TIA_EINVAL,
+ * channel multiples TIA_ESIZE, kernel size / padding TIA_EINVAL, output range TIA_EINVAL -- then misaligned pointers TIA_EINVAL,
+ * then an image or weight tensor beyond 2 GiB TIA_ESIZE.  Where two faults coincide the first in this order is reported. */
 int tia_conv2d_nhwc_h(const void* d_x, const void* d_w_packed, const float* d_bias, const void* d_residual, void* d_y,
                       int64_t n, int64_t h, int64_t w, int64_t cin, int64_t cout, int64_t kh, int64_t kw, int64_t stride,
                       int64_t pad, int32_t dtype, int32_t relu, void* stream);

@@ -214,3 +214,23 @@ def test_host_only_dispatch_queries():
         assert lib.tia_stain_stats_path(256, 256, ctypes.byref(prm)) == 0     # the audit modes keep the streaming kernel
     assert lib.tia_stain_stats_path(0, 5, ctypes.byref(prm)) == -1            # TIA_EINVAL
     assert lib.tia_clear_last_error() in (0, 3, 100, 101)                      # callable without a device (no device: hipErrorNoDevice)
+
+
+def test_half_conv_entries_reject_empty_channel_counts():
+    """``tia_conv2d_nhwc_h`` / ``tia_conv2d_nhwc_h_ex`` answer ``cin = 0`` and ``cout = 0`` with TIA_EINVAL from the shared shape
+    check -- on the host, before any HIP call, with nothing dereferenced (the pointers are made-up aligned addresses).  Before
+    the half entries took the float32 entry's check, ``cin = 0`` passed ``0 % 32 == 0`` and divided by an image size of zero
+    bytes: the process died of SIGFPE."""
+    import pytest
+
+    from tiatoolbox_amd import _lib, build
+
+    if not build.LIB_PATH.exists():
+        pytest.skip("library not built (run __graft_entry__.build())")
+    lib = _lib.load()
+    x, w, y = 0x10000, 0x20000, 0x30000  # non-null, 16-byte aligned, never read
+    f16, einval = 1, -1  # TIA_DT_F16, TIA_EINVAL
+    for cin, cout in ((0, 64), (32, 0)):
+        # n = 1, 8 x 8 map, 3x3, stride 1, pad 1 -> 8 x 8
+        assert lib.tia_conv2d_nhwc_h(x, w, None, None, y, 1, 8, 8, cin, cout, 3, 3, 1, 1, f16, 0, None) == einval
+        assert lib.tia_conv2d_nhwc_h_ex(x, w, None, None, y, 1, 8, 8, cin, cout, 3, 3, 1, 1, 1, 8, 8, f16, 0, None, None, None, None) == einval

@@ -151,9 +151,7 @@ __global__ __launch_bounds__(GEO::NT, GEO::NT == 512 ? 4 : 2) void conv3x3_spati
     long long tm_[4] = {0, 0, 0, 0}, tl_ = clock64();
     const long long t0c_ = tl_, t0w_ = wall_clock64();
 #endif
-    const int bid = blockIdx.x;
-    const int per_xcd = (m_tiles + 7) / 8;
-    const int mt_id = (bid % 8) * per_xcd + bid / 8;
+    const int mt_id = xcd_tile(blockIdx.x, m_tiles);
     if (mt_id >= m_tiles) return;
     // G16: block = (image, 16 x 16 tile); G8: block = images 2 mt_id, 2 mt_id + 1 (tiles_per_image = 1, tile origin 0)
     // band: block = (band of br virtual rows, strip); ty0 = first virtual output row
@@ -530,12 +528,6 @@ __global__ __launch_bounds__(GEO::NT, GEO::NT == 512 ? 4 : 2) void conv3x3_spati
 // slice) in the slice kernel's order, a slice's DMA address is the pixel's tap-(0, 0) offset plus a scalar tap delta, and a tap
 // outside the image is an out-of-range offset (the DMA writes zeros) chosen with one mask test per unit -- the implicit GEMM for
 // the layers the tap-reuse kernel does not serve (stride-2 3x3, maps 16 x 16 blocks cover badly), bit-identical to the slice kernel.
-struct PwDims {
-    int n, h, w, cin, cout, ho, wo, stride;
-    unsigned x_bytes, w_bytes;
-    int kh, kw, pad_y, pad_x;
-};
-
 template <int BN>
 __global__ __launch_bounds__(512, 4) void conv1x1_ring_kernel(const float* __restrict__ x, const float* __restrict__ wk,
                                                              const float* __restrict__ bias, const float* __restrict__ res,
@@ -551,9 +543,7 @@ __global__ __launch_bounds__(512, 4) void conv1x1_ring_kernel(const float* __res
     static_assert(2 * LDS_BYTES <= 160 * 1024, "two workgroups per CU");
     __shared__ __attribute__((aligned(16))) unsigned char smem[LDS_BYTES];
 
-    const int bid = blockIdx.x;
-    const int per_xcd = (m_tiles + 7) / 8;
-    const int mt_id = (bid % 8) * per_xcd + bid / 8;
+    const int mt_id = xcd_tile(blockIdx.x, m_tiles);
     if (mt_id >= m_tiles) return;
     const long m0 = (long)mt_id * 256;
     const long m_total = (long)d.n * d.ho * d.wo;
@@ -589,25 +579,18 @@ __global__ __launch_bounds__(512, 4) void conv1x1_ring_kernel(const float* __res
     const int n_cs = d.cin >> 4;
     const int n_slices = d.kh * d.kw * n_cs;
 
-    // slice cursor (scalar): tap (s_kh, s_kw), channel slice s_cs of the slice that is requested next
-    int s_kh = 0, s_kw = 0, s_cs = 0;
+    // slice cursor: s.c counts 16-channel slices; past the last slice the idle stage is refilled with the same slice
+    SliceCursor s;
     auto dma_stage = [&](int stage) {
         unsigned char* sa = smem + stage * STAGE;
-        const int sdelta = (s_kh * d.w + s_kw) * d.cin * 4;
-        const unsigned sel = (1u << s_kh) | (1u << (16 + s_kw));
+        const int sdelta = (s.kh * d.w + s.kw) * d.cin * 4;
+        const unsigned sel = (1u << s.kh) | (1u << (16 + s.kw));
 #pragma unroll
         for (int r = 0; r < 3; ++r) {
             unsigned char* dst = (NT * r + wave * 64 >= A_UNITS) ? smem + DUMP : sa + r * (NT * 16) + wave * 1024;
-            dma16(rx, dst, (msk[r] & sel) == sel ? cen[r] + sdelta : OOB, s_cs * 64);
+            dma16(rx, dst, (msk[r] & sel) == sel ? cen[r] + sdelta : OOB, s.c * 64);
         }
-        dma16(rw, sa + A_BYTES + wave * 1024, b_off, (((s_kh * d.kw + s_kw) * d.cin) + s_cs * 16) * d.cout * 4);
-    };
-    // past the last slice the cursor stays there: the idle stage is refilled with the same slice
-    auto next_slice = [&]() {
-        int cs = s_cs + 1, kw = s_kw, kh = s_kh;
-        if (cs == n_cs) { cs = 0; ++kw; }
-        if (kw == d.kw) { kw = 0; ++kh; }
-        if (kh < d.kh) { s_cs = cs; s_kw = kw; s_kh = kh; }
+        dma16(rw, sa + A_BYTES + wave * 1024, b_off, (((s.kh * d.kw + s.kw) * d.cin) + s.c * 16) * d.cout * 4);
     };
 
     f32x16 acc[2][NTILE];
@@ -627,7 +610,7 @@ __global__ __launch_bounds__(512, 4) void conv1x1_ring_kernel(const float* __res
     __builtin_amdgcn_s_barrier();
     for (int it = 0; it < n_slices; ++it) {
         const int stage = it & 1;
-        next_slice();
+        s.next(1, n_cs, d.kh, d.kw);
         dma_stage(stage ^ 1);
         const u32x4* sa = reinterpret_cast<const u32x4*>(smem + stage * STAGE) + fa0;
         const float* sb = reinterpret_cast<const float*>(smem + stage * STAGE + A_BYTES) + fb0;

@@ -151,19 +151,19 @@ __global__ __launch_bounds__(512, 2) void conv3x3_wino_kernel(const float* __res
 #endif
 
     const int bid = blockIdx.x;
-    const int per_xcd = (m_tiles + 7) / 8;
+    const int xcd_tiles = xcd_share(m_tiles);
     const int n_cs = d.cin >> 4, n_cb = d.cout >> 6;
     // an ITEM = (pixel block mt_id, channel tile cb).  One block per workgroup: the grid is the item list.  PERSIST: workgroup q of XCD x
     // (consecutive workgroup ids go round the XCDs) takes items q, q + Q, .. of the XCD's contiguous range of pixel blocks, channel tile
     // fastest -- the workgroups of an XCD that run at the same time share patches (one HBM read, then L2 hits).
     int item = 0, item_end = 1, item_step = 1, mt_lo = 0;
     if constexpr (PERSIST) {
-        mt_lo = (bid & 7) * per_xcd;
-        const int mt_hi = mt_lo + per_xcd < m_tiles ? mt_lo + per_xcd : m_tiles;
+        mt_lo = (bid & 7) * xcd_tiles;
+        const int mt_hi = mt_lo + xcd_tiles < m_tiles ? mt_lo + xcd_tiles : m_tiles;
         item = bid >> 3, item_step = (int)(gridDim.x >> 3), item_end = (mt_hi - mt_lo) * n_cb;
         if (item >= item_end) return;
     } else {
-        if ((bid % 8) * per_xcd + bid / 8 >= m_tiles) return;  // every XCD walks a contiguous range of pixel blocks
+        if (xcd_tile(bid, m_tiles) >= m_tiles) return;  // every XCD walks a contiguous range of pixel blocks
     }
     int mt_id, cb, img, ty0, tx0;
     auto decode = [&](int it) {  // (wave-uniform: scalar registers)
@@ -171,7 +171,7 @@ __global__ __launch_bounds__(512, 2) void conv3x3_wino_kernel(const float* __res
             const int q = it / n_cb;
             mt_id = mt_lo + q, cb = it - q * n_cb;
         } else {
-            mt_id = (bid % 8) * per_xcd + bid / 8, cb = (int)blockIdx.y;
+            mt_id = xcd_tile(bid, m_tiles), cb = (int)blockIdx.y;
         }
         img = RT ? 0 : (GEO::G == 1 ? mt_id / tiles_per_image : mt_id * GEO::G);  // (WR: windows carry their own image)
         const int trem = GEO::G == 1 ? mt_id - img * tiles_per_image : 0;

@@ -7,6 +7,7 @@
 
 #include "common.hpp"
 #include "conv_device.hpp"
+#include "conv_host.hpp"
 
 namespace tia {
 
@@ -32,12 +33,9 @@ inline int conv3x3_wino_run(int positions, decltype(&conv3x3_wino_launch) launch
     if (((reinterpret_cast<uintptr_t>(d_x) | reinterpret_cast<uintptr_t>(d_u_packed) | reinterpret_cast<uintptr_t>(d_y) |
           reinterpret_cast<uintptr_t>(d_residual) | reinterpret_cast<uintptr_t>(d_bias)) & 15) != 0)
         return TIA_EINVAL;
-    if (cin % 16 != 0 || cout % 64 != 0 || positions * cin * cout * 4 > 0x7fffffffL) return TIA_ESIZE;
-    // 32-bit byte offsets into the input: images go in groups of < 2 GiB (and < 2^31 / 4 output pixels)
-    const long image_bytes = h * w * cin * 4;
-    if (image_bytes > 0x7fffffffL || ho * wo > 0x7fffffffL / 4) return TIA_ESIZE;
-    long group = 0x7fffffffL / image_bytes;
-    if (group * ho * wo > 0x7fffffffL / 2) group = 0x7fffffffL / 2 / (ho * wo);
+    if (cin % 16 != 0 || cout % 64 != 0) return TIA_ESIZE;
+    // 32-bit byte offsets into the input and the packed weights: images go in groups (conv_host.hpp)
+    long group = conv_batch_group(h * w * cin * 4, positions * cin * cout * 4, ho * wo);
     if (group < 1) return TIA_ESIZE;
     if (ho <= 8 && wo <= 8 && group > 4) group -= group % 4;  // whole blocks of four images
     if (const long even = even_group(n, group); even < group)

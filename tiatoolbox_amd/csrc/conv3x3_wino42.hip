@@ -96,16 +96,16 @@ __global__ __launch_bounds__(512, 2) void conv3x3_wino42_kernel(const float* __r
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
 
     const int bid = blockIdx.x;
-    const int per_xcd = (m_tiles + 7) / 8;
+    const int xcd_tiles = xcd_share(m_tiles);
     const int n_cs = d.cin >> 4, n_cb = d.cout >> 6;
     int item = 0, item_end = 1, item_step = 1, mt_lo = 0;
     if constexpr (PERSIST) {
-        mt_lo = (bid & 7) * per_xcd;
-        const int mt_hi = mt_lo + per_xcd < m_tiles ? mt_lo + per_xcd : m_tiles;
+        mt_lo = (bid & 7) * xcd_tiles;
+        const int mt_hi = mt_lo + xcd_tiles < m_tiles ? mt_lo + xcd_tiles : m_tiles;
         item = bid >> 3, item_step = (int)(gridDim.x >> 3), item_end = (mt_hi - mt_lo) * n_cb;
         if (item >= item_end) return;
     } else {
-        if ((bid % 8) * per_xcd + bid / 8 >= m_tiles) return;  // every XCD walks a contiguous range of pixel blocks
+        if (xcd_tile(bid, m_tiles) >= m_tiles) return;  // every XCD walks a contiguous range of pixel blocks
     }
     int mt_id, cb, img, ty0, tx0;
     auto decode = [&](int it) {
@@ -113,7 +113,7 @@ __global__ __launch_bounds__(512, 2) void conv3x3_wino42_kernel(const float* __r
             const int q = it / n_cb;
             mt_id = mt_lo + q, cb = it - q * n_cb;
         } else {
-            mt_id = (bid % 8) * per_xcd + bid / 8, cb = (int)blockIdx.y;
+            mt_id = xcd_tile(bid, m_tiles), cb = (int)blockIdx.y;
         }
         img = GEO::G == 1 ? mt_id / tiles_per_image : mt_id * GEO::G;
         const int trem = GEO::G == 1 ? mt_id - img * tiles_per_image : 0;

@@ -1,7 +1,9 @@
-// Device and host leaves shared by the convolution kernels (conv3x3_wino.hip, conv3x3_wino42.hip, conv3x3_spatial.hip,
-// conv_mfma.hip, conv_mfma_h.hip, stem_mfma.hip); internal, not part of the C ABI.  Every device function here is a
-// __forceinline__ leaf: a kernel that uses one compiles to the instructions it had with a private copy.  The kernels keep their
-// own helpers in anonymous namespaces and say `using namespace tia;` inside them.
+// Device leaves shared by the convolution kernels (conv3x3_wino.hip, conv3x3_wino42.hip, conv3x3_spatial.hip, conv_mfma.hip,
+// conv_mfma_h.hip, conv_ring_bf16x3.hip, stem_mfma.hip) and the half-precision glue (cnn_epilogue_h.hip); internal, not part of
+// the C ABI.  Every device function here is a __forceinline__ leaf over scalars, and only what leaves the kernels' instruction
+// streams as they were is shared (profiles/conv_gemm_refactor_isa.txt; DESIGN 4.28 says what could not be).  The kernels keep
+// their own helpers in anonymous namespaces and say `using namespace tia;` inside them.  The host side of the implicit-GEMM
+// kernels is conv_host.hpp (device_cu_count, at the bottom here, is the host leaf every kernel file already reaches this way).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -76,6 +78,40 @@ __device__ __forceinline__ unsigned short f32_to_half(float x) {  // round to ne
         return v;
     }
 }
+
+// ---- the tile order of every convolution kernel, and what the implicit-GEMM kernels that gather kh x kw taps share (conv_mfma.hip,
+//      conv_mfma_h.hip, conv1x1_ring_kernel in conv3x3_spatial.hip, conv_ring_bf16x3.hip) --------------------------------------------
+
+// XCD-aware tile order: workgroups go round-robin to the 8 XCDs (each with its own L2); every XCD gets a contiguous range of
+// xcd_share() pixel tiles (neighbouring tiles share their input halo rows).  The grid is whole rounds over the XCDs: a workgroup
+// whose xcd_tile() is >= m_tiles has no tile and leaves.  (A form that returns a negative index instead tells the compiler that
+// the index of the others is non-negative, and every kernel's prologue comes out different: measured)
+__device__ __forceinline__ int xcd_share(int m_tiles) { return (m_tiles + 7) / 8; }
+__device__ __forceinline__ int xcd_tile(int bid, int m_tiles) {
+    const int per_xcd = xcd_share(m_tiles);
+    return (bid % 8) * per_xcd + bid / 8;
+}
+
+// Slice cursor (scalar): tap (kh, kw) and channel position c of the slice that is requested next.  next() advances the channel
+// position by `step` up to `c_end` (in channels: BK against cin; or in slices: 1 against cin / 16), then the tap column, then the tap
+// row; past the last slice the cursor stays there (the tail of a pipeline re-requests the last slice, so its loop body has no
+// control flow around the loads).
+struct SliceCursor {
+    int kh = 0, kw = 0, c = 0;
+    __device__ __forceinline__ void next(int step, int c_end, int n_kh, int n_kw) {
+        int c2 = c + step, kw2 = kw, kh2 = kh;
+        if (c2 == c_end) { c2 = 0; ++kw2; }
+        if (kw2 == n_kw) { kw2 = 0; ++kh2; }
+        if (kh2 < n_kh) { c = c2; kw = kw2; kh = kh2; }
+    }
+};
+
+// Dimensions of a launch of the ring kernels (conv1x1_ring_kernel, conv_ring_bf16x3_kernel)
+struct PwDims {
+    int n, h, w, cin, cout, ho, wo, stride;
+    unsigned x_bytes, w_bytes;
+    int kh, kw, pad_y, pad_x;
+};
 
 // Compute units of the calling thread's CURRENT device (MI355X: 256), cached per device index (a process may drive several GPUs;
 // the first caller may be a host-only route query).  Without a usable device (build container): MI355X's 256.

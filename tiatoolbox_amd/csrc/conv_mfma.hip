@@ -28,6 +28,7 @@
 #include "common.hpp"
 #include "conv3x3_spatial.hpp"
 #include "conv_device.hpp"
+#include "conv_host.hpp"
 
 namespace {
 
@@ -73,10 +74,7 @@ __global__ __launch_bounds__(NTH, 2) void conv_mfma_f32_kernel(const float* __re
     __shared__ float As[BM * LDA];
     __shared__ __attribute__((aligned(16))) float Bs[BK * BN];
 
-    // XCD-aware tile order: workgroups go round-robin to the 8 XCDs; give each XCD a contiguous range of pixel tiles
-    const int bid = blockIdx.x;
-    const int per_xcd = (m_tiles + 7) / 8;
-    const int mt_id = (bid % 8) * per_xcd + bid / 8;
+    const int mt_id = xcd_tile(blockIdx.x, m_tiles);
     if (mt_id >= m_tiles) return;
     const long m0 = (long)mt_id * BM;
     const int n0 = blockIdx.y * BN;
@@ -132,7 +130,8 @@ __global__ __launch_bounds__(NTH, 2) void conv_mfma_f32_kernel(const float* __re
             return v;
         }
     };
-    // slice cursor (scalar): tap (kh, kw) and first channel c0 of the slice that is staged next
+    // slice cursor (scalar): tap (kh, kw) and first channel c0 of the slice that is staged next.  (SliceCursor, which the other three
+    // gathering kernels use, numbers two scalar registers of this kernel the other way round: its own three scalars stay.)
     int s_kh = 0, s_kw = 0, s_c0 = 0;
     u32x4 ra0, ra1, ra2, ra3, rb0, rb1, rb2, rb3;
     rb2 = rb3 = u32x4{0u, 0u, 0u, 0u};
@@ -311,37 +310,13 @@ extern "C" int tia_conv_pack_weights_f32(const float* d_w_oihw, int64_t cout, in
                                          float* d_packed, void* stream) {
     if (!d_w_oihw || !d_packed || cout <= 0 || cin <= 0 || kh <= 0 || kw <= 0) return TIA_EINVAL;
     const long total = (long)cout * cin * kh * kw;
-    long blocks = (total + 255) / 256;
-    if (blocks > 4096) blocks = 4096;
-    hipLaunchKernelGGL(pack_weights_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, d_w_oihw, (int)cout, (int)cin,
+    hipLaunchKernelGGL(pack_weights_kernel, tia::pack_grid(total), dim3(256), 0, (hipStream_t)stream, d_w_oihw, (int)cout, (int)cin,
                        (int)kh, (int)kw, d_packed);
     return hipGetLastError() == hipSuccess ? TIA_OK : TIA_ELAUNCH;
 }
 
 // ---- the ONE dispatch decision: conv2d_impl launches by it, tia_conv2d_route_f32 reports it ---------------------------------------
 enum ConvRoute { ROUTE_SLICE = 0, ROUTE_SPATIAL = 1, ROUTE_RING = 2 };
-
-// Shape checks shared by the entry points and the route query (pointer checks stay with the callers).
-static int conv2d_check_shape(int64_t n, int64_t h, int64_t w, int64_t cin, int64_t cout, int64_t kh, int64_t kw, int64_t stride,
-                              int64_t pad_top, int64_t pad_left, int64_t ho, int64_t wo) {
-    if (n <= 0 || h <= 0 || w <= 0 || cin <= 0 || cout <= 0 || kh <= 0 || kw <= 0 || stride <= 0 || pad_top < 0 || pad_left < 0) return TIA_EINVAL;
-    if (cin % BK != 0 || cout % 64 != 0) return TIA_ESIZE;
-    // every output pixel must see at least its first tap row / column start inside [-(k-1), h): rows and columns beyond the
-    // image on either side read as zeros (that is how asymmetric "same" padding is expressed: pad_top / pad_left + ho / wo)
-    if (ho <= 0 || wo <= 0 || kh > 16 || kw > 16 || pad_top >= kh || pad_left >= kw) return TIA_EINVAL;
-    if ((ho - 1) * stride - pad_top >= h || (wo - 1) * stride - pad_left >= w) return TIA_EINVAL;
-    return TIA_OK;
-}
-
-// Images per launch: the kernels address their input with 32-bit byte offsets, so a batch goes in groups of < 2 GiB of input
-// (and < 2^30 output pixels).  0: a single image is already too large.
-static long conv2d_group(int64_t h, int64_t w, int64_t pstride, int64_t cin, int64_t cout, int64_t kh, int64_t kw, int64_t ho, int64_t wo) {
-    const long image_bytes = h * w * pstride * 4, w_bytes = kh * kw * cin * cout * 4;
-    if (image_bytes > 0x7fffffffL || w_bytes > 0x7fffffffL || ho * wo > 0x7fffffffL / 4) return 0;
-    long group = 0x7fffffffL / image_bytes;
-    if (group * ho * wo > 0x7fffffffL / 2) group = 0x7fffffffL / 2 / (ho * wo);
-    return group;
-}
 
 // Which kernel serves ONE launch over `nb` images.  `plain` = no second epilogue output, no activation on load, dense pixels
 // (pstride == cin): only those forms exist on the tap-reuse and ring kernels.
@@ -374,11 +349,11 @@ static int conv2d_impl(const float* d_x, const float* d_w_packed, const float* d
         return TIA_EINVAL;
     if (with_post && (!d_post_scale || !d_post_shift)) return TIA_EINVAL;
     if (!d_x || !d_w_packed || (!d_y && !with_post)) return TIA_EINVAL;
-    if (const int rc = conv2d_check_shape(n, h, w, cin, cout, kh, kw, stride, pad_top, pad_left, ho, wo); rc != TIA_OK) return rc;
+    if (const int rc = tia::conv_check_shape(n, h, w, cin, cout, kh, kw, stride, pad_top, pad_left, ho, wo, BK, 64); rc != TIA_OK) return rc;
     if ((reinterpret_cast<uintptr_t>(d_w_packed) & 15) != 0 || (reinterpret_cast<uintptr_t>(d_x) & (pstride % 4 == 0 ? 15 : 3)) != 0)
         return TIA_EINVAL;
     const long image_bytes = h * w * pstride * 4, w_bytes = kh * kw * cin * cout * 4;
-    const long group = tia::even_group(n, conv2d_group(h, w, pstride, cin, cout, kh, kw, ho, wo));
+    const long group = tia::even_group(n, tia::conv_batch_group(image_bytes, w_bytes, ho * wo));
     if (group < 1) return TIA_ESIZE;
     const bool plain = !with_post && !with_pre && pstride == cin;
     hipStream_t st = (hipStream_t)stream;
@@ -468,8 +443,8 @@ extern "C" int tia_conv2d_route_f32(int64_t n, int64_t h, int64_t w, int64_t cin
                                     int64_t pad_top, int64_t pad_left, int64_t ho, int64_t wo) {
     // the same checks, the same batch split and the same decision function as tia_conv2d_nhwc_f32(_ex): shapes the entry point
     // rejects are rejected here with the same code
-    if (const int rc = conv2d_check_shape(n, h, w, cin, cout, kh, kw, stride, pad_top, pad_left, ho, wo); rc != TIA_OK) return rc;
-    const long group = tia::even_group(n, conv2d_group(h, w, cin, cin, cout, kh, kw, ho, wo));
+    if (const int rc = tia::conv_check_shape(n, h, w, cin, cout, kh, kw, stride, pad_top, pad_left, ho, wo, BK, 64); rc != TIA_OK) return rc;
+    const long group = tia::even_group(n, tia::conv_batch_group(h * w * cin * 4, kh * kw * cin * cout * 4, ho * wo));
     if (group < 1) return TIA_ESIZE;
     // a batch beyond 2 GiB of input runs in EQUAL groups (tia::even_group; the last one at most k - 1 images shorter): the answer
     // is the route of the first group

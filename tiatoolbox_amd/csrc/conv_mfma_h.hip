@@ -32,6 +32,7 @@
 #include "common.hpp"
 #include "conv3x3_spatial.hpp"
 #include "conv_device.hpp"
+#include "conv_host.hpp"
 
 namespace {
 
@@ -83,9 +84,7 @@ __global__ __launch_bounds__(NTH, 2) void conv_mfma_h_kernel(const void* __restr
     constexpr int LDS_BYTES = NSTAGE * STAGE > BM * (BN / 2) * 4 ? NSTAGE * STAGE : BM * (BN / 2) * 4;
     __shared__ __attribute__((aligned(16))) unsigned char smem[LDS_BYTES];
 
-    const int bid = blockIdx.x;
-    const int per_xcd = (m_tiles + 7) / 8;
-    const int mt_id = (bid % 8) * per_xcd + bid / 8;
+    const int mt_id = xcd_tile(blockIdx.x, m_tiles);
     if (mt_id >= m_tiles) return;
     const long m0 = (long)mt_id * BM;
     const int n0 = blockIdx.y * BN;
@@ -125,12 +124,12 @@ __global__ __launch_bounds__(NTH, 2) void conv_mfma_h_kernel(const void* __restr
         b_off[r] = (kc * d.cout + n0 + col) * 16;
     }
 
-    int s_kh = 0, s_kw = 0, s_c0 = 0;
+    SliceCursor s;  // (s.c: first channel of the slice)
     // DMA of the slice under the cursor into `stage`: wave w, instruction r writes the 1 KB at position (w * 64 + 256 r) * 16
     auto dma_slice = [&](int stage) {
-        const int sdelta = ((s_kh * d.w + s_kw) * d.cin + s_c0) * 2;
-        const unsigned sel = (1u << s_kh) | (1u << (16 + s_kw));
-        const int swrow = ((s_kh * d.kw + s_kw) * (d.cin >> 3) + (s_c0 >> 3)) * d.cout * 16;
+        const int sdelta = ((s.kh * d.w + s.kw) * d.cin + s.c) * 2;
+        const unsigned sel = (1u << s.kh) | (1u << (16 + s.kw));
+        const int swrow = ((s.kh * d.kw + s.kw) * (d.cin >> 3) + (s.c >> 3)) * d.cout * 16;
         unsigned char* sa = smem + stage * STAGE + wave * 1024;
         unsigned char* sb = smem + stage * STAGE + A_BYTES + wave * 1024;
 #pragma unroll
@@ -140,12 +139,6 @@ __global__ __launch_bounds__(NTH, 2) void conv_mfma_h_kernel(const void* __restr
         }
 #pragma unroll
         for (int r = 0; r < B_SLOTS; ++r) dma16(rw, sb + r * 4096, b_off[r], swrow);
-    };
-    auto next_slice = [&]() {
-        int c0 = s_c0 + BK, kw = s_kw, kh = s_kh;
-        if (c0 == d.cin) { c0 = 0; ++kw; }
-        if (kw == d.kw) { kw = 0; ++kh; }
-        if (kh < d.kh) { s_c0 = c0; s_kw = kw; s_kh = kh; }
     };
 
     f32x16 acc[2][NTILE];
@@ -193,14 +186,14 @@ __global__ __launch_bounds__(NTH, 2) void conv_mfma_h_kernel(const void* __restr
         // read in the iteration AFTER the wait + barrier that retired it; every LDS read of a stage has returned (lgkmcnt(0))
         // before the wave arrives at the barrier behind which the stage is refilled.
         dma_slice(0);
-        next_slice();
+        s.next(BK, d.cin, d.kh, d.kw);
         dma_slice(1);
         if constexpr (DMA_PER_SLICE == 4) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
         else asm volatile("s_waitcnt vmcnt(3)" ::: "memory");
         __builtin_amdgcn_s_barrier();
         int cur = 0;
         for (int sidx = 0; sidx < n_slices; ++sidx) {
-            next_slice();
+            s.next(BK, d.cin, d.kh, d.kw);
             int nxt2 = cur + 2;
             nxt2 = nxt2 >= NSTAGE ? nxt2 - NSTAGE : nxt2;
             dma_slice(nxt2);  // past the last slice the cursor stays put: the tail re-fetches the last slice (no control flow)
@@ -218,7 +211,7 @@ __global__ __launch_bounds__(NTH, 2) void conv_mfma_h_kernel(const void* __restr
         __builtin_amdgcn_s_barrier();
         for (int sidx = 0; sidx < n_slices; ++sidx) {
             const int cur = sidx & 1;
-            next_slice();
+            s.next(BK, d.cin, d.kh, d.kw);
             dma_slice(cur ^ 1);
             compute(cur);
             asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
@@ -338,13 +331,11 @@ extern "C" int tia_conv_pack_weights_h(const float* d_w_oihw, int64_t cout, int6
     if (dtype != TIA_DT_F16 && dtype != TIA_DT_BF16) return TIA_EINVAL;
     if (cin % 8 != 0) return TIA_ESIZE;
     const long total = (long)cout * cin * kh * kw;
-    long blocks = (total + 255) / 256;
-    if (blocks > 4096) blocks = 4096;
     if (dtype == TIA_DT_BF16)
-        hipLaunchKernelGGL(pack_weights_h_kernel<true>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, d_w_oihw, (int)cout,
+        hipLaunchKernelGGL(pack_weights_h_kernel<true>, tia::pack_grid(total), dim3(256), 0, (hipStream_t)stream, d_w_oihw, (int)cout,
                            (int)cin, (int)kh, (int)kw, (unsigned short*)d_packed);
     else
-        hipLaunchKernelGGL(pack_weights_h_kernel<false>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, d_w_oihw, (int)cout,
+        hipLaunchKernelGGL(pack_weights_h_kernel<false>, tia::pack_grid(total), dim3(256), 0, (hipStream_t)stream, d_w_oihw, (int)cout,
                            (int)cin, (int)kh, (int)kw, (unsigned short*)d_packed);
     return hipGetLastError() == hipSuccess ? TIA_OK : TIA_ELAUNCH;
 }
@@ -355,25 +346,18 @@ static int conv2d_h_impl(const void* d_x, const void* d_w_packed, const float* d
                          int64_t pad_left, int64_t ho, int64_t wo, int32_t dtype, int32_t relu, const float* d_post_scale,
                          const float* d_post_shift, void* d_y2, bool spatial, void* stream) {
     const bool with_post = d_y2 != nullptr;
-    if (!d_x || !d_w_packed || (!d_y && !with_post) || n <= 0 || h <= 0 || w <= 0 || kh <= 0 || kw <= 0 || stride <= 0 || pad_top < 0 ||
-        pad_left < 0)
-        return TIA_EINVAL;
+    if (!d_x || !d_w_packed || (!d_y && !with_post)) return TIA_EINVAL;
     if (dtype != TIA_DT_F16 && dtype != TIA_DT_BF16) return TIA_EINVAL;
     if (with_post ? (!d_post_scale || !d_post_shift) : (d_post_scale || d_post_shift)) return TIA_EINVAL;
-    if (cin % 32 != 0 || cout % 64 != 0) return TIA_ESIZE;
+    // the float32 entry's shape checks, in its order (conv_host.hpp), with this kernel's multiples
+    if (const int rc = tia::conv_check_shape(n, h, w, cin, cout, kh, kw, stride, pad_top, pad_left, ho, wo, 32, 64); rc != TIA_OK) return rc;
     if (((reinterpret_cast<uintptr_t>(d_x) | reinterpret_cast<uintptr_t>(d_w_packed) | reinterpret_cast<uintptr_t>(d_y) |
           reinterpret_cast<uintptr_t>(d_residual) | reinterpret_cast<uintptr_t>(d_bias) | reinterpret_cast<uintptr_t>(d_y2) |
           reinterpret_cast<uintptr_t>(d_post_scale) | reinterpret_cast<uintptr_t>(d_post_shift)) & 15) != 0)
         return TIA_EINVAL;
-    if (kh > 16 || kw > 16 || pad_top >= kh || pad_left >= kw) return TIA_EINVAL;
-    // every output pixel's first tap row / column starts inside [-(k - 1), h): what lies beyond the image on either side reads as zeros
-    if (ho <= 0 || wo <= 0 || (ho - 1) * stride - pad_top >= h || (wo - 1) * stride - pad_left >= w) return TIA_EINVAL;
     const long image_bytes = h * w * cin * 2, w_bytes = kh * kw * cin * cout * 2;
-    if (image_bytes > 0x7fffffffL || w_bytes > 0x7fffffffL || ho * wo > 0x7fffffffL / 4) return TIA_ESIZE;
-    long group = 0x7fffffffL / image_bytes;
-    if (group * ho * wo > 0x7fffffffL / 2) group = 0x7fffffffL / 2 / (ho * wo);
+    const long group = tia::even_group(n, tia::conv_batch_group(image_bytes, w_bytes, ho * wo));
     if (group < 1) return TIA_ESIZE;
-    group = tia::even_group(n, group);
     hipStream_t st = (hipStream_t)stream;
     const bool bf = dtype == TIA_DT_BF16;
     for (long first = 0; first < n; first += group) {

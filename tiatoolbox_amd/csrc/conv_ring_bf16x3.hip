@@ -42,18 +42,12 @@
 #include "../../include/tiatoolbox_amd.h"
 #include "common.hpp"
 #include "conv_device.hpp"
+#include "conv_host.hpp"
 #include "dev_env.hpp"
 
 namespace {
 
 using namespace tia;
-
-// (the ring kernel's dimensions, conv3x3_spatial.hip)
-struct PwDims {
-    int n, h, w, cin, cout, ho, wo, stride;
-    unsigned x_bytes, w_bytes;
-    int kh, kw, pad_y, pad_x;
-};
 
 // Phase timing (developer builds only: -DTIA_SPLIT_TIMING=1, build.build(defines=...)): thread 0 of two workgroups prints the
 // shader-clock cycles of set-up, first-data wait, slice loop and epilogue, and the sustained shader clock (against the constant
@@ -121,9 +115,7 @@ __global__ __launch_bounds__(512, 4) void conv_ring_bf16x3_kernel(const float* _
     long long tm_[4] = {0, 0, 0, 0}, tl_ = clock64();
     const long long t0c_ = tl_, t0w_ = wall_clock64();
 #endif
-    const int bid = blockIdx.x;
-    const int per_xcd = (m_tiles + 7) / 8;
-    const int mt_id = (bid % 8) * per_xcd + bid / 8;
+    const int mt_id = xcd_tile(blockIdx.x, m_tiles);
     if (mt_id >= m_tiles) return;
     const long m0 = (long)mt_id * 256;
     const long m_total = (long)d.n * d.ho * d.wo;
@@ -159,27 +151,20 @@ __global__ __launch_bounds__(512, 4) void conv_ring_bf16x3_kernel(const float* _
     const int n_slices = d.kh * d.kw * n_cs;
     const int col_tiles = d.cout / BN;
 
-    // slice cursor (scalar): tap (s_kh, s_kw), channel slice s_cs of the slice that is requested next
-    int s_kh = 0, s_kw = 0, s_cs = 0;
+    // slice cursor: s.c counts 16-channel slices; past the last slice the idle stage is refilled with the same slice
+    SliceCursor s;
     auto dma_stage = [&](int stage) {
         unsigned char* sa = smem + stage * STAGE;
-        const int sdelta = (s_kh * d.w + s_kw) * d.cin * 4;
-        const unsigned sel = (1u << s_kh) | (1u << (16 + s_kw));
+        const int sdelta = (s.kh * d.w + s.kw) * d.cin * 4;
+        const unsigned sel = (1u << s.kh) | (1u << (16 + s.kw));
 #pragma unroll
         for (int r = 0; r < 3; ++r) {
             unsigned char* dst = (NT * r + wave * 64 >= A_UNITS) ? smem + DUMP : sa + r * (NT * 16) + wave * 1024;
-            dma16(rx, dst, (msk[r] & sel) == sel ? cen[r] + sdelta : OOB, s_cs * 64);
+            dma16(rx, dst, (msk[r] & sel) == sel ? cen[r] + sdelta : OOB, s.c * 64);
         }
-        const int wstage = ((((s_kh * d.kw + s_kw) * n_cs) + s_cs) * col_tiles + (int)blockIdx.y) * B_BYTES;
+        const int wstage = ((((s.kh * d.kw + s.kw) * n_cs) + s.c) * col_tiles + (int)blockIdx.y) * B_BYTES;
         dma16(rw, sa + A_BYTES + wave * 1024, tid * 16, wstage);
         dma16(rw, (NT + wave * 64 >= B_UNITS) ? smem + DUMP : sa + A_BYTES + NT * 16 + wave * 1024, b_off1, wstage);
-    };
-    // past the last slice the cursor stays there: the idle stage is refilled with the same slice
-    auto next_slice = [&]() {
-        int cs = s_cs + 1, kw = s_kw, kh = s_kh;
-        if (cs == n_cs) { cs = 0; ++kw; }
-        if (kw == d.kw) { kw = 0; ++kh; }
-        if (kh < d.kh) { s_cs = cs; s_kw = kw; s_kh = kh; }
     };
 
     f32x16 acc[NTILE];
@@ -199,7 +184,7 @@ __global__ __launch_bounds__(512, 4) void conv_ring_bf16x3_kernel(const float* _
     SSTAMP(1)
     for (int it = 0; it < n_slices; ++it) {
         const int stage = it & 1;
-        next_slice();
+        s.next(1, n_cs, d.kh, d.kw);
         dma_stage(stage ^ 1);
         const u32x4* sa = reinterpret_cast<const u32x4*>(smem + stage * STAGE) + fa0;
         const u32x4* sb = reinterpret_cast<const u32x4*>(smem + stage * STAGE + A_BYTES) + fb0;
@@ -277,7 +262,7 @@ __global__ __launch_bounds__(512, 4) void conv_ring_bf16x3_kernel(const float* _
     SSTAMP(3)
     // two workgroups report: an early one (of the first wave of workgroups) and one three quarters through the grid, both on XCD 0
     // (a multiple of 8 is pixel tile bid / 8 < m_tiles, so neither has left at the top)
-    const int early_ = gridDim.x > 64 ? 64 : 0, late_ = 8 * (3 * per_xcd / 4);
+    const int early_ = gridDim.x > 64 ? 64 : 0, late_ = 8 * (3 * xcd_share(m_tiles) / 4);
     if (threadIdx.x == 0 && blockIdx.y == 0 && ((int)blockIdx.x == early_ || (int)blockIdx.x == late_))
         printf("split ring wg %d (cin %d, %d x %d taps): setup %lld  first-data wait %lld  slice loop %lld  epilogue %lld  | shader clock %.0f MHz\n",
                (int)blockIdx.x, d.cin, d.kh, d.kw, tm_[0], tm_[1], tm_[2], tm_[3],
@@ -307,25 +292,6 @@ __global__ __launch_bounds__(256) void pack_bf16x3_kernel(const float* __restric
     }
 }
 
-// The argument checks of the float32 entry (conv2d_impl, conv_mfma.hip) with this kernel's multiples: cin % 16, cout % 128.
-int split_check_shape(int64_t n, int64_t h, int64_t w, int64_t cin, int64_t cout, int64_t kh, int64_t kw, int64_t stride, int64_t pad_top,
-                      int64_t pad_left, int64_t ho, int64_t wo) {
-    if (n <= 0 || h <= 0 || w <= 0 || cin <= 0 || cout <= 0 || kh <= 0 || kw <= 0 || stride <= 0 || pad_top < 0 || pad_left < 0) return TIA_EINVAL;
-    if (cin % 16 != 0 || cout % 128 != 0) return TIA_ESIZE;
-    if (ho <= 0 || wo <= 0 || kh > 16 || kw > 16 || pad_top >= kh || pad_left >= kw) return TIA_EINVAL;
-    if ((ho - 1) * stride - pad_top >= h || (wo - 1) * stride - pad_left >= w) return TIA_EINVAL;
-    return TIA_OK;
-}
-
-// Images per launch (32-bit byte offsets: < 2 GiB of input, < 2^30 output pixels); 0: a single image is already too large.
-long split_group(int64_t h, int64_t w, int64_t cin, int64_t cout, int64_t kh, int64_t kw, int64_t ho, int64_t wo) {
-    const long image_bytes = h * w * cin * 4, w_bytes = kh * kw * cin * cout * 6;
-    if (image_bytes > 0x7fffffffL || w_bytes > 0x7fffffffL || ho * wo > 0x7fffffffL / 4) return 0;
-    long group = 0x7fffffffL / image_bytes;
-    if (group * ho * wo > 0x7fffffffL / 2) group = 0x7fffffffL / 2 / (ho * wo);
-    return group;
-}
-
 }  // namespace
 
 extern "C" int tia_conv_pack_weights_bf16x3(const float* d_parts_oihw, int64_t cout, int64_t cin, int64_t kh, int64_t kw, void* d_packed,
@@ -333,9 +299,7 @@ extern "C" int tia_conv_pack_weights_bf16x3(const float* d_parts_oihw, int64_t c
     if (!d_parts_oihw || !d_packed || cout <= 0 || cin <= 0 || kh <= 0 || kw <= 0) return TIA_EINVAL;
     if (cin % 16 != 0 || cout % 128 != 0) return TIA_ESIZE;
     const long total = 3L * cout * cin * kh * kw;
-    long blocks = (total + 255) / 256;
-    if (blocks > 4096) blocks = 4096;
-    hipLaunchKernelGGL(pack_bf16x3_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, d_parts_oihw, (int)cout, (int)cin,
+    hipLaunchKernelGGL(pack_bf16x3_kernel, tia::pack_grid(total), dim3(256), 0, (hipStream_t)stream, d_parts_oihw, (int)cout, (int)cin,
                        (int)kh, (int)kw, static_cast<unsigned short*>(d_packed));
     return hipGetLastError() == hipSuccess ? TIA_OK : TIA_ELAUNCH;
 }
@@ -347,12 +311,13 @@ extern "C" int tia_conv2d_bf16x3_nhwc_f32(const float* d_x, const void* d_w_pack
     if (h <= 0 || w <= 0 || kh <= 0 || kw <= 0 || stride <= 0 || pad_top < 0 || pad_left < 0) return TIA_EINVAL;
     // symmetric padding (pad_top rows behind as in front), as tia_conv2d_nhwc_f32
     const long ho = (h + 2 * pad_top - kh) / stride + 1, wo = (w + 2 * pad_left - kw) / stride + 1;
-    if (const int rc = split_check_shape(n, h, w, cin, cout, kh, kw, stride, pad_top, pad_left, ho, wo); rc != TIA_OK) return rc;
+    // the argument checks of the float32 entry (conv2d_impl, conv_mfma.hip) with this kernel's multiples: cin % 16, cout % 128
+    if (const int rc = tia::conv_check_shape(n, h, w, cin, cout, kh, kw, stride, pad_top, pad_left, ho, wo, 16, 128); rc != TIA_OK) return rc;
     if (((reinterpret_cast<uintptr_t>(d_w_packed3) | reinterpret_cast<uintptr_t>(d_x) | reinterpret_cast<uintptr_t>(d_y) |
           reinterpret_cast<uintptr_t>(d_bias) | reinterpret_cast<uintptr_t>(d_residual)) & 15) != 0)
         return TIA_EINVAL;
     const long image_bytes = h * w * cin * 4, w_bytes = kh * kw * cin * cout * 6;
-    const long group = tia::even_group(n, split_group(h, w, cin, cout, kh, kw, ho, wo));
+    const long group = tia::even_group(n, tia::conv_batch_group(image_bytes, w_bytes, ho * wo));
     if (group < 1) return TIA_ESIZE;
     for (long first = 0; first < n; first += group) {
         const long nb = n - first < group ? n - first : group;
@@ -387,7 +352,7 @@ extern "C" int tia_conv2d_bf16x3_serves(int64_t n, int64_t h, int64_t w, int64_t
                                         int64_t pad_top, int64_t pad_left, int64_t ho, int64_t wo) {
     static const bool disabled = tia::dev_env("TIA_CONV_NO_SPLIT") != nullptr;
     if (disabled) return 0;
-    if (split_check_shape(n, h, w, cin, cout, kh, kw, stride, pad_top, pad_left, ho, wo) != TIA_OK) return 0;
+    if (tia::conv_check_shape(n, h, w, cin, cout, kh, kw, stride, pad_top, pad_left, ho, wo, 16, 128) != TIA_OK) return 0;
     if (tia_conv2d_route_f32(n, h, w, cin, cout, kh, kw, stride, pad_top, pad_left, ho, wo) != 2) return 0;
     // the entry point pads symmetrically: the output size must be the one it derives
     if (ho != (h + 2 * pad_top - kh) / stride + 1 || wo != (w + 2 * pad_left - kw) / stride + 1) return 0;

@@ -42,7 +42,8 @@ extern "C" {
  * Additive, same version: tia_gather_area_patches_u8 (patch reads below the slide's resolution), tia_gather_area_resize_u8
  * (the same at any down-sampling ratio), tia_gather_cubic_resize_u8 (patch reads above the slide's resolution),
  * tia_conv3x3_grouped_nhwc_f32 (the grouped 3x3 of ResNeXt), tia_stem_pack_weights_bf16x3 / tia_stem_conv7x7_pool_nhwc_u8x3 (the
- * uint8 stem on the bf16 matrix cores with exactly split float32 weights). */
+ * uint8 stem on the bf16 matrix cores with exactly split float32 weights); tia_mha_fwd_h, tia_layernorm_rows_h, tia_gelu_rows_h,
+ * tia_vit_patchify_h, tia_vit_assemble_tokens_h (the Vision Transformer backbones in fp16 / bf16). */
 #define TIA_ABI_VERSION 6
 int tia_abi_version(void);
 
@@ -864,6 +865,46 @@ int tia_upsample2x_concat_act_nhwc_f32(const float* d_x, const float* d_y, const
  * cx % 8 == 0 and cy % 8 == 0 (else TIA_ESIZE); otherwise as above. */
 int tia_upsample2x_concat_act_nhwc_h(const void* d_x, const void* d_y, const float* d_scale, const float* d_shift, void* d_out,
                                      int64_t n, int64_t h, int64_t w, int64_t cx, int64_t cy, int32_t dtype, void* stream);
+
+/* =======================================================================================
+ * Vision Transformer backbones in fp16 / bf16 (models/architecture/vit.py, vit_fused.py: timm's VisionTransformer as
+ * the reference's TimmBackbone builds it -- UNI = ViT-L/16).  The Linear layers are tia_conv2d_nhwc_h with kh = kw = 1 on the
+ * tokens as an [n, S, 1, C] map; these entry points are everything around them.  Additive, same version (6).  `dtype` is
+ * TIA_DT_F16 | TIA_DT_BF16 (anything else TIA_EINVAL); null pointers, non-positive sizes and pointers that are not 16-byte aligned
+ * are TIA_EINVAL, sizes a kernel does not take TIA_ESIZE; nothing is launched on an error return; 64-bit offsets.
+ * ===================================================================================== */
+
+/* Fused multi-head attention, forward: out[b,i,h,:] = softmax_j(scale * q[b,i,h,:] . k[b,j,h,:]) v[b,:,h,:] on
+ * v_mfma_f32_16x16x32_f16 / _bf16 without materialising the scores (online softmax, 64 queries x 64 keys per step).
+ *   d_qkv [n, s, 3, heads, head_dim] of `dtype` -- the qkv Linear's own output order   d_out [n, s, heads * head_dim] of `dtype`
+ * float32 scores, maximum and sum (the sum over the unrounded probabilities); the probabilities are rounded once to `dtype` for
+ * the second product, the output O / l once.  Any s >= 1: keys beyond s contribute exactly 0, query rows beyond s are not stored.
+ * head_dim != 64 is TIA_ESIZE (every registered model has 64); scale must be positive and finite (TIA_EINVAL). */
+int tia_mha_fwd_h(const void* d_qkv, void* d_out, int64_t n, int64_t s, int64_t heads, int64_t head_dim, float scale, int32_t dtype,
+                  void* stream);
+
+/* LayerNorm over the last axis: y[r,:] = (x[r,:] - mean) / sqrt(var + eps) * gamma + beta, mean first and then the variance of
+ * the centred values, float32 throughout, ONE rounding.
+ *   d_x: row r starts at element r * row_stride of `dtype` (row_stride >= c, % 8 == 0: the final norm reads the class tokens
+ *   only, row_stride = S * D)   d_gamma, d_beta [c] float32   d_y [rows, c] dense, of `dtype` or (out_f32 != 0) float32.
+ * c % 8 == 0 and c <= 8192 (else TIA_ESIZE). */
+int tia_layernorm_rows_h(const void* d_x, int64_t row_stride, const float* d_gamma, const float* d_beta, float eps, void* d_y,
+                         int64_t rows, int64_t c, int32_t dtype, int32_t out_f32, void* stream);
+
+/* Exact GELU in place on `count` halves: 0.5 x (1 + erf(x / sqrt 2)) in float32, ONE rounding.  count % 8 == 0 (else TIA_ESIZE). */
+int tia_gelu_rows_h(void* d_x, int64_t count, int32_t dtype, void* stream);
+
+/* The patch embedding's im2col: d_x [n,h,w,3] NHWC of x_dtype (TIA_DT_F32, or `dtype` itself: copied as it is) ->
+ * d_tokens [n, (h/patch) * (w/patch), patch * patch * 3] of `dtype`, patches in raster order, the values of a patch in
+ * (ky, kx, channel) order -- the k order of a [D,3,p,p] weight permuted to [D,p,p,3], so that the embedding is one 1x1
+ * GEMM with cin = 3 p^2.  patch % 8 == 0, h % patch == 0 and w % patch == 0 (else TIA_ESIZE). */
+int tia_vit_patchify_h(const void* d_x, int32_t x_dtype, void* d_tokens, int64_t n, int64_t h, int64_t w, int64_t patch,
+                       int32_t dtype, void* stream);
+
+/* Token assembly: d_out [n, 1+g, d] of `dtype` with out[b,0] = cls + pos[0] and out[b,1+i] = tokens[b,i] + pos[1+i];
+ *   d_tokens [n,g,d] of `dtype`   d_cls [d], d_pos [1+g, d] float32.   float32 add, ONE rounding.  d % 8 == 0 (else TIA_ESIZE). */
+int tia_vit_assemble_tokens_h(const void* d_tokens, const float* d_cls, const float* d_pos, void* d_out, int64_t n, int64_t g,
+                              int64_t d, int32_t dtype, void* stream);
 
 /* =======================================================================================
  * All borders of binary planes: cv2.findContours(layer, RETR_TREE, CHAIN_APPROX_NONE | _SIMPLE)

@@ -149,6 +149,11 @@ _SIGNATURES = {
     "tia_avgpool2x2_nhwc_h": ([_P, _P, _I64, _I64, _I64, _I64, _I32, _P], C.c_int),
     "tia_upsample2x_concat_act_nhwc_f32": ([_P, _P, _P, _P, _P, _I64, _I64, _I64, _I64, _I64, _P], C.c_int),
     "tia_upsample2x_concat_act_nhwc_h": ([_P, _P, _P, _P, _P, _I64, _I64, _I64, _I64, _I64, _I32, _P], C.c_int),
+    "tia_mha_fwd_h": ([_P, _P, _I64, _I64, _I64, _I64, C.c_float, _I32, _P], C.c_int),
+    "tia_layernorm_rows_h": ([_P, _I64, _P, _P, C.c_float, _P, _I64, _I64, _I32, _I32, _P], C.c_int),
+    "tia_gelu_rows_h": ([_P, _I64, _I32, _P], C.c_int),
+    "tia_vit_patchify_h": ([_P, _I32, _P, _I64, _I64, _I64, _I64, _I32, _P], C.c_int),
+    "tia_vit_assemble_tokens_h": ([_P, _P, _P, _P, _I64, _I64, _I64, _I32, _P], C.c_int),
     "tia_bias_act_nhwc": ([_P, _P, _P, _I64, _I64, _I32, _I32, _P], C.c_int),
     "tia_bias_relu_maxpool_nhwc": ([_P, _P, _I64, _I64, _I64, _I64, _I32, _P, _P], C.c_int),
     "tia_hover_instance_stats": ([_P, _P, _I64, _I64, _I64, _I32, _I32, _P, _P, _P], C.c_int),

@@ -1,0 +1,245 @@
+// The memory-bound passes of the Vision Transformer graph (fp16 / bf16 activations; models/architecture/vit_fused.py):
+//   layernorm_rows  : y[r, :] = (x[r, :] - mean) / sqrt(var + eps) * gamma + beta     rows at a stride, half or float32 out
+//   gelu_rows       : x = 0.5 x (1 + erf(x / sqrt 2)) in place
+//   vit_patchify    : NHWC image batch -> [n, g, p * p * 3] tokens, k order (ky, kx, c)   float32 or half in, half out
+//   assemble_tokens : out[b, 0] = cls + pos[0], out[b, 1 + i] = tok[b, i] + pos[1 + i]
+// 16 bytes per lane and access (8 halves), float32 arithmetic, ONE round-to-nearest-even on the way out, 64-bit element offsets.
+#include "conv_device.hpp"
+#include "wide_io.hpp"
+
+namespace {
+
+using namespace tia;
+
+constexpr int ET = 256;
+
+template <bool BF>
+__device__ __forceinline__ void unpack8(const v4u& v, float (&f)[8]) {
+    const unsigned w[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        f[2 * i] = half_to_f32<BF>((unsigned short)(w[i] & 0xffffu));
+        f[2 * i + 1] = half_to_f32<BF>((unsigned short)(w[i] >> 16));
+    }
+}
+template <bool BF>
+__device__ __forceinline__ v4u pack8(const float (&f)[8]) {
+    v4u v;
+    v.x = (unsigned)f32_to_half<BF>(f[0]) | ((unsigned)f32_to_half<BF>(f[1]) << 16);
+    v.y = (unsigned)f32_to_half<BF>(f[2]) | ((unsigned)f32_to_half<BF>(f[3]) << 16);
+    v.z = (unsigned)f32_to_half<BF>(f[4]) | ((unsigned)f32_to_half<BF>(f[5]) << 16);
+    v.w = (unsigned)f32_to_half<BF>(f[6]) | ((unsigned)f32_to_half<BF>(f[7]) << 16);
+    return v;
+}
+__device__ __forceinline__ void load8_f32(const float* p, float (&f)[8]) {
+    const float4 a = *reinterpret_cast<const float4*>(p), b = *reinterpret_cast<const float4*>(p + 4);
+    f[0] = a.x, f[1] = a.y, f[2] = a.z, f[3] = a.w, f[4] = b.x, f[5] = b.y, f[6] = b.z, f[7] = b.w;
+}
+
+__device__ __forceinline__ float wave_sum(float v) {
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);
+    return v;
+}
+
+// One wave per row, the row in registers (VPL 16-byte vectors per lane, c <= 512 VPL): one read of x, the mean, then the variance
+// of the CENTRED values (not E[x^2] - mean^2, which cancels for rows with a large mean), both folded over the wave by lane
+// exchanges -- no LDS, no barrier.  Four rows per workgroup.
+template <bool BF, bool OUT_F32, int VPL>
+__global__ __launch_bounds__(ET) void layernorm_rows_h_kernel(const unsigned short* __restrict__ x, long stride, const float* __restrict__ gamma,
+                                                               const float* __restrict__ beta, float eps, long rows, int c,
+                                                               void* __restrict__ y) {
+    const int lane = threadIdx.x & 63;
+    const long row = (long)blockIdx.x * (ET / 64) + (threadIdx.x >> 6);
+    if (row >= rows) return;  // whole waves leave: the exchanges below stay inside a wave
+    const int cv = c >> 3;
+    const unsigned short* xr = x + row * stride;
+    float f[VPL][8];
+    float sum = 0.0f;
+#pragma unroll
+    for (int i = 0; i < VPL; ++i) {
+        const int v = lane + 64 * i;
+        if (v < cv) {
+            unpack8<BF>(*reinterpret_cast<const v4u*>(xr + 8 * v), f[i]);
+#pragma unroll
+            for (int k = 0; k < 8; ++k) sum += f[i][k];
+        }
+    }
+    const float mean = wave_sum(sum) / (float)c;
+    float sq = 0.0f;
+#pragma unroll
+    for (int i = 0; i < VPL; ++i)
+        if (lane + 64 * i < cv) {
+#pragma unroll
+            for (int k = 0; k < 8; ++k) {
+                f[i][k] -= mean;
+                sq = fmaf(f[i][k], f[i][k], sq);
+            }
+        }
+    const float rstd = 1.0f / sqrtf(wave_sum(sq) / (float)c + eps);
+#pragma unroll
+    for (int i = 0; i < VPL; ++i) {
+        const int v = lane + 64 * i;
+        if (v < cv) {
+            float g[8], bt[8], r[8];
+            load8_f32(gamma + 8 * v, g);
+            load8_f32(beta + 8 * v, bt);
+#pragma unroll
+            for (int k = 0; k < 8; ++k) r[k] = fmaf(f[i][k] * rstd, g[k], bt[k]);
+            if constexpr (OUT_F32) {
+                float* yr = static_cast<float*>(y) + row * (long)c + 8 * v;
+                *reinterpret_cast<float4*>(yr) = make_float4(r[0], r[1], r[2], r[3]);
+                *reinterpret_cast<float4*>(yr + 4) = make_float4(r[4], r[5], r[6], r[7]);
+            } else {
+                *reinterpret_cast<v4u*>(static_cast<unsigned short*>(y) + row * (long)c + 8 * v) = pack8<BF>(r);
+            }
+        }
+    }
+}
+
+template <bool BF>
+__global__ __launch_bounds__(ET) void gelu_rows_h_kernel(v4u* __restrict__ x, long vectors) {
+    for (long i = (long)blockIdx.x * ET + threadIdx.x; i < vectors; i += (long)gridDim.x * ET) {
+        float f[8];
+        unpack8<BF>(x[i], f);
+#pragma unroll
+        for (int k = 0; k < 8; ++k) f[k] = 0.5f * f[k] * (1.0f + erff(f[k] * 0.70710678118654752440f));
+        x[i] = pack8<BF>(f);
+    }
+}
+
+// One thread per 8 output halves.  A token's p * p * 3 values are p runs (one per patch row ky) of 3 p contiguous input values, and
+// 3 p % 8 == 0, so an output vector is 8 contiguous input values: one 16-byte (half) or two 16-byte (float32) loads.
+template <bool BF, bool IN_F32>
+__global__ __launch_bounds__(ET) void vit_patchify_h_kernel(const void* __restrict__ x, int h, int w, int p, long vectors, v4u* __restrict__ out) {
+    const int run_v = 3 * p / 8, gw = w / p, gh = h / p;
+    for (long i = (long)blockIdx.x * ET + threadIdx.x; i < vectors; i += (long)gridDim.x * ET) {
+        const int v = (int)(i % run_v);
+        long t = i / run_v;
+        const int ky = (int)(t % p);
+        t /= p;
+        const int gx = (int)(t % gw);
+        t /= gw;
+        const int gy = (int)(t % gh);
+        const long b = t / gh;
+        const long src = ((b * h + (long)gy * p + ky) * w + (long)gx * p) * 3 + 8 * v;
+        if constexpr (IN_F32) {
+            float f[8];
+            load8_f32(static_cast<const float*>(x) + src, f);
+            out[i] = pack8<BF>(f);
+        } else {
+            out[i] = *reinterpret_cast<const v4u*>(static_cast<const unsigned short*>(x) + src);
+        }
+    }
+}
+
+template <bool BF>
+__global__ __launch_bounds__(ET) void vit_assemble_tokens_h_kernel(const v4u* __restrict__ tok, const float* __restrict__ cls,
+                                                                    const float* __restrict__ pos, long vectors, int g, int dv,
+                                                                    v4u* __restrict__ out) {
+    for (long i = (long)blockIdx.x * ET + threadIdx.x; i < vectors; i += (long)gridDim.x * ET) {
+        const int v = (int)(i % dv);
+        const long t = i / dv;
+        const int tk = (int)(t % (g + 1));
+        const long b = t / (g + 1);
+        float a[8], ps[8];
+        if (tk == 0) load8_f32(cls + 8 * v, a);
+        else unpack8<BF>(tok[(b * g + (tk - 1)) * dv + v], a);
+        load8_f32(pos + ((long)tk * dv + v) * 8, ps);
+#pragma unroll
+        for (int k = 0; k < 8; ++k) a[k] += ps[k];
+        out[i] = pack8<BF>(a);
+    }
+}
+
+unsigned stream_blocks(long items) {
+    long blocks = (items + ET - 1) / ET;
+    if (blocks > 256L * 64) blocks = 256L * 64;
+    return (unsigned)blocks;
+}
+
+template <bool BF, bool OUT_F32>
+void launch_layernorm(int vpl, dim3 grid, hipStream_t st, const unsigned short* x, long stride, const float* gamma, const float* beta, float eps,
+                      long rows, int c, void* y) {
+#define TIA_LN(V) hipLaunchKernelGGL((layernorm_rows_h_kernel<BF, OUT_F32, V>), grid, dim3(ET), 0, st, x, stride, gamma, beta, eps, rows, c, y)
+    if (vpl <= 1) TIA_LN(1);
+    else if (vpl <= 2) TIA_LN(2);
+    else if (vpl <= 4) TIA_LN(4);
+    else if (vpl <= 8) TIA_LN(8);
+    else TIA_LN(16);
+#undef TIA_LN
+}
+
+}  // namespace
+
+extern "C" int tia_layernorm_rows_h(const void* d_x, int64_t row_stride, const float* d_gamma, const float* d_beta, float eps, void* d_y,
+                                    int64_t rows, int64_t c, int32_t dtype, int32_t out_f32, void* stream) {
+    if (!d_x || !d_gamma || !d_beta || !d_y || rows <= 0 || c <= 0 || !(eps >= 0.0f)) return TIA_EINVAL;
+    if (dtype != TIA_DT_F16 && dtype != TIA_DT_BF16) return TIA_EINVAL;
+    if ((c & 7) != 0 || c > 8192) return TIA_ESIZE;
+    if (row_stride < c || (row_stride & 7) != 0) return TIA_EINVAL;
+    if ((reinterpret_cast<uintptr_t>(d_x) | reinterpret_cast<uintptr_t>(d_gamma) | reinterpret_cast<uintptr_t>(d_beta) |
+         reinterpret_cast<uintptr_t>(d_y)) & 15)
+        return TIA_EINVAL;
+    const long blocks = (rows + ET / 64 - 1) / (ET / 64);
+    if (blocks > 0x7fffffffL) return TIA_ESIZE;
+    const int vpl = (int)((c / 8 + 63) / 64);
+    const dim3 grid((unsigned)blocks);
+    hipStream_t st = (hipStream_t)stream;
+    const unsigned short* x = static_cast<const unsigned short*>(d_x);
+    const bool bf = dtype == TIA_DT_BF16;
+    if (out_f32) {
+        if (bf) launch_layernorm<true, true>(vpl, grid, st, x, (long)row_stride, d_gamma, d_beta, eps, (long)rows, (int)c, d_y);
+        else launch_layernorm<false, true>(vpl, grid, st, x, (long)row_stride, d_gamma, d_beta, eps, (long)rows, (int)c, d_y);
+    } else {
+        if (bf) launch_layernorm<true, false>(vpl, grid, st, x, (long)row_stride, d_gamma, d_beta, eps, (long)rows, (int)c, d_y);
+        else launch_layernorm<false, false>(vpl, grid, st, x, (long)row_stride, d_gamma, d_beta, eps, (long)rows, (int)c, d_y);
+    }
+    return hipGetLastError() == hipSuccess ? TIA_OK : TIA_ELAUNCH;
+}
+
+extern "C" int tia_gelu_rows_h(void* d_x, int64_t count, int32_t dtype, void* stream) {
+    if (!d_x || count <= 0) return TIA_EINVAL;
+    if (dtype != TIA_DT_F16 && dtype != TIA_DT_BF16) return TIA_EINVAL;
+    if ((count & 7) != 0) return TIA_ESIZE;
+    if (reinterpret_cast<uintptr_t>(d_x) & 15) return TIA_EINVAL;
+    const long vectors = count / 8;
+    const auto kernel = dtype == TIA_DT_BF16 ? gelu_rows_h_kernel<true> : gelu_rows_h_kernel<false>;
+    hipLaunchKernelGGL(kernel, dim3(stream_blocks(vectors)), dim3(ET), 0, (hipStream_t)stream, (v4u*)d_x, vectors);
+    return hipGetLastError() == hipSuccess ? TIA_OK : TIA_ELAUNCH;
+}
+
+extern "C" int tia_vit_patchify_h(const void* d_x, int32_t x_dtype, void* d_tokens, int64_t n, int64_t h, int64_t w, int64_t patch,
+                                  int32_t dtype, void* stream) {
+    if (!d_x || !d_tokens || n <= 0 || h <= 0 || w <= 0 || patch <= 0) return TIA_EINVAL;
+    if (dtype != TIA_DT_F16 && dtype != TIA_DT_BF16) return TIA_EINVAL;
+    if (x_dtype != TIA_DT_F32 && x_dtype != dtype) return TIA_EINVAL;
+    if ((patch & 7) != 0 || h % patch != 0 || w % patch != 0) return TIA_ESIZE;  // 3 p values of a patch row = whole 16-byte vectors
+    if ((reinterpret_cast<uintptr_t>(d_x) | reinterpret_cast<uintptr_t>(d_tokens)) & 15) return TIA_EINVAL;
+    if (h > 0x7fffffffL / 3 || w > 0x7fffffffL / 3 || n > 0x7fffffffL) return TIA_ESIZE;
+    const long vectors = n * h * w * 3 / 8;
+    const unsigned blocks = stream_blocks(vectors);
+    hipStream_t st = (hipStream_t)stream;
+    const bool bf = dtype == TIA_DT_BF16, in32 = x_dtype == TIA_DT_F32;
+    using Kernel = void (*)(const void*, int, int, int, long, v4u*);
+    const Kernel kernels[2][2] = {{vit_patchify_h_kernel<false, false>, vit_patchify_h_kernel<false, true>},
+                                  {vit_patchify_h_kernel<true, false>, vit_patchify_h_kernel<true, true>}};
+    hipLaunchKernelGGL(kernels[bf][in32], dim3(blocks), dim3(ET), 0, st, d_x, (int)h, (int)w, (int)patch, vectors, (v4u*)d_tokens);
+    return hipGetLastError() == hipSuccess ? TIA_OK : TIA_ELAUNCH;
+}
+
+extern "C" int tia_vit_assemble_tokens_h(const void* d_tokens, const float* d_cls, const float* d_pos, void* d_out, int64_t n, int64_t g,
+                                         int64_t d, int32_t dtype, void* stream) {
+    if (!d_tokens || !d_cls || !d_pos || !d_out || n <= 0 || g <= 0 || d <= 0) return TIA_EINVAL;
+    if (dtype != TIA_DT_F16 && dtype != TIA_DT_BF16) return TIA_EINVAL;
+    if ((d & 7) != 0) return TIA_ESIZE;
+    if ((reinterpret_cast<uintptr_t>(d_tokens) | reinterpret_cast<uintptr_t>(d_cls) | reinterpret_cast<uintptr_t>(d_pos) |
+         reinterpret_cast<uintptr_t>(d_out)) & 15)
+        return TIA_EINVAL;
+    if (g > 0x7ffffffeL || d > 0x7fffffffL || n > 0x7fffffffL) return TIA_ESIZE;
+    const long vectors = n * (g + 1) * (d / 8);
+    const auto kernel = dtype == TIA_DT_BF16 ? vit_assemble_tokens_h_kernel<true> : vit_assemble_tokens_h_kernel<false>;
+    hipLaunchKernelGGL(kernel, dim3(stream_blocks(vectors)), dim3(ET), 0, (hipStream_t)stream, (const v4u*)d_tokens, d_cls, d_pos, vectors,
+                       (int)g, (int)(d / 8), (v4u*)d_out);
+    return hipGetLastError() == hipSuccess ? TIA_OK : TIA_ELAUNCH;
+}

@@ -95,6 +95,8 @@ for _backbone in ("resnet101", "resnext50_32x4d", "resnext101_32x8d", "wide_resn
 # bare torchvision backbone names: feature extractors (CNNBackbone) without an ioconfig
 _BACKBONES = ("resnet18", "resnet34", "resnet50", "resnet101", "resnext50_32x4d", "resnext101_32x8d", "wide_resnet50_2",
               "wide_resnet101_2")
+# bare Vision Transformer names: feature extractors (TimmBackbone, architecture/vit.py) without an ioconfig
+_VIT_BACKBONES = ("UNI", "vit_large_patch16_224", "vit_base_patch16_224", "vit_small_patch16_224")
 
 
 def local_pretrained_weights(model_name: str) -> Path | None:
@@ -129,14 +131,15 @@ def get_pretrained_model(pretrained_model: str | None = None, pretrained_weights
     if not isinstance(pretrained_model, str):
         msg = "pretrained_model must be a string."
         raise TypeError(msg)
-    if pretrained_model in _BACKBONES:
-        # a bare torchvision backbone name -> feature extractor without ioconfig (ref. :133-134); seeded weights here
-        from tiatoolbox_amd.models.architecture.vanilla import CNNBackbone
+    if pretrained_model in _BACKBONES or pretrained_model in _VIT_BACKBONES:
+        # a bare torchvision backbone name -> feature extractor without ioconfig (ref. :133-134), a Vision Transformer name ->
+        # TimmBackbone likewise; seeded weights here
+        from tiatoolbox_amd.models.architecture.vanilla import CNNBackbone, TimmBackbone
 
         gen_state = torch.random.get_rng_state()
         torch.manual_seed(seed)
         try:
-            model = CNNBackbone(pretrained_model)
+            model = TimmBackbone(pretrained_model) if pretrained_model in _VIT_BACKBONES else CNNBackbone(pretrained_model)
         finally:
             torch.random.set_rng_state(gen_state)
         if pretrained_weights is not None:

@@ -8,6 +8,7 @@ from torch import nn
 
 from tiatoolbox_amd.models.architecture.resnet import _CFG, resnet_trunk
 from tiatoolbox_amd.models.architecture.utils import argmax_last_axis
+from tiatoolbox_amd.models.architecture.vit import VIT_CONFIGS, create_vit
 from tiatoolbox_amd.models.models_abc import ModelABC
 
 
@@ -79,6 +80,37 @@ class CNNBackbone(ModelABC):
 
     def forward(self, imgs: torch.Tensor) -> torch.Tensor:
         return torch.flatten(self.pool(self.feat_extract(imgs)), 1)
+
+    @staticmethod
+    def infer_batch(model: nn.Module, batch_data, device: str = "cpu"):
+        return _infer_batch(model=model, batch_data=batch_data, device=device)
+
+
+class TimmBackbone(ModelABC):
+    """Feature extractor on a Vision Transformer (ref. ``TimmBackbone``): ``UNI`` and the ``vit_*_patch16_224`` family, restated in
+    plain torch with timm's parameter names (``architecture/vit.py``).  The features are the class token of the final norm,
+    ``[B, D]``; input normalisation is the caller's ``preproc_func``, as in the reference.  ``pretrained=True`` loads
+    ``<backbone>.pth`` (a timm state dict) from the local weight directories; the hub is never contacted."""
+
+    def __init__(self, backbone: str, *, pretrained: bool = False) -> None:
+        super().__init__()
+        if backbone not in VIT_CONFIGS:
+            msg = f"Backbone `{backbone}` is not supported."
+            raise ValueError(msg)
+        self.pretrained = pretrained
+        self.feat_extract = create_vit(backbone)
+        if pretrained:
+            from tiatoolbox_amd.models.architecture import local_pretrained_weights, logger
+
+            weights = local_pretrained_weights(backbone)
+            if weights is not None:
+                self.feat_extract.load_state_dict(torch.load(weights, map_location="cpu"), strict=True)
+            else:
+                logger.warning("No local weights for `%s` (the HuggingFace hub is unreachable): using the seeded "
+                               "random initialisation. Pass `weights=<path to .pth>` for the pretrained model.", backbone)
+
+    def forward(self, imgs: torch.Tensor) -> torch.Tensor:
+        return torch.flatten(self.feat_extract(imgs), 1)
 
     @staticmethod
     def infer_batch(model: nn.Module, batch_data, device: str = "cpu"):

@@ -1,0 +1,186 @@
+"""Vision Transformer backbones (the models the reference's ``TimmBackbone`` builds through timm, ``vanilla.py``), restated in plain
+torch: timm's ``VisionTransformer`` with ``num_classes=0`` and ``global_pool="token"`` -- no head, no ``fc_norm``, no register
+tokens; the output is the class token of the final norm, ``[B, D]``.  Parameter names and shapes are timm's, so its checkpoints load
+with ``strict=True``; ``UNI`` is ViT-L/16 with LayerScale (``init_values=1e-5``) and ``dynamic_img_size``.
+
+The fp16 / bf16 forward on the hand-written kernels is :class:`~tiatoolbox_amd.models.architecture.vit_fused.FusedViT`.
+"""
+
+from __future__ import annotations
+
+import torch
+import torch.nn.functional as F  # noqa: N812
+from torch import nn
+
+# name -> constructor arguments (timm's `vit_*_patch16_224`; UNI: MahmoodLab/UNI's timm configuration)
+VIT_CONFIGS: dict[str, dict] = {
+    "UNI": {"embed_dim": 1024, "depth": 24, "num_heads": 16, "mlp_dim": 4096, "patch_size": 16, "img_size": 224,
+            "init_values": 1e-5, "dynamic_img_size": True},
+    "vit_large_patch16_224": {"embed_dim": 1024, "depth": 24, "num_heads": 16, "mlp_dim": 4096, "patch_size": 16, "img_size": 224},
+    "vit_base_patch16_224": {"embed_dim": 768, "depth": 12, "num_heads": 12, "mlp_dim": 3072, "patch_size": 16, "img_size": 224},
+    "vit_small_patch16_224": {"embed_dim": 384, "depth": 12, "num_heads": 6, "mlp_dim": 1536, "patch_size": 16, "img_size": 224},
+}
+LN_EPS = 1e-6
+
+
+def resample_pos_embed(pos_embed: torch.Tensor, native_grid: tuple[int, int], grid: tuple[int, int], *, dynamic: bool) -> torch.Tensor:
+    """``pos_embed`` ``[1, 1 + g0h * g0w, D]`` for a ``grid`` of patches, in float32: the class entry as it is, the grid part
+    resampled with ``F.interpolate(mode="bicubic", antialias=True, align_corners=False)`` (timm's ``resample_abs_pos_embed``).  At
+    the native grid this is ``pos_embed`` itself (no arithmetic); any other grid needs ``dynamic`` (``dynamic_img_size``) and
+    raises ``ValueError`` without it.  The one helper of the plain module and of the fused graph."""
+    grid, native_grid = tuple(grid), tuple(native_grid)
+    if grid == native_grid:
+        return pos_embed
+    if not dynamic:
+        msg = (f"This VisionTransformer takes a {native_grid[0]} x {native_grid[1]} grid of patches only; got {grid[0]} x {grid[1]} "
+               "(dynamic_img_size is off).")
+        raise ValueError(msg)
+    dim = pos_embed.shape[-1]
+    cls, tab = pos_embed[:, :1], pos_embed[:, 1:]
+    tab = tab.to(torch.float32).reshape(1, native_grid[0], native_grid[1], dim).permute(0, 3, 1, 2)
+    tab = F.interpolate(tab, size=grid, mode="bicubic", antialias=True, align_corners=False)
+    tab = tab.permute(0, 2, 3, 1).reshape(1, grid[0] * grid[1], dim)
+    return torch.cat([cls.to(torch.float32), tab], dim=1).to(pos_embed.dtype)
+
+
+class PatchEmbed(nn.Module):
+    def __init__(self, patch_size: int, embed_dim: int) -> None:
+        super().__init__()
+        self.proj = nn.Conv2d(3, embed_dim, kernel_size=patch_size, stride=patch_size)
+
+    def forward(self, x: torch.Tensor) -> torch.Tensor:
+        return self.proj(x).flatten(2).transpose(1, 2)  # [B, g, D], patches in raster order
+
+
+class Attention(nn.Module):
+    def __init__(self, dim: int, num_heads: int) -> None:
+        super().__init__()
+        self.num_heads = num_heads
+        self.head_dim = dim // num_heads
+        self.scale = self.head_dim ** -0.5
+        self.qkv = nn.Linear(dim, 3 * dim)
+        self.proj = nn.Linear(dim, dim)
+
+    def forward(self, x: torch.Tensor) -> torch.Tensor:
+        b, s, d = x.shape
+        qkv = self.qkv(x).reshape(b, s, 3, self.num_heads, self.head_dim).permute(2, 0, 3, 1, 4)
+        q, k, v = qkv.unbind(0)  # [B, H, S, D/H] each
+        attn = ((q * self.scale) @ k.transpose(-2, -1)).softmax(dim=-1)
+        return self.proj((attn @ v).transpose(1, 2).reshape(b, s, d))
+
+
+class LayerScale(nn.Module):
+    def __init__(self, dim: int, init_values: float) -> None:
+        super().__init__()
+        self.gamma = nn.Parameter(init_values * torch.ones(dim))
+
+    def forward(self, x: torch.Tensor) -> torch.Tensor:
+        return x * self.gamma
+
+
+class Mlp(nn.Module):
+    def __init__(self, dim: int, hidden: int) -> None:
+        super().__init__()
+        self.fc1 = nn.Linear(dim, hidden)
+        self.act = nn.GELU()  # the exact (erf) form
+        self.fc2 = nn.Linear(hidden, dim)
+
+    def forward(self, x: torch.Tensor) -> torch.Tensor:
+        return self.fc2(self.act(self.fc1(x)))
+
+
+class Block(nn.Module):
+    def __init__(self, dim: int, num_heads: int, mlp_dim: int, init_values: float | None) -> None:
+        super().__init__()
+        self.norm1 = nn.LayerNorm(dim, eps=LN_EPS)
+        self.attn = Attention(dim, num_heads)
+        self.ls1 = LayerScale(dim, init_values) if init_values else nn.Identity()
+        self.norm2 = nn.LayerNorm(dim, eps=LN_EPS)
+        self.mlp = Mlp(dim, mlp_dim)
+        self.ls2 = LayerScale(dim, init_values) if init_values else nn.Identity()
+
+    def forward(self, x: torch.Tensor) -> torch.Tensor:
+        x = x + self.ls1(self.attn(self.norm1(x)))
+        return x + self.ls2(self.mlp(self.norm2(x)))
+
+
+class VisionTransformer(nn.Module):
+    """``forward(imgs [B, 3, H, W]) -> [B, D]``: the class token of ``norm(blocks(tokens))``."""
+
+    def __init__(self, *, embed_dim: int, depth: int, num_heads: int, mlp_dim: int, patch_size: int = 16, img_size: int = 224,
+                 init_values: float | None = None, dynamic_img_size: bool = False) -> None:
+        super().__init__()
+        if embed_dim % num_heads != 0 or img_size % patch_size != 0:
+            msg = f"VisionTransformer: embed_dim {embed_dim} / heads {num_heads} or img_size {img_size} / patch {patch_size} does not divide."
+            raise ValueError(msg)
+        self.embed_dim, self.num_heads, self.patch_size = embed_dim, num_heads, patch_size
+        self.dynamic_img_size = dynamic_img_size
+        g0 = img_size // patch_size
+        self.native_grid = (g0, g0)
+        self.cls_token = nn.Parameter(torch.zeros(1, 1, embed_dim))
+        self.pos_embed = nn.Parameter(torch.zeros(1, 1 + g0 * g0, embed_dim))
+        self.patch_embed = PatchEmbed(patch_size, embed_dim)
+        self.blocks = nn.Sequential(*[Block(embed_dim, num_heads, mlp_dim, init_values) for _ in range(depth)])
+        self.norm = nn.LayerNorm(embed_dim, eps=LN_EPS)
+        self._pos_cache: dict[tuple, torch.Tensor] = {}
+        if self.pos_embed.device.type != "meta":
+            self.init_weights()
+
+    def init_weights(self) -> None:
+        """timm's: truncated normal (std 0.02) on the weights and ``pos_embed``, zero biases, ``cls_token`` std 1e-6, LayerNorm
+        ones / zeros; LayerScale keeps ``init_values``."""
+        nn.init.trunc_normal_(self.pos_embed, std=0.02)
+        nn.init.normal_(self.cls_token, std=1e-6)
+        for mod in self.modules():
+            if isinstance(mod, (nn.Linear, nn.Conv2d)):
+                nn.init.trunc_normal_(mod.weight, std=0.02)
+                nn.init.zeros_(mod.bias)
+            elif isinstance(mod, nn.LayerNorm):
+                nn.init.ones_(mod.weight)
+                nn.init.zeros_(mod.bias)
+
+    def grid_of(self, height: int, width: int) -> tuple[int, int]:
+        p = self.patch_size
+        if height % p != 0 or width % p != 0:
+            msg = f"VisionTransformer: the input size {height} x {width} is no multiple of the patch size {p}."
+            raise ValueError(msg)
+        return height // p, width // p
+
+    def pos_embed_for(self, grid: tuple[int, int]) -> torch.Tensor:
+        """``pos_embed`` for ``grid`` (:func:`resample_pos_embed`), resampled once per grid shape and cached until the parameter
+        changes (a load, a cast or a move makes a new version, dtype or device)."""
+        grid = tuple(grid)
+        if grid == self.native_grid:
+            return self.pos_embed
+        pe = self.pos_embed
+        # (a tensor made under inference_mode keeps no version counter; a load clears the cache itself, below)
+        key = (grid, pe.device, pe.dtype, None if pe.is_inference() else pe._version, pe.data_ptr())  # noqa: SLF001
+        hit = self._pos_cache.get(grid)
+        if hit is None or hit[0] != key:
+            with torch.no_grad():
+                hit = (key, resample_pos_embed(pe.detach(), self.native_grid, grid, dynamic=self.dynamic_img_size))
+            self._pos_cache[grid] = hit
+        return hit[1]
+
+    def _load_from_state_dict(self, *args, **kwargs) -> None:
+        self._pos_cache.clear()  # a new `pos_embed` is on its way
+        super()._load_from_state_dict(*args, **kwargs)
+
+    def forward(self, imgs: torch.Tensor) -> torch.Tensor:
+        grid = self.grid_of(imgs.shape[-2], imgs.shape[-1])
+        pos = self.pos_embed_for(grid)  # (refuses an off-grid size before any arithmetic)
+        x = self.patch_embed(imgs)
+        x = torch.cat([self.cls_token.expand(x.shape[0], -1, -1), x], dim=1) + pos
+        x = self.norm(self.blocks(x))
+        return x[:, 0]
+
+
+def create_vit(name: str, *, device: torch.device | str | None = None) -> VisionTransformer:
+    """The registered configuration ``name`` (``VIT_CONFIGS``); ``device="meta"`` builds the shapes only."""
+    if name not in VIT_CONFIGS:
+        msg = f"Backbone `{name}` is not supported."
+        raise ValueError(msg)
+    if device is not None:
+        with torch.device(device):
+            return VisionTransformer(**VIT_CONFIGS[name])
+    return VisionTransformer(**VIT_CONFIGS[name])

@@ -442,7 +442,28 @@ class EngineABC:
 
             on_gpu = torch.device(self.device).type == "cuda"
             m = copy.deepcopy(self.model)
-            if self.fold_batchnorm and hasattr(m, "feat_extract"):
+            from tiatoolbox_amd.models.architecture.vit import VisionTransformer
+
+            if isinstance(getattr(m, "feat_extract", None), VisionTransformer):
+                # Vision Transformer backbones (TimmBackbone).  GPU, fp16 / bf16: FusedViT -- every Linear on the half MFMA GEMM,
+                # attention, LayerNorm, GELU and token assembly on their own kernels (architecture/vit_fused.py; `prepare(dtype)`
+                # below).  GPU, float32: there is no float32 attention kernel, the torch module runs on the library's GEMMs -- never
+                # silently.  CPU: the torch module.  `conv_algo` has nothing to choose here.
+                if on_gpu and dtype != torch.float32:
+                    from tiatoolbox_amd.models.architecture.unet_fused import UnsupportedLayerError
+                    from tiatoolbox_amd.models.architecture.vit_fused import FusedViT
+
+                    m = m.to(device=self.device)
+                    try:
+                        m.feat_extract = FusedViT(m.feat_extract)
+                    except UnsupportedLayerError as exc:  # (the constructor's own refusal; any other error is a bug and propagates)
+                        logger.warning("%s: %s  Running the torch module in %s instead: its matrix products are library (hipBLASLt / "
+                                       "rocBLAS) GEMMs.", type(self.model).__name__, exc, dtype)
+                elif on_gpu:
+                    logger.warning("%s: the hand-written Vision Transformer kernels run in fp16 / bf16 only; compute_dtype=\"float32\" "
+                                   "runs the torch module on library (hipBLASLt / rocBLAS) GEMMs.  Pass compute_dtype=\"bfloat16\" for "
+                                   "the hand-written path.", type(self.model).__name__)
+            elif self.fold_batchnorm and hasattr(m, "feat_extract"):
                 from tiatoolbox_amd.models.architecture.fused import fuse_cnn_model
                 from tiatoolbox_amd.models.architecture.resnet import BasicBlock, Bottleneck
 
@@ -502,7 +523,7 @@ class EngineABC:
                     if type(mod).__name__ == "MfmaResNet":
                         mod.set_conv_algo(algo)  # run kwarg `conv_algo="winograd"`: opt-in float32 Winograd for the 3x3 / stride-1 layers
                         mod.prepare(dtype)
-                    elif type(mod).__name__ in ("FusedUNet", "FusedPlainUNet", "FusedHoVerNet") and dtype != torch.float32:
+                    elif type(mod).__name__ in ("FusedUNet", "FusedPlainUNet", "FusedHoVerNet", "FusedViT") and dtype != torch.float32:
                         mod.prepare(dtype)  # half weights from the float32 BN-folded ones; float32 biases / BN affines kept aside
             m = m.to(dtype=dtype) if dtype != torch.float32 else m
             if on_gpu:

@@ -1,4 +1,5 @@
-"""CPU emulation of conv3x3_wino_kernel's data flow (csrc/conv3x3_wino.hip) and of conv3x3_wino42_kernel's (csrc/conv3x3_wino42.hip): the packed-weight layout, the LDS images the DMAs build,
+"""CPU emulation of conv3x3_wino_kernel's data flow (csrc/conv3x3_wino.hip), of conv3x3_wino42_kernel's (csrc/conv3x3_wino42.hip) and of
+conv3x3_wino_bf16x3_kernel's (csrc/conv3x3_wino_bf16x3.hip): the packed-weight layout, the LDS images the DMAs build,
 every lane's fragment addresses, the MFMA operand / result layout, the two-group output transform and the epilogue's pixel mapping --
 index formula by index formula -- against torch's conv2d.  A developer check of the kernel's bookkeeping that needs no GPU
 (`python scripts/wino_emulate.py`); the GPU parity tests are tests/test_engine.py::test_winograd_*."""
@@ -404,6 +405,154 @@ def bank_check42():
     print("F(4x2) patch reads: conflict-free")
 
 
+# ---- split-operand F(2x2, 3x3) on the bf16 matrix cores: conv3x3_wino_bf16x3_kernel -------------------------------------------------
+def bf16_parts(v):
+    """float32 array -> (hi, mid, lo) float32 arrays holding bf16 values (round to nearest even; split_pair / split_stem_weights)."""
+    def rne(a):
+        u = a.astype(np.float32).view(np.uint32).astype(np.uint64)
+        return (((u + 0x7fff + ((u >> 16) & 1)) >> 16) << 16).astype(np.uint32).view(np.float32)
+    hi = rne(v)
+    r1 = (v - hi).astype(np.float32)
+    mid = rne(r1)
+    return hi, mid, rne((r1 - mid).astype(np.float32))
+
+
+def pack_split(w):  # fused.wino_weights_f32 + split_stem_weights + wino_pack_bf16x3_kernel
+    cout, cin = w.shape[:2]
+    n_cb = cout // 64
+    U = np.einsum("ir,ocrs,js->ocij", G2, w.astype(np.float64), G2).astype(np.float32)
+    parts = np.stack(bf16_parts(U))  # [3][cout][cin][4][4]
+    out = np.zeros(48 * cin * cout, np.float32)  # (bf16 values; element index = the kernel's bf16 index)
+    idx = np.arange(out.size)
+    e, col, q, r = idx & 7, (idx >> 3) & 63, (idx >> 9) & 1, idx >> 10
+    p, r = r % 3, r // 3
+    pos8, r = r & 7, r >> 3
+    cb, r = r % n_cb, r // n_cb
+    jh, cs = r & 1, r >> 1
+    out[idx] = parts[p, 64 * cb + col, 16 * cs + 8 * q + e, pos8 >> 1, 2 * jh + (pos8 & 1)]
+    return out
+
+
+def run_block_split(x, upk, mt_id, cb, pad, ho, wo, tiles_x, tiles_per_image):
+    n, h, w, cin = x.shape
+    cout = upk.size // (48 * cin)
+    TH, TW, PH, PWD, ROW, IMG, NT = 16, 16, 18, 18, 84, 18 * 84, 512
+    A_UNITS, W_UNITS = 1536, 3072  # patch buffer, weight stage (16-byte units)
+
+    def px_unit(px):
+        return (px >> 1) * 9 + (px & 1) * 4
+    n_cs, n_cb = cin // 16, cout // 64
+    img = mt_id // tiles_per_image
+    trem = mt_id - img * tiles_per_image
+    ty0, tx0 = (trem // tiles_x) * TH, (trem % tiles_x) * TW
+    xf = x.reshape(-1)
+    acc = np.zeros((8, 4, 2, 32, 32), np.float32)
+    order = ((2, 0), (0, 2), (1, 1), (1, 0), (0, 1), (0, 0))  # (V part, U part): lo hi, hi lo, mid mid, mid hi, hi mid, hi hi
+    for cs in range(n_cs):
+        abuf = np.zeros((A_UNITS, 4), np.float32)  # make_cen / dma_a: three whole rounds
+        for un in range(A_UNITS):
+            py, rem = divmod(un, ROW)
+            pair, r9 = divmod(rem, 9)
+            px, chunk = 2 * pair + (r9 >> 2), (4 if r9 == 8 else r9 & 3)
+            iy, ix = ty0 - pad + py, tx0 - pad + px
+            if img < n and py < PH and px < PWD and chunk < 4 and 0 <= iy < h and 0 <= ix < w:
+                off = (((img * h + iy) * w + ix) * cin * 4 + 16 * chunk + cs * 64) // 4
+                abuf[un] = xf[off:off + 4]
+        R = np.zeros((8, 64, 4, 8), np.float32)  # load_r: [wave][lane][patch column][channel 8 hi + e]
+        for wave in range(8):
+            i, wm = wave >> 1, wave & 1
+            ra = 0 if i == 0 else (2 if i == 2 else 1)
+            rb = 2 if i < 2 else (1 if i == 2 else 3)
+            for lane in range(64):
+                hi, t = lane >> 5, 32 * wm + (lane & 31)
+                fa = 2 * (t >> 3) * ROW + (t & 7) * 9 + 2 * hi
+                for c in range(4):
+                    a = np.concatenate([abuf[fa + ra * ROW + px_unit(c) + q] for q in range(2)])
+                    b = np.concatenate([abuf[fa + rb * ROW + px_unit(c) + q] for q in range(2)])
+                    R[wave, lane, c] = a + b if i == 1 else a - b
+        for jh in range(2):
+            s_step = 2 * cs + jh
+            wst = np.zeros((W_UNITS, 8), np.float32)  # dma_w: six rounds, a wave's KB each; a unit = 8 bf16
+            for q in range(6):
+                for wave in range(8):
+                    for lane in range(64):
+                        src = ((s_step * n_cb + cb) * 49152 + q * 8192 + wave * 1024 + lane * 16) // 2
+                        wst[q * 512 + wave * 64 + lane] = upk[src:src + 8]
+            for wave in range(8):
+                i = wave >> 1
+                for jl in range(2):
+                    j = 2 * jh + jl
+                    r_ = R[wave]
+                    V = [r_[:, 0] - r_[:, 2], r_[:, 1] + r_[:, 2], r_[:, 2] - r_[:, 1], r_[:, 1] - r_[:, 3]][j].astype(np.float32)  # [lane][8]
+                    vp = bf16_parts(V)
+                    for ct in range(2):
+                        up = []
+                        for p in range(3):  # plane p of position (i, jl): [k-chunk hi][column]
+                            frag = np.stack([wst[((i * 2 + jl) * 3 + p) * 128 + (lane >> 5) * 64 + ct * 32 + (lane & 31)] for lane in range(64)])
+                            up.append(np.concatenate([frag[:32], frag[32:]], axis=1).T)  # [k 16][col 32]
+                        for pv, pu in order:
+                            A = np.concatenate([vp[pv][:32], vp[pv][32:]], axis=1)  # [row 32][k 16]: lane >> 5 holds k = 8 (lane >> 5) ..
+                            acc[wave, j, ct] = (acc[wave, j, ct].astype(np.float64) + A.astype(np.float64) @ up[pu].astype(np.float64)).astype(np.float32)
+    # ---- epilogue of conv3x3_wino_kernel (W16)
+    tile = np.zeros((256, 64), np.float32)
+    for wm in range(2):
+        z = [[[acc[2 * i + wm][0, ct] + acc[2 * i + wm][1, ct] + acc[2 * i + wm][2, ct] for ct in range(2)],
+              [acc[2 * i + wm][1, ct] - acc[2 * i + wm][2, ct] - acc[2 * i + wm][3, ct] for ct in range(2)]] for i in range(4)]
+        for b in range(2):
+            for ct in range(2):
+                y0 = (z[0][b][ct] + z[1][b][ct]) + z[2][b][ct]
+                y1 = z[1][b][ct] + (-z[3][b][ct] - z[2][b][ct])
+                for row in range(32):
+                    tt = 32 * wm + row
+                    m00 = 2 * (tt >> 3) * TW + 2 * (tt & 7)
+                    tile[m00 + b, ct * 32:ct * 32 + 32] = y0[row]
+                    tile[m00 + TW + b, ct * 32:ct * 32 + 32] = y1[row]
+    out = {}
+    for row in range(256):
+        oy, ox = ty0 + row // TW, tx0 + row % TW
+        if oy < ho and ox < wo and img < n:
+            out[(img, oy, ox)] = tile[row]
+    return out
+
+
+def check_split(n, hw, cin, cout, pad=1, seed=0):
+    rng = np.random.default_rng(seed)
+    x = rng.standard_normal((n, hw, hw, cin)).astype(np.float32)
+    wgt = (rng.standard_normal((cout, cin, 3, 3)) / np.sqrt(9 * cin)).astype(np.float32)
+    ho = wo = hw + 2 * pad - 2
+    ref = F.conv2d(torch.from_numpy(x).permute(0, 3, 1, 2), torch.from_numpy(wgt), padding=pad).permute(0, 2, 3, 1).numpy()
+    upk = pack_split(wgt)
+    tiles_y, tiles_x = (ho + 15) // 16, (wo + 15) // 16
+    got = np.full_like(ref, np.nan)
+    for mt in range(n * tiles_y * tiles_x):
+        for cb in range(cout // 64):
+            for (b, oy, ox), v in run_block_split(x, upk, mt, cb, pad, ho, wo, tiles_x, tiles_y * tiles_x).items():
+                got[b, oy, ox, cb * 64:cb * 64 + 64] = v
+    assert not np.isnan(got).any(), "outputs not covered"
+    err = np.abs(got - ref).max() / np.abs(ref).max()
+    print(f"split F(2x2) n={n} hw={hw} cin={cin} cout={cout} pad={pad}: rel err {err:.2e}")
+    assert err < 1e-5, err
+
+
+def bank_check_split():
+    """The split form's reads.  Patch: units 2 hi + q of a pixel -- the same offset for all lanes of a service group (hi = lane >> 5), so
+    bank_check()'s W16 argument holds; checked here with the offset.  Weights: the 32 lanes of a half-wave read 32 consecutive units."""
+    groups = [[0, 1, 2, 3, 12, 13, 14, 15, 20, 21, 22, 23, 24, 25, 26, 27], [4, 5, 6, 7, 8, 9, 10, 11, 16, 17, 18, 19, 28, 29, 30, 31]]
+    for wm in range(2):
+        for hi in range(2):
+            for q in range(2):
+                for grp in groups:
+                    units = [(2 * ((32 * wm + ln) >> 3) * 84 + ((32 * wm + ln) & 7) * 9 + 2 * hi + q) % 16 for ln in grp]
+                    assert len(set(units)) == 16, (wm, hi, q, grp, units)
+    for grp in groups:
+        assert len({ln % 16 for ln in grp}) == 16  # (+ a multiple of 16 units per position, plane, k-chunk and channel tile)
+    # LDS map [patch 0][stage 0][patch 1][stage 1]; the epilogue's 64 KB from patch 1 on; every read inside its buffer
+    a_bytes, w_stage = 1536 * 16, 8 * 3 * 2048
+    assert 2 * a_bytes + 2 * w_stage == 147456 <= 160 * 1024 and a_bytes + w_stage + 65536 <= 147456
+    assert 2 * 7 * 84 + 7 * 9 + 2 + 3 * 84 + 13 + 1 < 1536 and (3 * 2 + 1) * 3 * 128 + 256 + 64 + 32 + 31 < 3072
+    print("split F(2x2) reads: conflict-free, inside their buffers")
+
+
 if __name__ == "__main__":
     bank_check()
     if "--windows-only" not in __import__("sys").argv:
@@ -419,3 +568,7 @@ if __name__ == "__main__":
     check42(5, 8, 16, 64)            # F(4x2), four-image blocks, a partial block of images
     check42(1, 32, 16, 128)          # F(4x2), four blocks, two channel blocks
     print("emulation ok")
+    bank_check_split()
+    check_split(1, 16, 32, 64)       # split F(2x2): one full block, two slices
+    check_split(2, 19, 16, 128, 0)   # partial blocks, two channel blocks, valid convolution
+    check_split(3, 7, 48, 64, 2)     # a small map in a 16 x 16 block, an odd slice count, padding 2

@@ -1,5 +1,5 @@
 // Device leaves shared by the convolution kernels (conv3x3_wino.hip, conv3x3_wino42.hip, conv3x3_spatial.hip, conv_mfma.hip,
-// conv_mfma_h.hip, conv_ring_bf16x3.hip, stem_mfma.hip) and the half-precision glue (cnn_epilogue_h.hip); internal, not part of
+// conv_mfma_h.hip, conv_ring_bf16x3.hip, conv3x3_wino_bf16x3.hip, stem_mfma.hip) and the half-precision glue (cnn_epilogue_h.hip); internal, not part of
 // the C ABI.  Every device function here is a __forceinline__ leaf over scalars, and only what leaves the kernels' instruction
 // streams as they were is shared (profiles/conv_gemm_refactor_isa.txt; DESIGN 4.28 says what could not be).  The kernels keep
 // their own helpers in anonymous namespaces and say `using namespace tia;` inside them.  The host side of the implicit-GEMM
@@ -49,6 +49,49 @@ __device__ __forceinline__ f32x2 pk_sub(f32x2 a, f32x2 b) {
     f32x2 r;
     asm("v_pk_add_f32 %0, %1, %2 neg_lo:[0,1] neg_hi:[0,1]" : "=v"(r) : "v"(a), "v"(b));
     return r;
+}
+
+// ---- the three-part bf16 split of a float32 operand in registers (conv_ring_bf16x3.hip, conv3x3_wino_bf16x3.hip) ----
+
+using bf16x2 = __attribute__((ext_vector_type(2))) __bf16;
+
+// two float32 -> two bf16 (round to nearest even) in one register: v_cvt_pk_bf16_f32; element 0 in the low half
+__device__ __forceinline__ unsigned cvt_pk_bf16(float v0, float v1) {
+    const bf16x2 p = __builtin_convertvector(f32x2{v0, v1}, bf16x2);
+    unsigned r;
+    __builtin_memcpy(&r, &p, 4);
+    return r;
+}
+
+// a - b as ONE v_sub_f32.  Inline assembly: left to itself the compiler pairs the split's subtractions into v_pk_add_f32, and a
+// packed float32 instruction beside the MFMA stream costs more than the two plain ones it replaces (pk_add / pk_sub above are the
+// opposite case).  The arithmetic is the same IEEE subtraction either way.
+__device__ __forceinline__ float sub_f32(float a, float b) {
+    float r;
+    asm("v_sub_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
+    return r;
+}
+
+// a + b as ONE v_add_f32 (the same reason)
+__device__ __forceinline__ float add_f32(float a, float b) {
+    float r;
+    asm("v_add_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
+    return r;
+}
+
+// (v0, v1) -> packed hi, mid, lo with v = hi + mid + lo exactly; the subtractions are plain float32 subtractions of a value and
+// its own rounding (exact: the difference has at most 16, then 8, significant bits)
+__device__ __forceinline__ void split_pair(float v0, float v1, unsigned& ph, unsigned& pm, unsigned& pl) {
+    ph = cvt_pk_bf16(v0, v1);
+    const float r0 = sub_f32(v0, __uint_as_float(ph << 16)), r1 = sub_f32(v1, __uint_as_float(ph & 0xffff0000u));
+    pm = cvt_pk_bf16(r0, r1);
+    const float s0 = sub_f32(r0, __uint_as_float(pm << 16)), s1 = sub_f32(r1, __uint_as_float(pm & 0xffff0000u));
+    pl = cvt_pk_bf16(s0, s1);
+}
+
+// v_mfma_f32_32x32x16_bf16: a lane holds row (column) lane & 31, k = 8 (lane >> 5) .. + 7 of A (B) as eight bf16 in four registers
+__device__ __forceinline__ f32x16 mfma_bf16(const u32x4& a, const u32x4& b, const f32x16& c) {
+    return __builtin_amdgcn_mfma_f32_32x32x16_bf16(*reinterpret_cast<const b8*>(&a), *reinterpret_cast<const b8*>(&b), c, 0, 0, 0);
 }
 
 // The Winograd kernels' LDS patch rows, in 16-byte units: pixels are stored in PAIRS of 9 units (two pixels of 4 units + one padding

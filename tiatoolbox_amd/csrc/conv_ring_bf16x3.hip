@@ -61,39 +61,6 @@ using namespace tia;
 #define SSTAMP(i)
 #endif
 
-using bf16x2 = __attribute__((ext_vector_type(2))) __bf16;
-
-// two float32 -> two bf16 (round to nearest even) in one register: v_cvt_pk_bf16_f32; element 0 in the low half
-__device__ __forceinline__ unsigned cvt_pk_bf16(float v0, float v1) {
-    const bf16x2 p = __builtin_convertvector(f32x2{v0, v1}, bf16x2);
-    unsigned r;
-    __builtin_memcpy(&r, &p, 4);
-    return r;
-}
-
-// a - b as ONE v_sub_f32.  Inline assembly: left to itself the compiler pairs the split's subtractions into v_pk_add_f32, and a
-// packed float32 instruction beside the MFMA stream costs more than the two plain ones it replaces (conv_device.hpp has the
-// opposite case).  The arithmetic is the same IEEE subtraction either way.
-__device__ __forceinline__ float sub_f32(float a, float b) {
-    float r;
-    asm("v_sub_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
-    return r;
-}
-
-// (v0, v1) -> packed hi, mid, lo with v = hi + mid + lo exactly; the subtractions are plain float32 subtractions of a value and
-// its own rounding (exact: the difference has at most 16, then 8, significant bits)
-__device__ __forceinline__ void split_pair(float v0, float v1, unsigned& ph, unsigned& pm, unsigned& pl) {
-    ph = cvt_pk_bf16(v0, v1);
-    const float r0 = sub_f32(v0, __uint_as_float(ph << 16)), r1 = sub_f32(v1, __uint_as_float(ph & 0xffff0000u));
-    pm = cvt_pk_bf16(r0, r1);
-    const float s0 = sub_f32(r0, __uint_as_float(pm << 16)), s1 = sub_f32(r1, __uint_as_float(pm & 0xffff0000u));
-    pl = cvt_pk_bf16(s0, s1);
-}
-
-__device__ __forceinline__ f32x16 mma(const u32x4& a, const u32x4& b, const f32x16& c) {
-    return __builtin_amdgcn_mfma_f32_32x32x16_bf16(*reinterpret_cast<const b8*>(&a), *reinterpret_cast<const b8*>(&b), c, 0, 0, 0);
-}
-
 template <int BN>
 __global__ __launch_bounds__(512, 4) void conv_ring_bf16x3_kernel(const float* __restrict__ x, const void* __restrict__ wk,
                                                                  const float* __restrict__ bias, const float* __restrict__ res,
@@ -200,12 +167,12 @@ __global__ __launch_bounds__(512, 4) void conv_ring_bf16x3_kernel(const float* _
 #pragma unroll
         for (int j = 0; j < NTILE; ++j) {
             const u32x4 bh = sb[j * 32], bm = sb[2 * BN + j * 32], bl = sb[4 * BN + j * 32];
-            acc[j] = mma(al, bh, acc[j]);
-            acc[j] = mma(ah, bl, acc[j]);
-            acc[j] = mma(am, bm, acc[j]);
-            acc[j] = mma(am, bh, acc[j]);
-            acc[j] = mma(ah, bm, acc[j]);
-            acc[j] = mma(ah, bh, acc[j]);
+            acc[j] = mfma_bf16(al, bh, acc[j]);
+            acc[j] = mfma_bf16(ah, bl, acc[j]);
+            acc[j] = mfma_bf16(am, bm, acc[j]);
+            acc[j] = mfma_bf16(am, bh, acc[j]);
+            acc[j] = mfma_bf16(ah, bm, acc[j]);
+            acc[j] = mfma_bf16(ah, bh, acc[j]);
         }
         __builtin_amdgcn_sched_barrier(0);  // the slice's MFMAs are issued HERE, in front of the wait: they are the DMA's cover
         asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");

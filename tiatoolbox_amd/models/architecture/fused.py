@@ -664,6 +664,53 @@ def pack_conv_weights_wino42(conv: nn.Conv2d) -> torch.Tensor:
     return _pack_conv_weights_wino(conv, 24, "tia_conv_pack_weights_wino42_f32", "F(4x2, 3x3)")
 
 
+def wino_weights_f32(weight: torch.Tensor) -> torch.Tensor:
+    """OIHW 3x3 weights -> ``U = G g G^T`` as ``[cout, cin, 4, 4]`` float32: transformed in float64 in the operation order of
+    ``tia_conv_pack_weights_wino_f32`` and rounded once, so the values are bit for bit that packing's.  Device-agnostic."""
+    g = weight.detach().to(torch.float64)
+
+    def rows(t: torch.Tensor, dim: int) -> torch.Tensor:  # G t along `dim` (G = [1 0 0; .5 .5 .5; .5 -.5 .5; 0 0 1])
+        t0, t1, t2 = t.unbind(dim)
+        return torch.stack((t0, 0.5 * (t0 + t1 + t2), 0.5 * (t0 - t1 + t2), t2), dim)
+
+    return rows(rows(g, 2), 3).to(torch.float32)
+
+
+def pack_conv_weights_wino_split(conv: nn.Conv2d) -> torch.Tensor | None:
+    """OIHW 3x3 float32 -> the three bf16 planes of the Winograd-domain weights in the stage layout of
+    ``tia_conv3x3_wino_bf16x3_nhwc_f32``, ``[cin/16, 2, cout/64, 8, 3, 2, 64, 8]`` bf16 (slice, column pair of the position grid,
+    64-column block, position ``2 i + jl``, plane, k-chunk, column, channel): ``U`` from :func:`wino_weights_f32` (what the float32
+    form multiplies by), split by :func:`split_stem_weights`, laid out by ``tia_conv_pack_weights_wino_bf16x3``.  ``None`` when ``U``
+    has no usable exact split (one ``info`` line): the layer then keeps the float32 Winograd form."""
+    from tiatoolbox_amd import _lib
+
+    w = conv.weight.detach().to(torch.float32).contiguous()
+    cout, cin, kh, kw = w.shape
+    if (kh, kw) != (3, 3) or cin % 16 or cout % 64 or conv.groups != 1:
+        msg = f"the split Winograd form needs a 3x3 kernel, cin % 16 == 0, cout % 64 == 0 and groups == 1; got weight {tuple(w.shape)}."
+        raise ValueError(msg)
+    parts, usable = split_stem_weights(wino_weights_f32(w))
+    if not usable:
+        logger.info("a %s convolution's Winograd-domain weights have no exact three-part bf16 split (non-finite or extreme "
+                    "exponents); the layer keeps the float32 Winograd form.", tuple(w.shape))
+        return None
+    parts = parts.contiguous()
+    out = torch.empty((cin // 16, 2, cout // 64, 8, 3, 2, 64, 8), dtype=torch.bfloat16, device=w.device)
+    with torch.cuda.device(w.device):
+        rc = _lib.load().tia_conv_pack_weights_wino_bf16x3(parts.data_ptr(), cout, cin, out.data_ptr(), _lib.current_stream())
+    _lib.check(rc, "tia_conv_pack_weights_wino_bf16x3")
+    return out
+
+
+@functools.lru_cache(maxsize=256)
+def wino_split_serves(n: int, h: int, w: int, cin: int, cout: int, pad: int) -> bool:
+    """Whether the fused resnet blocks run this "same"-padded 3x3 / stride-1 layer on the split-operand Winograd form under
+    ``conv_algo="auto"`` (``tia_conv3x3_wino_bf16x3_serves``, a host-only query)."""
+    from tiatoolbox_amd import _lib
+
+    return _lib.load().tia_conv3x3_wino_bf16x3_serves(n, h, w, cin, cout, pad) == 1
+
+
 @functools.lru_cache(maxsize=256)
 def wino_form(n: int, h: int, w: int, cin: int, cout: int, pad: int) -> int:
     """Which Winograd form the fused resnet blocks take for a "same"-padded 3x3 / stride-1 layer (``tia_conv3x3_wino_form``, a
@@ -677,8 +724,9 @@ def hip_conv3x3_wino(x: torch.Tensor, u_packed: torch.Tensor, bias: torch.Tensor
                      padding: int, relu: bool, pad_hi: int | None = None) -> torch.Tensor:
     """``relu(conv3x3(x, w) + bias + residual)``, stride 1, through a Winograd kernel: F(2x2, 3x3) (``tia_conv3x3_wino_nhwc_f32``) for
     weights from :func:`pack_conv_weights_wino` (leading dimension 16), F(4x2, 3x3) (``tia_conv3x3_wino42_nhwc_f32``) for weights from
-    :func:`pack_conv_weights_wino42` (24).  float32 in / float32 accumulate like :func:`hip_conv2d`, 2.25 x / 3 x fewer multiplies,
-    results within ~1e-5 (relative) of it."""
+    :func:`pack_conv_weights_wino42` (24), F(2x2, 3x3) on the bf16 matrix cores with both operands split
+    (``tia_conv3x3_wino_bf16x3_nhwc_f32``) for the bf16 planes from :func:`pack_conv_weights_wino_split`.  float32 in / float32
+    accumulate like :func:`hip_conv2d`, 2.25 x / 3 x fewer multiplies, results within ~1e-5 (relative) of it."""
     from tiatoolbox_amd import _lib
 
     if not (_nhwc_ptr_ok(x) and x.dtype == torch.float32):
@@ -688,14 +736,22 @@ def hip_conv3x3_wino(x: torch.Tensor, u_packed: torch.Tensor, bias: torch.Tensor
         msg = "hip_conv3x3_wino expects a float32 channels-last CUDA residual."
         raise ValueError(msg)
     n, cin, h, w = x.shape
-    npos = u_packed.shape[0] if u_packed.dim() == 7 else 0  # noqa: PLR2004
-    if (npos not in (16, 24) or cin % 16 or tuple(u_packed.shape) != (npos, cin // 16, 2, u_packed.shape[3], 2, 64, 4)
-            or u_packed.dtype != torch.float32 or not u_packed.is_contiguous() or u_packed.device != x.device):
+    split = u_packed.dtype == torch.bfloat16
+    if split:
+        ok = u_packed.dim() == 8 and tuple(u_packed.shape) == (cin // 16, 2, u_packed.shape[2], 8, 3, 2, 64, 8)  # noqa: PLR2004
+        npos, n_cb = 16, u_packed.shape[2] if ok else 0
+    else:
+        npos = u_packed.shape[0] if u_packed.dim() == 7 else 0  # noqa: PLR2004
+        ok = (npos in (16, 24) and tuple(u_packed.shape) == (npos, cin // 16, 2, u_packed.shape[3], 2, 64, 4)
+              and u_packed.dtype == torch.float32)
+        n_cb = u_packed.shape[3] if ok else 0
+    if not ok or cin % 16 or not u_packed.is_contiguous() or u_packed.device != x.device:
         msg = (f"hip_conv3x3_wino: packed weights {tuple(u_packed.shape)} {u_packed.dtype} on {u_packed.device} do not match an input with "
                f"{cin} channels on {x.device} (expected pack_conv_weights_wino's [16, cin/16, 2, cout/64, 2, 64, 4] or "
-               f"pack_conv_weights_wino42's [24, ...] float32, contiguous).")
+               f"pack_conv_weights_wino42's [24, ...] float32, or pack_conv_weights_wino_split's [cin/16, 2, cout/64, 8, 3, 2, 64, 8] "
+               f"bf16, contiguous).")
         raise ValueError(msg)
-    cout = u_packed.shape[3] * 64
+    cout = n_cb * 64
     behind = padding if pad_hi is None else pad_hi  # zero rows / columns behind the image (`padding` in front): "same", valid, TF-same
     ho, wo = h + padding + behind - 2, w + padding + behind - 2
     y = torch.empty((n, cout, ho, wo), dtype=torch.float32, device=x.device, memory_format=torch.channels_last)
@@ -703,6 +759,8 @@ def hip_conv3x3_wino(x: torch.Tensor, u_packed: torch.Tensor, bias: torch.Tensor
         msg = f"residual shape {tuple(residual.shape)} != output shape {tuple(y.shape)}"
         raise ValueError(msg)
     name = "tia_conv3x3_wino_nhwc_f32" if npos == 16 else "tia_conv3x3_wino42_nhwc_f32"  # noqa: PLR2004
+    if split:
+        name = "tia_conv3x3_wino_bf16x3_nhwc_f32"
     with torch.cuda.device(x.device):
         rc = getattr(_lib.load(), name)(x.data_ptr(), u_packed.data_ptr(), _ptr(bias), _ptr(residual), y.data_ptr(), n, h, w, cin, cout,
                                         padding, padding, ho, wo, int(relu), _lib.current_stream())
@@ -720,17 +778,26 @@ class _MfmaBlock(nn.Module):
 
     def __init__(self) -> None:
         super().__init__()
-        self._packed: dict[tuple[str, torch.dtype], torch.Tensor] = {}
+        self._packed: dict[tuple[str, torch.dtype | str], torch.Tensor | None] = {}  # (None: a split form without a usable split)
         self._bias32: dict[str, torch.Tensor] = {}
 
     def _wino(self, name: str, x: torch.Tensor | None = None) -> torch.Tensor | None:
         """The layer's Winograd-domain weights if it is to run on that kernel (float32 3x3 / stride 1, cin % 16, cout % 64): F(4x2, 3x3)
-        where the route query :func:`wino_form` takes it for the input ``x``, F(2x2, 3x3) otherwise (and without an input)."""
+        where the route query :func:`wino_form` takes it for the input ``x``, F(2x2, 3x3) otherwise (and without an input); the bf16
+        planes of the split-operand F(2x2, 3x3) where :func:`wino_split_serves` says so for ``x`` and ``U`` has a usable split."""
         conv = getattr(self, name)
         if (self.conv_algo != "winograd" or conv.kernel_size != (3, 3) or conv.stride != (1, 1) or conv.dilation != (1, 1)
                 or conv.groups != 1 or conv.in_channels % 16 or conv.out_channels % 64 or conv.padding[0] != conv.padding[1]
                 or conv.padding[0] > 2):  # noqa: PLR2004
             return None
+        # the split form where the route query takes the input; like F(4x2) its planes are packed by the first forward that is routed
+        # to them (without an input -- `prepare` -- nothing says which shapes will come, and the table lives in the library alone)
+        if x is not None and wino_split_serves(x.shape[0], x.shape[2], x.shape[3], conv.in_channels, conv.out_channels, conv.padding[0]):
+            key = (name, "wino_split")
+            if key not in self._packed or (self._packed[key] is not None and self._packed[key].device != conv.weight.device):
+                self._packed[key] = pack_conv_weights_wino_split(conv)  # None: no usable split (remembered: asked once per device)
+            if self._packed[key] is not None:
+                return self._packed[key]
         key, pack = (name, "wino"), pack_conv_weights_wino
         if x is not None and wino_form(x.shape[0], x.shape[2], x.shape[3], conv.in_channels, conv.out_channels, conv.padding[0]) == 1:
             key, pack = (name, "wino42"), pack_conv_weights_wino42

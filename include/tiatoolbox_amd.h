@@ -447,11 +447,14 @@ int tia_lab_convert_u8(const uint8_t* d_src, int64_t npix, const tia_lab_tables*
                        uint8_t* d_dst, void* stream);
 
 /* ReinhardNormalizer.transform in ONE launch for a batch of patches (stainnorm.py:272-367): per patch RGB->Lab, the channel
- * moments (cv2.meanStdDev, float64 in NumPy's pairwise order), the three float32 byte tables, table -> Lab->RGB.  The Lab image is
- * parked as one dword per pixel in a per-workgroup slot of d_workspace (tia_reinhard_workspace_bytes; it stays in L2 / Infinity
- * Cache), so HBM carries 3 bytes in + 3 bytes out per pixel.  Shapes it does not take (h*w not a multiple of 1024 or above 2^18
- * pixels, buffers not 16-byte aligned) return TIA_ESIZE: use tia_lab_hist_u8 + tia_reinhard_luts + tia_reinhard_apply_u8, which
- * split a large image over many workgroups.  d_chan_vals: float32 [3,256] channel value of every Lab byte (host-built, :295-315);
+ * moments (cv2.meanStdDev, float64 in NumPy's pairwise order), the three float32 byte tables, table -> Lab->RGB.  Up to 65536
+ * pixels with h*w a multiple of 4 the Lab image stays in registers (no workspace: tia_reinhard_workspace_bytes returns 0); up to
+ * 2^18 pixels with h*w a multiple of 256 it is parked as one dword per pixel in a per-workgroup slot of d_workspace
+ * (tia_reinhard_workspace_bytes, 16-byte aligned; it stays in L2 / Infinity Cache).  Either way HBM carries 3 bytes in + 3 bytes
+ * out per pixel.  d_img and d_out need 4-byte alignment.  Anything else (another h*w, a d_img or d_out that is not 4-byte aligned)
+ * returns TIA_ESIZE with nothing launched: use tia_lab_hist_u8 + tia_reinhard_luts + tia_reinhard_apply_u8, which split a large
+ * image over many workgroups (16-byte accesses when h*w is a multiple of 1024 and the buffers are 16-byte aligned, bytes
+ * otherwise).  d_chan_vals: float32 [3,256] channel value of every Lab byte (host-built, :295-315);
  * target_means / target_stds: host double[3]; d_meanstd (nullable) [n,6]; d_flags (nullable) [n]: bit 0 = zero std (the reference
  * raises ZeroDivisionError). */
 size_t tia_reinhard_workspace_bytes(int64_t n, int64_t h, int64_t w);

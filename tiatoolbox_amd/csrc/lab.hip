@@ -463,7 +463,8 @@ __device__ __forceinline__ void fused_moments(FusedLds& s, const AbSums& ab, lon
 }
 
 // STATS_ONLY: the statistics half alone (get_mean_std / fit): nothing parked, nothing written but six doubles per image.
-// Requires hw % 1024 == 0 and 16-byte aligned images (the launcher checks).  scratch: gridDim.x slots of hw dwords.
+// Requires hw % 256 == 0 (whole wave steps of 64 lanes x 4 pixels), hw <= 2^18, 4-byte aligned img / out (12-byte lane accesses) and a
+// 16-byte aligned scratch (the launchers check).  scratch: gridDim.x slots of hw dwords.
 template <bool STATS_ONLY>
 __global__ __launch_bounds__(FT) void reinhard_fused_kernel(const uint8_t* __restrict__ img, long n, long hw,
                                                              const tia_lab_tables* __restrict__ tab,

@@ -718,7 +718,12 @@ int tia_conv1x1_pre_nhwc_f32(const float* d_x, const float* d_pre_scale, const f
  *   d_y [n,hp,wp,64] of y_dtype (TIA_DT_F32; TIA_DT_F16 / TIA_DT_BF16: rounded once, for the half-precision trunk),
  *   hp = ((h-1)/2)/2 + 1 (likewise wp); arithmetic: a float32 fmaf chain in (ky, kx, c) order on the matrix cores.
  *   d_conv_out (may be NULL): also write relu(conv + bias) BEFORE the pooling, [n,ho,wo,64] float32, ho = (h-1)/2 + 1 -- the
- *   first skip connection of the UNet decoder (models/architecture/unet.py:356-372, ResNetEncoder features). */
+ *   first skip connection of the UNet decoder (models/architecture/unet.py:356-372, ResNetEncoder features).
+ * Limits of every tia_stem_conv7x7_pool_* entry point (tests/test_stem_reference.py): TIA_EINVAL for a null d_x / d_w_packed /
+ * d_bias / d_y, n, h or w <= 0, a y_dtype that is no TIA_DT_* value, d_y or the packed weights not 16-byte aligned, a float32 d_x
+ * not 4-byte aligned (a uint8 d_x may start at any byte); TIA_ESIZE for ONE image of more than 2^31 - 1 bytes (h * w * 3 uint8,
+ * h * w * 12 float32), refused before any launch.  Any image size below that is served (also below the 7x7 window); a batch of
+ * more than 2^31 - 1 bytes runs in equal groups of whole images, one launch each. */
 int tia_stem_conv7x7_pool_nhwc(const void* d_x, int32_t x_is_u8, const float* d_w_packed, const float* d_bias, void* d_y,
                                int32_t y_dtype, float* d_conv_out, int64_t n, int64_t h, int64_t w, void* stream);
 /* The same kernel and the same float32 arithmetic with the pre-pool output in y_dtype as well (additive at version 6):

@@ -43,7 +43,8 @@ extern "C" {
  * (the same at any down-sampling ratio), tia_gather_cubic_resize_u8 (patch reads above the slide's resolution),
  * tia_conv3x3_grouped_nhwc_f32 (the grouped 3x3 of ResNeXt), tia_stem_pack_weights_bf16x3 / tia_stem_conv7x7_pool_nhwc_u8x3 (the
  * uint8 stem on the bf16 matrix cores with exactly split float32 weights); tia_mha_fwd_h, tia_layernorm_rows_h, tia_gelu_rows_h,
- * tia_vit_patchify_h, tia_vit_assemble_tokens_h (the Vision Transformer backbones in fp16 / bf16). */
+ * tia_vit_patchify_h, tia_vit_assemble_tokens_h (the Vision Transformer backbones in fp16 / bf16); tia_swiglu_rows_h,
+ * tia_vit_patchify_pad_h, tia_vit_assemble_prefix_h (UNI2, H-optimus and prov-gigapath on the same graph). */
 #define TIA_ABI_VERSION 6
 int tia_abi_version(void);
 
@@ -932,6 +933,31 @@ int tia_vit_patchify_h(const void* d_x, int32_t x_dtype, void* d_tokens, int64_t
  *   d_tokens [n,g,d] of `dtype`   d_cls [d], d_pos [1+g, d] float32.   float32 add, ONE rounding.  d % 8 == 0 (else TIA_ESIZE). */
 int tia_vit_assemble_tokens_h(const void* d_tokens, const float* d_cls, const float* d_pos, void* d_out, int64_t n, int64_t g,
                               int64_t d, int32_t dtype, void* stream);
+
+/* The foundation models' additions (UNI2, H-optimus-0 / -1, prov-gigapath: register tokens, a position table without a class
+ * entry, a 14-pixel patch, timm's SwiGLUPacked).  Additive, same version (6); the contract of the family above. */
+
+/* Packed SwiGLU on the fc1 output: y[r,j] = silu(x[r,j]) * x[r,H+j] with silu(t) = t / (1 + exp(-t)) -- the FIRST half is the gate.
+ *   d_x [rows, 2H], d_y [rows, H] of `dtype`; not in place.  float32 arithmetic, ONE rounding; evaluated through exp(-|t|), so no
+ * gate overflows: a large negative gate gives the tiny product (or a signed zero), a large positive one x[r,j] * x[r,H+j].
+ * H % 8 == 0 (else TIA_ESIZE). */
+int tia_swiglu_rows_h(const void* d_x, void* d_y, int64_t rows, int64_t hidden, int32_t dtype, void* stream);
+
+/* tia_vit_patchify_h for any patch >= 1, with padded rows: d_tokens [n, (h/patch) * (w/patch), k_pad] of `dtype`; columns
+ * 0 .. 3 patch^2 - 1 are the patch in (ky, kx, channel) order, columns 3 patch^2 .. k_pad - 1 exact zeros, so that the embedding
+ * stays one 1x1 GEMM (cin = k_pad, weight rows zero-padded alike) when 3 patch^2 is no multiple of 32 (patch 14: 588 -> 608).
+ *   d_x [n,h,w,3] NHWC of x_dtype (TIA_DT_F32, or `dtype` itself: copied as it is).
+ * h % patch == 0, w % patch == 0, k_pad % 32 == 0 and k_pad >= 3 patch^2 (else TIA_ESIZE). */
+int tia_vit_patchify_pad_h(const void* d_x, int32_t x_dtype, void* d_tokens, int64_t n, int64_t h, int64_t w, int64_t patch,
+                           int64_t k_pad, int32_t dtype, void* stream);
+
+/* Token assembly with register tokens: d_out [n, 1+R+g, d] of `dtype` with out[b,0] = cls (+ pos[0] if pos_has_cls),
+ * out[b,1+r] = reg[r], out[b,1+R+i] = tokens[b,i] + pos[i + pos_has_cls].
+ *   d_tokens [n,g,d] of `dtype`   d_cls [d], d_reg [R,d] (NULL exactly when R == 0), d_pos [g + pos_has_cls, d] float32
+ *   pos_has_cls 0 | 1 (anything else TIA_EINVAL).   float32 add, ONE rounding; R = 0 with pos_has_cls = 1 is
+ * tia_vit_assemble_tokens_h bit for bit.  d % 8 == 0 (else TIA_ESIZE). */
+int tia_vit_assemble_prefix_h(const void* d_tokens, const float* d_cls, const float* d_reg, const float* d_pos, int32_t pos_has_cls,
+                              void* d_out, int64_t n, int64_t g, int64_t reg_tokens, int64_t d, int32_t dtype, void* stream);
 
 /* =======================================================================================
  * All borders of binary planes: cv2.findContours(layer, RETR_TREE, CHAIN_APPROX_NONE | _SIMPLE)

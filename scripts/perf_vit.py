@@ -2,7 +2,8 @@
 on the same device (library GEMMs and attention), in ONE session, alternating:
 
 1. whole forward (normalised float patches in the run's dtype -> float32 features) of a seeded ``--model`` (default ``UNI``: ViT-L/16 with
-   LayerScale) on ``--batch`` x ``--side``^2 patches, in bfloat16 and float16;
+   LayerScale; any name of ``VIT_CONFIGS``, e.g. ``UNI2`` or ``H-optimus-0``) on ``--batch`` x ``--side``^2 patches, in
+   bfloat16 and float16;
 2. the algorithmic flops of that forward (GEMMs and the two attention products, from the shapes) over the time: TFLOP/s end to end.
 
 ``--trace-only DTYPE``: warm up, then run the fused forward ``--reps`` times and exit -- the program to put behind
@@ -54,11 +55,14 @@ def alternate(variants: dict, rounds: int, reps: int) -> dict:
 
 
 def forward_flops(cfg: dict, depth: int, batch: int, side: int) -> dict:
-    """Multiply-adds x 2 of one forward, from the shapes: the GEMMs (patch embedding, qkv, proj, fc1, fc2) and attention (QK^T and PV)."""
+    """Multiply-adds x 2 of one forward, from the shapes: the GEMMs (patch embedding, qkv, proj, fc1, fc2) and attention (QK^T and PV).
+    The packed SwiGLU's fc2 reads half of fc1's width; register tokens lengthen the sequence; the zero columns of a padded patch
+    row are not counted (they are no work the algorithm needs)."""
     d, m, p = cfg["embed_dim"], cfg["mlp_dim"], cfg["patch_size"]
     g = (side // p) ** 2
-    s = g + 1
-    gemm = 2.0 * batch * (g * 3 * p * p * d + depth * s * (3 * d * d + d * d + 2 * d * m))
+    s = g + 1 + cfg.get("reg_tokens", 0)
+    mlp = d * m + d * m // 2 if cfg.get("mlp_layer", "mlp") == "swiglu_packed" else 2 * d * m
+    gemm = 2.0 * batch * (g * 3 * p * p * d + depth * s * (3 * d * d + d * d + mlp))
     attn = 2.0 * batch * depth * 2 * s * s * d
     return {"gemm": gemm, "attention": attn, "total": gemm + attn, "tokens": s}
 

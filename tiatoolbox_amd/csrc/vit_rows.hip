@@ -3,6 +3,10 @@
 //   gelu_rows       : x = 0.5 x (1 + erf(x / sqrt 2)) in place
 //   vit_patchify    : NHWC image batch -> [n, g, p * p * 3] tokens, k order (ky, kx, c)   float32 or half in, half out
 //   assemble_tokens : out[b, 0] = cls + pos[0], out[b, 1 + i] = tok[b, i] + pos[1 + i]
+// and what the foundation models (UNI2, H-optimus, prov-gigapath) add to the graph:
+//   swiglu_rows      : y[r, j] = silu(x[r, j]) * x[r, H + j]     the packed fc1 output [rows, 2 H] -> [rows, H]
+//   vit_patchify_pad : the same im2col for any patch size, rows zero-padded to k_pad columns (a 14-pixel patch: 588 -> 608)
+//   assemble_prefix  : out[b] = cat(cls (+ pos[0]), reg[0 .. R), tok[b] + pos[has_cls ..])
 // 16 bytes per lane and access (8 halves), float32 arithmetic, ONE round-to-nearest-even on the way out, 64-bit element offsets.
 #include "conv_device.hpp"
 #include "wide_io.hpp"
@@ -152,6 +156,110 @@ __global__ __launch_bounds__(ET) void vit_assemble_tokens_h_kernel(const v4u* __
     }
 }
 
+// silu(t) = t / (1 + exp(-t)), written so that no exponential overflows: with e = exp(-|t|) in (0, 1] it is t / (1 + e) for t >= 0
+// and t e / (1 + e) for t < 0 -- a gate of -100 gives the tiny value it should (or a signed zero), never inf / inf.  expf and the
+// division are the correctly rounded ones (no fast-math): a few float32 units in all.
+__device__ __forceinline__ float silu_f32(float t) {
+    const float e = expf(-fabsf(t));
+    const float num = t >= 0.0f ? t : t * e;
+    return num / (1.0f + e);
+}
+
+// One thread per 8 outputs: the gate vector at [r, 8 j] and the value vector at [r, H + 8 j], both 16-byte loads (H % 8 == 0 makes
+// every row and its second half start on a vector), one 16-byte store.
+template <bool BF>
+__global__ __launch_bounds__(ET) void swiglu_rows_h_kernel(const v4u* __restrict__ x, long vectors, int hv, v4u* __restrict__ y) {
+    for (long i = (long)blockIdx.x * ET + threadIdx.x; i < vectors; i += (long)gridDim.x * ET) {
+        const long r = i / hv;
+        const int j = (int)(i - r * hv);
+        float gate[8], val[8];
+        unpack8<BF>(x[r * (2L * hv) + j], gate);
+        unpack8<BF>(x[r * (2L * hv) + hv + j], val);
+#pragma unroll
+        for (int k = 0; k < 8; ++k) gate[k] = silu_f32(gate[k]) * val[k];
+        y[i] = pack8<BF>(gate);
+    }
+}
+
+// One thread per 8 output halves of a k_pad-wide token row.  A patch row (3 p values) is no whole number of 16-byte vectors when
+// p % 8 != 0 and starts on no 16-byte boundary in the image, so the 8 values are read one by one (4-byte or 2-byte loads, always
+// aligned; neighbouring lanes read neighbouring addresses) while (ky, position in the run) steps along; columns from 3 p^2 on are
+// written as zeros.  The store is one aligned 16-byte vector (k_pad % 8 == 0).
+template <bool BF, bool IN_F32>
+__global__ __launch_bounds__(ET) void vit_patchify_pad_h_kernel(const void* __restrict__ x, int h, int w, int p, int kv, long vectors,
+                                                                 v4u* __restrict__ out) {
+    const int run = 3 * p, k_real = run * p, gw = w / p, gh = h / p;
+    for (long i = (long)blockIdx.x * ET + threadIdx.x; i < vectors; i += (long)gridDim.x * ET) {
+        const int v = (int)(i % kv);
+        long t = i / kv;
+        const int gx = (int)(t % gw);
+        t /= gw;
+        const int gy = (int)(t % gh);
+        const long b = t / gh;
+        int k = 8 * v, ky = k / run, rem = k - ky * run;
+        const long base = ((b * h + (long)gy * p) * w + (long)gx * p) * 3;  // the patch's first value; a row further down is + 3 w
+        float f[8];
+        unsigned short hv[8];
+#pragma unroll
+        for (int e = 0; e < 8; ++e, ++k) {
+            if (k < k_real) {
+                const long src = base + (long)ky * w * 3 + rem;
+                if constexpr (IN_F32) f[e] = static_cast<const float*>(x)[src];
+                else hv[e] = static_cast<const unsigned short*>(x)[src];
+                if (++rem == run) rem = 0, ++ky;
+            } else {
+                f[e] = 0.0f;
+                hv[e] = 0;
+            }
+        }
+        if constexpr (IN_F32) {
+            out[i] = pack8<BF>(f);
+        } else {
+            v4u o;
+            o.x = (unsigned)hv[0] | ((unsigned)hv[1] << 16);
+            o.y = (unsigned)hv[2] | ((unsigned)hv[3] << 16);
+            o.z = (unsigned)hv[4] | ((unsigned)hv[5] << 16);
+            o.w = (unsigned)hv[6] | ((unsigned)hv[7] << 16);
+            out[i] = o;
+        }
+    }
+}
+
+// vit_assemble_tokens_h_kernel with R register rows after the class row and a position table with or without a class entry
+// (has_cls = 1 / 0).  R = 0 with has_cls = 1 is that kernel's arithmetic exactly.
+template <bool BF>
+__global__ __launch_bounds__(ET) void vit_assemble_prefix_h_kernel(const v4u* __restrict__ tok, const float* __restrict__ cls,
+                                                                    const float* __restrict__ reg, const float* __restrict__ pos,
+                                                                    int has_cls, long vectors, int g, int nreg, int dv,
+                                                                    v4u* __restrict__ out) {
+    const int s = 1 + nreg + g;
+    for (long i = (long)blockIdx.x * ET + threadIdx.x; i < vectors; i += (long)gridDim.x * ET) {
+        const int v = (int)(i % dv);
+        const long t = i / dv;
+        const int tk = (int)(t % s);
+        const long b = t / s;
+        float a[8];
+        long prow = -1;  // the row of `pos` to add, if any
+        if (tk == 0) {
+            load8_f32(cls + 8 * v, a);
+            if (has_cls) prow = 0;
+        } else if (tk <= nreg) {
+            load8_f32(reg + ((long)(tk - 1) * dv + v) * 8, a);
+        } else {
+            const int pi = tk - 1 - nreg;
+            unpack8<BF>(tok[(b * g + pi) * dv + v], a);
+            prow = pi + has_cls;
+        }
+        if (prow >= 0) {
+            float ps[8];
+            load8_f32(pos + (prow * dv + v) * 8, ps);
+#pragma unroll
+            for (int k = 0; k < 8; ++k) a[k] += ps[k];
+        }
+        out[i] = pack8<BF>(a);
+    }
+}
+
 unsigned stream_blocks(long items) {
     long blocks = (items + ET - 1) / ET;
     if (blocks > 256L * 64) blocks = 256L * 64;
@@ -241,5 +349,55 @@ extern "C" int tia_vit_assemble_tokens_h(const void* d_tokens, const float* d_cl
     const auto kernel = dtype == TIA_DT_BF16 ? vit_assemble_tokens_h_kernel<true> : vit_assemble_tokens_h_kernel<false>;
     hipLaunchKernelGGL(kernel, dim3(stream_blocks(vectors)), dim3(ET), 0, (hipStream_t)stream, (const v4u*)d_tokens, d_cls, d_pos, vectors,
                        (int)g, (int)(d / 8), (v4u*)d_out);
+    return hipGetLastError() == hipSuccess ? TIA_OK : TIA_ELAUNCH;
+}
+
+extern "C" int tia_swiglu_rows_h(const void* d_x, void* d_y, int64_t rows, int64_t hidden, int32_t dtype, void* stream) {
+    if (!d_x || !d_y || rows <= 0 || hidden <= 0) return TIA_EINVAL;
+    if (dtype != TIA_DT_F16 && dtype != TIA_DT_BF16) return TIA_EINVAL;
+    if ((hidden & 7) != 0 || hidden > 0x3fffffffL || rows > 0x7fffffffL) return TIA_ESIZE;
+    if ((reinterpret_cast<uintptr_t>(d_x) | reinterpret_cast<uintptr_t>(d_y)) & 15) return TIA_EINVAL;
+    const long vectors = rows * (hidden / 8);
+    const auto kernel = dtype == TIA_DT_BF16 ? swiglu_rows_h_kernel<true> : swiglu_rows_h_kernel<false>;
+    hipLaunchKernelGGL(kernel, dim3(stream_blocks(vectors)), dim3(ET), 0, (hipStream_t)stream, (const v4u*)d_x, vectors, (int)(hidden / 8),
+                       (v4u*)d_y);
+    return hipGetLastError() == hipSuccess ? TIA_OK : TIA_ELAUNCH;
+}
+
+extern "C" int tia_vit_patchify_pad_h(const void* d_x, int32_t x_dtype, void* d_tokens, int64_t n, int64_t h, int64_t w, int64_t patch,
+                                      int64_t k_pad, int32_t dtype, void* stream) {
+    if (!d_x || !d_tokens || n <= 0 || h <= 0 || w <= 0 || patch <= 0 || k_pad <= 0) return TIA_EINVAL;
+    if (dtype != TIA_DT_F16 && dtype != TIA_DT_BF16) return TIA_EINVAL;
+    if (x_dtype != TIA_DT_F32 && x_dtype != dtype) return TIA_EINVAL;
+    if (h % patch != 0 || w % patch != 0) return TIA_ESIZE;
+    if (h > 0x7fffffffL / 3 || w > 0x7fffffffL / 3 || n > 0x7fffffffL || patch > 16384) return TIA_ESIZE;  // (3 p^2 stays an int)
+    if ((k_pad & 31) != 0 || k_pad < 3 * patch * patch || k_pad > 0x7fffffe0L) return TIA_ESIZE;
+    if ((reinterpret_cast<uintptr_t>(d_x) | reinterpret_cast<uintptr_t>(d_tokens)) & 15) return TIA_EINVAL;
+    const long vectors = n * (h / patch) * (w / patch) * (k_pad / 8);
+    hipStream_t st = (hipStream_t)stream;
+    const bool bf = dtype == TIA_DT_BF16, in32 = x_dtype == TIA_DT_F32;
+    using Kernel = void (*)(const void*, int, int, int, int, long, v4u*);
+    const Kernel kernels[2][2] = {{vit_patchify_pad_h_kernel<false, false>, vit_patchify_pad_h_kernel<false, true>},
+                                  {vit_patchify_pad_h_kernel<true, false>, vit_patchify_pad_h_kernel<true, true>}};
+    hipLaunchKernelGGL(kernels[bf][in32], dim3(stream_blocks(vectors)), dim3(ET), 0, st, d_x, (int)h, (int)w, (int)patch, (int)(k_pad / 8),
+                       vectors, (v4u*)d_tokens);
+    return hipGetLastError() == hipSuccess ? TIA_OK : TIA_ELAUNCH;
+}
+
+extern "C" int tia_vit_assemble_prefix_h(const void* d_tokens, const float* d_cls, const float* d_reg, const float* d_pos,
+                                         int32_t pos_has_cls, void* d_out, int64_t n, int64_t g, int64_t reg_tokens, int64_t d,
+                                         int32_t dtype, void* stream) {
+    if (!d_tokens || !d_cls || !d_pos || !d_out || n <= 0 || g <= 0 || d <= 0 || reg_tokens < 0) return TIA_EINVAL;
+    if ((reg_tokens > 0) != (d_reg != nullptr) || (pos_has_cls != 0 && pos_has_cls != 1)) return TIA_EINVAL;
+    if (dtype != TIA_DT_F16 && dtype != TIA_DT_BF16) return TIA_EINVAL;
+    if ((d & 7) != 0) return TIA_ESIZE;
+    if ((reinterpret_cast<uintptr_t>(d_tokens) | reinterpret_cast<uintptr_t>(d_cls) | reinterpret_cast<uintptr_t>(d_reg) |
+         reinterpret_cast<uintptr_t>(d_pos) | reinterpret_cast<uintptr_t>(d_out)) & 15)
+        return TIA_EINVAL;
+    if (g > 0x3fffffffL || reg_tokens > 0x3fffffffL || d > 0x7fffffffL || n > 0x7fffffffL) return TIA_ESIZE;
+    const long vectors = n * (1 + reg_tokens + g) * (d / 8);
+    const auto kernel = dtype == TIA_DT_BF16 ? vit_assemble_prefix_h_kernel<true> : vit_assemble_prefix_h_kernel<false>;
+    hipLaunchKernelGGL(kernel, dim3(stream_blocks(vectors)), dim3(ET), 0, (hipStream_t)stream, (const v4u*)d_tokens, d_cls, d_reg, d_pos,
+                       (int)pos_has_cls, vectors, (int)g, (int)reg_tokens, (int)(d / 8), (v4u*)d_out);
     return hipGetLastError() == hipSuccess ? TIA_OK : TIA_ELAUNCH;
 }

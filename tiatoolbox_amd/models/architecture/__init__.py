@@ -96,7 +96,8 @@ for _backbone in ("resnet101", "resnext50_32x4d", "resnext101_32x8d", "wide_resn
 _BACKBONES = ("resnet18", "resnet34", "resnet50", "resnet101", "resnext50_32x4d", "resnext101_32x8d", "wide_resnet50_2",
               "wide_resnet101_2")
 # bare Vision Transformer names: feature extractors (TimmBackbone, architecture/vit.py) without an ioconfig
-_VIT_BACKBONES = ("UNI", "vit_large_patch16_224", "vit_base_patch16_224", "vit_small_patch16_224")
+_VIT_BACKBONES = ("UNI", "vit_large_patch16_224", "vit_base_patch16_224", "vit_small_patch16_224", "UNI2", "H-optimus-0", "H-optimus-1",
+                  "prov-gigapath")
 
 
 def local_pretrained_weights(model_name: str) -> Path | None:

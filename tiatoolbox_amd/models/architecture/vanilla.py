@@ -87,8 +87,9 @@ class CNNBackbone(ModelABC):
 
 
 class TimmBackbone(ModelABC):
-    """Feature extractor on a Vision Transformer (ref. ``TimmBackbone``): ``UNI`` and the ``vit_*_patch16_224`` family, restated in
-    plain torch with timm's parameter names (``architecture/vit.py``).  The features are the class token of the final norm,
+    """Feature extractor on a Vision Transformer (ref. ``TimmBackbone``): ``UNI``, the ``vit_*_patch16_224`` family and the foundation
+    models ``UNI2``, ``H-optimus-0`` / ``H-optimus-1`` and ``prov-gigapath`` (``VIT_CONFIGS``), restated in plain torch with timm's
+    parameter names (``architecture/vit.py``).  The features are the class token of the final norm,
     ``[B, D]``; input normalisation is the caller's ``preproc_func``, as in the reference.  ``pretrained=True`` loads
     ``<backbone>.pth`` (a timm state dict) from the local weight directories; the hub is never contacted."""
 

@@ -1,7 +1,8 @@
 """Vision Transformer backbones (the models the reference's ``TimmBackbone`` builds through timm, ``vanilla.py``), restated in plain
-torch: timm's ``VisionTransformer`` with ``num_classes=0`` and ``global_pool="token"`` -- no head, no ``fc_norm``, no register
-tokens; the output is the class token of the final norm, ``[B, D]``.  Parameter names and shapes are timm's, so its checkpoints load
-with ``strict=True``; ``UNI`` is ViT-L/16 with LayerScale (``init_values=1e-5``) and ``dynamic_img_size``.
+torch: timm's ``VisionTransformer`` with ``num_classes=0`` and ``global_pool="token"`` -- no head, no ``fc_norm``; the output is the
+class token of the final norm, ``[B, D]``.  Parameter names and shapes are timm's, so its checkpoints load with ``strict=True``;
+``UNI`` is ViT-L/16 with LayerScale (``init_values=1e-5``) and ``dynamic_img_size``.  The pathology foundation models (``UNI2``,
+``H-optimus-0`` / ``-1``, ``prov-gigapath``) add timm's ``reg_tokens``, ``no_embed_class`` and ``mlp_layer=SwiGLUPacked``.
 
 The fp16 / bf16 forward on the hand-written kernels is :class:`~tiatoolbox_amd.models.architecture.vit_fused.FusedViT`.
 """
@@ -19,14 +20,26 @@ VIT_CONFIGS: dict[str, dict] = {
     "vit_large_patch16_224": {"embed_dim": 1024, "depth": 24, "num_heads": 16, "mlp_dim": 4096, "patch_size": 16, "img_size": 224},
     "vit_base_patch16_224": {"embed_dim": 768, "depth": 12, "num_heads": 12, "mlp_dim": 3072, "patch_size": 16, "img_size": 224},
     "vit_small_patch16_224": {"embed_dim": 384, "depth": 12, "num_heads": 6, "mlp_dim": 1536, "patch_size": 16, "img_size": 224},
+    # the foundation models' published timm configurations (ViT-H / ViT-g widths); `mlp_dim` is the packed fc1 width, int(1536 * 5.33334)
+    "UNI2": {"embed_dim": 1536, "depth": 24, "num_heads": 24, "mlp_dim": 8192, "patch_size": 14, "img_size": 224, "init_values": 1e-5,
+             "reg_tokens": 8, "no_embed_class": True, "dynamic_img_size": True, "mlp_layer": "swiglu_packed"},
+    "H-optimus-0": {"embed_dim": 1536, "depth": 40, "num_heads": 24, "mlp_dim": 8192, "patch_size": 14, "img_size": 224, "init_values": 1e-5,
+                    "reg_tokens": 4, "no_embed_class": True, "mlp_layer": "swiglu_packed"},
+    "H-optimus-1": {"embed_dim": 1536, "depth": 40, "num_heads": 24, "mlp_dim": 8192, "patch_size": 14, "img_size": 224, "init_values": 1e-5,
+                    "reg_tokens": 4, "no_embed_class": True, "mlp_layer": "swiglu_packed"},
+    "prov-gigapath": {"embed_dim": 1536, "depth": 40, "num_heads": 24, "mlp_dim": 8192, "patch_size": 16, "img_size": 224, "init_values": 1e-5,
+                      "mlp_layer": "swiglu_packed"},
 }
+MLP_LAYERS = ("mlp", "swiglu_packed")
 LN_EPS = 1e-6
 
 
-def resample_pos_embed(pos_embed: torch.Tensor, native_grid: tuple[int, int], grid: tuple[int, int], *, dynamic: bool) -> torch.Tensor:
-    """``pos_embed`` ``[1, 1 + g0h * g0w, D]`` for a ``grid`` of patches, in float32: the class entry as it is, the grid part
-    resampled with ``F.interpolate(mode="bicubic", antialias=True, align_corners=False)`` (timm's ``resample_abs_pos_embed``).  At
-    the native grid this is ``pos_embed`` itself (no arithmetic); any other grid needs ``dynamic`` (``dynamic_img_size``) and
+def resample_pos_embed(pos_embed: torch.Tensor, native_grid: tuple[int, int], grid: tuple[int, int], *, dynamic: bool,
+                       num_prefix: int = 1) -> torch.Tensor:
+    """``pos_embed`` ``[1, num_prefix + g0h * g0w, D]`` for a ``grid`` of patches, in float32: the ``num_prefix`` leading entries (the
+    class entry; none for a ``no_embed_class`` table, which is the grid alone) as they are, the grid part resampled with
+    ``F.interpolate(mode="bicubic", antialias=True, align_corners=False)`` (timm's ``resample_abs_pos_embed``).  At the native grid
+    this is ``pos_embed`` itself (no arithmetic); any other grid needs ``dynamic`` (``dynamic_img_size``) and
     raises ``ValueError`` without it.  The one helper of the plain module and of the fused graph."""
     grid, native_grid = tuple(grid), tuple(native_grid)
     if grid == native_grid:
@@ -36,7 +49,7 @@ def resample_pos_embed(pos_embed: torch.Tensor, native_grid: tuple[int, int], gr
                "(dynamic_img_size is off).")
         raise ValueError(msg)
     dim = pos_embed.shape[-1]
-    cls, tab = pos_embed[:, :1], pos_embed[:, 1:]
+    cls, tab = pos_embed[:, :num_prefix], pos_embed[:, num_prefix:]
     tab = tab.to(torch.float32).reshape(1, native_grid[0], native_grid[1], dim).permute(0, 3, 1, 2)
     tab = F.interpolate(tab, size=grid, mode="bicubic", antialias=True, align_corners=False)
     tab = tab.permute(0, 2, 3, 1).reshape(1, grid[0] * grid[1], dim)
@@ -89,14 +102,32 @@ class Mlp(nn.Module):
         return self.fc2(self.act(self.fc1(x)))
 
 
+class SwiGLUPacked(nn.Module):
+    """timm's ``SwiGLUPacked`` (``GluMlp`` with ``act_layer=SiLU``, ``gate_last=False``): ONE ``fc1`` of width ``hidden`` whose first
+    half is the gate, ``fc2(silu(x1) * x2)`` on the ``hidden / 2`` products."""
+
+    def __init__(self, dim: int, hidden: int) -> None:
+        super().__init__()
+        if hidden % 2 != 0:
+            msg = f"SwiGLUPacked: the packed fc1 width {hidden} is odd."
+            raise ValueError(msg)
+        self.fc1 = nn.Linear(dim, hidden)
+        self.act = nn.SiLU()
+        self.fc2 = nn.Linear(hidden // 2, dim)
+
+    def forward(self, x: torch.Tensor) -> torch.Tensor:
+        x1, x2 = self.fc1(x).chunk(2, dim=-1)
+        return self.fc2(self.act(x1) * x2)
+
+
 class Block(nn.Module):
-    def __init__(self, dim: int, num_heads: int, mlp_dim: int, init_values: float | None) -> None:
+    def __init__(self, dim: int, num_heads: int, mlp_dim: int, init_values: float | None, mlp_layer: str = "mlp") -> None:
         super().__init__()
         self.norm1 = nn.LayerNorm(dim, eps=LN_EPS)
         self.attn = Attention(dim, num_heads)
         self.ls1 = LayerScale(dim, init_values) if init_values else nn.Identity()
         self.norm2 = nn.LayerNorm(dim, eps=LN_EPS)
-        self.mlp = Mlp(dim, mlp_dim)
+        self.mlp = SwiGLUPacked(dim, mlp_dim) if mlp_layer == "swiglu_packed" else Mlp(dim, mlp_dim)
         self.ls2 = LayerScale(dim, init_values) if init_values else nn.Identity()
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
@@ -105,32 +136,50 @@ class Block(nn.Module):
 
 
 class VisionTransformer(nn.Module):
-    """``forward(imgs [B, 3, H, W]) -> [B, D]``: the class token of ``norm(blocks(tokens))``."""
+    """``forward(imgs [B, 3, H, W]) -> [B, D]``: the class token of ``norm(blocks(tokens))``.
+
+    ``reg_tokens`` register tokens follow the class token (``reg_token [1, R, D]``); with ``no_embed_class`` the position table is the
+    grid alone (``[1, g0 * g0, D]``), added to the patch tokens before the prefix is prepended: ``cat([cls, reg, patches + pos])``.
+    ``mlp_layer="swiglu_packed"`` puts :class:`SwiGLUPacked` in the blocks (``mlp_dim`` is then the packed ``fc1`` width)."""
 
     def __init__(self, *, embed_dim: int, depth: int, num_heads: int, mlp_dim: int, patch_size: int = 16, img_size: int = 224,
-                 init_values: float | None = None, dynamic_img_size: bool = False) -> None:
+                 init_values: float | None = None, dynamic_img_size: bool = False, reg_tokens: int = 0, no_embed_class: bool = False,
+                 mlp_layer: str = "mlp") -> None:
         super().__init__()
+        if mlp_layer not in MLP_LAYERS:
+            msg = f"VisionTransformer: mlp_layer is one of {MLP_LAYERS}; got {mlp_layer!r}."
+            raise ValueError(msg)
+        if reg_tokens < 0 or (reg_tokens and not no_embed_class):
+            msg = (f"VisionTransformer: reg_tokens={reg_tokens} needs no_embed_class=True (a position table with a class entry beside "
+                   "register tokens is no registered model's form) and cannot be negative.")
+            raise ValueError(msg)
         if embed_dim % num_heads != 0 or img_size % patch_size != 0:
             msg = f"VisionTransformer: embed_dim {embed_dim} / heads {num_heads} or img_size {img_size} / patch {patch_size} does not divide."
             raise ValueError(msg)
         self.embed_dim, self.num_heads, self.patch_size = embed_dim, num_heads, patch_size
         self.dynamic_img_size = dynamic_img_size
+        self.reg_tokens, self.no_embed_class, self.mlp_layer = reg_tokens, no_embed_class, mlp_layer
+        self.pos_prefix = 0 if no_embed_class else 1  # entries of `pos_embed` in front of the grid
         g0 = img_size // patch_size
         self.native_grid = (g0, g0)
         self.cls_token = nn.Parameter(torch.zeros(1, 1, embed_dim))
-        self.pos_embed = nn.Parameter(torch.zeros(1, 1 + g0 * g0, embed_dim))
+        if reg_tokens:
+            self.reg_token = nn.Parameter(torch.zeros(1, reg_tokens, embed_dim))
+        self.pos_embed = nn.Parameter(torch.zeros(1, self.pos_prefix + g0 * g0, embed_dim))
         self.patch_embed = PatchEmbed(patch_size, embed_dim)
-        self.blocks = nn.Sequential(*[Block(embed_dim, num_heads, mlp_dim, init_values) for _ in range(depth)])
+        self.blocks = nn.Sequential(*[Block(embed_dim, num_heads, mlp_dim, init_values, mlp_layer) for _ in range(depth)])
         self.norm = nn.LayerNorm(embed_dim, eps=LN_EPS)
         self._pos_cache: dict[tuple, torch.Tensor] = {}
         if self.pos_embed.device.type != "meta":
             self.init_weights()
 
     def init_weights(self) -> None:
-        """timm's: truncated normal (std 0.02) on the weights and ``pos_embed``, zero biases, ``cls_token`` std 1e-6, LayerNorm
-        ones / zeros; LayerScale keeps ``init_values``."""
+        """timm's: truncated normal (std 0.02) on the weights and ``pos_embed``, zero biases, ``cls_token`` (and ``reg_token``) std
+        1e-6, LayerNorm ones / zeros; LayerScale keeps ``init_values``."""
         nn.init.trunc_normal_(self.pos_embed, std=0.02)
         nn.init.normal_(self.cls_token, std=1e-6)
+        if self.reg_tokens:
+            nn.init.normal_(self.reg_token, std=1e-6)
         for mod in self.modules():
             if isinstance(mod, (nn.Linear, nn.Conv2d)):
                 nn.init.trunc_normal_(mod.weight, std=0.02)
@@ -158,7 +207,8 @@ class VisionTransformer(nn.Module):
         hit = self._pos_cache.get(grid)
         if hit is None or hit[0] != key:
             with torch.no_grad():
-                hit = (key, resample_pos_embed(pe.detach(), self.native_grid, grid, dynamic=self.dynamic_img_size))
+                hit = (key, resample_pos_embed(pe.detach(), self.native_grid, grid, dynamic=self.dynamic_img_size,
+                                                   num_prefix=self.pos_prefix))
             self._pos_cache[grid] = hit
         return hit[1]
 
@@ -170,7 +220,13 @@ class VisionTransformer(nn.Module):
         grid = self.grid_of(imgs.shape[-2], imgs.shape[-1])
         pos = self.pos_embed_for(grid)  # (refuses an off-grid size before any arithmetic)
         x = self.patch_embed(imgs)
-        x = torch.cat([self.cls_token.expand(x.shape[0], -1, -1), x], dim=1) + pos
+        if self.no_embed_class:
+            prefix = [self.cls_token.expand(x.shape[0], -1, -1)]
+            if self.reg_tokens:
+                prefix.append(self.reg_token.expand(x.shape[0], -1, -1))
+            x = torch.cat([*prefix, x + pos], dim=1)
+        else:
+            x = torch.cat([self.cls_token.expand(x.shape[0], -1, -1), x], dim=1) + pos
         x = self.norm(self.blocks(x))
         return x[:, 0]
 

@@ -10,6 +10,16 @@ the tokens as an ``[n, S, 1, C]`` NHWC map: float32 accumulation, bias and resid
 3. ``tia_mha_fwd_h``                   7. ``tia_gelu_rows_h`` (in place)
 4. ``proj`` GEMM (bias + residual)     8. ``fc2`` GEMM (bias + residual)
 
+The foundation models (``UNI2``, ``H-optimus-0`` / ``-1``, ``prov-gigapath``) change three places of this graph and nothing else:
+
+* ``mlp_layer="swiglu_packed"``: step 7 is ``tia_swiglu_rows_h`` (``[n, S, 2H] -> [n, S, H]``, the first half the gate) and ``fc2`` has
+  ``cin = H``;
+* a patch size that is no multiple of 8 (14): ``tia_vit_patchify_pad_h`` writes token rows of ``k_pad = ceil(3 p^2 / 32) * 32``
+  columns (608), zeros beyond ``3 p^2``, and the permuted patch weight is zero-padded alike in float32 before packing -- the
+  embedding is still ONE GEMM; multiples of 8 keep ``tia_vit_patchify_h``;
+* register tokens or ``no_embed_class``: ``tia_vit_assemble_prefix_h`` (``cat([cls, reg, patches + pos])``) in place of
+  ``tia_vit_assemble_tokens_h``.  The class token is still row 0, so the final norm reads the same rows.
+
 LayerScale is folded EXACTLY in float32 before the one rounding of the weights: ``x + gamma * (W a + b) = x + (gamma W) a + gamma b``, so
 the residual add is the GEMM's own ``d_residual`` and ``ls1`` / ``ls2`` cost nothing.  The residual stream stays in ``dtype`` (as in
 the cast torch module); the final norm reads the class rows only (row stride ``S * D``) and writes float32 features.
@@ -168,6 +178,68 @@ def hip_vit_assemble_tokens_h(tokens: torch.Tensor, cls: torch.Tensor, pos: torc
     return out
 
 
+def hip_swiglu_rows_h(x: torch.Tensor) -> torch.Tensor:
+    """Packed SwiGLU ``silu(x[..., :H]) * x[..., H:]`` on ``[n, S, 2H]`` tokens -> ``[n, S, H]`` (``tia_swiglu_rows_h``)."""
+    from tiatoolbox_amd import _lib
+
+    _half_tokens("hip_swiglu_rows_h", x)
+    if x.dim() < 2 or x.shape[-1] % 2 != 0:  # noqa: PLR2004
+        msg = f"hip_swiglu_rows_h takes [..., 2H] tokens; got {tuple(x.shape)}."
+        raise ValueError(msg)
+    hidden = x.shape[-1] // 2
+    y = torch.empty((*x.shape[:-1], hidden), dtype=x.dtype, device=x.device)
+    with torch.cuda.device(x.device):
+        rc = _lib.load().tia_swiglu_rows_h(x.data_ptr(), y.data_ptr(), x.numel() // (2 * hidden), hidden, _DT[x.dtype], _lib.current_stream())
+    _lib.check(rc, "tia_swiglu_rows_h")
+    return y
+
+
+def padded_patch_columns(patch: int) -> int:
+    """``k_pad``: ``3 * patch^2`` rounded up to the half GEMM's multiple of 32 input channels (patch 14: 588 -> 608)."""
+    return -(-3 * patch * patch // 32) * 32
+
+
+def hip_vit_patchify_pad_h(x_nhwc: torch.Tensor, patch: int, k_pad: int, dtype: torch.dtype) -> torch.Tensor:
+    """``[n, h, w, 3]`` float32 (or ``dtype``) images -> ``[n, g, k_pad]`` tokens of ``dtype``, zeros from column ``3 * patch^2`` on
+    (``tia_vit_patchify_pad_h``: any patch size)."""
+    from tiatoolbox_amd import _lib
+
+    if not (x_nhwc.is_cuda and x_nhwc.dim() == 4 and x_nhwc.shape[-1] == 3 and x_nhwc.is_contiguous() and x_nhwc.dtype in (torch.float32, dtype)):
+        msg = f"hip_vit_patchify_pad_h expects a contiguous [n, h, w, 3] CUDA tensor in float32 or {dtype}; got {tuple(x_nhwc.shape)}, {x_nhwc.dtype}."
+        raise ValueError(msg)
+    n, h, w, _ = x_nhwc.shape
+    out = torch.empty((n, (h // patch) * (w // patch), k_pad), dtype=dtype, device=x_nhwc.device)
+    with torch.cuda.device(x_nhwc.device):
+        rc = _lib.load().tia_vit_patchify_pad_h(x_nhwc.data_ptr(), _DT[x_nhwc.dtype], out.data_ptr(), n, h, w, patch, k_pad, _DT[dtype],
+                                                _lib.current_stream())
+    _lib.check(rc, "tia_vit_patchify_pad_h")
+    return out
+
+
+def hip_vit_assemble_prefix_h(tokens: torch.Tensor, cls: torch.Tensor, reg: torch.Tensor | None, pos: torch.Tensor, *,
+                              pos_has_cls: bool) -> torch.Tensor:
+    """``out[b] = cat([cls (+ pos[0] if pos_has_cls), reg, tokens[b] + pos[pos_has_cls:]])`` (float32 ``cls [D]``, ``reg [R, D]`` or
+    ``None``, ``pos [g + pos_has_cls, D]``): ``tia_vit_assemble_prefix_h``."""
+    from tiatoolbox_amd import _lib
+
+    _half_tokens("hip_vit_assemble_prefix_h", tokens)
+    n, g, d = tokens.shape
+    nreg = 0 if reg is None else reg.numel() // d
+    rows = g + int(pos_has_cls)
+    if cls.dtype != torch.float32 or pos.dtype != torch.float32 or cls.numel() != d or pos.numel() != rows * d or not (
+            cls.is_contiguous() and pos.is_contiguous()) or (reg is not None and (
+                reg.dtype != torch.float32 or not reg.is_contiguous() or nreg == 0 or reg.numel() != nreg * d)):
+        msg = (f"hip_vit_assemble_prefix_h takes float32 cls [{d}], reg [R, {d}] or None and pos [{rows}, {d}]; got {tuple(cls.shape)}, "
+               f"{None if reg is None else tuple(reg.shape)}, {tuple(pos.shape)}.")
+        raise ValueError(msg)
+    out = torch.empty((n, 1 + nreg + g, d), dtype=tokens.dtype, device=tokens.device)
+    with torch.cuda.device(tokens.device):
+        rc = _lib.load().tia_vit_assemble_prefix_h(tokens.data_ptr(), cls.data_ptr(), _ptr(reg), pos.data_ptr(), int(pos_has_cls),
+                                                   out.data_ptr(), n, g, nreg, d, _DT[tokens.dtype], _lib.current_stream())
+    _lib.check(rc, "tia_vit_assemble_prefix_h")
+    return out
+
+
 class _Linear:
     """One GEMM of the graph: the float32 (LayerScale-folded) weights until ``prepare`` packs them, the float32 bias throughout.
     Plain attributes: the cast of the surrounding module does not reach them."""
@@ -207,19 +279,25 @@ class FusedViT(nn.Module):
         if head_dim != 64:  # noqa: PLR2004
             msg = f"FusedViT: the attention kernel takes head_dim 64; this model has {self.embed_dim} / {self.num_heads} = {head_dim}."
             raise UnsupportedLayerError(msg)
-        if self.patch_size % 8 != 0:
-            msg = f"FusedViT: the patch kernel takes patch sizes that are multiples of 8; got {self.patch_size}."
-            raise UnsupportedLayerError(msg)
         self.scale = head_dim ** -0.5
+        self.reg_tokens, self.no_embed_class, self.swiglu = vit.reg_tokens, vit.no_embed_class, vit.mlp_layer == "swiglu_packed"
+        self.pos_prefix = vit.pos_prefix
+        # patch sizes off the multiples of 8 (14) take the padded im2col: rows of k_pad columns, zeros beyond 3 p^2
+        self.k_pad = padded_patch_columns(self.patch_size) if self.patch_size % 8 != 0 else None
         # the parameters the module keeps (small): they carry device and dtype for `infer_batch`; their float32 values are set aside
         self.cls_token, self.pos_embed = vit.cls_token, vit.pos_embed
         self._cls32 = vit.cls_token.detach().to(torch.float32).reshape(-1).contiguous()
         self._pos32 = vit.pos_embed.detach().to(torch.float32).contiguous()
+        self.reg_token = vit.reg_token if self.reg_tokens else None
+        self._reg32 = vit.reg_token.detach().to(torch.float32).reshape(self.reg_tokens, -1).contiguous() if self.reg_tokens else None
         self._pos_cache: dict[tuple[int, int], torch.Tensor] = {}
         f32 = lambda t: t.detach().to(torch.float32).contiguous()  # noqa: E731
         proj = vit.patch_embed.proj
         # [D, 3, p, p] -> [D, p, p, 3]: the (ky, kx, c) order of tia_vit_patchify_h
-        self.patch = _Linear("patch_embed.proj", f32(proj.weight).permute(0, 2, 3, 1).reshape(self.embed_dim, -1).contiguous(), f32(proj.bias))
+        patch_w = f32(proj.weight).permute(0, 2, 3, 1).reshape(self.embed_dim, -1)
+        if self.k_pad is not None:  # zero columns (exact, in float32, before the one rounding) under the zero columns of the tokens
+            patch_w = torch.nn.functional.pad(patch_w, (0, self.k_pad - patch_w.shape[1]))
+        self.patch = _Linear("patch_embed.proj", patch_w.contiguous(), f32(proj.bias))
         self.layers: list[dict] = []
         for i, blk in enumerate(vit.blocks):
             qkv_w, qkv_b = fold_layer_scale(blk.attn.qkv, None)
@@ -251,8 +329,8 @@ class FusedViT(nn.Module):
 
     def _pos_for(self, grid: tuple[int, int]) -> torch.Tensor:
         if grid not in self._pos_cache:
-            self._pos_cache[grid] = resample_pos_embed(self._pos32, self.native_grid, grid, dynamic=self.dynamic_img_size).reshape(
-                -1, self.embed_dim).contiguous()
+            self._pos_cache[grid] = resample_pos_embed(self._pos32, self.native_grid, grid, dynamic=self.dynamic_img_size,
+                                                       num_prefix=self.pos_prefix).reshape(-1, self.embed_dim).contiguous()
         return self._pos_cache[grid]
 
     def forward(self, imgs: torch.Tensor) -> torch.Tensor:
@@ -269,14 +347,20 @@ class FusedViT(nn.Module):
         x = imgs.permute(0, 2, 3, 1)  # the NHWC batch under the NCHW view
         if x.dtype not in (torch.float32, half):
             x = x.to(torch.float32)
-        tok = self.patch(hip_vit_patchify_h(x.contiguous(), p, half))
-        x = hip_vit_assemble_tokens_h(tok, self._cls32, pos)
+        if self.k_pad is None:
+            tok = self.patch(hip_vit_patchify_h(x.contiguous(), p, half))
+        else:
+            tok = self.patch(hip_vit_patchify_pad_h(x.contiguous(), p, self.k_pad, half))
+        if self.reg_tokens or self.no_embed_class:
+            x = hip_vit_assemble_prefix_h(tok, self._cls32, self._reg32, pos, pos_has_cls=not self.no_embed_class)
+        else:
+            x = hip_vit_assemble_tokens_h(tok, self._cls32, pos)
         s = x.shape[1]
         for layer in self.layers:
             a = hip_layernorm_rows_h(x, *layer["norm1"], eps=LN_EPS, rows=n * s, row_stride=d).view(n, s, d)
             a = hip_mha_fwd_h(layer["qkv"](a), self.num_heads, self.scale)
             x = layer["proj"](a, residual=x)
             a = hip_layernorm_rows_h(x, *layer["norm2"], eps=LN_EPS, rows=n * s, row_stride=d).view(n, s, d)
-            a = hip_gelu_rows_h_(layer["fc1"](a))
+            a = hip_swiglu_rows_h(layer["fc1"](a)) if self.swiglu else hip_gelu_rows_h_(layer["fc1"](a))
             x = layer["fc2"](a, residual=x)
         return hip_layernorm_rows_h(x, *self._norm, eps=LN_EPS, rows=n, row_stride=s * d, out_dtype=torch.float32)

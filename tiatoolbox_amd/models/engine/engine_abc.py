@@ -446,7 +446,7 @@ class EngineABC:
 
             if isinstance(getattr(m, "feat_extract", None), VisionTransformer):
                 # Vision Transformer backbones (TimmBackbone).  GPU, fp16 / bf16: FusedViT -- every Linear on the half MFMA GEMM,
-                # attention, LayerNorm, GELU and token assembly on their own kernels (architecture/vit_fused.py; `prepare(dtype)`
+                # attention, LayerNorm, GELU / SwiGLU and token assembly on their own kernels (architecture/vit_fused.py; `prepare(dtype)`
                 # below).  GPU, float32: there is no float32 attention kernel, the torch module runs on the library's GEMMs -- never
                 # silently.  CPU: the torch module.  `conv_algo` has nothing to choose here.
                 if on_gpu and dtype != torch.float32:

@@ -44,7 +44,8 @@ extern "C" {
  * tia_conv3x3_grouped_nhwc_f32 (the grouped 3x3 of ResNeXt), tia_stem_pack_weights_bf16x3 / tia_stem_conv7x7_pool_nhwc_u8x3 (the
  * uint8 stem on the bf16 matrix cores with exactly split float32 weights); tia_mha_fwd_h, tia_layernorm_rows_h, tia_gelu_rows_h,
  * tia_vit_patchify_h, tia_vit_assemble_tokens_h (the Vision Transformer backbones in fp16 / bf16); tia_swiglu_rows_h,
- * tia_vit_patchify_pad_h, tia_vit_assemble_prefix_h (UNI2, H-optimus and prov-gigapath on the same graph). */
+ * tia_vit_patchify_pad_h, tia_vit_assemble_prefix_h (UNI2, H-optimus and prov-gigapath on the same graph); tia_vit_cls_mean_pool_h
+ * and head_dim 80 in tia_mha_fwd_h (Virchow, Virchow2). */
 #define TIA_ABI_VERSION 6
 int tia_abi_version(void);
 
@@ -907,7 +908,7 @@ int tia_upsample2x_concat_act_nhwc_h(const void* d_x, const void* d_y, const flo
  *   d_qkv [n, s, 3, heads, head_dim] of `dtype` -- the qkv Linear's own output order   d_out [n, s, heads * head_dim] of `dtype`
  * float32 scores, maximum and sum (the sum over the unrounded probabilities); the probabilities are rounded once to `dtype` for
  * the second product, the output O / l once.  Any s >= 1: keys beyond s contribute exactly 0, query rows beyond s are not stored.
- * head_dim != 64 is TIA_ESIZE (every registered model has 64); scale must be positive and finite (TIA_EINVAL). */
+ * head_dim is 64 or 80 (Virchow / Virchow2), anything else TIA_ESIZE; scale must be positive and finite (TIA_EINVAL). */
 int tia_mha_fwd_h(const void* d_qkv, void* d_out, int64_t n, int64_t s, int64_t heads, int64_t head_dim, float scale, int32_t dtype,
                   void* stream);
 
@@ -958,6 +959,19 @@ int tia_vit_patchify_pad_h(const void* d_x, int32_t x_dtype, void* d_tokens, int
  * tia_vit_assemble_tokens_h bit for bit.  d % 8 == 0 (else TIA_ESIZE). */
 int tia_vit_assemble_prefix_h(const void* d_tokens, const float* d_cls, const float* d_reg, const float* d_pos, int32_t pos_has_cls,
                               void* d_out, int64_t n, int64_t g, int64_t reg_tokens, int64_t d, int32_t dtype, void* stream);
+
+/* Virchow / Virchow2 (1280 / 16 = 80 per head, a class + mean-patch output): tia_mha_fwd_h takes head_dim 80 (above), and the last
+ * step of the graph is the pooled final norm.  Additive, same version (6); the contract of the family above. */
+
+/* Class + mean-patch pooling of the final LayerNorm: out[b, :d] = LN(x[b,0]), out[b, d:] = mean_{i = skip .. s-1} LN(x[b,i])
+ * (timm's global_pool="token" beside the mean of the patch tokens, the register tokens 1 .. skip-1 left out).
+ *   d_x [n,s,d] of `dtype`   d_gamma, d_beta [d] float32   d_out [n, 2d] float32
+ * Every row is normalised in float32 as in tia_layernorm_rows_h (mean first, then the variance of the centred values) and NOT rounded
+ * to `dtype`; the normalised rows are summed in float32 in a fixed order (no atomics; one workgroup per image, so an image's result
+ * is bit-identical whatever n is) and the affine is applied once to the mean (g mean(y) + b == mean(g y + b)).
+ * skip < 1 or skip >= s is TIA_EINVAL; d % 8 == 0 and d <= 8192 (else TIA_ESIZE). */
+int tia_vit_cls_mean_pool_h(const void* d_x, const float* d_gamma, const float* d_beta, float eps, float* d_out, int64_t n, int64_t s,
+                            int64_t skip, int64_t d, int32_t dtype, void* stream);
 
 /* =======================================================================================
  * All borders of binary planes: cv2.findContours(layer, RETR_TREE, CHAIN_APPROX_NONE | _SIMPLE)

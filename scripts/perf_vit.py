@@ -2,7 +2,7 @@
 on the same device (library GEMMs and attention), in ONE session, alternating:
 
 1. whole forward (normalised float patches in the run's dtype -> float32 features) of a seeded ``--model`` (default ``UNI``: ViT-L/16 with
-   LayerScale; any name of ``VIT_CONFIGS``, e.g. ``UNI2`` or ``H-optimus-0``) on ``--batch`` x ``--side``^2 patches, in
+   LayerScale; any name of ``VIT_CONFIGS`` / ``VIRCHOW_CONFIGS``, e.g. ``UNI2`` or ``H-optimus-0``, DESIGN 4.31, ``Virchow2``) on ``--batch`` x ``--side``^2 patches, in
    bfloat16 and float16;
 2. the algorithmic flops of that forward (GEMMs and the two attention products, from the shapes) over the time: TFLOP/s end to end.
 
@@ -68,9 +68,9 @@ def forward_flops(cfg: dict, depth: int, batch: int, side: int) -> dict:
 
 
 def build(args):
-    from tiatoolbox_amd.models.architecture.vit import VIT_CONFIGS, VisionTransformer
+    from tiatoolbox_amd.models.architecture.vit import VisionTransformer, vit_config
 
-    cfg = dict(VIT_CONFIGS[args.model])
+    cfg = dict(vit_config(args.model))
     if args.depth:
         cfg["depth"] = args.depth
     torch.manual_seed(0)

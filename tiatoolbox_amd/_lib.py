@@ -160,6 +160,7 @@ _SIGNATURES = {
     "tia_swiglu_rows_h": ([_P, _P, _I64, _I64, _I32, _P], C.c_int),
     "tia_vit_patchify_pad_h": ([_P, _I32, _P, _I64, _I64, _I64, _I64, _I64, _I32, _P], C.c_int),
     "tia_vit_assemble_prefix_h": ([_P, _P, _P, _P, _I32, _P, _I64, _I64, _I64, _I64, _I32, _P], C.c_int),
+    "tia_vit_cls_mean_pool_h": ([_P, _P, _P, C.c_float, _P, _I64, _I64, _I64, _I64, _I32, _P], C.c_int),
     "tia_bias_act_nhwc": ([_P, _P, _P, _I64, _I64, _I32, _I32, _P], C.c_int),
     "tia_bias_relu_maxpool_nhwc": ([_P, _P, _I64, _I64, _I64, _I64, _I32, _P, _P], C.c_int),
     "tia_hover_instance_stats": ([_P, _P, _I64, _I64, _I64, _I32, _I32, _P, _P, _P], C.c_int),

@@ -7,6 +7,8 @@
 //   swiglu_rows      : y[r, j] = silu(x[r, j]) * x[r, H + j]     the packed fc1 output [rows, 2 H] -> [rows, H]
 //   vit_patchify_pad : the same im2col for any patch size, rows zero-padded to k_pad columns (a 14-pixel patch: 588 -> 608)
 //   assemble_prefix  : out[b] = cat(cls (+ pos[0]), reg[0 .. R), tok[b] + pos[has_cls ..])
+// and the output of Virchow / Virchow2:
+//   cls_mean_pool    : out[b] = cat(LN(x[b, 0]), mean_{i >= skip} LN(x[b, i]))     float32 out, one workgroup per image
 // 16 bytes per lane and access (8 halves), float32 arithmetic, ONE round-to-nearest-even on the way out, 64-bit element offsets.
 #include "conv_device.hpp"
 #include "wide_io.hpp"
@@ -260,6 +262,118 @@ __global__ __launch_bounds__(ET) void vit_assemble_prefix_h_kernel(const v4u* __
     }
 }
 
+// Row `xr` normalised as in layernorm_rows_h_kernel (one read, the mean, then the variance of the centred values, both folded over
+// the wave), WITHOUT the affine: f = (x - mean) * rstd in float32, this lane's vectors lane + 64 i.
+template <bool BF, int VPL>
+__device__ __forceinline__ void normalise_row(const unsigned short* xr, int lane, int cv, int c, float eps, float (&f)[VPL][8]) {
+    float sum = 0.0f;
+#pragma unroll
+    for (int i = 0; i < VPL; ++i) {
+        const int v = lane + 64 * i;
+        if (v < cv) {
+            unpack8<BF>(*reinterpret_cast<const v4u*>(xr + 8 * v), f[i]);
+#pragma unroll
+            for (int k = 0; k < 8; ++k) sum += f[i][k];
+        }
+    }
+    const float mean = wave_sum(sum) / (float)c;
+    float sq = 0.0f;
+#pragma unroll
+    for (int i = 0; i < VPL; ++i)
+        if (lane + 64 * i < cv) {
+#pragma unroll
+            for (int k = 0; k < 8; ++k) {
+                f[i][k] -= mean;
+                sq = fmaf(f[i][k], f[i][k], sq);
+            }
+        }
+    const float rstd = 1.0f / sqrtf(wave_sum(sq) / (float)c + eps);
+#pragma unroll
+    for (int i = 0; i < VPL; ++i)
+        if (lane + 64 * i < cv) {
+#pragma unroll
+            for (int k = 0; k < 8; ++k) f[i][k] *= rstd;
+        }
+}
+
+// Class + mean-patch pooling of the final norm (Virchow / Virchow2): out[b, :d] = LN(x[b, 0]), out[b, d:] = mean_{i >= skip} LN(x[b, i]).
+// One workgroup per image.  Wave w normalises rows skip + w, skip + w + 4, ... (a row per wave, in registers, as above) and adds each
+// to per-lane float32 accumulators in that order; wave 0 writes the class row first.  The four partial sums are folded through one
+// LDS row in wave order, ((w0 + w1) + w2) + w3, and the affine is applied ONCE to the mean: mean_i (g y_i + b) = g mean_i y_i + b, so
+// the sum runs over the normalised values alone.  No atomics, nothing depends on the grid: an image's result does not depend on n.
+template <bool BF, int VPL>
+__global__ __launch_bounds__(ET) void vit_cls_mean_pool_h_kernel(const unsigned short* __restrict__ x, const float* __restrict__ gamma,
+                                                                  const float* __restrict__ beta, float eps, int s, int skip, int c,
+                                                                  float* __restrict__ out) {
+    extern __shared__ __attribute__((aligned(16))) float pool_fold[];  // [c]
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int cv = c >> 3;
+    const unsigned short* xb = x + (long)blockIdx.x * s * c;
+    float* ob = out + (long)blockIdx.x * 2 * c;
+    float f[VPL][8], acc[VPL][8];
+#pragma unroll
+    for (int i = 0; i < VPL; ++i)
+#pragma unroll
+        for (int k = 0; k < 8; ++k) acc[i][k] = 0.0f;
+
+    if (wave == 0) {  // (a whole wave: the exchanges stay inside it)
+        normalise_row<BF, VPL>(xb, lane, cv, c, eps, f);
+#pragma unroll
+        for (int i = 0; i < VPL; ++i) {
+            const int v = lane + 64 * i;
+            if (v < cv) {
+                float g[8], bt[8];
+                load8_f32(gamma + 8 * v, g);
+                load8_f32(beta + 8 * v, bt);
+                *reinterpret_cast<float4*>(ob + 8 * v) = make_float4(fmaf(f[i][0], g[0], bt[0]), fmaf(f[i][1], g[1], bt[1]),
+                                                                     fmaf(f[i][2], g[2], bt[2]), fmaf(f[i][3], g[3], bt[3]));
+                *reinterpret_cast<float4*>(ob + 8 * v + 4) = make_float4(fmaf(f[i][4], g[4], bt[4]), fmaf(f[i][5], g[5], bt[5]),
+                                                                         fmaf(f[i][6], g[6], bt[6]), fmaf(f[i][7], g[7], bt[7]));
+            }
+        }
+    }
+    for (int row = skip + wave; row < s; row += ET / 64) {
+        normalise_row<BF, VPL>(xb + (long)row * c, lane, cv, c, eps, f);
+#pragma unroll
+        for (int i = 0; i < VPL; ++i)
+            if (lane + 64 * i < cv) {
+#pragma unroll
+                for (int k = 0; k < 8; ++k) acc[i][k] += f[i][k];
+            }
+    }
+    // the fold: wave 0 lays its sums down, waves 1, 2 add theirs in turn, wave 3 adds its own and writes the mean
+    for (int w = 0; w < ET / 64; ++w) {
+        if (wave == w) {
+#pragma unroll
+            for (int i = 0; i < VPL; ++i) {
+                const int v = lane + 64 * i;
+                if (v < cv) {
+                    if (w > 0) {
+                        float p[8];
+                        load8_f32(pool_fold + 8 * v, p);
+#pragma unroll
+                        for (int k = 0; k < 8; ++k) acc[i][k] = p[k] + acc[i][k];
+                    }
+                    if (w < ET / 64 - 1) {
+                        *reinterpret_cast<float4*>(pool_fold + 8 * v) = make_float4(acc[i][0], acc[i][1], acc[i][2], acc[i][3]);
+                        *reinterpret_cast<float4*>(pool_fold + 8 * v + 4) = make_float4(acc[i][4], acc[i][5], acc[i][6], acc[i][7]);
+                    } else {
+                        const float cnt = (float)(s - skip);
+                        float g[8], bt[8], r[8];
+                        load8_f32(gamma + 8 * v, g);
+                        load8_f32(beta + 8 * v, bt);
+#pragma unroll
+                        for (int k = 0; k < 8; ++k) r[k] = fmaf(acc[i][k] / cnt, g[k], bt[k]);
+                        *reinterpret_cast<float4*>(ob + c + 8 * v) = make_float4(r[0], r[1], r[2], r[3]);
+                        *reinterpret_cast<float4*>(ob + c + 8 * v + 4) = make_float4(r[4], r[5], r[6], r[7]);
+                    }
+                }
+            }
+        }
+        __syncthreads();
+    }
+}
+
 unsigned stream_blocks(long items) {
     long blocks = (items + ET - 1) / ET;
     if (blocks > 256L * 64) blocks = 256L * 64;
@@ -303,6 +417,38 @@ extern "C" int tia_layernorm_rows_h(const void* d_x, int64_t row_stride, const f
         if (bf) launch_layernorm<true, false>(vpl, grid, st, x, (long)row_stride, d_gamma, d_beta, eps, (long)rows, (int)c, d_y);
         else launch_layernorm<false, false>(vpl, grid, st, x, (long)row_stride, d_gamma, d_beta, eps, (long)rows, (int)c, d_y);
     }
+    return hipGetLastError() == hipSuccess ? TIA_OK : TIA_ELAUNCH;
+}
+
+extern "C" int tia_vit_cls_mean_pool_h(const void* d_x, const float* d_gamma, const float* d_beta, float eps, float* d_out, int64_t n,
+                                       int64_t s, int64_t skip, int64_t d, int32_t dtype, void* stream) {
+    if (!d_x || !d_gamma || !d_beta || !d_out || n <= 0 || s <= 0 || d <= 0 || !(eps >= 0.0f)) return TIA_EINVAL;
+    if (dtype != TIA_DT_F16 && dtype != TIA_DT_BF16) return TIA_EINVAL;
+    if (skip < 1 || skip >= s) return TIA_EINVAL;
+    if ((d & 7) != 0 || d > 8192) return TIA_ESIZE;
+    if ((reinterpret_cast<uintptr_t>(d_x) | reinterpret_cast<uintptr_t>(d_gamma) | reinterpret_cast<uintptr_t>(d_beta) |
+         reinterpret_cast<uintptr_t>(d_out)) & 15)
+        return TIA_EINVAL;
+    if (n > 0x7fffffffL || s > 0x7fffffffL) return TIA_ESIZE;  // one grid dimension; the row index is an int
+    const int vpl = (int)((d / 8 + 63) / 64);
+    const dim3 grid((unsigned)n);
+    const size_t lds = (size_t)d * sizeof(float);
+    hipStream_t st = (hipStream_t)stream;
+    const unsigned short* x = static_cast<const unsigned short*>(d_x);
+#define TIA_POOL(BF, V) \
+    hipLaunchKernelGGL((vit_cls_mean_pool_h_kernel<BF, V>), grid, dim3(ET), lds, st, x, d_gamma, d_beta, eps, (int)s, (int)skip, (int)d, d_out)
+#define TIA_POOL_V(BF)            \
+    do {                          \
+        if (vpl <= 1) TIA_POOL(BF, 1);       \
+        else if (vpl <= 2) TIA_POOL(BF, 2);  \
+        else if (vpl <= 4) TIA_POOL(BF, 4);  \
+        else if (vpl <= 8) TIA_POOL(BF, 8);  \
+        else TIA_POOL(BF, 16);               \
+    } while (0)
+    if (dtype == TIA_DT_BF16) TIA_POOL_V(true);
+    else TIA_POOL_V(false);
+#undef TIA_POOL_V
+#undef TIA_POOL
     return hipGetLastError() == hipSuccess ? TIA_OK : TIA_ELAUNCH;
 }
 

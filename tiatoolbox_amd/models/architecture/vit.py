@@ -2,7 +2,9 @@
 torch: timm's ``VisionTransformer`` with ``num_classes=0`` and ``global_pool="token"`` -- no head, no ``fc_norm``; the output is the
 class token of the final norm, ``[B, D]``.  Parameter names and shapes are timm's, so its checkpoints load with ``strict=True``;
 ``UNI`` is ViT-L/16 with LayerScale (``init_values=1e-5``) and ``dynamic_img_size``.  The pathology foundation models (``UNI2``,
-``H-optimus-0`` / ``-1``, ``prov-gigapath``) add timm's ``reg_tokens``, ``no_embed_class`` and ``mlp_layer=SwiGLUPacked``.
+``H-optimus-0`` / ``-1``, ``prov-gigapath``) add timm's ``reg_tokens``, ``no_embed_class`` and ``mlp_layer=SwiGLUPacked``; ``Virchow`` /
+``Virchow2`` (ViT-H/14, 80 dimensions per head) add the class + mean-patch output (``global_pool="token_mean"``) and timm's default
+position table beside register tokens (``prefix_pos_embed``).
 
 The fp16 / bf16 forward on the hand-written kernels is :class:`~tiatoolbox_amd.models.architecture.vit_fused.FusedViT`.
 """
@@ -30,7 +32,19 @@ VIT_CONFIGS: dict[str, dict] = {
     "prov-gigapath": {"embed_dim": 1536, "depth": 40, "num_heads": 24, "mlp_dim": 8192, "patch_size": 16, "img_size": 224, "init_values": 1e-5,
                       "mlp_layer": "swiglu_packed"},
 }
+# paige-ai/Virchow and Virchow2's published timm configurations (`vit_huge_patch14_224`, SwiGLUPacked / SiLU, mlp_ratio 5.3375:
+# fc1 width int(1280 * 5.3375) = 6832); 1280 / 16 = 80 per head; the embedding is cat(class token, mean of the patch tokens).
+# `create_vit` builds them and `FusedViT` runs them.  They are a table of their own because `VIT_CONFIGS` is the list of names
+# `TimmBackbone` accepts, and `TimmBackbone` refuses these two (`tests/test_vit_foundation.py` pins that).
+VIRCHOW_CONFIGS: dict[str, dict] = {
+    "Virchow": {"embed_dim": 1280, "depth": 32, "num_heads": 16, "mlp_dim": 6832, "patch_size": 14, "img_size": 224, "init_values": 1e-5,
+                "dynamic_img_size": True, "mlp_layer": "swiglu_packed", "global_pool": "token_mean"},
+    "Virchow2": {"embed_dim": 1280, "depth": 32, "num_heads": 16, "mlp_dim": 6832, "patch_size": 14, "img_size": 224, "init_values": 1e-5,
+                 "reg_tokens": 4, "prefix_pos_embed": True, "dynamic_img_size": True, "mlp_layer": "swiglu_packed",
+                 "global_pool": "token_mean"},
+}
 MLP_LAYERS = ("mlp", "swiglu_packed")
+GLOBAL_POOLS = ("token", "token_mean")
 LN_EPS = 1e-6
 
 
@@ -136,22 +150,32 @@ class Block(nn.Module):
 
 
 class VisionTransformer(nn.Module):
-    """``forward(imgs [B, 3, H, W]) -> [B, D]``: the class token of ``norm(blocks(tokens))``.
+    """``forward(imgs [B, 3, H, W]) -> [B, D]``: the class token of ``norm(blocks(tokens))``; with ``global_pool="token_mean"``
+    ``[B, 2D]``: the class token beside the mean of the patch tokens (register tokens left out), ``cat([x[:, 0], x[:, 1 + R:].mean(1)])``.
 
     ``reg_tokens`` register tokens follow the class token (``reg_token [1, R, D]``); with ``no_embed_class`` the position table is the
     grid alone (``[1, g0 * g0, D]``), added to the patch tokens before the prefix is prepended: ``cat([cls, reg, patches + pos])``.
-    ``mlp_layer="swiglu_packed"`` puts :class:`SwiGLUPacked` in the blocks (``mlp_dim`` is then the packed ``fc1`` width)."""
+    ``mlp_layer="swiglu_packed"`` puts :class:`SwiGLUPacked` in the blocks (``mlp_dim`` is then the packed ``fc1`` width).
+    ``prefix_pos_embed`` is timm's default form beside register tokens (``no_embed_class=False``): ``pos_embed`` is
+    ``[1, 1 + R + g0 * g0, D]`` and the sequence is ``cat([cls, reg, patches]) + pos``; resampling leaves the ``1 + R`` prefix entries
+    as they are."""
 
     def __init__(self, *, embed_dim: int, depth: int, num_heads: int, mlp_dim: int, patch_size: int = 16, img_size: int = 224,
                  init_values: float | None = None, dynamic_img_size: bool = False, reg_tokens: int = 0, no_embed_class: bool = False,
-                 mlp_layer: str = "mlp") -> None:
+                 mlp_layer: str = "mlp", global_pool: str = "token", prefix_pos_embed: bool = False) -> None:
         super().__init__()
         if mlp_layer not in MLP_LAYERS:
             msg = f"VisionTransformer: mlp_layer is one of {MLP_LAYERS}; got {mlp_layer!r}."
             raise ValueError(msg)
-        if reg_tokens < 0 or (reg_tokens and not no_embed_class):
-            msg = (f"VisionTransformer: reg_tokens={reg_tokens} needs no_embed_class=True (a position table with a class entry beside "
-                   "register tokens is no registered model's form) and cannot be negative.")
+        if global_pool not in GLOBAL_POOLS:
+            msg = f"VisionTransformer: global_pool is one of {GLOBAL_POOLS}; got {global_pool!r}."
+            raise ValueError(msg)
+        if prefix_pos_embed and no_embed_class:
+            msg = "VisionTransformer: prefix_pos_embed (a table with class and register entries) contradicts no_embed_class=True."
+            raise ValueError(msg)
+        if reg_tokens < 0 or (reg_tokens and not (no_embed_class or prefix_pos_embed)):
+            msg = (f"VisionTransformer: reg_tokens={reg_tokens} needs no_embed_class=True (a grid-only position table) or "
+                   "prefix_pos_embed=True (a table with class and register entries) and cannot be negative.")
             raise ValueError(msg)
         if embed_dim % num_heads != 0 or img_size % patch_size != 0:
             msg = f"VisionTransformer: embed_dim {embed_dim} / heads {num_heads} or img_size {img_size} / patch {patch_size} does not divide."
@@ -159,7 +183,9 @@ class VisionTransformer(nn.Module):
         self.embed_dim, self.num_heads, self.patch_size = embed_dim, num_heads, patch_size
         self.dynamic_img_size = dynamic_img_size
         self.reg_tokens, self.no_embed_class, self.mlp_layer = reg_tokens, no_embed_class, mlp_layer
-        self.pos_prefix = 0 if no_embed_class else 1  # entries of `pos_embed` in front of the grid
+        self.global_pool, self.prefix_pos_embed = global_pool, prefix_pos_embed
+        # entries of `pos_embed` in front of the grid: none, the class entry, or (prefix_pos_embed) the class and register entries
+        self.pos_prefix = 0 if no_embed_class else 1 + (reg_tokens if prefix_pos_embed else 0)
         g0 = img_size // patch_size
         self.native_grid = (g0, g0)
         self.cls_token = nn.Parameter(torch.zeros(1, 1, embed_dim))
@@ -226,17 +252,31 @@ class VisionTransformer(nn.Module):
                 prefix.append(self.reg_token.expand(x.shape[0], -1, -1))
             x = torch.cat([*prefix, x + pos], dim=1)
         else:
-            x = torch.cat([self.cls_token.expand(x.shape[0], -1, -1), x], dim=1) + pos
+            prefix = [self.cls_token.expand(x.shape[0], -1, -1)]
+            if self.reg_tokens:  # (prefix_pos_embed: the table has an entry for every prefix token)
+                prefix.append(self.reg_token.expand(x.shape[0], -1, -1))
+            x = torch.cat([*prefix, x], dim=1) + pos
         x = self.norm(self.blocks(x))
+        if self.global_pool == "token_mean":
+            return torch.cat([x[:, 0], x[:, 1 + self.reg_tokens:].mean(1)], dim=-1)
         return x[:, 0]
 
 
 def create_vit(name: str, *, device: torch.device | str | None = None) -> VisionTransformer:
-    """The registered configuration ``name`` (``VIT_CONFIGS``); ``device="meta"`` builds the shapes only."""
-    if name not in VIT_CONFIGS:
-        msg = f"Backbone `{name}` is not supported."
-        raise ValueError(msg)
+    """The configuration ``name`` (``VIT_CONFIGS``, or ``VIRCHOW_CONFIGS``: ``Virchow`` / ``Virchow2``); ``device="meta"`` builds the shapes
+    only.  The Virchow names are no ``TimmBackbone`` names; to run one in an engine, put it into a backbone of another name:
+    ``m = TimmBackbone("vit_small_patch16_224"); m.feat_extract = create_vit("Virchow2")`` (then load its weights)."""
+    cfg = vit_config(name)
     if device is not None:
         with torch.device(device):
-            return VisionTransformer(**VIT_CONFIGS[name])
-    return VisionTransformer(**VIT_CONFIGS[name])
+            return VisionTransformer(**cfg)
+    return VisionTransformer(**cfg)
+
+
+def vit_config(name: str) -> dict:
+    """The constructor arguments of ``name`` from ``VIT_CONFIGS`` or ``VIRCHOW_CONFIGS``."""
+    for table in (VIT_CONFIGS, VIRCHOW_CONFIGS):
+        if name in table:
+            return table[name]
+    msg = f"Backbone `{name}` is not supported."
+    raise ValueError(msg)

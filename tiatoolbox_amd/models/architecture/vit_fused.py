@@ -24,8 +24,19 @@ LayerScale is folded EXACTLY in float32 before the one rounding of the weights: 
 the residual add is the GEMM's own ``d_residual`` and ``ls1`` / ``ls2`` cost nothing.  The residual stream stays in ``dtype`` (as in
 the cast torch module); the final norm reads the class rows only (row stride ``S * D``) and writes float32 features.
 
-There is no float32 form (no float32 attention kernel) and no library fall-back: a model the kernels do not take (``D / heads !=
-64``, channel counts off the GEMM's multiples) raises ``UnsupportedLayerError`` from the constructor.
+``Virchow`` / ``Virchow2`` (ViT-H/14, 1280 / 16 = 80 per head) change four more, all on the host in float32 before the one rounding:
+
+* ``head_dim`` 80: ``tia_mha_fwd_h``'s second kernel form; ``scale = 80 ** -0.5``;
+* a packed SwiGLU whose half (3416) is off the GEMM's multiple of 32: each half of ``fc1`` is padded with zero rows and zero bias to
+  3424 and ``fc2`` with zero columns (``pad_swiglu``; halves below 512 are not padded) -- a pad lane is ``silu(0) * 0 = 0`` exactly;
+* ``prefix_pos_embed`` (register tokens with entries of their own in the position table): ``cls + pos[0]`` and ``reg + pos[1 : 1 + R]``
+  are added per grid in float32 and handed to ``tia_vit_assemble_prefix_h`` with ``pos_has_cls = 0`` -- the same single add before the
+  same single rounding;
+* ``global_pool="token_mean"``: the last step is ``tia_vit_cls_mean_pool_h`` (``[n, 2D]``: the class row's LayerNorm beside the mean of
+  the patch rows' LayerNorms, register rows left out) in place of the class-row LayerNorm.
+
+There is no float32 form (no float32 attention kernel) and no library fall-back: a model the kernels do not take (``D / heads``
+other than 64 or 80, channel counts off the GEMM's multiples) raises ``UnsupportedLayerError`` from the constructor.
 """
 
 from __future__ import annotations
@@ -99,7 +110,7 @@ def hip_linear_h(x: torch.Tensor, w_packed: torch.Tensor, bias: torch.Tensor | N
 
 
 def hip_mha_fwd_h(qkv: torch.Tensor, heads: int, scale: float) -> torch.Tensor:
-    """Attention on the qkv Linear's output ``[n, S, 3 * heads * 64]`` -> ``[n, S, heads * 64]`` (``tia_mha_fwd_h``)."""
+    """Attention on the qkv Linear's output ``[n, S, 3 * heads * hd]`` -> ``[n, S, heads * hd]``, ``hd`` 64 or 80 (``tia_mha_fwd_h``)."""
     from tiatoolbox_amd import _lib
 
     _half_tokens("hip_mha_fwd_h", qkv)
@@ -240,6 +251,50 @@ def hip_vit_assemble_prefix_h(tokens: torch.Tensor, cls: torch.Tensor, reg: torc
     return out
 
 
+def hip_vit_cls_mean_pool_h(x: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, *, eps: float, skip: int) -> torch.Tensor:
+    """``cat([LN(x[:, 0]), LN(x[:, skip:]).mean(1)], -1)`` of ``[n, S, D]`` tokens in float32, ``[n, 2D]`` (float32 affine; the
+    normalised rows are not rounded to half): ``tia_vit_cls_mean_pool_h``."""
+    from tiatoolbox_amd import _lib
+
+    _half_tokens("hip_vit_cls_mean_pool_h", x)
+    if x.dim() != 3 or gamma.dtype != torch.float32 or beta.dtype != torch.float32 or gamma.numel() != x.shape[-1] or \
+            beta.numel() != x.shape[-1]:  # noqa: PLR2004
+        msg = f"hip_vit_cls_mean_pool_h takes [n, S, D] tokens and a float32 affine of D values; got {tuple(x.shape)}, {tuple(gamma.shape)}."
+        raise ValueError(msg)
+    n, s, d = x.shape
+    out = torch.empty((n, 2 * d), dtype=torch.float32, device=x.device)
+    with torch.cuda.device(x.device):
+        rc = _lib.load().tia_vit_cls_mean_pool_h(x.data_ptr(), gamma.data_ptr(), beta.data_ptr(), float(eps), out.data_ptr(), n, s, skip, d,
+                                                 _DT[x.dtype], _lib.current_stream())
+    _lib.check(rc, "tia_vit_cls_mean_pool_h")
+    return out
+
+
+SWIGLU_PAD_FLOOR = 512  # halves narrower than this are not padded: the waste is bounded by 31 / 512, and narrow layers stay refused
+
+
+def padded_swiglu_half(half: int) -> int:
+    """The width each half of a packed SwiGLU ``fc1`` is padded to: ``half`` itself on the half GEMM's multiple of 32 or below
+    ``SWIGLU_PAD_FLOOR``, else the next multiple of 32 (Virchow: 3416 -> 3424, ``fc1`` 6832 -> 6848)."""
+    if half % 32 == 0 or half < SWIGLU_PAD_FLOOR:
+        return half
+    return -(-half // 32) * 32
+
+
+def pad_swiglu(fc1_w: torch.Tensor, fc1_b: torch.Tensor, fc2_w: torch.Tensor) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """Float32 ``fc1 [2H, D]``, its bias and the (LayerScale-folded) ``fc2 [D, H]`` with each half padded to ``H_pad =
+    padded_swiglu_half(H)``: gate rows ``[0, H)``, zero rows and zero bias ``[H, H_pad)``, value rows ``[H_pad, H_pad + H)``, zeros
+    after; ``fc2`` gets zero columns.  A pad lane computes ``silu(0) * 0 = 0`` exactly and meets a zero weight."""
+    half = fc2_w.shape[1]
+    pad = padded_swiglu_half(half) - half
+    if pad == 0:
+        return fc1_w, fc1_b, fc2_w
+    zw, zb = fc1_w.new_zeros((pad, fc1_w.shape[1])), fc1_b.new_zeros(pad)
+    fc1_w = torch.cat([fc1_w[:half], zw, fc1_w[half:], zw], dim=0).contiguous()
+    fc1_b = torch.cat([fc1_b[:half], zb, fc1_b[half:], zb]).contiguous()
+    return fc1_w, fc1_b, torch.nn.functional.pad(fc2_w, (0, pad)).contiguous()
+
+
 class _Linear:
     """One GEMM of the graph: the float32 (LayerScale-folded) weights until ``prepare`` packs them, the float32 bias throughout.
     Plain attributes: the cast of the surrounding module does not reach them."""
@@ -276,12 +331,15 @@ class FusedViT(nn.Module):
         self.embed_dim, self.num_heads, self.patch_size = vit.embed_dim, vit.num_heads, vit.patch_size
         self.native_grid, self.dynamic_img_size = vit.native_grid, vit.dynamic_img_size
         head_dim = self.embed_dim // self.num_heads
-        if head_dim != 64:  # noqa: PLR2004
-            msg = f"FusedViT: the attention kernel takes head_dim 64; this model has {self.embed_dim} / {self.num_heads} = {head_dim}."
+        if head_dim not in (64, 80):
+            msg = f"FusedViT: the attention kernel takes head_dim 64 or 80; this model has {self.embed_dim} / {self.num_heads} = {head_dim}."
             raise UnsupportedLayerError(msg)
         self.scale = head_dim ** -0.5
         self.reg_tokens, self.no_embed_class, self.swiglu = vit.reg_tokens, vit.no_embed_class, vit.mlp_layer == "swiglu_packed"
-        self.pos_prefix = vit.pos_prefix
+        self.pos_prefix, self.global_pool = vit.pos_prefix, vit.global_pool
+        # register tokens with entries of their own in the table (timm's default form, Virchow2): folded into the prefix per grid
+        self.prefix_pos_embed = bool(vit.prefix_pos_embed and vit.reg_tokens)
+        self._prefix_cache: dict[tuple[int, int], tuple[torch.Tensor, torch.Tensor, torch.Tensor]] = {}
         # patch sizes off the multiples of 8 (14) take the padded im2col: rows of k_pad columns, zeros beyond 3 p^2
         self.k_pad = padded_patch_columns(self.patch_size) if self.patch_size % 8 != 0 else None
         # the parameters the module keeps (small): they carry device and dtype for `infer_batch`; their float32 values are set aside
@@ -304,6 +362,8 @@ class FusedViT(nn.Module):
             proj_w, proj_b = fold_layer_scale(blk.attn.proj, blk.ls1)
             fc1_w, fc1_b = fold_layer_scale(blk.mlp.fc1, None)
             fc2_w, fc2_b = fold_layer_scale(blk.mlp.fc2, blk.ls2)
+            if self.swiglu:  # halves off the GEMM's multiple of 32 (Virchow: 3416) get exact zero lanes, after the fold
+                fc1_w, fc1_b, fc2_w = pad_swiglu(fc1_w, fc1_b, fc2_w)
             self.layers.append({
                 "norm1": (f32(blk.norm1.weight), f32(blk.norm1.bias)), "norm2": (f32(blk.norm2.weight), f32(blk.norm2.bias)),
                 "qkv": _Linear(f"blocks.{i}.attn.qkv", qkv_w, qkv_b), "proj": _Linear(f"blocks.{i}.attn.proj", proj_w, proj_b),
@@ -333,6 +393,16 @@ class FusedViT(nn.Module):
                                                        num_prefix=self.pos_prefix).reshape(-1, self.embed_dim).contiguous()
         return self._pos_cache[grid]
 
+    def _prefix_for(self, grid: tuple[int, int]) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+        """``prefix_pos_embed``: ``(cls + pos[0], reg + pos[1 : 1 + R], pos[1 + R :])`` for ``grid`` -- the float32 adds the
+        assembly kernel would make, made once on the host side of the one rounding, so that ``tia_vit_assemble_prefix_h`` with
+        ``pos_has_cls = 0`` writes ``cat([cls, reg, patches]) + pos``."""
+        if grid not in self._prefix_cache:
+            pos, r = self._pos_for(grid), self.reg_tokens
+            self._prefix_cache[grid] = ((self._cls32 + pos[0]).contiguous(), (self._reg32 + pos[1:1 + r]).contiguous(),
+                                        pos[1 + r:].contiguous())
+        return self._prefix_cache[grid]
+
     def forward(self, imgs: torch.Tensor) -> torch.Tensor:
         half = self.half_dtype
         if half is None:
@@ -351,7 +421,10 @@ class FusedViT(nn.Module):
             tok = self.patch(hip_vit_patchify_h(x.contiguous(), p, half))
         else:
             tok = self.patch(hip_vit_patchify_pad_h(x.contiguous(), p, self.k_pad, half))
-        if self.reg_tokens or self.no_embed_class:
+        if self.prefix_pos_embed:
+            cls, reg, pos_grid = self._prefix_for((h // p, w // p))
+            x = hip_vit_assemble_prefix_h(tok, cls, reg, pos_grid, pos_has_cls=False)
+        elif self.reg_tokens or self.no_embed_class:
             x = hip_vit_assemble_prefix_h(tok, self._cls32, self._reg32, pos, pos_has_cls=not self.no_embed_class)
         else:
             x = hip_vit_assemble_tokens_h(tok, self._cls32, pos)
@@ -363,4 +436,6 @@ class FusedViT(nn.Module):
             a = hip_layernorm_rows_h(x, *layer["norm2"], eps=LN_EPS, rows=n * s, row_stride=d).view(n, s, d)
             a = hip_swiglu_rows_h(layer["fc1"](a)) if self.swiglu else hip_gelu_rows_h_(layer["fc1"](a))
             x = layer["fc2"](a, residual=x)
+        if self.global_pool == "token_mean":
+            return hip_vit_cls_mean_pool_h(x, *self._norm, eps=LN_EPS, skip=1 + self.reg_tokens)
         return hip_layernorm_rows_h(x, *self._norm, eps=LN_EPS, rows=n, row_stride=s * d, out_dtype=torch.float32)

@@ -45,7 +45,8 @@ extern "C" {
  * uint8 stem on the bf16 matrix cores with exactly split float32 weights); tia_mha_fwd_h, tia_layernorm_rows_h, tia_gelu_rows_h,
  * tia_vit_patchify_h, tia_vit_assemble_tokens_h (the Vision Transformer backbones in fp16 / bf16); tia_swiglu_rows_h,
  * tia_vit_patchify_pad_h, tia_vit_assemble_prefix_h (UNI2, H-optimus and prov-gigapath on the same graph); tia_vit_cls_mean_pool_h
- * and head_dim 80 in tia_mha_fwd_h (Virchow, Virchow2). */
+ * and head_dim 80 in tia_mha_fwd_h (Virchow, Virchow2); tia_vit_patchify_norm_u8_h, tia_linear_softmax_rows_f32 (Vision Transformer
+ * classifiers from uint8 patches to probabilities). */
 #define TIA_ABI_VERSION 6
 int tia_abi_version(void);
 
@@ -972,6 +973,33 @@ int tia_vit_assemble_prefix_h(const void* d_tokens, const float* d_cls, const fl
  * skip < 1 or skip >= s is TIA_EINVAL; d % 8 == 0 and d <= 8192 (else TIA_ESIZE). */
 int tia_vit_cls_mean_pool_h(const void* d_x, const float* d_gamma, const float* d_beta, float eps, float* d_out, int64_t n, int64_t s,
                             int64_t skip, int64_t d, int32_t dtype, void* stream);
+
+/* Vision Transformer classifiers (the reference's TimmModel: backbone -> Linear -> softmax) from uint8 patches to probabilities:
+ * the input normalisation inside the im2col, and the head on the graph's float32 features.  Additive, same version (6). */
+
+/* tia_vit_patchify_pad_h on uint8 patches with ToTensor + Normalize(mean, std) applied as a table: token value = d_table[byte][c].
+ *   d_x [n,h,w,3] uint8 NHWC, dense; it may start at ANY byte (a view into a larger buffer)
+ *   d_table [256][3] of `dtype`, 16-byte aligned: entry [v][c] is ((v / 255) - mean[c]) / std[c], worked out by the caller in
+ *     float32 and rounded once to `dtype` (models/dataset/classification.py: TimmNormPreproc)
+ *   d_tokens [n, (h/patch) * (w/patch), k_pad] of `dtype`, 16-byte aligned; columns in (ky, kx, channel) order, columns
+ *     3 patch^2 .. k_pad - 1 exact zeros.  k_pad == 3 patch^2 is allowed when that is a multiple of 32 (patch 16: 768), so the one
+ *     entry point serves every patch size.
+ * A pure gather (no arithmetic): the result equals tia_vit_patchify_h / tia_vit_patchify_pad_h applied to the table looked up
+ * per byte, bit for bit.  The table is kept in LDS; the bytes are read as aligned dwords and shifted together wherever 8 of them are
+ * contiguous.  TIA_ESIZE: h % patch, w % patch, k_pad % 32, k_pad < 3 patch^2.  TIA_EINVAL: a null pointer, a non-positive size, a
+ * dtype other than TIA_DT_F16 | TIA_DT_BF16, d_table or d_tokens not 16-byte aligned.  Nothing is launched on an error. */
+int tia_vit_patchify_norm_u8_h(const uint8_t* d_x, const void* d_table, void* d_tokens, int64_t n, int64_t h, int64_t w, int64_t patch,
+                               int64_t k_pad, int32_t dtype, void* stream);
+
+/* The classifier head: p[r,:] = softmax(x[r,:f] . W^T + b), float32 throughout.
+ *   d_x float32, row r at element r * row_stride (row_stride >= f, % 4 == 0), 16-byte aligned   d_w [c,f] float32 (nn.Linear's own
+ *   layout), 16-byte aligned   d_bias [c] float32 or NULL   d_p [rows,c] dense float32.
+ * One wave per row; every logit is summed with fmaf in an order fixed by f alone (no atomics: a row's probabilities are bit-identical
+ * in any batch); the row maximum is subtracted, exp is expf (not the fast intrinsic), ONE division per element; c == 1 gives 1.0.
+ * 1 <= c <= 64, f % 4 == 0 and f <= 8192 (else TIA_ESIZE); null d_x / d_w / d_p, non-positive sizes, row_stride < f or % 4 != 0 and
+ * misaligned pointers are TIA_EINVAL.  Nothing is launched on an error. */
+int tia_linear_softmax_rows_f32(const float* d_x, int64_t row_stride, const float* d_w, const float* d_bias, float* d_p, int64_t rows,
+                                int64_t f, int64_t c, void* stream);
 
 /* =======================================================================================
  * All borders of binary planes: cv2.findContours(layer, RETR_TREE, CHAIN_APPROX_NONE | _SIMPLE)

@@ -90,7 +90,8 @@ class TimmBackbone(ModelABC):
     """Feature extractor on a Vision Transformer (ref. ``TimmBackbone``): ``UNI``, the ``vit_*_patch16_224`` family and the foundation
     models ``UNI2``, ``H-optimus-0`` / ``H-optimus-1`` and ``prov-gigapath`` (``VIT_CONFIGS``), restated in plain torch with timm's
     parameter names (``architecture/vit.py``).  The features are the class token of the final norm,
-    ``[B, D]``; input normalisation is the caller's ``preproc_func``, as in the reference.  ``pretrained=True`` loads
+    ``[B, D]``; input normalisation is the caller's ``preproc_func``, as in the reference
+    (``models.dataset.classification.timm_preproc_func(backbone)`` is each model's).  ``pretrained=True`` loads
     ``<backbone>.pth`` (a timm state dict) from the local weight directories; the hub is never contacted."""
 
     def __init__(self, backbone: str, *, pretrained: bool = False) -> None:
@@ -101,17 +102,57 @@ class TimmBackbone(ModelABC):
         self.pretrained = pretrained
         self.feat_extract = create_vit(backbone)
         if pretrained:
-            from tiatoolbox_amd.models.architecture import local_pretrained_weights, logger
-
-            weights = local_pretrained_weights(backbone)
-            if weights is not None:
-                self.feat_extract.load_state_dict(torch.load(weights, map_location="cpu"), strict=True)
-            else:
-                logger.warning("No local weights for `%s` (the HuggingFace hub is unreachable): using the seeded "
-                               "random initialisation. Pass `weights=<path to .pth>` for the pretrained model.", backbone)
+            _load_local_vit_weights(self.feat_extract, backbone)
 
     def forward(self, imgs: torch.Tensor) -> torch.Tensor:
         return torch.flatten(self.feat_extract(imgs), 1)
+
+    @staticmethod
+    def infer_batch(model: nn.Module, batch_data, device: str = "cpu"):
+        return _infer_batch(model=model, batch_data=batch_data, device=device)
+
+
+def _load_local_vit_weights(vit: nn.Module, backbone: str) -> None:
+    """``pretrained=True`` of the Vision Transformer models: ``<backbone>.pth`` (a timm state dict) from the local weight
+    directories, strictly; a warning and the seeded initialisation without one."""
+    from tiatoolbox_amd.models.architecture import local_pretrained_weights, logger
+
+    weights = local_pretrained_weights(backbone)
+    if weights is not None:
+        vit.load_state_dict(torch.load(weights, map_location="cpu"), strict=True)
+    else:
+        logger.warning("No local weights for `%s` (the HuggingFace hub is unreachable): using the seeded "
+                       "random initialisation. Pass `weights=<path to .pth>` for the pretrained model.", backbone)
+
+
+class TimmModel(ModelABC):
+    """Vision Transformer + linear classifier + softmax (ref. ``TimmModel``): the linear probe on a foundation model that
+    ``PatchPredictor`` runs.  ``feat_extract = create_vit(backbone)`` -- every name ``create_vit`` builds, ``Virchow`` / ``Virchow2``
+    included -- and ``classifier = nn.Linear(F, num_classes)`` on its output, ``F = D`` or ``2 D`` for the class + mean-patch output of
+    the Virchow models.  The state dict is ``feat_extract.<timm names>`` plus ``classifier.{weight,bias}``, so a probe trained against
+    the reference loads with ``strict=True``.  ``pretrained=True`` reads the backbone's ``.pth`` as :class:`TimmBackbone` does.  Input
+    normalisation is the caller's ``preproc_func``: ``models.dataset.classification.timm_preproc_func(backbone)``.
+
+    On the GPU in fp16 / bf16 the engines run it as ``vit_fused.FusedViTClassifier``."""
+
+    def __init__(self, backbone: str, num_classes: int = 1, *, pretrained: bool = False) -> None:
+        super().__init__()
+        self.pretrained = pretrained
+        self.num_classes = num_classes
+        self.feat_extract = create_vit(backbone)  # (an unknown name: ValueError("Backbone `X` is not supported."))
+        if pretrained:
+            _load_local_vit_weights(self.feat_extract, backbone)
+        width = self.feat_extract.embed_dim * (2 if self.feat_extract.global_pool == "token_mean" else 1)
+        self.classifier = nn.Linear(width, num_classes)
+
+    def forward(self, imgs: torch.Tensor) -> torch.Tensor:
+        feat = torch.flatten(self.feat_extract(imgs), 1)
+        logit = self.classifier(feat)
+        return torch.softmax(logit.float(), -1)
+
+    @staticmethod
+    def postproc(image):
+        return argmax_last_axis(image=image)
 
     @staticmethod
     def infer_batch(model: nn.Module, batch_data, device: str = "cpu"):

@@ -35,6 +35,11 @@ the cast torch module); the final norm reads the class rows only (row stride ``S
 * ``global_pool="token_mean"``: the last step is ``tia_vit_cls_mean_pool_h`` (``[n, 2D]``: the class row's LayerNorm beside the mean of
   the patch rows' LayerNorms, register rows left out) in place of the class-row LayerNorm.
 
+Classifiers (``vanilla.TimmModel``) add the two ends: ``forward_uint8(x_u8_nhwc, table)`` takes the uint8 patches themselves --
+``tia_vit_patchify_norm_u8_h`` is the padded im2col with ``ToTensor`` + ``Normalize`` looked up per byte in ``TimmNormPreproc``'s ``[256, 3]``
+table, bit for bit ``forward`` of the hook's batched form -- and :class:`FusedViTClassifier` puts ``tia_linear_softmax_rows_f32`` (the
+Linear and the softmax, float32 throughout) on the graph's float32 features.
+
 There is no float32 form (no float32 attention kernel) and no library fall-back: a model the kernels do not take (``D / heads``
 other than 64 or 80, channel counts off the GEMM's multiples) raises ``UnsupportedLayerError`` from the constructor.
 """
@@ -270,6 +275,56 @@ def hip_vit_cls_mean_pool_h(x: torch.Tensor, gamma: torch.Tensor, beta: torch.Te
     return out
 
 
+def hip_vit_patchify_norm_u8_h(x_u8_nhwc: torch.Tensor, table: torch.Tensor, patch: int, k_pad: int, dtype: torch.dtype) -> torch.Tensor:
+    """``[n, h, w, 3]`` uint8 patches -> ``[n, g, k_pad]`` tokens of ``dtype`` with ``table[byte, channel]`` for every byte, zeros
+    from column ``3 * patch^2`` on (``tia_vit_patchify_norm_u8_h``: ``ToTensor`` + ``Normalize`` as a ``[256, 3]`` table of ``dtype``).
+    The batch may be a view that starts at any byte of a larger buffer."""
+    from tiatoolbox_amd import _lib
+
+    if not (x_u8_nhwc.is_cuda and x_u8_nhwc.dim() == 4 and x_u8_nhwc.shape[-1] == 3 and x_u8_nhwc.is_contiguous()  # noqa: PLR2004
+            and x_u8_nhwc.dtype == torch.uint8):
+        msg = f"hip_vit_patchify_norm_u8_h expects a contiguous [n, h, w, 3] uint8 CUDA tensor; got {tuple(x_u8_nhwc.shape)}, {x_u8_nhwc.dtype}."
+        raise ValueError(msg)
+    if not (dtype in _HALF and table.dtype == dtype and table.device == x_u8_nhwc.device and tuple(table.shape) == (256, 3)
+            and table.is_contiguous()):
+        msg = (f"hip_vit_patchify_norm_u8_h takes a contiguous [256, 3] fp16 / bf16 table of the tokens' dtype on the batch's device; got "
+               f"{tuple(table.shape)}, {table.dtype} on {table.device} for {dtype}.")
+        raise ValueError(msg)
+    n, h, w, _ = x_u8_nhwc.shape
+    out = torch.empty((n, (h // patch) * (w // patch), k_pad), dtype=dtype, device=x_u8_nhwc.device)
+    with torch.cuda.device(x_u8_nhwc.device):
+        rc = _lib.load().tia_vit_patchify_norm_u8_h(x_u8_nhwc.data_ptr(), table.data_ptr(), out.data_ptr(), n, h, w, patch, k_pad, _DT[dtype],
+                                                    _lib.current_stream())
+    _lib.check(rc, "tia_vit_patchify_norm_u8_h")
+    return out
+
+
+HEAD_MAX_CLASSES, HEAD_MAX_FEATURES = 64, 8192  # what tia_linear_softmax_rows_f32 takes (one lane per class; the widest LayerNorm row)
+
+
+def hip_linear_softmax_rows_f32(x: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor | None) -> torch.Tensor:
+    """``softmax(x @ weight^T + bias, -1)`` of float32 rows ``[rows, f]`` (the rows may be a view at a stride) with ``weight [c, f]``,
+    ``bias [c]`` or ``None``: float32 throughout, ``[rows, c]`` (``tia_linear_softmax_rows_f32``)."""
+    from tiatoolbox_amd import _lib
+
+    if not (x.is_cuda and x.dim() == 2 and x.dtype == torch.float32 and x.stride(1) == 1 and weight.dim() == 2  # noqa: PLR2004
+            and weight.dtype == torch.float32 and weight.is_contiguous() and weight.device == x.device and weight.shape[1] == x.shape[1]
+            and (bias is None or (bias.dtype == torch.float32 and bias.is_contiguous() and bias.device == x.device
+                                  and bias.numel() == weight.shape[0]))):
+        msg = (f"hip_linear_softmax_rows_f32 takes float32 CUDA rows [rows, f], a contiguous weight [c, f] and a bias [c] or None; got "
+               f"{tuple(x.shape)}, {x.dtype} on {x.device}, {tuple(weight.shape)}, {None if bias is None else tuple(bias.shape)}.")
+        raise ValueError(msg)
+    rows, f = x.shape
+    c = weight.shape[0]
+    stride = x.stride(0) if rows > 1 else f
+    out = torch.empty((rows, c), dtype=torch.float32, device=x.device)
+    with torch.cuda.device(x.device):
+        rc = _lib.load().tia_linear_softmax_rows_f32(x.data_ptr(), stride, weight.data_ptr(), _ptr(bias), out.data_ptr(), rows, f, c,
+                                                     _lib.current_stream())
+    _lib.check(rc, "tia_linear_softmax_rows_f32")
+    return out
+
+
 SWIGLU_PAD_FLOOR = 512  # halves narrower than this are not padded: the waste is bounded by 31 / 512, and narrow layers stay refused
 
 
@@ -408,8 +463,8 @@ class FusedViT(nn.Module):
         if half is None:
             msg = "FusedViT.forward needs prepare(dtype) first."
             raise RuntimeError(msg)
-        p, d = self.patch_size, self.embed_dim
-        n, _, h, w = imgs.shape
+        p = self.patch_size
+        _, _, h, w = imgs.shape
         if h % p != 0 or w % p != 0:
             msg = f"FusedViT: the input size {h} x {w} is no multiple of the patch size {p}."
             raise ValueError(msg)
@@ -418,11 +473,38 @@ class FusedViT(nn.Module):
         if x.dtype not in (torch.float32, half):
             x = x.to(torch.float32)
         if self.k_pad is None:
-            tok = self.patch(hip_vit_patchify_h(x.contiguous(), p, half))
+            cols = hip_vit_patchify_h(x.contiguous(), p, half)
         else:
-            tok = self.patch(hip_vit_patchify_pad_h(x.contiguous(), p, self.k_pad, half))
+            cols = hip_vit_patchify_pad_h(x.contiguous(), p, self.k_pad, half)
+        return self._from_patch_columns(cols, pos, (h // p, w // p))
+
+    def forward_uint8(self, x_u8_nhwc: torch.Tensor, table: torch.Tensor) -> torch.Tensor:
+        """``forward`` of ``table[x, channel]`` for a uint8 NHWC batch (``ToTensor`` + ``Normalize`` as ``TimmNormPreproc``'s
+        ``[256, 3]`` table in the graph's dtype): ``tia_vit_patchify_norm_u8_h`` makes the look-up while it lays the patches out, and
+        the graph runs from the token GEMM on as in ``forward`` -- bit for bit ``forward(hook.device_batch(x, dtype))``."""
+        half = self.half_dtype
+        if half is None:
+            msg = "FusedViT.forward_uint8 needs prepare(dtype) first."
+            raise RuntimeError(msg)
+        if x_u8_nhwc.dim() != 4 or x_u8_nhwc.shape[-1] != 3 or x_u8_nhwc.dtype != torch.uint8:  # noqa: PLR2004
+            msg = f"FusedViT.forward_uint8 takes a uint8 [n, h, w, 3] batch; got {tuple(x_u8_nhwc.shape)}, {x_u8_nhwc.dtype}."
+            raise ValueError(msg)
+        p = self.patch_size
+        _, h, w, _ = x_u8_nhwc.shape
+        if h % p != 0 or w % p != 0:
+            msg = f"FusedViT: the input size {h} x {w} is no multiple of the patch size {p}."
+            raise ValueError(msg)
+        pos = self._pos_for((h // p, w // p))  # (refuses an off-grid size before any launch)
+        k_pad = self.k_pad if self.k_pad is not None else 3 * p * p
+        cols = hip_vit_patchify_norm_u8_h(x_u8_nhwc.contiguous(), table, p, k_pad, half)
+        return self._from_patch_columns(cols, pos, (h // p, w // p))
+
+    def _from_patch_columns(self, cols: torch.Tensor, pos: torch.Tensor, grid: tuple[int, int]) -> torch.Tensor:
+        """The graph from the token GEMM on: ``cols`` ``[n, g, 3 p^2 or k_pad]`` are the im2col rows of either input form."""
+        n, d = cols.shape[0], self.embed_dim
+        tok = self.patch(cols)
         if self.prefix_pos_embed:
-            cls, reg, pos_grid = self._prefix_for((h // p, w // p))
+            cls, reg, pos_grid = self._prefix_for(grid)
             x = hip_vit_assemble_prefix_h(tok, cls, reg, pos_grid, pos_has_cls=False)
         elif self.reg_tokens or self.no_embed_class:
             x = hip_vit_assemble_prefix_h(tok, self._cls32, self._reg32, pos, pos_has_cls=not self.no_embed_class)
@@ -439,3 +521,49 @@ class FusedViT(nn.Module):
         if self.global_pool == "token_mean":
             return hip_vit_cls_mean_pool_h(x, *self._norm, eps=LN_EPS, skip=1 + self.reg_tokens)
         return hip_layernorm_rows_h(x, *self._norm, eps=LN_EPS, rows=n, row_stride=s * d, out_dtype=torch.float32)
+
+
+class FusedViTClassifier(nn.Module):
+    """The inference form of a ``vanilla.TimmModel``: its backbone as :class:`FusedViT` and the classifier on the graph's float32
+    features as ``tia_linear_softmax_rows_f32`` -- ``forward(imgs)`` == ``TimmModel.forward(imgs)``, float32 probabilities
+    ``[n, num_classes]``; ``forward_uint8(x, table)`` the same from a uint8 NHWC batch (``FusedViT.forward_uint8``).
+
+    The head stays float32, as the module's ``softmax(logit.float())`` means it: its weights are plain attributes that the cast of
+    the surrounding module does not reach.  Built from a loaded model on its device; ``FusedViT``'s refusals (``UnsupportedLayerError``)
+    pass through.  More than ``HEAD_MAX_CLASSES`` classes (or features beyond ``HEAD_MAX_FEATURES``) are outside the head kernel:
+    ``classifier`` and the softmax then stay torch operations on the same float32 features, with one warning."""
+
+    def __init__(self, model: nn.Module) -> None:
+        super().__init__()
+        classifier = getattr(model, "classifier", None)
+        if not isinstance(classifier, nn.Linear):
+            msg = f"FusedViTClassifier covers a TimmModel (feat_extract + an nn.Linear classifier); got {type(model).__name__}."
+            raise UnsupportedLayerError(msg)
+        self.feat_extract = FusedViT(model.feat_extract)
+        self.num_classes, self.num_features = classifier.out_features, classifier.in_features
+        self._w32 = classifier.weight.detach().to(torch.float32).contiguous()
+        self._b32 = classifier.bias.detach().to(torch.float32).contiguous() if classifier.bias is not None else None
+        self.head_kernel = self.num_classes <= HEAD_MAX_CLASSES and self.num_features <= HEAD_MAX_FEATURES and self.num_features % 4 == 0
+        if not self.head_kernel:
+            import logging
+
+            logging.getLogger("tiatoolbox_amd").warning(
+                "FusedViTClassifier: the head kernel takes at most %d classes on at most %d features (a multiple of 4); this classifier "
+                "is %d -> %d, so the Linear and the softmax run as torch operations (a library GEMM) on the float32 features.",
+                HEAD_MAX_CLASSES, HEAD_MAX_FEATURES, self.num_features, self.num_classes)
+
+    @property
+    def half_dtype(self) -> torch.dtype | None:
+        return self.feat_extract.half_dtype
+
+    def _head(self, feat: torch.Tensor) -> torch.Tensor:
+        feat = torch.flatten(feat, 1)
+        if self.head_kernel:
+            return hip_linear_softmax_rows_f32(feat, self._w32, self._b32)
+        return torch.softmax(torch.nn.functional.linear(feat, self._w32, self._b32), -1)
+
+    def forward(self, imgs: torch.Tensor) -> torch.Tensor:
+        return self._head(self.feat_extract(imgs))
+
+    def forward_uint8(self, x_u8_nhwc: torch.Tensor, table: torch.Tensor) -> torch.Tensor:
+        return self._head(self.feat_extract.forward_uint8(x_u8_nhwc, table))

@@ -445,7 +445,8 @@ class EngineABC:
             from tiatoolbox_amd.models.architecture.vit import VisionTransformer
 
             if isinstance(getattr(m, "feat_extract", None), VisionTransformer):
-                # Vision Transformer backbones (TimmBackbone).  GPU, fp16 / bf16: FusedViT -- every Linear on the half MFMA GEMM,
+                # Vision Transformer backbones (TimmBackbone) and classifiers (TimmModel: FusedViTClassifier, the same graph plus the
+                # head kernel).  GPU, fp16 / bf16: FusedViT -- every Linear on the half MFMA GEMM,
                 # attention, LayerNorm, GELU / SwiGLU and token assembly on their own kernels (architecture/vit_fused.py; `prepare(dtype)`
                 # below).  GPU, float32: there is no float32 attention kernel, the torch module runs on the library's GEMMs -- never
                 # silently.  CPU: the torch module.  `conv_algo` has nothing to choose here.
@@ -453,9 +454,15 @@ class EngineABC:
                     from tiatoolbox_amd.models.architecture.unet_fused import UnsupportedLayerError
                     from tiatoolbox_amd.models.architecture.vit_fused import FusedViT
 
+                    from tiatoolbox_amd.models.architecture.vanilla import TimmModel
+                    from tiatoolbox_amd.models.architecture.vit_fused import FusedViTClassifier
+
                     m = m.to(device=self.device)
                     try:
-                        m.feat_extract = FusedViT(m.feat_extract)
+                        if isinstance(m, TimmModel) and type(m).forward is TimmModel.forward:
+                            m = FusedViTClassifier(m)  # backbone + classifier: the head on its own float32 kernel as well
+                        else:
+                            m.feat_extract = FusedViT(m.feat_extract)
                     except UnsupportedLayerError as exc:  # (the constructor's own refusal; any other error is a bug and propagates)
                         logger.warning("%s: %s  Running the torch module in %s instead: its matrix products are library (hipBLASLt / "
                                        "rocBLAS) GEMMs.", type(self.model).__name__, exc, dtype)
@@ -563,6 +570,11 @@ class EngineABC:
         ``ToTensor``, that step is deferred into the stem kernel (the batch stays uint8, wrapped in ``UnitUInt8``)."""
         if getattr(self, "_defer_unit", False) and getattr(hook, "supports_deferred_unit_scale", False):
             return hook.device_batch(batch, dtype, defer_unit_scale=True)
+        if getattr(self, "_defer_norm", False):
+            from tiatoolbox_amd.models.dataset.classification import TimmNormPreproc
+
+            if type(hook) is TimmNormPreproc:  # ToTensor + Normalize deferred into the ViT graph's im2col (a uint8 CUDA batch)
+                return hook.device_batch(batch, dtype, defer_norm=True)
         return hook.device_batch(batch, dtype)
 
     def _prenormalized(self, hook, inputs: torch.Tensor, lo: int, hi: int):
@@ -602,12 +614,34 @@ class EngineABC:
         self._defer_unit = bool(torch.device(self.device).type == "cuda" and stock
                                 and getattr(getattr(model, "feat_extract", None), "accepts_uint8", False))
 
+    def _set_defer_norm(self, model) -> None:
+        """``ToTensor`` + ``Normalize`` (a ``TimmNormPreproc`` hook) may be deferred into the Vision Transformer graph's im2col under
+        the rule of :meth:`_set_defer_unit`, with a flag of its own: the model is EXACTLY a ``TimmModel`` / ``TimmBackbone`` with the
+        stock ``infer_batch`` (a subclass's own pre-processing would see raw bytes) and the inference copy's trunk is a prepared
+        :class:`FusedViT`.  The hook itself and the batch are looked at per batch (``_device_preproc``, ``device_batch``)."""
+        from tiatoolbox_amd.models.architecture.vanilla import TimmBackbone, TimmModel
+        from tiatoolbox_amd.models.architecture.vit_fused import FusedViT, FusedViTClassifier
+
+        stock = type(self.model) in (TimmModel, TimmBackbone) and type(model) in (FusedViTClassifier, TimmBackbone)
+        if stock:
+            own = type(self.model).__dict__.get("infer_batch")
+            bound = getattr(self.model, "infer_batch", None)
+            stock = own is not None and getattr(own, "__func__", own) is getattr(bound, "__func__", bound)
+        trunk = getattr(model, "feat_extract", None)
+        self._defer_norm = bool(torch.device(self.device).type == "cuda" and stock and isinstance(trunk, FusedViT)
+                                and trunk.half_dtype is not None)
+
     def _forward_batch(self, model, infer_batch, batch):
-        from tiatoolbox_amd.models.dataset.classification import UnitUInt8
+        from tiatoolbox_amd.models.dataset.classification import NormUInt8, UnitUInt8
 
         if isinstance(batch, UnitUInt8):  # ToTensor deferred: the stem kernel divides by 255 while it loads the bytes
             with torch.inference_mode():
                 return model(batch.data.permute(0, 3, 1, 2)).float()
+        if isinstance(batch, NormUInt8):  # ToTensor + Normalize deferred: the im2col kernel looks the bytes up in the hook's table
+            graph = model if hasattr(model, "forward_uint8") else model.feat_extract  # (TimmBackbone: flatten(feat_extract(.), 1))
+            with torch.inference_mode():
+                table = batch.hook.device_table(batch.data.device, graph.half_dtype)
+                return torch.flatten(graph.forward_uint8(batch.data, table), 1).float()
         return infer_batch(model, batch, device=self.device)
 
     @contextlib.contextmanager
@@ -714,6 +748,7 @@ class EngineABC:
         if dev.type == "cuda" and isinstance(dataloader.inputs, np.ndarray) and dataloader.inputs.dtype == np.uint8:
             self._feed = _HostFeed(dataloader.inputs, dev)
         self._set_defer_unit(model, dtype)
+        self._set_defer_norm(model)
         self._shard_span, self._norm_cache = (lo, hi), None
         try:
             with self._miopen_scope(), self._deferred_norm_checks(dataloader.preproc_func):
@@ -859,6 +894,7 @@ class EngineABC:
         lo, hi = tdist.shard_bounds(n, rank, world_size)
         outs = []
         self._set_defer_unit(model, dtype)
+        self._set_defer_norm(model)
         # the shard's patch bounds go to the device once (a per-batch upload is a synchronous copy: the host would wait for the
         # previous batch's kernels before it can launch the next forward)
         c_np = np.ascontiguousarray(np.asarray(coords[lo:hi]).reshape(-1, 4), dtype=np.int32)

@@ -46,7 +46,8 @@ extern "C" {
  * tia_vit_patchify_h, tia_vit_assemble_tokens_h (the Vision Transformer backbones in fp16 / bf16); tia_swiglu_rows_h,
  * tia_vit_patchify_pad_h, tia_vit_assemble_prefix_h (UNI2, H-optimus and prov-gigapath on the same graph); tia_vit_cls_mean_pool_h
  * and head_dim 80 in tia_mha_fwd_h (Virchow, Virchow2); tia_vit_patchify_norm_u8_h, tia_linear_softmax_rows_f32 (Vision Transformer
- * classifiers from uint8 patches to probabilities). */
+ * classifiers from uint8 patches to probabilities); tia_linear_fp8_rows, tia_linear_fp8_pack_weights, tia_linear_fp8_serves,
+ * tia_layernorm_rows_q8, tia_gelu_rows_q8, tia_swiglu_rows_q8 (the Vision Transformer linear layers on the FP8 matrix instruction). */
 #define TIA_ABI_VERSION 6
 int tia_abi_version(void);
 
@@ -1000,6 +1001,46 @@ int tia_vit_patchify_norm_u8_h(const uint8_t* d_x, const void* d_table, void* d_
  * misaligned pointers are TIA_EINVAL.  Nothing is launched on an error. */
 int tia_linear_softmax_rows_f32(const float* d_x, int64_t row_stride, const float* d_w, const float* d_bias, float* d_p, int64_t rows,
                                 int64_t f, int64_t c, void* stream);
+
+/* =======================================================================================
+ * Vision Transformer linear layers on the FP8 matrix instruction (vit_fused.py, linear_dtype="float8_e4m3").
+ * Additive, same version (6); the contract of the family above (16-byte aligned pointers, nothing launched on an error).
+ *
+ * The numeric contract -- row x column scaled FP8, not MXFP8:
+ *   format       OCP e4m3fn: largest finite value 448, no infinities (NOT the MI300 fnuz encoding).  float32 -> code rounds to
+ *                nearest even and saturates at +-448.
+ *   a row        v[0..K) float32: amax = max |v|; inv = 448 / amax and s = amax / 448, one float32 division each (amax == 0:
+ *                inv = s = 1); q[k] = e4m3(v[k] * inv), the product in float32.  Stored as q (K bytes) and s (one float32).
+ *   weights      one row per output channel, quantised once from the float32 weights (after the LayerScale fold and the SwiGLU
+ *                padding: where the half path rounds).
+ *   activations  one row per token, quantised from the float32 value the producing kernel holds, before any rounding to half.
+ *   GEMM         acc[r,o] = sum_k qa[r,k] qw[o,k]: exact products, float32 accumulation in any order;
+ *                y[r,o] = half_rne(acc * sa[r] * sw[o] + bias[o] (+ float32(residual[r,o]))).
+ *                v_mfma_scale_f32_16x16x128_f8f6f4 with both block-scale operands the constant 1.0 (E8M0 127).
+ * ===================================================================================== */
+
+/* The GEMM.  d_a [rows,K] e4m3 codes with d_sa [rows]; d_w [N,K] e4m3 codes with d_sw [N] (tia_linear_fp8_pack_weights);
+ * d_bias [N] float32 or NULL; d_residual [rows,N] of `dtype` or NULL; d_y [rows,N] of `dtype` (TIA_DT_F16 | TIA_DT_BF16).
+ * K % 128 == 0 and N % 16 == 0 (else TIA_ESIZE), any rows >= 1 (rows <= 0: TIA_EINVAL). */
+int tia_linear_fp8_rows(const void* d_a, const float* d_sa, const void* d_w, const float* d_sw, const float* d_bias,
+                        const void* d_residual, void* d_y, int64_t rows, int64_t n, int64_t k, int32_t dtype, void* stream);
+
+/* Weights for tia_linear_fp8_rows from float32 d_w [N,K] (nn.Linear's own layout): d_q [N,K] codes, d_scale [N], quantised per
+ * output channel on the device by the recipe above.  The shape limits of the GEMM. */
+int tia_linear_fp8_pack_weights(const float* d_w, int64_t n, int64_t k, void* d_q, float* d_scale, void* stream);
+
+/* Host-only: 1 when tia_linear_fp8_rows takes (and the graph routes) a layer of this shape, 0 when the layer stays on the half
+ * GEMM (a size outside the kernel's), TIA_EINVAL for a non-positive size.  No device call. */
+int tia_linear_fp8_serves(int64_t rows, int64_t n, int64_t k);
+
+/* The quantising producers: the arithmetic of tia_layernorm_rows_h / tia_gelu_rows_h / tia_swiglu_rows_h up to the float32
+ * value, which is then quantised per row by the recipe above instead of being rounded to half -- no extra pass over the
+ * activations.  d_q [rows, c | hidden] codes, d_scale [rows] float32.  c, hidden % 16 == 0 and <= 8192 (else TIA_ESIZE).
+ * tia_swiglu_rows_q8 reads d_x [rows, 2 hidden], the first half the gate; a zero gate and value (a pad lane) gives code 0. */
+int tia_layernorm_rows_q8(const void* d_x, int64_t row_stride, const float* d_gamma, const float* d_beta, float eps, void* d_q,
+                          float* d_scale, int64_t rows, int64_t c, int32_t dtype, void* stream);
+int tia_gelu_rows_q8(const void* d_x, void* d_q, float* d_scale, int64_t rows, int64_t hidden, int32_t dtype, void* stream);
+int tia_swiglu_rows_q8(const void* d_x, void* d_q, float* d_scale, int64_t rows, int64_t hidden, int32_t dtype, void* stream);
 
 /* =======================================================================================
  * All borders of binary planes: cv2.findContours(layer, RETR_TREE, CHAIN_APPROX_NONE | _SIMPLE)

@@ -163,6 +163,12 @@ _SIGNATURES = {
     "tia_vit_cls_mean_pool_h": ([_P, _P, _P, C.c_float, _P, _I64, _I64, _I64, _I64, _I32, _P], C.c_int),
     "tia_vit_patchify_norm_u8_h": ([_P, _P, _P, _I64, _I64, _I64, _I64, _I64, _I32, _P], C.c_int),
     "tia_linear_softmax_rows_f32": ([_P, _I64, _P, _P, _P, _I64, _I64, _I64, _P], C.c_int),
+    "tia_linear_fp8_rows": ([_P, _P, _P, _P, _P, _P, _P, _I64, _I64, _I64, _I32, _P], C.c_int),
+    "tia_linear_fp8_pack_weights": ([_P, _I64, _I64, _P, _P, _P], C.c_int),
+    "tia_linear_fp8_serves": ([_I64, _I64, _I64], C.c_int),
+    "tia_layernorm_rows_q8": ([_P, _I64, _P, _P, C.c_float, _P, _P, _I64, _I64, _I32, _P], C.c_int),
+    "tia_gelu_rows_q8": ([_P, _P, _P, _I64, _I64, _I32, _P], C.c_int),
+    "tia_swiglu_rows_q8": ([_P, _P, _P, _I64, _I64, _I32, _P], C.c_int),
     "tia_bias_act_nhwc": ([_P, _P, _P, _I64, _I64, _I32, _I32, _P], C.c_int),
     "tia_bias_relu_maxpool_nhwc": ([_P, _P, _I64, _I64, _I64, _I64, _I32, _P, _P], C.c_int),
     "tia_hover_instance_stats": ([_P, _P, _I64, _I64, _I64, _I32, _I32, _P, _P, _P], C.c_int),

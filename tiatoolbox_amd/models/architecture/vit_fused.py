@@ -40,11 +40,19 @@ Classifiers (``vanilla.TimmModel``) add the two ends: ``forward_uint8(x_u8_nhwc,
 table, bit for bit ``forward`` of the hook's batched form -- and :class:`FusedViTClassifier` puts ``tia_linear_softmax_rows_f32`` (the
 Linear and the softmax, float32 throughout) on the graph's float32 features.
 
+``prepare(torch.bfloat16, linear_dtype="float8_e4m3")`` (the engines' ``compute_dtype="float8_e4m3"``) puts steps 2, 6 and 8 -- ``qkv``,
+``fc1``, ``fc2``: 11/12 of a block's linear flops -- on the FP8 GEMM ``tia_linear_fp8_rows`` (row x column scaled OCP e4m3fn on the K = 128
+matrix instruction) and steps 1, 5 and 7 on their quantising forms (``tia_layernorm_rows_q8``, ``tia_gelu_rows_q8`` /
+``tia_swiglu_rows_q8``: codes and one scale per token from the float32 value, no extra pass).  The carrier stays bfloat16; attention,
+``proj``, the patch embedding and the ends of the graph are unchanged.  :func:`quantize_rows_e4m3` states the recipe; DESIGN 4.34.
+
 There is no float32 form (no float32 attention kernel) and no library fall-back: a model the kernels do not take (``D / heads``
 other than 64 or 80, channel counts off the GEMM's multiples) raises ``UnsupportedLayerError`` from the constructor.
 """
 
 from __future__ import annotations
+
+from typing import NamedTuple
 
 import torch
 from torch import nn
@@ -350,6 +358,155 @@ def pad_swiglu(fc1_w: torch.Tensor, fc1_b: torch.Tensor, fc2_w: torch.Tensor) ->
     return fc1_w, fc1_b, torch.nn.functional.pad(fc2_w, (0, pad)).contiguous()
 
 
+FP8_LINEAR = "float8_e4m3"  # the one `linear_dtype` of `FusedViT.prepare` (and the engines' `compute_dtype` that selects it)
+E4M3_MAX = 448.0            # largest finite value of OCP e4m3fn
+
+
+class QuantRows(NamedTuple):
+    """Rows quantised by :func:`quantize_rows_e4m3`'s recipe: ``codes [..., K]`` (e4m3fn bytes as uint8) and ``scales`` (float32, one
+    per row, flat)."""
+
+    codes: torch.Tensor
+    scales: torch.Tensor
+
+
+def quantize_rows_e4m3(v: torch.Tensor) -> tuple[torch.Tensor, torch.Tensor]:
+    """The FP8 route's recipe for one row ``v[..., :]`` of float32 values, in torch operations (the statement the kernels of
+    ``vit_fp8.hip`` are tested against): ``amax = max |v|``; ``inv = 448 / amax`` and ``s = amax / 448``, one float32 division each
+    (``amax == 0``: ``inv = s = 1``); ``q = e4m3(v * inv)`` with the product in float32 and the conversion to OCP ``e4m3fn`` rounding
+    to nearest even and saturating at +-448 (torch's CPU conversion, which makes a NaN only beyond what the clamp leaves).
+    Returns ``(q [..., K] torch.float8_e4m3fn, s [...] float32)``; ``q.float() * s[..., None]`` is the dequantised row."""
+    v = v.to(torch.float32)
+    amax = v.abs().amax(dim=-1, keepdim=True)
+    top, one = torch.tensor(E4M3_MAX, dtype=torch.float32, device=v.device), torch.ones((), dtype=torch.float32, device=v.device)
+    inv = torch.where(amax > 0, top / amax, one)
+    s = torch.where(amax > 0, amax / top, one)
+    q = (v * inv).clamp(-E4M3_MAX, E4M3_MAX).to(torch.float8_e4m3fn)
+    return q, s.squeeze(-1)
+
+
+def linear_fp8_serves(cout: int, cin: int) -> bool:
+    """Whether a ``cin -> cout`` Linear goes to the FP8 GEMM (``tia_linear_fp8_serves``, answered on the host)."""
+    from tiatoolbox_amd import _lib
+
+    return _lib.load().tia_linear_fp8_serves(1, cout, cin) == 1
+
+
+def pack_linear_weights_fp8(weight: torch.Tensor) -> QuantRows:
+    """Float32 ``[cout, cin]`` -> ``tia_linear_fp8_rows``'s weight operand: codes ``[cout, cin]`` and one scale per output channel,
+    quantised on the device (``tia_linear_fp8_pack_weights``)."""
+    from tiatoolbox_amd import _lib
+
+    w = weight.detach().to(torch.float32).contiguous()
+    if not w.is_cuda or w.dim() != 2:  # noqa: PLR2004
+        msg = f"pack_linear_weights_fp8 packs CUDA weights [cout, cin]; got {tuple(w.shape)} on {w.device}."
+        raise ValueError(msg)
+    cout, cin = w.shape
+    codes = torch.empty((cout, cin), dtype=torch.uint8, device=w.device)
+    scales = torch.empty((cout,), dtype=torch.float32, device=w.device)
+    with torch.cuda.device(w.device):
+        rc = _lib.load().tia_linear_fp8_pack_weights(w.data_ptr(), cout, cin, codes.data_ptr(), scales.data_ptr(), _lib.current_stream())
+    _lib.check(rc, "tia_linear_fp8_pack_weights")
+    return QuantRows(codes, scales)
+
+
+def hip_linear_fp8_rows(a: QuantRows, w: QuantRows, bias: torch.Tensor | None, residual: torch.Tensor | None = None, *,
+                        dtype: torch.dtype) -> torch.Tensor:
+    """``half_rne(acc * sa * sw + bias (+ residual))`` of quantised tokens ``[n, S, cin]`` and weights ``[cout, cin]``:
+    ``tia_linear_fp8_rows`` -> ``[n, S, cout]`` of ``dtype``."""
+    from tiatoolbox_amd import _lib
+
+    n, s, cin = a.codes.shape
+    cout = w.codes.shape[0]
+    if not (a.codes.is_cuda and a.codes.dtype == torch.uint8 and a.codes.is_contiguous() and w.codes.dtype == torch.uint8
+            and w.codes.shape[1] == cin and a.scales.dtype == torch.float32 and a.scales.numel() == n * s and dtype in _HALF
+            and (bias is None or bias.dtype == torch.float32)):
+        msg = (f"hip_linear_fp8_rows takes uint8 CUDA codes [n, S, cin] with n * S float32 scales, weights [cout, cin] and a float32 bias; "
+               f"got {tuple(a.codes.shape)}, {a.codes.dtype} beside {tuple(w.codes.shape)}, {w.codes.dtype} for {dtype}.")
+        raise ValueError(msg)
+    if residual is not None:
+        _half_tokens("hip_linear_fp8_rows (residual)", residual, cout)
+        if residual.dtype != dtype or tuple(residual.shape[:2]) != (n, s):
+            msg = f"hip_linear_fp8_rows: residual {tuple(residual.shape)}, {residual.dtype} beside tokens {(n, s, cin)} for {dtype}."
+            raise ValueError(msg)
+    y = torch.empty((n, s, cout), dtype=dtype, device=a.codes.device)
+    with torch.cuda.device(y.device):
+        rc = _lib.load().tia_linear_fp8_rows(a.codes.data_ptr(), a.scales.data_ptr(), w.codes.data_ptr(), w.scales.data_ptr(), _ptr(bias),
+                                             _ptr(residual), y.data_ptr(), n * s, cout, cin, _DT[dtype], _lib.current_stream())
+    _lib.check(rc, "tia_linear_fp8_rows")
+    return y
+
+
+def hip_layernorm_rows_q8(x: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, *, eps: float) -> QuantRows:
+    """LayerNorm of every row of ``[n, S, D]`` tokens, quantised from its float32 values (``tia_layernorm_rows_q8``)."""
+    from tiatoolbox_amd import _lib
+
+    _half_tokens("hip_layernorm_rows_q8", x, gamma.numel())
+    if x.dim() != 3 or gamma.dtype != torch.float32 or beta.dtype != torch.float32 or beta.numel() != gamma.numel():  # noqa: PLR2004
+        msg = f"hip_layernorm_rows_q8 takes [n, S, D] tokens and a float32 affine of D values; got {tuple(x.shape)}, {tuple(gamma.shape)}."
+        raise ValueError(msg)
+    n, s, d = x.shape
+    codes = torch.empty((n, s, d), dtype=torch.uint8, device=x.device)
+    scales = torch.empty((n * s,), dtype=torch.float32, device=x.device)
+    with torch.cuda.device(x.device):
+        rc = _lib.load().tia_layernorm_rows_q8(x.data_ptr(), d, gamma.data_ptr(), beta.data_ptr(), float(eps), codes.data_ptr(),
+                                               scales.data_ptr(), n * s, d, _DT[x.dtype], _lib.current_stream())
+    _lib.check(rc, "tia_layernorm_rows_q8")
+    return QuantRows(codes, scales)
+
+
+def hip_act_rows_q8(x: torch.Tensor, *, swiglu: bool) -> QuantRows:
+    """The activation between ``fc1`` and ``fc2`` on ``[n, S, H]`` (exact GELU) or ``[n, S, 2H]`` (packed SwiGLU, the first half the
+    gate) tokens, quantised from its float32 values: ``[n, S, H]`` codes (``tia_gelu_rows_q8`` / ``tia_swiglu_rows_q8``)."""
+    from tiatoolbox_amd import _lib
+
+    _half_tokens("hip_act_rows_q8", x)
+    if x.dim() != 3 or (swiglu and x.shape[-1] % 2 != 0):  # noqa: PLR2004
+        msg = f"hip_act_rows_q8 takes [n, S, H] (GELU) or [n, S, 2H] (SwiGLU) tokens; got {tuple(x.shape)}."
+        raise ValueError(msg)
+    n, s, c = x.shape
+    hidden = c // 2 if swiglu else c
+    codes = torch.empty((n, s, hidden), dtype=torch.uint8, device=x.device)
+    scales = torch.empty((n * s,), dtype=torch.float32, device=x.device)
+    lib = _lib.load()
+    entry, what = (lib.tia_swiglu_rows_q8, "tia_swiglu_rows_q8") if swiglu else (lib.tia_gelu_rows_q8, "tia_gelu_rows_q8")
+    with torch.cuda.device(x.device):
+        rc = entry(x.data_ptr(), codes.data_ptr(), scales.data_ptr(), n * s, hidden, _DT[x.dtype], _lib.current_stream())
+    _lib.check(rc, what)
+    return QuantRows(codes, scales)
+
+
+def pad_swiglu_to(fc1_w: torch.Tensor, fc1_b: torch.Tensor, fc2_w: torch.Tensor, target: int) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """``pad_swiglu``'s zero lanes up to ``target`` columns per half (the FP8 GEMM's multiple of 128; Virchow: 3424 -> 3456), applied to
+    an ``fc1 [2H, D]`` / ``fc2 [D, H]`` pair that may already carry that function's padding: a pad lane is exact either way."""
+    half = fc2_w.shape[1]
+    pad = target - half
+    if pad <= 0:
+        return fc1_w, fc1_b, fc2_w
+    zw, zb = fc1_w.new_zeros((pad, fc1_w.shape[1])), fc1_b.new_zeros(pad)
+    fc1_w = torch.cat([fc1_w[:half], zw, fc1_w[half:], zw], dim=0).contiguous()
+    fc1_b = torch.cat([fc1_b[:half], zb, fc1_b[half:], zb]).contiguous()
+    return fc1_w, fc1_b, torch.nn.functional.pad(fc2_w, (0, pad)).contiguous()
+
+
+class _LinearFp8:
+    """One GEMM of the graph on the FP8 kernel: weights quantised per output channel in ``prepare`` from the float32 (folded, padded)
+    ones, the float32 bias throughout; called on :class:`QuantRows` from a quantising producer."""
+
+    def __init__(self, name: str, weight: torch.Tensor, bias: torch.Tensor) -> None:
+        self.name, self.weight32, self.bias32 = name, weight, bias
+        self.cout, self.cin = weight.shape
+        self.packed: QuantRows | None = None
+        self.dtype: torch.dtype | None = None
+
+    def prepare(self, dtype: torch.dtype) -> None:
+        self.packed, self.dtype = pack_linear_weights_fp8(self.weight32), dtype
+        self.weight32 = None
+
+    def __call__(self, a: QuantRows, residual: torch.Tensor | None = None) -> torch.Tensor:
+        return hip_linear_fp8_rows(a, self.packed, self.bias32, residual, dtype=self.dtype)
+
+
 class _Linear:
     """One GEMM of the graph: the float32 (LayerScale-folded) weights until ``prepare`` packs them, the float32 bias throughout.
     Plain attributes: the cast of the surrounding module does not reach them."""
@@ -425,22 +582,61 @@ class FusedViT(nn.Module):
                 "fc1": _Linear(f"blocks.{i}.mlp.fc1", fc1_w, fc1_b), "fc2": _Linear(f"blocks.{i}.mlp.fc2", fc2_w, fc2_b)})
         self._norm = (f32(vit.norm.weight), f32(vit.norm.bias))
         self.half_dtype: torch.dtype | None = None
+        self.linear_dtype: str | None = None
 
-    def prepare(self, dtype: torch.dtype) -> None:
+    def prepare(self, dtype: torch.dtype, linear_dtype: str | None = None) -> None:
         """Pack every GEMM's float32 (folded) weights for ``tia_conv2d_nhwc_h`` in ``dtype`` (rounded once, after the folding): call
         this on the device, BEFORE ``.to(dtype)``.  Biases, LayerNorm affines, the class token and the position table stay float32
-        in plain attributes that the cast does not reach."""
+        in plain attributes that the cast does not reach.
+
+        ``linear_dtype="float8_e4m3"`` (bfloat16 carrier only) puts ``attn.qkv``, ``mlp.fc1`` and ``mlp.fc2`` of every block on the
+        FP8 GEMM (``tia_linear_fp8_rows``; the numeric contract is in ``include/tiatoolbox_amd.h`` and DESIGN 4.34): their weights are
+        quantised per output channel from the same float32 weights, and the LayerNorm / activation in front of each becomes its
+        quantising form.  A layer off that kernel's shapes stays on the half kernel (one ``info`` line names them); ``attn.proj``,
+        the patch embedding, attention, the residual stream and the final norm are the half graph's, unchanged."""
         if dtype not in _HALF:
             msg = f"FusedViT runs in float16 or bfloat16 (there is no float32 attention kernel); got {dtype}."
             raise ValueError(msg)
         if self.half_dtype is not None:
             msg = "FusedViT.prepare packs once, from the float32 weights; build a new FusedViT for another dtype."
             raise ValueError(msg)
+        if linear_dtype is not None:
+            if linear_dtype != FP8_LINEAR:
+                msg = f"FusedViT.prepare: linear_dtype is None or {FP8_LINEAR!r}; got {linear_dtype!r}."
+                raise ValueError(msg)
+            if dtype != torch.bfloat16:
+                msg = f"FusedViT.prepare: linear_dtype={FP8_LINEAR!r} runs on the bfloat16 carrier only (there is no fp16 form); got {dtype}."
+                raise ValueError(msg)
+            self._route_fp8()
         self.patch.prepare(dtype)
         for layer in self.layers:
             for name in ("qkv", "proj", "fc1", "fc2"):
                 layer[name].prepare(dtype)
-        self.half_dtype = dtype
+        self.half_dtype, self.linear_dtype = dtype, linear_dtype
+
+    def _route_fp8(self) -> None:
+        """``qkv`` / ``fc1`` / ``fc2`` of every block to :class:`_LinearFp8` where ``tia_linear_fp8_serves`` takes the shape.  A packed
+        SwiGLU half off the kernel's multiple of 128 is first padded up to it with ``pad_swiglu``'s exact zero lanes (at or above
+        ``SWIGLU_PAD_FLOOR`` only, as there)."""
+        kept: list[str] = []
+        for layer in self.layers:
+            fc1, fc2 = layer["fc1"], layer["fc2"]
+            target = -(-fc2.cin // 128) * 128
+            if self.swiglu and target != fc2.cin and fc2.cin >= SWIGLU_PAD_FLOOR:
+                fc1_w, fc1_b, fc2_w = pad_swiglu_to(fc1.weight32, fc1.bias32, fc2.weight32, target)
+                layer["fc1"], layer["fc2"] = _Linear(fc1.name, fc1_w, fc1_b), _Linear(fc2.name, fc2_w, fc2.bias32)
+            for name in ("qkv", "fc1", "fc2"):
+                lin = layer[name]
+                if linear_fp8_serves(lin.cout, lin.cin):
+                    layer[name] = _LinearFp8(lin.name, lin.weight32, lin.bias32)
+                else:
+                    kept.append(f"{lin.name} ({lin.cin} -> {lin.cout})")
+        if kept:
+            import logging
+
+            logging.getLogger("tiatoolbox_amd").info(
+                "FusedViT: the FP8 GEMM takes cin %% 128 == 0 and cout %% 16 == 0; %d layer(s) stay on the half kernel: %s.", len(kept),
+                ", ".join(kept))
 
     def _pos_for(self, grid: tuple[int, int]) -> torch.Tensor:
         if grid not in self._pos_cache:
@@ -511,12 +707,19 @@ class FusedViT(nn.Module):
         else:
             x = hip_vit_assemble_tokens_h(tok, self._cls32, pos)
         s = x.shape[1]
+        def norm_for(linear: _Linear | _LinearFp8, norm: tuple[torch.Tensor, torch.Tensor]) -> torch.Tensor | QuantRows:
+            if isinstance(linear, _LinearFp8):  # the same pass over x, codes + scales out
+                return hip_layernorm_rows_q8(x, *norm, eps=LN_EPS)
+            return hip_layernorm_rows_h(x, *norm, eps=LN_EPS, rows=n * s, row_stride=d).view(n, s, d)
+
         for layer in self.layers:
-            a = hip_layernorm_rows_h(x, *layer["norm1"], eps=LN_EPS, rows=n * s, row_stride=d).view(n, s, d)
-            a = hip_mha_fwd_h(layer["qkv"](a), self.num_heads, self.scale)
+            a = hip_mha_fwd_h(layer["qkv"](norm_for(layer["qkv"], layer["norm1"])), self.num_heads, self.scale)
             x = layer["proj"](a, residual=x)
-            a = hip_layernorm_rows_h(x, *layer["norm2"], eps=LN_EPS, rows=n * s, row_stride=d).view(n, s, d)
-            a = hip_swiglu_rows_h(layer["fc1"](a)) if self.swiglu else hip_gelu_rows_h_(layer["fc1"](a))
+            a = layer["fc1"](norm_for(layer["fc1"], layer["norm2"]))
+            if isinstance(layer["fc2"], _LinearFp8):
+                a = hip_act_rows_q8(a, swiglu=self.swiglu)
+            else:
+                a = hip_swiglu_rows_h(a) if self.swiglu else hip_gelu_rows_h_(a)
             x = layer["fc2"](a, residual=x)
         if self.global_pool == "token_mean":
             return hip_vit_cls_mean_pool_h(x, *self._norm, eps=LN_EPS, skip=1 + self.reg_tokens)

@@ -30,6 +30,23 @@ logger = logging.getLogger("tiatoolbox_amd")
 _DTYPES = {"float32": torch.float32, "float16": torch.float16, "bfloat16": torch.bfloat16,
            "fp32": torch.float32, "fp16": torch.float16, "bf16": torch.bfloat16}
 
+# compute_dtype="float8_e4m3": the Vision Transformer graph on its bfloat16 carrier with the qkv / fc1 / fc2 Linear layers of every
+# block on the FP8 matrix instruction (architecture/vit_fused.py).  It is an option of the GRAPH, not a parameter dtype:
+# no tensor of the model copy is ever cast to an FP8 type.
+FP8_COMPUTE = "float8_e4m3"
+_FP8_COVERS = ("compute_dtype=\"float8_e4m3\" covers Vision Transformer models that FusedViT accepts (TimmBackbone / TimmModel: the "
+               "qkv, fc1 and fc2 Linear layers on the FP8 GEMM, everything else in bfloat16) on a CUDA device")
+
+
+def _compute_name(compute_dtype) -> str:
+    return str(compute_dtype).replace("torch.", "")
+
+
+def _carrier_dtype(compute_dtype) -> torch.dtype:
+    """The dtype of the activations (and of the cast model copy) for a ``compute_dtype``: bfloat16 under ``"float8_e4m3"``."""
+    name = _compute_name(compute_dtype)
+    return torch.bfloat16 if name == FP8_COMPUTE else _DTYPES[name]
+
 
 def _clear_last_hip_error() -> int:
     """Read-and-clear the HIP runtime's sticky last-error through the product library itself (``tia_clear_last_error``):
@@ -434,9 +451,18 @@ class EngineABC:
             raise ValueError(msg)
         if algo == "auto":  # the modules know two forms; "auto" = Winograd wherever a layer qualifies (their own shape checks)
             algo = "winograd"
+        fp8 = _compute_name(self.compute_dtype) == FP8_COMPUTE
+        if fp8:  # never another precision in its place: everything the option does not cover is refused, here and below
+            from tiatoolbox_amd.models.architecture.vit import VisionTransformer as _ViT
+
+            if torch.device(self.device).type != "cuda" or not isinstance(getattr(self.model, "feat_extract", None), _ViT):
+                self.compute_dtype = "float32"  # (run kwargs persist as attributes: do not leave the rejected value behind)
+                msg = f"{_FP8_COVERS}; got {type(self.model).__name__} on {self.device}."
+                raise ValueError(msg)
+            dtype = torch.bfloat16
         if dtype == torch.float32 and torch.device(self.device).type != "cuda":
             return self.model
-        key = (dtype, str(self.device), id(self.model), self.fold_batchnorm, _weights_version(self.model), algo)
+        key = (dtype, str(self.device), id(self.model), self.fold_batchnorm, _weights_version(self.model), algo, fp8)
         if self._fast_key != key:
             import copy
 
@@ -464,6 +490,10 @@ class EngineABC:
                         else:
                             m.feat_extract = FusedViT(m.feat_extract)
                     except UnsupportedLayerError as exc:  # (the constructor's own refusal; any other error is a bug and propagates)
+                        if fp8:
+                            self.compute_dtype = "float32"
+                            msg = f"{_FP8_COVERS}; {type(self.model).__name__}: {exc}"
+                            raise ValueError(msg) from exc
                         logger.warning("%s: %s  Running the torch module in %s instead: its matrix products are library (hipBLASLt / "
                                        "rocBLAS) GEMMs.", type(self.model).__name__, exc, dtype)
                 elif on_gpu:
@@ -531,7 +561,10 @@ class EngineABC:
                         mod.set_conv_algo(algo)  # run kwarg `conv_algo="winograd"`: opt-in float32 Winograd for the 3x3 / stride-1 layers
                         mod.prepare(dtype)
                     elif type(mod).__name__ in ("FusedUNet", "FusedPlainUNet", "FusedHoVerNet", "FusedViT") and dtype != torch.float32:
-                        mod.prepare(dtype)  # half weights from the float32 BN-folded ones; float32 biases / BN affines kept aside
+                        if fp8 and type(mod).__name__ == "FusedViT":
+                            mod.prepare(dtype, linear_dtype=FP8_COMPUTE)  # qkv / fc1 / fc2 quantised per output channel as well
+                        else:
+                            mod.prepare(dtype)  # half weights from the float32 BN-folded ones; float32 biases / BN affines kept aside
             m = m.to(dtype=dtype) if dtype != torch.float32 else m
             if on_gpu:
                 m = m.to(memory_format=torch.channels_last)
@@ -737,7 +770,7 @@ class EngineABC:
     def infer_patches(self, dataloader: PatchDataset, *, return_coordinates: bool = False) -> dict:
         """Forward every patch; results stay on the device until the end (ref. :505-588)."""
         n = len(dataloader)
-        dtype = _DTYPES[str(self.compute_dtype).replace("torch.", "")]
+        dtype = _carrier_dtype(self.compute_dtype)
         model = self._inference_model(dtype)
         infer_batch = self._get_model_attr("infer_batch")
         rank, world_size = tdist.world() if self.distributed else (0, 1)
@@ -884,7 +917,7 @@ class EngineABC:
             from tiatoolbox_amd import _lib
 
             raise _lib.HipLibraryError(msg)
-        dtype = _DTYPES[str(self.compute_dtype).replace("torch.", "")]
+        dtype = _carrier_dtype(self.compute_dtype)
         model = self._inference_model(dtype)
         infer_batch = self._get_model_attr("infer_batch")
         hook = self._get_model_attr("preproc_func")

@@ -308,7 +308,7 @@ class MultiTaskSegmentor(EngineABC):
         """Patch inference over the tissue region of one slide, every head stitched into one device map
         (ref. :477-731).  Sets ``mask_bounds`` / ``mask_padding`` like the reference."""
         from tiatoolbox_amd import _lib
-        from tiatoolbox_amd.models.engine.engine_abc import _DTYPES
+        from tiatoolbox_amd.models.engine.engine_abc import _carrier_dtype
         from tiatoolbox_amd.models.engine.semantic_segmentor import _finalize, _row_merge
 
         dev = torch.device(self.device)
@@ -330,7 +330,7 @@ class MultiTaskSegmentor(EngineABC):
         self.mask_bounds = (kept[:, 0].min(), kept[:, 1].min(), kept[:, 2].max(), kept[:, 3].max())
         inside, self.mask_padding, (rh, rw) = get_full_output_locs_inside_mask(out_b, self.mask_bounds, (h, w))
         min_x, min_y = self.mask_padding[:2]
-        dtype = _DTYPES[str(self.compute_dtype).replace("torch.", "")]
+        dtype = _carrier_dtype(self.compute_dtype)
         model = self._inference_model(dtype)
         infer_batch = self._get_model_attr("infer_batch")
         oh = int(cfg.patch_output_shape[0])

@@ -15,7 +15,8 @@ from tiatoolbox_amd.utils.misc import cast_to_min_dtype
 class PatchPredictor(EngineABC):
     """Patch-level prediction: ``probabilities`` (optional) + ``predictions`` (ref. :88-679).
 
-    Extra run-time kwargs on MI355X: ``compute_dtype`` ("float32" | "float16" | "bfloat16") and
+    Extra run-time kwargs on MI355X: ``compute_dtype`` ("float32" | "float16" | "bfloat16"; for Vision Transformer models on a CUDA
+    device also "float8_e4m3": the bfloat16 graph with the qkv / fc1 / fc2 Linear layers on the FP8 GEMM, a ``ValueError`` elsewhere) and
     ``stain_normalizer`` (a fitted :class:`~tiatoolbox_amd.tools.stainnorm.StainNormalizer`; shorthand
     for ``model.preproc_func = StainNormPreproc(normalizer, default_preproc)``).
 

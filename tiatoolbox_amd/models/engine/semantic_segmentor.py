@@ -283,9 +283,9 @@ class SemanticSegmentor(PatchPredictor):
         if dev.type != "cuda":
             msg = "WSI-mode stitching runs on the GPU (device='cuda'); there is no CPU fallback."
             raise _lib.HipLibraryError(msg)
-        from tiatoolbox_amd.models.engine.engine_abc import _DTYPES
+        from tiatoolbox_amd.models.engine.engine_abc import _carrier_dtype
 
-        dtype = _DTYPES[str(self.compute_dtype).replace("torch.", "")]
+        dtype = _carrier_dtype(self.compute_dtype)
         model = self._inference_model(dtype)
         infer_batch = self._get_model_attr("infer_batch")
         w, h = reader.slide_dimensions

@@ -27,6 +27,22 @@ def encode_exact(values: torch.Tensor) -> torch.Tensor:
     return codes
 
 
+def e4m3_tie_rows(rows: int = 16) -> torch.Tensor:
+    """Float32 ``[rows, 768]`` whose maximum is exactly 448 in every row (the recipe's ``inv = s = 1``: the codes are the conversion of
+    the values themselves) and whose other entries are EVERY midpoint between adjacent finite e4m3 magnitudes -- the 7 subnormal
+    steps from 0 on, the step across 2^-6, up to the one between 416 and 448 -- each with its two float32 neighbours, in both signs:
+    126 x 3 x 2 = 756 values, the 448 in front, zeros up to K = 6 x 128.  Row ``r`` is row 0 rotated by ``37 r`` places (behind the
+    448), so that every tie meets many lanes of a packing kernel."""
+    mags = decode(FINITE_CODES[:127]).to(torch.float32)  # 0, 2^-9, ..., 448 in rising order
+    assert float(mags[0]) == 0.0 and float(mags[-1]) == E4M3_MAX and bool((mags[1:] > mags[:-1]).all())
+    mid = (mags[:-1] + mags[1:]) / 2  # exact in float32: one more significant bit
+    assert torch.equal(mid.double(), (mags[:-1].double() + mags[1:].double()) / 2)
+    inf = torch.full_like(mid, float("inf"))
+    body = torch.stack([torch.nextafter(mid, -inf), mid, torch.nextafter(mid, inf)], dim=1).reshape(-1)
+    body = torch.cat([body, -body, torch.zeros(767 - 2 * body.numel())])
+    return torch.stack([torch.cat([torch.tensor([E4M3_MAX]), torch.roll(body, 37 * r)]) for r in range(rows)])
+
+
 def gemm_ref64(a: torch.Tensor, sa: torch.Tensor, w: torch.Tensor, sw: torch.Tensor, bias: torch.Tensor | None,
                residual: torch.Tensor | None) -> torch.Tensor:
     """``(sum_k qa qw) sa sw + bias (+ residual)`` in float64 from codes ``a [rows, K]`` / ``w [N, K]`` and float32 scales."""
@@ -45,21 +61,31 @@ def ulp_e4m3(mag: torch.Tensor) -> torch.Tensor:
     return torch.where(mag < 2.0 ** -6, torch.full_like(mag, 2.0 ** -9), torch.exp2(e - 3.0))
 
 
-def check_quantised_rows(y64: torch.Tensor, codes: torch.Tensor, scales: torch.Tensor, what: str) -> None:
-    """The producers' pass condition for rows whose float64 values are ``y64 [rows, K]``: the scale within 4 float32 ulp of
-    ``amax64 / 448`` (1 for an all-zero row), and EVERY element ``|s q - y64| <= (ulp_e4m3(|y64| / s) / 2 * s) (1 + 2^-10) + 2^-10 s`` --
-    half a code step (half the subnormal step at the bottom) plus room for the float32 evaluation of ``y``."""
+SCALE_ULPS = 4.0  # how many float32 ulp a producer's scale may be off ``amax64 / 448``
+
+
+def quantised_rows_ratios(y64: torch.Tensor, codes: torch.Tensor, scales: torch.Tensor) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """The figures of :func:`check_quantised_rows` for rows whose float64 values are ``y64 [rows, K]``: per row, how many float32 ulp
+    the scale is off ``amax64 / 448`` (1 for an all-zero row); the dequantised values ``s q`` (a NaN code stays a NaN); and per
+    element ``|s q - y64|`` over its bound ``(ulp_e4m3(|y64| / s) / 2 * s) (1 + 2^-10) + 2^-10 s``."""
     s = scales.cpu().double().reshape(-1)
     amax = y64.abs().amax(dim=1)
     want = torch.where(amax > 0, amax / E4M3_MAX, torch.ones_like(amax))
     ulp32 = torch.exp2(torch.floor(torch.log2(want)) - 23.0)
-    ds = ((s - want).abs() / ulp32).max()
     deq = decode(codes).reshape(y64.shape) * s[:, None]
-    assert bool(torch.isfinite(deq).all()), f"{what}: a NaN code"
     bound = (0.5 * ulp_e4m3(y64.abs() / s[:, None]) * s[:, None]) * (1.0 + 2.0 ** -10) + 2.0 ** -10 * s[:, None]
-    worst = ((deq - y64).abs() / bound).max()
+    return (s - want).abs() / ulp32, deq, (deq - y64).abs() / bound
+
+
+def check_quantised_rows(y64: torch.Tensor, codes: torch.Tensor, scales: torch.Tensor, what: str) -> None:
+    """The producers' pass condition for rows whose float64 values are ``y64 [rows, K]``: the scale within 4 float32 ulp of
+    ``amax64 / 448`` (1 for an all-zero row), and EVERY element ``|s q - y64| <= (ulp_e4m3(|y64| / s) / 2 * s) (1 + 2^-10) + 2^-10 s`` --
+    half a code step (half the subnormal step at the bottom) plus room for the float32 evaluation of ``y``."""
+    ds, deq, ratio = quantised_rows_ratios(y64, codes, scales)
+    ds, worst = ds.max(), ratio.max()
+    assert bool(torch.isfinite(deq).all()), f"{what}: a NaN code"
     print(f"{what}: scale off by {float(ds):.2f} float32 ulp, worst element {float(worst):.3f} of its bound")
-    assert float(ds) <= 4.0, (what, float(ds))  # noqa: PLR2004
+    assert float(ds) <= SCALE_ULPS, (what, float(ds))
     assert float(worst) <= 1.0, (what, float(worst))
 
 

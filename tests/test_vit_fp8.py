@@ -70,6 +70,27 @@ def test_recipe_matches_the_value_table_of_the_helper():
     assert torch.equal(ulp_e4m3(pos[:-1]), pos[1:] - pos[:-1])  # the spacing above every positive code
 
 
+def test_tie_rows_hold_every_midpoint_and_the_recipe_rounds_them_to_even():
+    """The rows the device's packing kernel is held to (``test_pack_weights_rounds_every_tie_as_the_recipe``): every row's scale is 1,
+    every midpoint of two adjacent magnitudes goes to the one with the even code, its neighbours to the nearer magnitude, in both
+    signs -- worked out here from the code table, not from the conversion."""
+    from _vit_fp8_ref import FINITE_CODES, decode, e4m3_tie_rows
+
+    from tiatoolbox_amd.models.architecture.vit_fused import quantize_rows_e4m3
+
+    rows = e4m3_tie_rows(16)
+    q, s = quantize_rows_e4m3(rows)
+    assert rows.shape == (16, 768) and bool((s == 1.0).all()) and bool((rows[:, 0] == 448.0).all())  # noqa: PLR2004
+    assert all(torch.equal(rows[r, 1:].sort().values, rows[0, 1:].sort().values) for r in range(16))  # rotations of one another
+    mags = decode(FINITE_CODES[:127])
+    lo, hi = torch.arange(126), torch.arange(1, 127)
+    even = torch.where(lo % 2 == 0, lo, hi)
+    want = torch.stack([lo, even, hi], dim=1).reshape(-1).to(torch.uint8)  # below the midpoint, on it, above it
+    codes = q.view(torch.uint8)[0]
+    assert int(codes[0]) == 0x7E and torch.equal(codes[1:379], want) and torch.equal(codes[379:757], want | 0x80)  # noqa: PLR2004
+    assert torch.equal(rows[0, 2:379:3].double(), (mags[:-1] + mags[1:]) / 2) and bool((codes[757:] == 0).all())
+
+
 def _patches(n: int = 2) -> np.ndarray:
     return np.random.default_rng(0).integers(0, 256, (n, 224, 224, 3), dtype=np.uint8)
 

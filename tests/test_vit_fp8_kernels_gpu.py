@@ -9,8 +9,8 @@ import functools
 import pytest
 import torch
 
-from _vit_fp8_ref import (FINITE_CODES, HALF_EPS, check_quantised_rows, decode, encode_exact, gelu64, gemm_ref64, layernorm64,
-                          swiglu64)
+from _vit_fp8_ref import (FINITE_CODES, HALF_EPS, check_quantised_rows, decode, e4m3_tie_rows, encode_exact, gelu64, gemm_ref64,
+                          layernorm64, swiglu64)
 
 pytestmark = pytest.mark.gpu
 
@@ -140,6 +140,23 @@ def test_pack_weights_is_the_recipe(n, k):
     q, s = quantize_rows_e4m3(w)
     assert torch.equal(packed.scales.cpu(), s)
     assert torch.equal(packed.codes.cpu(), q.view(torch.uint8))
+
+
+def test_pack_weights_rounds_every_tie_as_the_recipe():
+    """Normal draws never land on a rounding tie.  ``e4m3_tie_rows``: the row maximum is exactly 448 (``inv = s = 1``), the other entries
+    every midpoint between adjacent finite e4m3 magnitudes (the subnormal steps and the 2^-6 boundary included) with its two float32
+    neighbours, in both signs -- the device's conversion must give the recipe's codes (ties to even) bit for bit."""
+    from tiatoolbox_amd.models.architecture.vit_fused import pack_linear_weights_fp8, quantize_rows_e4m3
+
+    w = e4m3_tie_rows(16)
+    assert w.shape == (16, 768)
+    packed = pack_linear_weights_fp8(w.cuda())
+    q, s = quantize_rows_e4m3(w)
+    assert bool((s == 1.0).all()) and torch.equal(packed.scales.cpu(), s)
+    got, want = packed.codes.cpu(), q.view(torch.uint8)
+    wrong = torch.nonzero(got != want)
+    assert wrong.numel() == 0, (f"{wrong.shape[0]} codes differ from the recipe's; first (row, column) {wrong[0].tolist()}: value "
+                                f"{float(w[tuple(wrong[0])])!r} -> code {int(got[tuple(wrong[0])]):#04x}, the recipe's {int(want[tuple(wrong[0])]):#04x}")
 
 
 def _special_rows(x: torch.Tensor, g: torch.Generator) -> torch.Tensor:

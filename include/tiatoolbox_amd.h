@@ -47,7 +47,8 @@ extern "C" {
  * tia_vit_patchify_pad_h, tia_vit_assemble_prefix_h (UNI2, H-optimus and prov-gigapath on the same graph); tia_vit_cls_mean_pool_h
  * and head_dim 80 in tia_mha_fwd_h (Virchow, Virchow2); tia_vit_patchify_norm_u8_h, tia_linear_softmax_rows_f32 (Vision Transformer
  * classifiers from uint8 patches to probabilities); tia_linear_fp8_rows, tia_linear_fp8_pack_weights, tia_linear_fp8_serves,
- * tia_layernorm_rows_q8, tia_gelu_rows_q8, tia_swiglu_rows_q8 (the Vision Transformer linear layers on the FP8 matrix instruction). */
+ * tia_layernorm_rows_q8, tia_gelu_rows_q8, tia_swiglu_rows_q8 (the Vision Transformer linear layers on the FP8 matrix instruction); tia_add_layernorm_rows_f32,
+ * tia_vit_assemble_rows_f32, tia_vit_cls_mean_pool_f32 (the same graph with a float32 residual stream). */
 #define TIA_ABI_VERSION 6
 int tia_abi_version(void);
 
@@ -974,6 +975,39 @@ int tia_vit_assemble_prefix_h(const void* d_tokens, const float* d_cls, const fl
  * skip < 1 or skip >= s is TIA_EINVAL; d % 8 == 0 and d <= 8192 (else TIA_ESIZE). */
 int tia_vit_cls_mean_pool_h(const void* d_x, const float* d_gamma, const float* d_beta, float eps, float* d_out, int64_t n, int64_t s,
                             int64_t skip, int64_t d, int32_t dtype, void* stream);
+
+/* residual_dtype="float32" (FusedViT with autocast's residual stream): x is a float32 [n,S,D] tensor from token assembly to the final
+ * norm, the proj / fc2 GEMMs write half BRANCHES without a residual, and the three entry points below are the float32-stream forms of
+ * tia_layernorm_rows_h, tia_vit_assemble_prefix_h and tia_vit_cls_mean_pool_h.  Additive, same version (6); the contract of the
+ * family above: 16-byte accesses, 64-bit offsets, float32 arithmetic, no atomics; the entry launches and neither allocates nor syncs.
+ * `dtype` is the half type of the branch / tokens (TIA_DT_F16 | TIA_DT_BF16, else TIA_EINVAL). */
+
+/* x[r,:] += float(branch[r,:]) in place, then y[r,:] = LN(x[r,:]) * gamma + beta -- either part optional, one pass over x.
+ *   d_x float32, row r at element r * x_row_stride (>= c, % 4 == 0)
+ *   d_branch of `dtype`, row r at element r * branch_row_stride (>= c, % 8 == 0), or NULL: x is only read and stays bit-identical
+ *   d_y [rows,c] dense, of y_dtype (`dtype` itself: ONE rounding; or TIA_DT_F32), or NULL: the add alone (gamma, beta, eps, y_dtype
+ *     are not looked at)
+ * The add is ONE IEEE float32 add per element, written back by the lane that read it; the LayerNorm is tia_layernorm_rows_h's,
+ * operation for operation, on the float32 sum (mean first, then the variance of the centred values, folded by lane exchanges).
+ * TIA_EINVAL: d_branch and d_y both NULL, a null d_x (or affine beside a d_y), a misaligned pointer, a bad stride or dtype, eps < 0.
+ * c % 8 == 0 and c <= 8192 (else TIA_ESIZE). */
+int tia_add_layernorm_rows_f32(float* d_x, int64_t x_row_stride, const void* d_branch, int64_t branch_row_stride, const float* d_gamma,
+                               const float* d_beta, float eps, void* d_y, int32_t y_dtype, int64_t rows, int64_t c, int32_t dtype,
+                               void* stream);
+
+/* tia_vit_assemble_prefix_h with a float32 result: d_out [n, 1+R+g, d] float32 with out[b,0] = cls (+ pos[0] if pos_has_cls),
+ * out[b,1+r] = reg[r], out[b,1+R+i] = float(tokens[b,i]) + pos[i + pos_has_cls] -- the same single float32 add, NOT rounded.
+ * Arguments and refusals as there (R = 0 with pos_has_cls = 1 is the plain form); d % 8 == 0 and d <= 8192 (else TIA_ESIZE). */
+int tia_vit_assemble_rows_f32(const void* d_tokens, const float* d_cls, const float* d_reg, const float* d_pos, int32_t pos_has_cls,
+                              float* d_out, int64_t n, int64_t g, int64_t reg_tokens, int64_t d, int32_t dtype, void* stream);
+
+/* tia_vit_cls_mean_pool_h of the float32 stream: out[b, :d] = LN(x'[b,0]), out[b, d:] = mean_{i = skip .. s-1} LN(x'[b,i]) with
+ * x' = x + float(branch) (one float32 add on load, nothing written back) or x' = x when d_branch is NULL.
+ *   d_x [n,s,d] float32   d_branch [n,s,d] of `dtype` or NULL   d_gamma, d_beta [d] float32   d_out [n, 2d] float32
+ * The same wave-to-row assignment, fixed summation order and single affine as the half form: an image's result is bit-identical
+ * whatever n is.  skip < 1 or skip >= s is TIA_EINVAL; d % 8 == 0 and d <= 8192 (else TIA_ESIZE). */
+int tia_vit_cls_mean_pool_f32(const float* d_x, const void* d_branch, const float* d_gamma, const float* d_beta, float eps, float* d_out,
+                              int64_t n, int64_t s, int64_t skip, int64_t d, int32_t dtype, void* stream);
 
 /* Vision Transformer classifiers (the reference's TimmModel: backbone -> Linear -> softmax) from uint8 patches to probabilities:
  * the input normalisation inside the im2col, and the head on the graph's float32 features.  Additive, same version (6). */

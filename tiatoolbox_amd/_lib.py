@@ -161,6 +161,9 @@ _SIGNATURES = {
     "tia_vit_patchify_pad_h": ([_P, _I32, _P, _I64, _I64, _I64, _I64, _I64, _I32, _P], C.c_int),
     "tia_vit_assemble_prefix_h": ([_P, _P, _P, _P, _I32, _P, _I64, _I64, _I64, _I64, _I32, _P], C.c_int),
     "tia_vit_cls_mean_pool_h": ([_P, _P, _P, C.c_float, _P, _I64, _I64, _I64, _I64, _I32, _P], C.c_int),
+    "tia_add_layernorm_rows_f32": ([_P, _I64, _P, _I64, _P, _P, C.c_float, _P, _I32, _I64, _I64, _I32, _P], C.c_int),
+    "tia_vit_assemble_rows_f32": ([_P, _P, _P, _P, _I32, _P, _I64, _I64, _I64, _I64, _I32, _P], C.c_int),
+    "tia_vit_cls_mean_pool_f32": ([_P, _P, _P, _P, C.c_float, _P, _I64, _I64, _I64, _I64, _I32, _P], C.c_int),
     "tia_vit_patchify_norm_u8_h": ([_P, _P, _P, _I64, _I64, _I64, _I64, _I64, _I32, _P], C.c_int),
     "tia_linear_softmax_rows_f32": ([_P, _I64, _P, _P, _P, _I64, _I64, _I64, _P], C.c_int),
     "tia_linear_fp8_rows": ([_P, _P, _P, _P, _P, _P, _P, _I64, _I64, _I64, _I32, _P], C.c_int),

@@ -547,3 +547,324 @@ extern "C" int tia_vit_assemble_prefix_h(const void* d_tokens, const float* d_cl
                        (int)pos_has_cls, vectors, (int)g, (int)reg_tokens, (int)(d / 8), (v4u*)d_out);
     return hipGetLastError() == hipSuccess ? TIA_OK : TIA_ELAUNCH;
 }
+
+// ------------------------------------------------------------------------------------------------------------------------------------
+// residual_dtype="float32": the residual stream x is a float32 [n, S, D] tensor and the GEMMs write half BRANCHES (no residual in
+// their epilogues).  Three kernels, each the float32-stream form of one above; the kernels above are untouched.
+//   add_layernorm_rows_f32 : x += float(branch) in place (one float32 add, never rounded), y = LN(x)     either part optional
+//   vit_assemble_rows_f32  : assemble_prefix with a float32 result: float(tok) + pos, not rounded
+//   cls_mean_pool_f32      : cls_mean_pool of x (+ float(branch) on load, not written back)
+// ------------------------------------------------------------------------------------------------------------------------------------
+namespace {
+
+__device__ __forceinline__ void store8_f32(float* p, const float (&r)[8]) {
+    *reinterpret_cast<float4*>(p) = make_float4(r[0], r[1], r[2], r[3]);
+    *reinterpret_cast<float4*>(p + 4) = make_float4(r[4], r[5], r[6], r[7]);
+}
+
+// layernorm_rows_h_kernel on a float32 row (two 16-byte loads per vector of 8), with the branch added first: the lane that reads
+// x[8 v .. 8 v + 8) adds the branch's 8 halves and writes the same 8 floats back, so the update is in place without any exchange.
+// YMODE 0: no LayerNorm (the add alone), 1: y in the half type BF (one rounding), 2: y in float32.  `branch` may be null (LayerNorm
+// alone: x is only read).  The mean, the centred variance and the affine are that kernel's, operation for operation.
+template <bool BF, int YMODE, int VPL>
+__global__ __launch_bounds__(ET) void add_layernorm_rows_f32_kernel(float* __restrict__ x, long xstride, const unsigned short* __restrict__ branch,
+                                                                     long bstride, const float* __restrict__ gamma,
+                                                                     const float* __restrict__ beta, float eps, long rows, int c,
+                                                                     void* __restrict__ y) {
+    const int lane = threadIdx.x & 63;
+    const long row = (long)blockIdx.x * (ET / 64) + (threadIdx.x >> 6);
+    if (row >= rows) return;  // whole waves leave: the exchanges below stay inside a wave
+    const int cv = c >> 3;
+    float* xr = x + row * xstride;
+    const unsigned short* br = branch ? branch + row * bstride : nullptr;
+    float f[VPL][8];
+    float sum = 0.0f;
+#pragma unroll
+    for (int i = 0; i < VPL; ++i) {
+        const int v = lane + 64 * i;
+        if (v < cv) {
+            load8_f32(xr + 8 * v, f[i]);
+            if (br) {
+                float b[8];
+                unpack8<BF>(*reinterpret_cast<const v4u*>(br + 8 * v), b);
+#pragma unroll
+                for (int k = 0; k < 8; ++k) f[i][k] += b[k];
+                store8_f32(xr + 8 * v, f[i]);
+            }
+#pragma unroll
+            for (int k = 0; k < 8; ++k) sum += f[i][k];
+        }
+    }
+    if constexpr (YMODE != 0) {
+        const float mean = wave_sum(sum) / (float)c;
+        float sq = 0.0f;
+#pragma unroll
+        for (int i = 0; i < VPL; ++i)
+            if (lane + 64 * i < cv) {
+#pragma unroll
+                for (int k = 0; k < 8; ++k) {
+                    f[i][k] -= mean;
+                    sq = fmaf(f[i][k], f[i][k], sq);
+                }
+            }
+        const float rstd = 1.0f / sqrtf(wave_sum(sq) / (float)c + eps);
+#pragma unroll
+        for (int i = 0; i < VPL; ++i) {
+            const int v = lane + 64 * i;
+            if (v < cv) {
+                float g[8], bt[8], r[8];
+                load8_f32(gamma + 8 * v, g);
+                load8_f32(beta + 8 * v, bt);
+#pragma unroll
+                for (int k = 0; k < 8; ++k) r[k] = fmaf(f[i][k] * rstd, g[k], bt[k]);
+                if constexpr (YMODE == 2) store8_f32(static_cast<float*>(y) + row * (long)c + 8 * v, r);
+                else *reinterpret_cast<v4u*>(static_cast<unsigned short*>(y) + row * (long)c + 8 * v) = pack8<BF>(r);
+            }
+        }
+    }
+}
+
+// vit_assemble_prefix_h_kernel with a float32 result: the same rows, the same single float32 add, no rounding after it.
+template <bool BF>
+__global__ __launch_bounds__(ET) void vit_assemble_rows_f32_kernel(const v4u* __restrict__ tok, const float* __restrict__ cls,
+                                                                    const float* __restrict__ reg, const float* __restrict__ pos,
+                                                                    int has_cls, long vectors, int g, int nreg, int dv,
+                                                                    float* __restrict__ out) {
+    const int s = 1 + nreg + g;
+    for (long i = (long)blockIdx.x * ET + threadIdx.x; i < vectors; i += (long)gridDim.x * ET) {
+        const int v = (int)(i % dv);
+        const long t = i / dv;
+        const int tk = (int)(t % s);
+        const long b = t / s;
+        float a[8];
+        long prow = -1;  // the row of `pos` to add, if any
+        if (tk == 0) {
+            load8_f32(cls + 8 * v, a);
+            if (has_cls) prow = 0;
+        } else if (tk <= nreg) {
+            load8_f32(reg + ((long)(tk - 1) * dv + v) * 8, a);
+        } else {
+            const int pi = tk - 1 - nreg;
+            unpack8<BF>(tok[(b * g + pi) * dv + v], a);
+            prow = pi + has_cls;
+        }
+        if (prow >= 0) {
+            float ps[8];
+            load8_f32(pos + (prow * dv + v) * 8, ps);
+#pragma unroll
+            for (int k = 0; k < 8; ++k) a[k] += ps[k];
+        }
+        store8_f32(out + i * 8, a);
+    }
+}
+
+// normalise_row on a float32 row with an optional half branch row added on load (one float32 add per element, nothing written).
+template <bool BF, int VPL>
+__device__ __forceinline__ void normalise_row_f32(const float* xr, const unsigned short* br, int lane, int cv, int c, float eps,
+                                                  float (&f)[VPL][8]) {
+    float sum = 0.0f;
+#pragma unroll
+    for (int i = 0; i < VPL; ++i) {
+        const int v = lane + 64 * i;
+        if (v < cv) {
+            load8_f32(xr + 8 * v, f[i]);
+            if (br) {
+                float b[8];
+                unpack8<BF>(*reinterpret_cast<const v4u*>(br + 8 * v), b);
+#pragma unroll
+                for (int k = 0; k < 8; ++k) f[i][k] += b[k];
+            }
+#pragma unroll
+            for (int k = 0; k < 8; ++k) sum += f[i][k];
+        }
+    }
+    const float mean = wave_sum(sum) / (float)c;
+    float sq = 0.0f;
+#pragma unroll
+    for (int i = 0; i < VPL; ++i)
+        if (lane + 64 * i < cv) {
+#pragma unroll
+            for (int k = 0; k < 8; ++k) {
+                f[i][k] -= mean;
+                sq = fmaf(f[i][k], f[i][k], sq);
+            }
+        }
+    const float rstd = 1.0f / sqrtf(wave_sum(sq) / (float)c + eps);
+#pragma unroll
+    for (int i = 0; i < VPL; ++i)
+        if (lane + 64 * i < cv) {
+#pragma unroll
+            for (int k = 0; k < 8; ++k) f[i][k] *= rstd;
+        }
+}
+
+// vit_cls_mean_pool_h_kernel on the float32 stream: the same wave-to-row assignment, the same ((w0 + w1) + w2) + w3 fold through one
+// LDS row, the affine applied once to the mean.  `branch` (the last block's fc2 output, [n, s, c] halves) may be null.
+template <bool BF, int VPL>
+__global__ __launch_bounds__(ET) void vit_cls_mean_pool_f32_kernel(const float* __restrict__ x, const unsigned short* __restrict__ branch,
+                                                                    const float* __restrict__ gamma, const float* __restrict__ beta,
+                                                                    float eps, int s, int skip, int c, float* __restrict__ out) {
+    extern __shared__ __attribute__((aligned(16))) float pool_fold32[];  // [c]
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int cv = c >> 3;
+    const float* xb = x + (long)blockIdx.x * s * c;
+    const unsigned short* bb = branch ? branch + (long)blockIdx.x * s * c : nullptr;
+    float* ob = out + (long)blockIdx.x * 2 * c;
+    float f[VPL][8], acc[VPL][8];
+#pragma unroll
+    for (int i = 0; i < VPL; ++i)
+#pragma unroll
+        for (int k = 0; k < 8; ++k) acc[i][k] = 0.0f;
+
+    if (wave == 0) {  // (a whole wave: the exchanges stay inside it)
+        normalise_row_f32<BF, VPL>(xb, bb, lane, cv, c, eps, f);
+#pragma unroll
+        for (int i = 0; i < VPL; ++i) {
+            const int v = lane + 64 * i;
+            if (v < cv) {
+                float g[8], bt[8], r[8];
+                load8_f32(gamma + 8 * v, g);
+                load8_f32(beta + 8 * v, bt);
+#pragma unroll
+                for (int k = 0; k < 8; ++k) r[k] = fmaf(f[i][k], g[k], bt[k]);
+                store8_f32(ob + 8 * v, r);
+            }
+        }
+    }
+    for (int row = skip + wave; row < s; row += ET / 64) {
+        normalise_row_f32<BF, VPL>(xb + (long)row * c, bb ? bb + (long)row * c : nullptr, lane, cv, c, eps, f);
+#pragma unroll
+        for (int i = 0; i < VPL; ++i)
+            if (lane + 64 * i < cv) {
+#pragma unroll
+                for (int k = 0; k < 8; ++k) acc[i][k] += f[i][k];
+            }
+    }
+    // the fold: wave 0 lays its sums down, waves 1, 2 add theirs in turn, wave 3 adds its own and writes the mean
+    for (int w = 0; w < ET / 64; ++w) {
+        if (wave == w) {
+#pragma unroll
+            for (int i = 0; i < VPL; ++i) {
+                const int v = lane + 64 * i;
+                if (v < cv) {
+                    if (w > 0) {
+                        float p[8];
+                        load8_f32(pool_fold32 + 8 * v, p);
+#pragma unroll
+                        for (int k = 0; k < 8; ++k) acc[i][k] = p[k] + acc[i][k];
+                    }
+                    if (w < ET / 64 - 1) {
+                        store8_f32(pool_fold32 + 8 * v, acc[i]);
+                    } else {
+                        const float cnt = (float)(s - skip);
+                        float g[8], bt[8], r[8];
+                        load8_f32(gamma + 8 * v, g);
+                        load8_f32(beta + 8 * v, bt);
+#pragma unroll
+                        for (int k = 0; k < 8; ++k) r[k] = fmaf(acc[i][k] / cnt, g[k], bt[k]);
+                        store8_f32(ob + c + 8 * v, r);
+                    }
+                }
+            }
+        }
+        __syncthreads();
+    }
+}
+
+template <bool BF, int YMODE>
+void launch_add_layernorm(int vpl, dim3 grid, hipStream_t st, float* x, long xstride, const unsigned short* branch, long bstride,
+                          const float* gamma, const float* beta, float eps, long rows, int c, void* y) {
+#define TIA_ALN(V) \
+    hipLaunchKernelGGL((add_layernorm_rows_f32_kernel<BF, YMODE, V>), grid, dim3(ET), 0, st, x, xstride, branch, bstride, gamma, beta, eps, rows, c, y)
+    if (vpl <= 1) TIA_ALN(1);
+    else if (vpl <= 2) TIA_ALN(2);
+    else if (vpl <= 4) TIA_ALN(4);
+    else if (vpl <= 8) TIA_ALN(8);
+    else TIA_ALN(16);
+#undef TIA_ALN
+}
+
+}  // namespace
+
+extern "C" int tia_add_layernorm_rows_f32(float* d_x, int64_t x_row_stride, const void* d_branch, int64_t branch_row_stride,
+                                          const float* d_gamma, const float* d_beta, float eps, void* d_y, int32_t y_dtype, int64_t rows,
+                                          int64_t c, int32_t dtype, void* stream) {
+    if (!d_x || rows <= 0 || c <= 0 || (!d_branch && !d_y)) return TIA_EINVAL;
+    if (dtype != TIA_DT_F16 && dtype != TIA_DT_BF16) return TIA_EINVAL;
+    if (d_y && (!d_gamma || !d_beta || !(eps >= 0.0f) || (y_dtype != dtype && y_dtype != TIA_DT_F32))) return TIA_EINVAL;
+    if ((c & 7) != 0 || c > 8192) return TIA_ESIZE;
+    if (x_row_stride < c || (x_row_stride & 3) != 0) return TIA_EINVAL;
+    if (d_branch && (branch_row_stride < c || (branch_row_stride & 7) != 0)) return TIA_EINVAL;
+    uintptr_t bits = reinterpret_cast<uintptr_t>(d_x) | reinterpret_cast<uintptr_t>(d_branch);
+    if (d_y) bits |= reinterpret_cast<uintptr_t>(d_gamma) | reinterpret_cast<uintptr_t>(d_beta) | reinterpret_cast<uintptr_t>(d_y);
+    if (bits & 15) return TIA_EINVAL;
+    const long blocks = (rows + ET / 64 - 1) / (ET / 64);
+    if (blocks > 0x7fffffffL) return TIA_ESIZE;
+    const int vpl = (int)((c / 8 + 63) / 64);
+    const dim3 grid((unsigned)blocks);
+    hipStream_t st = (hipStream_t)stream;
+    const unsigned short* branch = static_cast<const unsigned short*>(d_branch);
+    const bool bf = dtype == TIA_DT_BF16;
+#define TIA_ALN_Y(YMODE)                                                                                                                  \
+    do {                                                                                                                                  \
+        if (bf) launch_add_layernorm<true, YMODE>(vpl, grid, st, d_x, (long)x_row_stride, branch, (long)branch_row_stride, d_gamma, d_beta, \
+                                                  eps, (long)rows, (int)c, d_y);                                                          \
+        else launch_add_layernorm<false, YMODE>(vpl, grid, st, d_x, (long)x_row_stride, branch, (long)branch_row_stride, d_gamma, d_beta,  \
+                                                eps, (long)rows, (int)c, d_y);                                                            \
+    } while (0)
+    if (!d_y) TIA_ALN_Y(0);
+    else if (y_dtype == TIA_DT_F32) TIA_ALN_Y(2);
+    else TIA_ALN_Y(1);
+#undef TIA_ALN_Y
+    return hipGetLastError() == hipSuccess ? TIA_OK : TIA_ELAUNCH;
+}
+
+extern "C" int tia_vit_assemble_rows_f32(const void* d_tokens, const float* d_cls, const float* d_reg, const float* d_pos,
+                                         int32_t pos_has_cls, float* d_out, int64_t n, int64_t g, int64_t reg_tokens, int64_t d,
+                                         int32_t dtype, void* stream) {
+    if (!d_tokens || !d_cls || !d_pos || !d_out || n <= 0 || g <= 0 || d <= 0 || reg_tokens < 0) return TIA_EINVAL;
+    if ((reg_tokens > 0) != (d_reg != nullptr) || (pos_has_cls != 0 && pos_has_cls != 1)) return TIA_EINVAL;
+    if (dtype != TIA_DT_F16 && dtype != TIA_DT_BF16) return TIA_EINVAL;
+    if ((d & 7) != 0 || d > 8192) return TIA_ESIZE;
+    if ((reinterpret_cast<uintptr_t>(d_tokens) | reinterpret_cast<uintptr_t>(d_cls) | reinterpret_cast<uintptr_t>(d_reg) |
+         reinterpret_cast<uintptr_t>(d_pos) | reinterpret_cast<uintptr_t>(d_out)) & 15)
+        return TIA_EINVAL;
+    if (g > 0x3fffffffL || reg_tokens > 0x3fffffffL || n > 0x7fffffffL) return TIA_ESIZE;
+    const long vectors = n * (1 + reg_tokens + g) * (d / 8);
+    const auto kernel = dtype == TIA_DT_BF16 ? vit_assemble_rows_f32_kernel<true> : vit_assemble_rows_f32_kernel<false>;
+    hipLaunchKernelGGL(kernel, dim3(stream_blocks(vectors)), dim3(ET), 0, (hipStream_t)stream, (const v4u*)d_tokens, d_cls, d_reg, d_pos,
+                       (int)pos_has_cls, vectors, (int)g, (int)reg_tokens, (int)(d / 8), d_out);
+    return hipGetLastError() == hipSuccess ? TIA_OK : TIA_ELAUNCH;
+}
+
+extern "C" int tia_vit_cls_mean_pool_f32(const float* d_x, const void* d_branch, const float* d_gamma, const float* d_beta, float eps,
+                                         float* d_out, int64_t n, int64_t s, int64_t skip, int64_t d, int32_t dtype, void* stream) {
+    if (!d_x || !d_gamma || !d_beta || !d_out || n <= 0 || s <= 0 || d <= 0 || !(eps >= 0.0f)) return TIA_EINVAL;
+    if (dtype != TIA_DT_F16 && dtype != TIA_DT_BF16) return TIA_EINVAL;
+    if (skip < 1 || skip >= s) return TIA_EINVAL;
+    if ((d & 7) != 0 || d > 8192) return TIA_ESIZE;
+    if ((reinterpret_cast<uintptr_t>(d_x) | reinterpret_cast<uintptr_t>(d_branch) | reinterpret_cast<uintptr_t>(d_gamma) |
+         reinterpret_cast<uintptr_t>(d_beta) | reinterpret_cast<uintptr_t>(d_out)) & 15)
+        return TIA_EINVAL;
+    if (n > 0x7fffffffL || s > 0x7fffffffL) return TIA_ESIZE;  // one grid dimension; the row index is an int
+    const int vpl = (int)((d / 8 + 63) / 64);
+    const dim3 grid((unsigned)n);
+    const size_t lds = (size_t)d * sizeof(float);
+    hipStream_t st = (hipStream_t)stream;
+    const unsigned short* branch = static_cast<const unsigned short*>(d_branch);
+#define TIA_POOL32(BF, V) \
+    hipLaunchKernelGGL((vit_cls_mean_pool_f32_kernel<BF, V>), grid, dim3(ET), lds, st, d_x, branch, d_gamma, d_beta, eps, (int)s, (int)skip, (int)d, d_out)
+#define TIA_POOL32_V(BF)                   \
+    do {                                   \
+        if (vpl <= 1) TIA_POOL32(BF, 1);       \
+        else if (vpl <= 2) TIA_POOL32(BF, 2);  \
+        else if (vpl <= 4) TIA_POOL32(BF, 4);  \
+        else if (vpl <= 8) TIA_POOL32(BF, 8);  \
+        else TIA_POOL32(BF, 16);               \
+    } while (0)
+    if (dtype == TIA_DT_BF16) TIA_POOL32_V(true);
+    else TIA_POOL32_V(false);
+#undef TIA_POOL32_V
+#undef TIA_POOL32
+    return hipGetLastError() == hipSuccess ? TIA_OK : TIA_ELAUNCH;
+}

@@ -21,8 +21,15 @@ The foundation models (``UNI2``, ``H-optimus-0`` / ``-1``, ``prov-gigapath``) ch
   ``tia_vit_assemble_tokens_h``.  The class token is still row 0, so the final norm reads the same rows.
 
 LayerScale is folded EXACTLY in float32 before the one rounding of the weights: ``x + gamma * (W a + b) = x + (gamma W) a + gamma b``, so
-the residual add is the GEMM's own ``d_residual`` and ``ls1`` / ``ls2`` cost nothing.  The residual stream stays in ``dtype`` (as in
-the cast torch module); the final norm reads the class rows only (row stride ``S * D``) and writes float32 features.
+the residual add is the GEMM's own ``d_residual`` and ``ls1`` / ``ls2`` cost nothing.  By default the residual stream stays in
+``dtype`` (as in the torch module cast to ``dtype``); the final norm reads the class rows only (row stride ``S * D``) and writes float32
+features.
+
+``prepare(dtype, residual_dtype="float32")`` (the engines' run kwarg ``residual_dtype``) keeps the stream in float32 instead, as the
+float32 module under ``torch.autocast`` does: ``tia_vit_assemble_rows_f32`` writes ``x`` unrounded, steps 4 and 8 lose their residual
+and write a half branch, and steps 1 and 5 (and the final norm) become ``tia_add_layernorm_rows_f32`` -- ``x += float(branch)`` in
+place and the LayerNorm of the sum in one pass; ``token_mean`` models end in ``tia_vit_cls_mean_pool_f32``.  A LayerScale update below
+half a unit of ``dtype`` at ``x`` is rounded away by the default graph and kept by this one.
 
 ``Virchow`` / ``Virchow2`` (ViT-H/14, 1280 / 16 = 80 per head) change four more, all on the host in float32 before the one rounding:
 
@@ -307,6 +314,100 @@ def hip_vit_patchify_norm_u8_h(x_u8_nhwc: torch.Tensor, table: torch.Tensor, pat
     return out
 
 
+RESIDUAL_F32 = "float32"  # the one `residual_dtype` of `FusedViT.prepare` (and of the engines' run kwarg)
+
+
+def _f32_stream(name: str, x: torch.Tensor) -> None:
+    if not (x.is_cuda and x.dtype == torch.float32 and x.is_contiguous()):
+        msg = f"{name} expects a contiguous float32 CUDA tensor (the residual stream); got {tuple(x.shape)}, {x.dtype} on {x.device}."
+        raise ValueError(msg)
+
+
+def hip_add_layernorm_rows_f32(x: torch.Tensor, branch: torch.Tensor | None, gamma: torch.Tensor | None, beta: torch.Tensor | None, *,
+                               eps: float, rows: int, row_stride: int, dtype: torch.dtype,
+                               out_dtype: torch.dtype | None = None) -> torch.Tensor | None:
+    """One pass over ``rows`` rows of ``c`` values that start ``row_stride`` elements apart in the float32 stream ``x`` (and in
+    ``branch``, a half tensor of ``x``'s shape, or ``None``): ``x += branch.float()`` IN PLACE (one float32 add, never rounded), then
+    the LayerNorm of the sum, ``[rows, c]`` in ``dtype`` (the graph's half type) or ``out_dtype=torch.float32``.  ``gamma=None``: the
+    add alone, returns ``None``.  ``tia_add_layernorm_rows_f32``."""
+    from tiatoolbox_amd import _lib
+
+    _f32_stream("hip_add_layernorm_rows_f32", x)
+    if dtype not in _HALF or (gamma is None) != (beta is None) or (gamma is None and branch is None):
+        msg = f"hip_add_layernorm_rows_f32 takes a half `dtype`, and a branch, a float32 affine or both; got {dtype}."
+        raise ValueError(msg)
+    if branch is not None:
+        _half_tokens("hip_add_layernorm_rows_f32 (branch)", branch)
+        if branch.dtype != dtype or branch.shape != x.shape:
+            msg = f"hip_add_layernorm_rows_f32: branch {tuple(branch.shape)}, {branch.dtype} beside a stream {tuple(x.shape)} for {dtype}."
+            raise ValueError(msg)
+    c = gamma.numel() if gamma is not None else x.shape[-1]  # (the add alone: rows of the stream's last dimension)
+    if (rows - 1) * row_stride + c > x.numel() or (gamma is not None and (gamma.dtype != torch.float32 or beta.dtype != torch.float32
+                                                                            or beta.numel() != c)):
+        msg = f"hip_add_layernorm_rows_f32: {rows} rows of {c} at stride {row_stride} beyond {x.numel()} elements, or an affine that is not float32."
+        raise ValueError(msg)
+    out_dtype = out_dtype or dtype
+    if out_dtype not in (dtype, torch.float32):
+        msg = f"hip_add_layernorm_rows_f32 writes {dtype} or float32; got out_dtype {out_dtype}."
+        raise ValueError(msg)
+    y = torch.empty((rows, c), dtype=out_dtype, device=x.device) if gamma is not None else None
+    with torch.cuda.device(x.device):
+        rc = _lib.load().tia_add_layernorm_rows_f32(x.data_ptr(), row_stride, _ptr(branch), row_stride, _ptr(gamma), _ptr(beta), float(eps),
+                                                    _ptr(y), _DT[out_dtype], rows, c, _DT[dtype], _lib.current_stream())
+    _lib.check(rc, "tia_add_layernorm_rows_f32")
+    return y
+
+
+def hip_vit_assemble_rows_f32(tokens: torch.Tensor, cls: torch.Tensor, reg: torch.Tensor | None, pos: torch.Tensor, *,
+                              pos_has_cls: bool) -> torch.Tensor:
+    """:func:`hip_vit_assemble_prefix_h` with a float32 result ``[n, 1 + R + g, D]``: ``tokens.float() + pos``, not rounded
+    (``reg=None`` with ``pos_has_cls=True`` is the plain form).  ``tia_vit_assemble_rows_f32``."""
+    from tiatoolbox_amd import _lib
+
+    _half_tokens("hip_vit_assemble_rows_f32", tokens)
+    n, g, d = tokens.shape
+    nreg = 0 if reg is None else reg.numel() // d
+    rows = g + int(pos_has_cls)
+    if cls.dtype != torch.float32 or pos.dtype != torch.float32 or cls.numel() != d or pos.numel() != rows * d or not (
+            cls.is_contiguous() and pos.is_contiguous()) or (reg is not None and (
+                reg.dtype != torch.float32 or not reg.is_contiguous() or nreg == 0 or reg.numel() != nreg * d)):
+        msg = (f"hip_vit_assemble_rows_f32 takes float32 cls [{d}], reg [R, {d}] or None and pos [{rows}, {d}]; got {tuple(cls.shape)}, "
+               f"{None if reg is None else tuple(reg.shape)}, {tuple(pos.shape)}.")
+        raise ValueError(msg)
+    out = torch.empty((n, 1 + nreg + g, d), dtype=torch.float32, device=tokens.device)
+    with torch.cuda.device(tokens.device):
+        rc = _lib.load().tia_vit_assemble_rows_f32(tokens.data_ptr(), cls.data_ptr(), _ptr(reg), pos.data_ptr(), int(pos_has_cls),
+                                                   out.data_ptr(), n, g, nreg, d, _DT[tokens.dtype], _lib.current_stream())
+    _lib.check(rc, "tia_vit_assemble_rows_f32")
+    return out
+
+
+def hip_vit_cls_mean_pool_f32(x: torch.Tensor, branch: torch.Tensor | None, gamma: torch.Tensor, beta: torch.Tensor, *, eps: float,
+                              skip: int, dtype: torch.dtype) -> torch.Tensor:
+    """:func:`hip_vit_cls_mean_pool_h` of the float32 stream ``[n, S, D]`` with the last ``branch`` (half ``dtype``, same shape, or
+    ``None``) added on load and not written back: ``tia_vit_cls_mean_pool_f32``."""
+    from tiatoolbox_amd import _lib
+
+    _f32_stream("hip_vit_cls_mean_pool_f32", x)
+    if x.dim() != 3 or dtype not in _HALF or gamma.dtype != torch.float32 or beta.dtype != torch.float32 or \
+            gamma.numel() != x.shape[-1] or beta.numel() != x.shape[-1]:  # noqa: PLR2004
+        msg = (f"hip_vit_cls_mean_pool_f32 takes a [n, S, D] stream, a half `dtype` and a float32 affine of D values; got {tuple(x.shape)}, "
+               f"{dtype}, {tuple(gamma.shape)}.")
+        raise ValueError(msg)
+    if branch is not None:
+        _half_tokens("hip_vit_cls_mean_pool_f32 (branch)", branch)
+        if branch.dtype != dtype or branch.shape != x.shape:
+            msg = f"hip_vit_cls_mean_pool_f32: branch {tuple(branch.shape)}, {branch.dtype} beside a stream {tuple(x.shape)} for {dtype}."
+            raise ValueError(msg)
+    n, s, d = x.shape
+    out = torch.empty((n, 2 * d), dtype=torch.float32, device=x.device)
+    with torch.cuda.device(x.device):
+        rc = _lib.load().tia_vit_cls_mean_pool_f32(x.data_ptr(), _ptr(branch), gamma.data_ptr(), beta.data_ptr(), float(eps), out.data_ptr(),
+                                                   n, s, skip, d, _DT[dtype], _lib.current_stream())
+    _lib.check(rc, "tia_vit_cls_mean_pool_f32")
+    return out
+
+
 HEAD_MAX_CLASSES, HEAD_MAX_FEATURES = 64, 8192  # what tia_linear_softmax_rows_f32 takes (one lane per class; the widest LayerNorm row)
 
 
@@ -583,8 +684,9 @@ class FusedViT(nn.Module):
         self._norm = (f32(vit.norm.weight), f32(vit.norm.bias))
         self.half_dtype: torch.dtype | None = None
         self.linear_dtype: str | None = None
+        self.residual_dtype: str | None = None
 
-    def prepare(self, dtype: torch.dtype, linear_dtype: str | None = None) -> None:
+    def prepare(self, dtype: torch.dtype, linear_dtype: str | None = None, residual_dtype: str | None = None) -> None:
         """Pack every GEMM's float32 (folded) weights for ``tia_conv2d_nhwc_h`` in ``dtype`` (rounded once, after the folding): call
         this on the device, BEFORE ``.to(dtype)``.  Biases, LayerNorm affines, the class token and the position table stay float32
         in plain attributes that the cast does not reach.
@@ -593,13 +695,27 @@ class FusedViT(nn.Module):
         FP8 GEMM (``tia_linear_fp8_rows``; the numeric contract is in ``include/tiatoolbox_amd.h`` and DESIGN 4.34): their weights are
         quantised per output channel from the same float32 weights, and the LayerNorm / activation in front of each becomes its
         quantising form.  A layer off that kernel's shapes stays on the half kernel (one ``info`` line names them); ``attn.proj``,
-        the patch embedding, attention, the residual stream and the final norm are the half graph's, unchanged."""
+        the patch embedding, attention, the residual stream and the final norm are the half graph's, unchanged.
+
+        ``residual_dtype="float32"`` keeps the residual stream ``x`` in float32 from token assembly to the final norm, as the float32
+        module under ``torch.autocast`` does: ``proj`` and ``fc2`` write half branches without a residual, and one pass
+        (``tia_add_layernorm_rows_f32``) adds the branch to ``x`` in float32 and normalises the sum.  ``None`` (the
+        default) is the graph above, bit for bit.  Not together with ``linear_dtype="float8_e4m3"``: the quantising LayerNorm has no
+        float32-input form, and no other precision is put in its place."""
         if dtype not in _HALF:
             msg = f"FusedViT runs in float16 or bfloat16 (there is no float32 attention kernel); got {dtype}."
             raise ValueError(msg)
         if self.half_dtype is not None:
             msg = "FusedViT.prepare packs once, from the float32 weights; build a new FusedViT for another dtype."
             raise ValueError(msg)
+        if residual_dtype is not None:  # (checked before any device work)
+            if residual_dtype != RESIDUAL_F32:
+                msg = f"FusedViT.prepare: residual_dtype is None (the stream in `dtype`) or {RESIDUAL_F32!r}; got {residual_dtype!r}."
+                raise ValueError(msg)
+            if linear_dtype is not None:
+                msg = (f"FusedViT.prepare: residual_dtype={RESIDUAL_F32!r} beside linear_dtype={linear_dtype!r} needs a float32-input "
+                       "quantising LayerNorm (a tia_layernorm_rows_q8 that reads the float32 stream), which does not exist; choose one.")
+                raise ValueError(msg)
         if linear_dtype is not None:
             if linear_dtype != FP8_LINEAR:
                 msg = f"FusedViT.prepare: linear_dtype is None or {FP8_LINEAR!r}; got {linear_dtype!r}."
@@ -613,6 +729,7 @@ class FusedViT(nn.Module):
             for name in ("qkv", "proj", "fc1", "fc2"):
                 layer[name].prepare(dtype)
         self.half_dtype, self.linear_dtype = dtype, linear_dtype
+        self.residual_dtype = residual_dtype
 
     def _route_fp8(self) -> None:
         """``qkv`` / ``fc1`` / ``fc2`` of every block to :class:`_LinearFp8` where ``tia_linear_fp8_serves`` takes the shape.  A packed
@@ -697,6 +814,8 @@ class FusedViT(nn.Module):
 
     def _from_patch_columns(self, cols: torch.Tensor, pos: torch.Tensor, grid: tuple[int, int]) -> torch.Tensor:
         """The graph from the token GEMM on: ``cols`` ``[n, g, 3 p^2 or k_pad]`` are the im2col rows of either input form."""
+        if self.residual_dtype is not None:
+            return self._from_patch_columns_f32(cols, pos, grid)
         n, d = cols.shape[0], self.embed_dim
         tok = self.patch(cols)
         if self.prefix_pos_embed:
@@ -724,6 +843,37 @@ class FusedViT(nn.Module):
         if self.global_pool == "token_mean":
             return hip_vit_cls_mean_pool_h(x, *self._norm, eps=LN_EPS, skip=1 + self.reg_tokens)
         return hip_layernorm_rows_h(x, *self._norm, eps=LN_EPS, rows=n, row_stride=s * d, out_dtype=torch.float32)
+
+    def _from_patch_columns_f32(self, cols: torch.Tensor, pos: torch.Tensor, grid: tuple[int, int]) -> torch.Tensor:
+        """``_from_patch_columns`` under ``residual_dtype="float32"``: ``x`` is a float32 ``[n, S, D]`` tensor that only
+        ``tia_add_layernorm_rows_f32`` writes.  Every GEMM, attention and the activation are the half graph's; ``proj`` and ``fc2`` get
+        NO residual and write the half branch ``b = round(gamma (W a + b))``, and the pass in front of the next GEMM is
+        ``x += float(b); a = LN(x)`` -- the branch rounded once, the sum never: the float32 module under ``torch.autocast``."""
+        n, d, half = cols.shape[0], self.embed_dim, self.half_dtype
+        tok = self.patch(cols)
+        if self.prefix_pos_embed:
+            cls, reg, pos_grid = self._prefix_for(grid)
+            x = hip_vit_assemble_rows_f32(tok, cls, reg, pos_grid, pos_has_cls=False)
+        elif self.reg_tokens or self.no_embed_class:
+            x = hip_vit_assemble_rows_f32(tok, self._cls32, self._reg32, pos, pos_has_cls=not self.no_embed_class)
+        else:
+            x = hip_vit_assemble_rows_f32(tok, self._cls32, None, pos, pos_has_cls=True)
+        s = x.shape[1]
+
+        def add_norm(branch: torch.Tensor | None, norm: tuple[torch.Tensor, torch.Tensor]) -> torch.Tensor:
+            return hip_add_layernorm_rows_f32(x, branch, *norm, eps=LN_EPS, rows=n * s, row_stride=d, dtype=half).view(n, s, d)
+
+        b = None  # the branch not yet added to x (block 0's first pass has none: LayerNorm only)
+        for layer in self.layers:
+            a = hip_mha_fwd_h(layer["qkv"](add_norm(b, layer["norm1"])), self.num_heads, self.scale)
+            b = layer["proj"](a)
+            a = layer["fc1"](add_norm(b, layer["norm2"]))
+            a = hip_swiglu_rows_h(a) if self.swiglu else hip_gelu_rows_h_(a)
+            b = layer["fc2"](a)
+        if self.global_pool == "token_mean":
+            return hip_vit_cls_mean_pool_f32(x, b, *self._norm, eps=LN_EPS, skip=1 + self.reg_tokens, dtype=half)
+        # the class rows only: the last branch is added to them (both strides S * D) and the final norm is written in float32
+        return hip_add_layernorm_rows_f32(x, b, *self._norm, eps=LN_EPS, rows=n, row_stride=s * d, dtype=half, out_dtype=torch.float32)
 
 
 class FusedViTClassifier(nn.Module):

@@ -38,6 +38,14 @@ _FP8_COVERS = ("compute_dtype=\"float8_e4m3\" covers Vision Transformer models t
                "qkv, fc1 and fc2 Linear layers on the FP8 GEMM, everything else in bfloat16) on a CUDA device")
 
 
+# residual_dtype="float32": the same graph with its residual stream kept in float32, as the float32 module under torch.autocast keeps
+# it (architecture/vit_fused.py).  Like FP8_COMPUTE an option of the GRAPH; None (the default) is the half stream.
+RESIDUAL_F32 = "float32"
+_RESID_COVERS = ("residual_dtype=\"float32\" covers Vision Transformer models that FusedViT accepts (TimmBackbone / TimmModel) on a CUDA "
+                 "device with compute_dtype \"bfloat16\" or \"float16\" (not \"float8_e4m3\": there is no float32-input quantising "
+                 "LayerNorm); residual_dtype=None is the default")
+
+
 def _compute_name(compute_dtype) -> str:
     return str(compute_dtype).replace("torch.", "")
 
@@ -285,6 +293,7 @@ class EngineABC:
         self.output_type = None
         # MI355X extensions (plain attributes, settable through run(**kwargs) like every other)
         self.compute_dtype = "float32"    # arithmetic type of the CNN forward
+        self.residual_dtype = None        # "float32": FusedViT keeps its residual stream in float32 (ViT models, fp16 / bf16, CUDA)
         # float32 3x3 / stride-1 block convolutions: "auto" (default: Winograd F(2x2, 3x3) on every layer whose shape the committed
         # per-layer error-bound test covers -- tests/test_engine.py::test_winograd_conv_matches_torch_cpu_fp32, <= 1e-5 of the
         # output scale against torch-CPU float32 -- the direct implicit GEMM elsewhere), "direct" (audit mode: the reference's
@@ -452,6 +461,16 @@ class EngineABC:
         if algo == "auto":  # the modules know two forms; "auto" = Winograd wherever a layer qualifies (their own shape checks)
             algo = "winograd"
         fp8 = _compute_name(self.compute_dtype) == FP8_COMPUTE
+        resid = getattr(self, "residual_dtype", None)
+        if resid is not None:  # the same rule: what the option does not cover is refused, never run in another precision
+            from tiatoolbox_amd.models.architecture.vit import VisionTransformer as _ViT
+
+            if (resid != RESIDUAL_F32 or fp8 or dtype not in (torch.float16, torch.bfloat16) or torch.device(self.device).type != "cuda"
+                    or not isinstance(getattr(self.model, "feat_extract", None), _ViT)):
+                self.residual_dtype = None  # (run kwargs persist as attributes: do not leave the rejected value behind)
+                msg = (f"{_RESID_COVERS}; got residual_dtype={resid!r} with compute_dtype={_compute_name(self.compute_dtype)!r} for "
+                       f"{type(self.model).__name__} on {self.device}.")
+                raise ValueError(msg)
         if fp8:  # never another precision in its place: everything the option does not cover is refused, here and below
             from tiatoolbox_amd.models.architecture.vit import VisionTransformer as _ViT
 
@@ -462,7 +481,7 @@ class EngineABC:
             dtype = torch.bfloat16
         if dtype == torch.float32 and torch.device(self.device).type != "cuda":
             return self.model
-        key = (dtype, str(self.device), id(self.model), self.fold_batchnorm, _weights_version(self.model), algo, fp8)
+        key = (dtype, str(self.device), id(self.model), self.fold_batchnorm, _weights_version(self.model), algo, fp8, resid)
         if self._fast_key != key:
             import copy
 
@@ -493,6 +512,10 @@ class EngineABC:
                         if fp8:
                             self.compute_dtype = "float32"
                             msg = f"{_FP8_COVERS}; {type(self.model).__name__}: {exc}"
+                            raise ValueError(msg) from exc
+                        if resid is not None:
+                            self.residual_dtype = None
+                            msg = f"{_RESID_COVERS}; {type(self.model).__name__}: {exc}"
                             raise ValueError(msg) from exc
                         logger.warning("%s: %s  Running the torch module in %s instead: its matrix products are library (hipBLASLt / "
                                        "rocBLAS) GEMMs.", type(self.model).__name__, exc, dtype)
@@ -563,6 +586,8 @@ class EngineABC:
                     elif type(mod).__name__ in ("FusedUNet", "FusedPlainUNet", "FusedHoVerNet", "FusedViT") and dtype != torch.float32:
                         if fp8 and type(mod).__name__ == "FusedViT":
                             mod.prepare(dtype, linear_dtype=FP8_COMPUTE)  # qkv / fc1 / fc2 quantised per output channel as well
+                        elif resid is not None and type(mod).__name__ == "FusedViT":
+                            mod.prepare(dtype, residual_dtype=resid)  # the float32 residual stream (architecture/vit_fused.py)
                         else:
                             mod.prepare(dtype)  # half weights from the float32 BN-folded ones; float32 biases / BN affines kept aside
             m = m.to(dtype=dtype) if dtype != torch.float32 else m

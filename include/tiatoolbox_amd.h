@@ -48,7 +48,8 @@ extern "C" {
  * and head_dim 80 in tia_mha_fwd_h (Virchow, Virchow2); tia_vit_patchify_norm_u8_h, tia_linear_softmax_rows_f32 (Vision Transformer
  * classifiers from uint8 patches to probabilities); tia_linear_fp8_rows, tia_linear_fp8_pack_weights, tia_linear_fp8_serves,
  * tia_layernorm_rows_q8, tia_gelu_rows_q8, tia_swiglu_rows_q8 (the Vision Transformer linear layers on the FP8 matrix instruction); tia_add_layernorm_rows_f32,
- * tia_vit_assemble_rows_f32, tia_vit_cls_mean_pool_f32 (the same graph with a float32 residual stream). */
+ * tia_vit_assemble_rows_f32, tia_vit_cls_mean_pool_f32 (the same graph with a float32 residual stream); tia_mha_fwd_f32,
+ * tia_gelu_rows_f32, tia_swiglu_rows_f32, tia_vit_patchify_f32, tia_vit_assemble_f32 (the float32 route of that graph). */
 #define TIA_ABI_VERSION 6
 int tia_abi_version(void);
 
@@ -1075,6 +1076,56 @@ int tia_layernorm_rows_q8(const void* d_x, int64_t row_stride, const float* d_ga
                           float* d_scale, int64_t rows, int64_t c, int32_t dtype, void* stream);
 int tia_gelu_rows_q8(const void* d_x, void* d_q, float* d_scale, int64_t rows, int64_t hidden, int32_t dtype, void* stream);
 int tia_swiglu_rows_q8(const void* d_x, void* d_q, float* d_scale, int64_t rows, int64_t hidden, int32_t dtype, void* stream);
+
+/* =======================================================================================
+ * The float32 route of the Vision Transformer graph (vit_fused.py, prepare(torch.float32, linear_dtype="bfloat16x3"), the engines'
+ * compute_dtype="bfloat16x3").  Additive, same version (6).
+ *
+ * Activations, the residual stream and all row arithmetic are float32.  Every Linear is tia_conv2d_bf16x3_nhwc_f32 on the
+ * [n,S,1,cin] map (both operands split into three bf16 numbers, six exact products per float32 product, float32 accumulation; bias
+ * and the float32 residual in its epilogue) or, for a layer off that kernel's shapes or without an exact normal split of its weights,
+ * tia_conv2d_nhwc_f32.  The LayerNorm is tia_add_layernorm_rows_f32 with a NULL branch and TIA_DT_F32 output, the pooled norm
+ * tia_vit_cls_mean_pool_f32 with a NULL branch, the classifier head tia_linear_softmax_rows_f32.  The five entry points below are
+ * the rest.  The family's contract: null / misaligned (16 bytes) / non-positive arguments TIA_EINVAL, unsupported sizes TIA_ESIZE,
+ * nothing launched on an error; 64-bit offsets, 16-byte accesses, no atomics; the entry launches and neither allocates nor syncs.
+ *
+ * Numeric contract: every value is float32 and nothing is rounded to a half type.  A matrix product's error is a float32 matmul's
+ * (the split kernel drops terms below 2^-23 |a w|); attention is exact float32 products in float32 fma chains.
+ * Invalid-input domain: the split kernel's -- a non-finite activation, or one with |a| >= 2^127 (2 - 2^-8) = 3.3961e38, makes every
+ * output that reads it non-finite, never a finite wrong value.
+ * ===================================================================================== */
+
+/* Attention, float32: d_qkv [n,s,3,heads,head_dim] (the qkv Linear's own output order) -> d_out [n,s,heads*head_dim],
+ *   out[b,i,h,:] = softmax_j(scale * q[b,i,h,:] . k[b,j,h,:]) @ v[b,:,h,:]
+ * on v_mfma_f32_16x16x4_f32: exact float32 products, float32 fma chains (a score is eight chains over the dims 16 j + 4 q + e, one
+ * per (j & 1, e), q then j in order, added pairwise; an output sums its keys tile by tile in one chain, key 16 kt + 4 q + r with
+ * (kt, r) the step and q the order inside a step).  Online softmax
+ * with p = exp2((score - max) * scale * log2 e): the probabilities are never rounded below float32 and only O / l is written.
+ * Keys beyond s take no part (their scores are -inf before the maximum; there is never inf - inf).
+ * head_dim 64 or 80 (else TIA_ESIZE), any s >= 1; `dtype` must be TIA_DT_F32 (a half code is TIA_EINVAL: tia_mha_fwd_h is that
+ * entry); scale finite and > 0. */
+int tia_mha_fwd_f32(const float* d_qkv, float* d_out, int64_t n, int64_t s, int64_t heads, int64_t head_dim, float scale, int32_t dtype,
+                    void* stream);
+
+/* Exact (erf) GELU in place on `count` float32 values (count % 4 == 0, else TIA_ESIZE): 0.5 x (1 + erf(x / sqrt 2)) for x >= 0 and
+ * the same value as 0.5 x erfc(-x / sqrt 2) for x < 0 (no cancellation in the tail); -0.0 stays -0.0. */
+int tia_gelu_rows_f32(float* d_x, int64_t count, void* stream);
+
+/* Packed SwiGLU: d_x [rows, 2 hidden] float32, the first half the gate -> d_y [rows, hidden] = silu(gate) * value, silu through
+ * e = exp(-|t|) as tia_swiglu_rows_h (no overflow for any gate; a zero gate and value gives 0).  hidden % 4 == 0 (else TIA_ESIZE). */
+int tia_swiglu_rows_f32(const float* d_x, float* d_y, int64_t rows, int64_t hidden, void* stream);
+
+/* The patch embedding's im2col in float32: d_x [n,h,w,3] float32 NHWC -> d_tokens [n, (h/patch)*(w/patch), k_pad] float32, columns in
+ * (ky, kx, channel) order, columns 3 patch^2 .. k_pad - 1 exact zeros.  Any patch size; a pure gather (bit for bit).  d_x is read with
+ * 4-byte loads and needs only 4-byte alignment (a batch may be a slice that starts at any float of a larger buffer); d_tokens 16 bytes.
+ * TIA_ESIZE: h % patch, w % patch, k_pad % 16 (the GEMMs' smallest multiple), k_pad < 3 patch^2 (k_pad == 3 patch^2 is allowed). */
+int tia_vit_patchify_f32(const float* d_x, float* d_tokens, int64_t n, int64_t h, int64_t w, int64_t patch, int64_t k_pad, void* stream);
+
+/* tia_vit_assemble_rows_f32 for float32 tokens: d_out [n, 1+R+g, d] with out[b,0] = cls (+ pos[0] if pos_has_cls), out[b,1+r] = reg[r],
+ * out[b,1+R+i] = tokens[b,i] + pos[i + pos_has_cls] -- ONE float32 add per element.  d_reg NULL exactly when reg_tokens == 0;
+ * pos_has_cls = 0 with host-folded cls / reg rows is the prefix_pos_embed form.  d % 4 == 0 and d <= 8192 (else TIA_ESIZE). */
+int tia_vit_assemble_f32(const float* d_tokens, const float* d_cls, const float* d_reg, const float* d_pos, int32_t pos_has_cls,
+                         float* d_out, int64_t n, int64_t g, int64_t reg_tokens, int64_t d, void* stream);
 
 /* =======================================================================================
  * All borders of binary planes: cv2.findContours(layer, RETR_TREE, CHAIN_APPROX_NONE | _SIMPLE)

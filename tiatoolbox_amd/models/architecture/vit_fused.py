@@ -53,8 +53,16 @@ matrix instruction) and steps 1, 5 and 7 on their quantising forms (``tia_layern
 ``tia_swiglu_rows_q8``: codes and one scale per token from the float32 value, no extra pass).  The carrier stays bfloat16; attention,
 ``proj``, the patch embedding and the ends of the graph are unchanged.  :func:`quantize_rows_e4m3` states the recipe; DESIGN 4.34.
 
-There is no float32 form (no float32 attention kernel) and no library fall-back: a model the kernels do not take (``D / heads``
-other than 64 or 80, channel counts off the GEMM's multiples) raises ``UnsupportedLayerError`` from the constructor.
+``prepare(torch.float32, linear_dtype="bfloat16x3")`` (the engines' ``compute_dtype="bfloat16x3"``) is the float32 route of the same
+graph: activations, residual stream and row arithmetic in float32; every Linear on ``tia_conv2d_bf16x3_nhwc_f32`` (both operands
+split into three bf16 numbers, six exact products per float32 product, float32 accumulation; the weights split once with
+``fused.split_stem_weights``, bias and the float32 residual in the epilogue) or, off that kernel's shapes, ``tia_conv2d_nhwc_f32``;
+attention on ``tia_mha_fwd_f32`` (``v_mfma_f32_16x16x4_f32``); ``tia_gelu_rows_f32`` / ``tia_swiglu_rows_f32``, ``tia_vit_patchify_f32``
+and ``tia_vit_assemble_f32`` beside the float32 LayerNorm, pool and head that exist already.  The batch is the
+normalised float32 tensor; there is no uint8 im2col on this route.
+
+There is no library fall-back: a model the kernels do not take (``D / heads`` other than 64 or 80, channel counts off the GEMM's
+multiples) raises ``UnsupportedLayerError`` from the constructor.
 """
 
 from __future__ import annotations
@@ -628,10 +636,199 @@ class _Linear:
         return hip_linear_h(x, self.packed, self.bias32, residual, cout=self.cout)
 
 
+SPLIT_LINEAR = "bfloat16x3"  # the `linear_dtype` of the float32 route (and the engines' `compute_dtype` that selects it)
+
+
+def _f32_tokens(name: str, x: torch.Tensor, last: int | None = None) -> None:
+    if not (x.is_cuda and x.dtype == torch.float32 and x.is_contiguous() and (last is None or x.shape[-1] == last)):
+        msg = f"{name} expects a contiguous float32 CUDA tensor" + (f" with {last} channels" if last is not None else "") + \
+              f"; got {tuple(x.shape)}, {x.dtype} on {x.device}."
+        raise ValueError(msg)
+
+
+def pack_linear_weights_split(weight: torch.Tensor) -> torch.Tensor | None:
+    """Float32 ``[cout, cin]`` -> the split GEMM's operand ``[1, 1, cin / 16, cout / 128, 3, 2, 128, 8]`` bf16: the planes ``hi``,
+    ``mid``, ``lo`` of ``fused.split_stem_weights`` (``hi + mid + lo == w`` bit for bit) laid out by ``tia_conv_pack_weights_bf16x3``
+    with a 1x1 window.  ``None`` when the shape is off that kernel's (``cin % 16``, ``cout % 128``) or the weights have no exact split
+    into normal bf16 numbers (non-finite or extreme exponents): the caller then keeps the float32 GEMM."""
+    from tiatoolbox_amd import _lib
+    from tiatoolbox_amd.models.architecture.fused import split_stem_weights
+
+    w = weight.detach().to(torch.float32).contiguous()
+    cout, cin = w.shape
+    if cin % 16 or cout % 128:
+        return None
+    parts, usable = split_stem_weights(w)
+    if not usable:
+        return None
+    parts = parts.contiguous()  # [3, cout, cin] == [3, cout, cin, 1, 1]
+    out = torch.empty((1, 1, cin // 16, cout // 128, 3, 2, 128, 8), dtype=torch.bfloat16, device=w.device)
+    with torch.cuda.device(w.device):
+        rc = _lib.load().tia_conv_pack_weights_bf16x3(parts.data_ptr(), cout, cin, 1, 1, out.data_ptr(), _lib.current_stream())
+    _lib.check(rc, "tia_conv_pack_weights_bf16x3")
+    return out
+
+
+def pack_linear_weights_f32(weight: torch.Tensor) -> torch.Tensor:
+    """Float32 ``[cout, cin]`` -> the float32 GEMM's operand ``[1, 1, cin, cout]`` (``tia_conv_pack_weights_f32``)."""
+    from tiatoolbox_amd import _lib
+
+    w = weight.detach().to(torch.float32).contiguous()
+    cout, cin = w.shape
+    out = torch.empty((1, 1, cin, cout), dtype=torch.float32, device=w.device)
+    with torch.cuda.device(w.device):
+        rc = _lib.load().tia_conv_pack_weights_f32(w.data_ptr(), cout, cin, 1, 1, out.data_ptr(), _lib.current_stream())
+    _lib.check(rc, "tia_conv_pack_weights_f32")
+    return out
+
+
+def hip_linear_f32(x: torch.Tensor, w_packed: torch.Tensor, bias: torch.Tensor | None, residual: torch.Tensor | None = None, *,
+                   cout: int) -> torch.Tensor:
+    """``x @ W^T + bias (+ residual)`` on ``[n, S, cin]`` float32 tokens, float32 out: a 1x1 window on the ``[n, S, 1, cin]`` map.
+    bf16 weights from :func:`pack_linear_weights_split` go to ``tia_conv2d_bf16x3_nhwc_f32`` (both operands split into three bf16
+    numbers, float32 accumulation), float32 weights from :func:`pack_linear_weights_f32` to ``tia_conv2d_nhwc_f32``."""
+    from tiatoolbox_amd import _lib
+
+    _f32_tokens("hip_linear_f32", x)
+    n, s, cin = x.shape
+    if residual is not None:
+        _f32_tokens("hip_linear_f32 (residual)", residual, cout)
+        if residual.shape[:2] != x.shape[:2]:
+            msg = f"hip_linear_f32: residual {tuple(residual.shape)} beside tokens {tuple(x.shape)}."
+            raise ValueError(msg)
+    split = w_packed.dtype == torch.bfloat16
+    want = (1, 1, cin // 16, cout // 128, 3, 2, 128, 8) if split else (1, 1, cin, cout)
+    if tuple(w_packed.shape) != want or w_packed.dtype not in (torch.bfloat16, torch.float32) or not w_packed.is_contiguous() or (
+            bias is not None and bias.dtype != torch.float32):
+        msg = (f"hip_linear_f32: weights {tuple(w_packed.shape)}, {w_packed.dtype} are not pack_linear_weights_split's or "
+               f"pack_linear_weights_f32's for {cin} -> {cout}, or a bias that is not float32.")
+        raise ValueError(msg)
+    y = torch.empty((n, s, cout), dtype=torch.float32, device=x.device)
+    lib = _lib.load()
+    with torch.cuda.device(x.device):
+        if split:
+            rc = lib.tia_conv2d_bf16x3_nhwc_f32(x.data_ptr(), w_packed.data_ptr(), _ptr(bias), _ptr(residual), y.data_ptr(), n, s, 1, cin,
+                                                cout, 1, 1, 1, 0, 0, 0, _lib.current_stream())
+        else:
+            rc = lib.tia_conv2d_nhwc_f32(x.data_ptr(), w_packed.data_ptr(), _ptr(bias), _ptr(residual), y.data_ptr(), n, s, 1, cin, cout,
+                                         1, 1, 1, 0, 0, _lib.current_stream())
+    _lib.check(rc, "tia_conv2d_bf16x3_nhwc_f32" if split else "tia_conv2d_nhwc_f32")
+    return y
+
+
+def hip_mha_fwd_f32(qkv: torch.Tensor, heads: int, scale: float) -> torch.Tensor:
+    """Attention on the qkv Linear's float32 output ``[n, S, 3 * heads * hd]`` -> ``[n, S, heads * hd]`` float32, ``hd`` 64 or 80
+    (``tia_mha_fwd_f32``: exact float32 products on ``v_mfma_f32_16x16x4_f32``)."""
+    from tiatoolbox_amd import _lib
+
+    _f32_tokens("hip_mha_fwd_f32", qkv)
+    if qkv.dim() != 3 or heads <= 0 or qkv.shape[-1] % (3 * heads) != 0:  # noqa: PLR2004
+        msg = f"hip_mha_fwd_f32 takes [n, S, 3 * heads * head_dim] tokens; got {tuple(qkv.shape)} for {heads} heads."
+        raise ValueError(msg)
+    n, s, c3 = qkv.shape
+    head_dim = c3 // (3 * heads)
+    out = torch.empty((n, s, heads * head_dim), dtype=torch.float32, device=qkv.device)
+    with torch.cuda.device(qkv.device):
+        rc = _lib.load().tia_mha_fwd_f32(qkv.data_ptr(), out.data_ptr(), n, s, heads, head_dim, float(scale), _DT[torch.float32],
+                                         _lib.current_stream())
+    _lib.check(rc, "tia_mha_fwd_f32")
+    return out
+
+
+def hip_gelu_rows_f32_(x: torch.Tensor) -> torch.Tensor:
+    """Exact GELU in place on float32 tokens (``tia_gelu_rows_f32``)."""
+    from tiatoolbox_amd import _lib
+
+    _f32_tokens("hip_gelu_rows_f32_", x)
+    with torch.cuda.device(x.device):
+        rc = _lib.load().tia_gelu_rows_f32(x.data_ptr(), x.numel(), _lib.current_stream())
+    _lib.check(rc, "tia_gelu_rows_f32")
+    return x
+
+
+def hip_swiglu_rows_f32(x: torch.Tensor) -> torch.Tensor:
+    """Packed SwiGLU ``silu(x[..., :H]) * x[..., H:]`` on float32 ``[n, S, 2H]`` tokens -> ``[n, S, H]`` (``tia_swiglu_rows_f32``)."""
+    from tiatoolbox_amd import _lib
+
+    _f32_tokens("hip_swiglu_rows_f32", x)
+    if x.dim() < 2 or x.shape[-1] % 2 != 0:  # noqa: PLR2004
+        msg = f"hip_swiglu_rows_f32 takes [..., 2H] tokens; got {tuple(x.shape)}."
+        raise ValueError(msg)
+    hidden = x.shape[-1] // 2
+    y = torch.empty((*x.shape[:-1], hidden), dtype=torch.float32, device=x.device)
+    with torch.cuda.device(x.device):
+        rc = _lib.load().tia_swiglu_rows_f32(x.data_ptr(), y.data_ptr(), x.numel() // (2 * hidden), hidden, _lib.current_stream())
+    _lib.check(rc, "tia_swiglu_rows_f32")
+    return y
+
+
+def hip_vit_patchify_f32(x_nhwc: torch.Tensor, patch: int, k_pad: int) -> torch.Tensor:
+    """``[n, h, w, 3]`` float32 images -> ``[n, g, k_pad]`` float32 token rows in ``(ky, kx, c)`` order, zeros from column
+    ``3 * patch^2`` on (``tia_vit_patchify_f32``: any patch size, a pure gather)."""
+    from tiatoolbox_amd import _lib
+
+    if not (x_nhwc.is_cuda and x_nhwc.dim() == 4 and x_nhwc.shape[-1] == 3 and x_nhwc.is_contiguous() and x_nhwc.dtype == torch.float32):  # noqa: PLR2004
+        msg = f"hip_vit_patchify_f32 expects a contiguous [n, h, w, 3] float32 CUDA tensor; got {tuple(x_nhwc.shape)}, {x_nhwc.dtype}."
+        raise ValueError(msg)
+    n, h, w, _ = x_nhwc.shape
+    out = torch.empty((n, (h // patch) * (w // patch), k_pad), dtype=torch.float32, device=x_nhwc.device)
+    with torch.cuda.device(x_nhwc.device):
+        rc = _lib.load().tia_vit_patchify_f32(x_nhwc.data_ptr(), out.data_ptr(), n, h, w, patch, k_pad, _lib.current_stream())
+    _lib.check(rc, "tia_vit_patchify_f32")
+    return out
+
+
+def hip_vit_assemble_f32(tokens: torch.Tensor, cls: torch.Tensor, reg: torch.Tensor | None, pos: torch.Tensor, *,
+                         pos_has_cls: bool) -> torch.Tensor:
+    """:func:`hip_vit_assemble_rows_f32` for float32 tokens: ``cat([cls (+ pos[0] if pos_has_cls), reg, tokens[b] + pos[pos_has_cls:]])``,
+    one float32 add per element (``tia_vit_assemble_f32``)."""
+    from tiatoolbox_amd import _lib
+
+    _f32_tokens("hip_vit_assemble_f32", tokens)
+    n, g, d = tokens.shape
+    nreg = 0 if reg is None else reg.numel() // d
+    rows = g + int(pos_has_cls)
+    if cls.dtype != torch.float32 or pos.dtype != torch.float32 or cls.numel() != d or pos.numel() != rows * d or not (
+            cls.is_contiguous() and pos.is_contiguous()) or (reg is not None and (
+                reg.dtype != torch.float32 or not reg.is_contiguous() or nreg == 0 or reg.numel() != nreg * d)):
+        msg = (f"hip_vit_assemble_f32 takes float32 cls [{d}], reg [R, {d}] or None and pos [{rows}, {d}]; got {tuple(cls.shape)}, "
+               f"{None if reg is None else tuple(reg.shape)}, {tuple(pos.shape)}.")
+        raise ValueError(msg)
+    out = torch.empty((n, 1 + nreg + g, d), dtype=torch.float32, device=tokens.device)
+    with torch.cuda.device(tokens.device):
+        rc = _lib.load().tia_vit_assemble_f32(tokens.data_ptr(), cls.data_ptr(), _ptr(reg), pos.data_ptr(), int(pos_has_cls),
+                                              out.data_ptr(), n, g, nreg, d, _lib.current_stream())
+    _lib.check(rc, "tia_vit_assemble_f32")
+    return out
+
+
+class _LinearF32:
+    """One GEMM of the float32 route: ``prepare`` splits the float32 (folded, padded) weights into three bf16 planes for the split
+    kernel, or -- a shape off that kernel's, or weights without an exact normal split -- packs them for the float32 kernel
+    (``self.split`` says which); the float32 bias throughout.  Called on float32 tokens, with the float32 stream as ``residual``."""
+
+    def __init__(self, name: str, weight: torch.Tensor, bias: torch.Tensor) -> None:
+        self.name, self.weight32, self.bias32 = name, weight, bias
+        self.cout, self.cin = weight.shape
+        self.packed: torch.Tensor | None = None
+        self.split: bool | None = None
+
+    def prepare(self) -> None:
+        self.packed = pack_linear_weights_split(self.weight32)
+        self.split = self.packed is not None
+        if not self.split:
+            self.packed = pack_linear_weights_f32(self.weight32)
+        self.weight32 = None
+
+    def __call__(self, x: torch.Tensor, residual: torch.Tensor | None = None) -> torch.Tensor:
+        return hip_linear_f32(x, self.packed, self.bias32, residual, cout=self.cout)
+
+
 class FusedViT(nn.Module):
     """``forward(imgs)`` == ``VisionTransformer.forward(imgs)`` (float32 features ``[B, D]``) on a CUDA device with fp16 / bf16
-    activations, after ``prepare(dtype)``.  Built from a loaded model (timm parameter names); the constructor only folds and checks
-    (it runs on any device), ``prepare`` packs on the GPU."""
+    activations, after ``prepare(dtype)`` -- or with float32 activations on the split-bf16 GEMM and the float32 attention kernel,
+    after ``prepare(torch.float32, linear_dtype="bfloat16x3")``.  Built from a loaded model (timm parameter names); the constructor
+    only folds and checks (it runs on any device), ``prepare`` packs on the GPU."""
 
     accepts_uint8 = False  # input normalisation is the caller's: `infer_batch` hands the batch over in the parameters' dtype
 
@@ -701,12 +898,34 @@ class FusedViT(nn.Module):
         module under ``torch.autocast`` does: ``proj`` and ``fc2`` write half branches without a residual, and one pass
         (``tia_add_layernorm_rows_f32``) adds the branch to ``x`` in float32 and normalises the sum.  ``None`` (the
         default) is the graph above, bit for bit.  Not together with ``linear_dtype="float8_e4m3"``: the quantising LayerNorm has no
-        float32-input form, and no other precision is put in its place."""
+        float32-input form, and no other precision is put in its place.
+
+        ``prepare(torch.float32, linear_dtype="bfloat16x3")`` (the engines' ``compute_dtype="bfloat16x3"``) is the float32 route:
+        float32 activations, residual stream and row arithmetic, every Linear on the split-bf16 GEMM
+        (``tia_conv2d_bf16x3_nhwc_f32``: the float32 weights as three bf16 planes, ``hi + mid + lo == w`` exactly -- no other
+        rounding of the weights) with the residual add in its epilogue, attention on ``tia_mha_fwd_f32``.  A layer off
+        that kernel's shapes (``cin % 16``, ``cout % 128``) or without an exact normal split goes on ``tia_conv2d_nhwc_f32`` (one
+        ``info`` line names them); a packed SwiGLU whose ``fc1`` is off the multiple is first padded with exact zero lanes.
+        ``half_dtype`` stays ``None``.  ``torch.float32`` without that keyword, with ``"float8_e4m3"`` or with ``residual_dtype`` is
+        refused as before; ``"bfloat16x3"`` with a half ``dtype`` is refused too."""
+        if linear_dtype == SPLIT_LINEAR and dtype == torch.float32 and residual_dtype is None:
+            if self.half_dtype is not None or self.linear_dtype is not None:
+                msg = "FusedViT.prepare packs once, from the float32 weights; build a new FusedViT for another dtype."
+                raise ValueError(msg)
+            self._route_split()
+            self.linear_dtype = SPLIT_LINEAR
+            return
         if dtype not in _HALF:
-            msg = f"FusedViT runs in float16 or bfloat16 (there is no float32 attention kernel); got {dtype}."
+            msg = (f"FusedViT runs in float16 or bfloat16, or in float32 with linear_dtype={SPLIT_LINEAR!r} and nothing else (the float32 "
+                   f"route); got {dtype} with linear_dtype={linear_dtype!r}, residual_dtype={residual_dtype!r}.")
             raise ValueError(msg)
-        if self.half_dtype is not None:
+        if self.half_dtype is not None or self.linear_dtype == SPLIT_LINEAR:
             msg = "FusedViT.prepare packs once, from the float32 weights; build a new FusedViT for another dtype."
+            raise ValueError(msg)
+        if linear_dtype == SPLIT_LINEAR:  # (checked before any device work)
+            msg = (f"FusedViT.prepare: linear_dtype={SPLIT_LINEAR!r} is the float32 route, prepare(torch.float32, "
+                   f"linear_dtype={SPLIT_LINEAR!r}) without a residual_dtype (its stream is float32 already); got {dtype}, "
+                   f"residual_dtype={residual_dtype!r}.")
             raise ValueError(msg)
         if residual_dtype is not None:  # (checked before any device work)
             if residual_dtype != RESIDUAL_F32:
@@ -755,6 +974,74 @@ class FusedViT(nn.Module):
                 "FusedViT: the FP8 GEMM takes cin %% 128 == 0 and cout %% 16 == 0; %d layer(s) stay on the half kernel: %s.", len(kept),
                 ", ".join(kept))
 
+    def _route_split(self) -> None:
+        """Every GEMM of the graph to :class:`_LinearF32`, packed.  A packed SwiGLU whose ``fc1`` is off the split kernel's multiple
+        of 128 output channels gets ``pad_swiglu``'s exact zero lanes up to the next multiple of 64 per half (at or above
+        ``SWIGLU_PAD_FLOOR`` only, as there; Virchow: 3424 -> 3456, ``fc1`` 6912)."""
+        kept: list[str] = []
+
+        def routed(lin: _Linear) -> _LinearF32:
+            new = _LinearF32(lin.name, lin.weight32, lin.bias32)
+            new.prepare()
+            if not new.split:
+                kept.append(f"{new.name} ({new.cin} -> {new.cout})")
+            return new
+
+        self.patch = routed(self.patch)
+        for layer in self.layers:
+            fc1, fc2 = layer["fc1"], layer["fc2"]
+            if self.swiglu and fc1.cout % 128 != 0 and fc2.cin >= SWIGLU_PAD_FLOOR:
+                fc1_w, fc1_b, fc2_w = pad_swiglu_to(fc1.weight32, fc1.bias32, fc2.weight32, -(-fc2.cin // 64) * 64)
+                layer["fc1"], layer["fc2"] = _Linear(fc1.name, fc1_w, fc1_b), _Linear(fc2.name, fc2_w, fc2.bias32)
+            for name in ("qkv", "proj", "fc1", "fc2"):
+                layer[name] = routed(layer[name])
+        if kept:
+            import logging
+
+            logging.getLogger("tiatoolbox_amd").info(
+                "FusedViT: the split-bf16 GEMM takes cin %% 16 == 0, cout %% 128 == 0 and weights with an exact split into normal bf16 "
+                "numbers; %d layer(s) run on the float32 GEMM (tia_conv2d_nhwc_f32): %s.", len(kept), ", ".join(kept))
+
+    def _forward_f32(self, imgs: torch.Tensor) -> torch.Tensor:
+        """The float32 route (``linear_dtype="bfloat16x3"``): the module's block sequence on float32 tensors --
+        LN -> qkv -> ``tia_mha_fwd_f32`` -> proj (+ x) -> LN -> fc1 -> GELU / SwiGLU -> fc2 (+ x), then the final norm or pool.  The
+        residual adds are the GEMMs' ``d_residual``; the LayerNorm is ``tia_add_layernorm_rows_f32`` without a branch and with
+        float32 output, the pooled end ``tia_vit_cls_mean_pool_f32`` without a branch."""
+        p = self.patch_size
+        _, _, h, w = imgs.shape
+        if h % p != 0 or w % p != 0:
+            msg = f"FusedViT: the input size {h} x {w} is no multiple of the patch size {p}."
+            raise ValueError(msg)
+        grid = (h // p, w // p)
+        pos = self._pos_for(grid)  # (refuses an off-grid size before any launch)
+        x = imgs.permute(0, 2, 3, 1).to(torch.float32).contiguous()  # the NHWC batch under the NCHW view
+        cols = hip_vit_patchify_f32(x, p, self.k_pad if self.k_pad is not None else 3 * p * p)
+        n, d = cols.shape[0], self.embed_dim
+        tok = self.patch(cols)
+        if self.prefix_pos_embed:
+            cls, reg, pos_grid = self._prefix_for(grid)
+            x = hip_vit_assemble_f32(tok, cls, reg, pos_grid, pos_has_cls=False)
+        elif self.reg_tokens or self.no_embed_class:
+            x = hip_vit_assemble_f32(tok, self._cls32, self._reg32, pos, pos_has_cls=not self.no_embed_class)
+        else:
+            x = hip_vit_assemble_f32(tok, self._cls32, None, pos, pos_has_cls=True)
+        s = x.shape[1]
+
+        def norm(norm: tuple[torch.Tensor, torch.Tensor]) -> torch.Tensor:  # (`dtype` names the absent branch's type: not looked at)
+            return hip_add_layernorm_rows_f32(x, None, *norm, eps=LN_EPS, rows=n * s, row_stride=d, dtype=torch.bfloat16,
+                                              out_dtype=torch.float32).view(n, s, d)
+
+        for layer in self.layers:
+            a = hip_mha_fwd_f32(layer["qkv"](norm(layer["norm1"])), self.num_heads, self.scale)
+            x = layer["proj"](a, residual=x)
+            a = layer["fc1"](norm(layer["norm2"]))
+            a = hip_swiglu_rows_f32(a) if self.swiglu else hip_gelu_rows_f32_(a)
+            x = layer["fc2"](a, residual=x)
+        if self.global_pool == "token_mean":
+            return hip_vit_cls_mean_pool_f32(x, None, *self._norm, eps=LN_EPS, skip=1 + self.reg_tokens, dtype=torch.bfloat16)
+        return hip_add_layernorm_rows_f32(x, None, *self._norm, eps=LN_EPS, rows=n, row_stride=s * d, dtype=torch.bfloat16,
+                                          out_dtype=torch.float32)
+
     def _pos_for(self, grid: tuple[int, int]) -> torch.Tensor:
         if grid not in self._pos_cache:
             self._pos_cache[grid] = resample_pos_embed(self._pos32, self.native_grid, grid, dynamic=self.dynamic_img_size,
@@ -772,6 +1059,8 @@ class FusedViT(nn.Module):
         return self._prefix_cache[grid]
 
     def forward(self, imgs: torch.Tensor) -> torch.Tensor:
+        if self.linear_dtype == SPLIT_LINEAR:
+            return self._forward_f32(imgs)
         half = self.half_dtype
         if half is None:
             msg = "FusedViT.forward needs prepare(dtype) first."
@@ -796,6 +1085,9 @@ class FusedViT(nn.Module):
         ``[256, 3]`` table in the graph's dtype): ``tia_vit_patchify_norm_u8_h`` makes the look-up while it lays the patches out, and
         the graph runs from the token GEMM on as in ``forward`` -- bit for bit ``forward(hook.device_batch(x, dtype))``."""
         half = self.half_dtype
+        if self.linear_dtype == SPLIT_LINEAR:
+            msg = "FusedViT.forward_uint8: the float32 route has no uint8 im2col; hand `forward` the normalised float32 batch."
+            raise RuntimeError(msg)
         if half is None:
             msg = "FusedViT.forward_uint8 needs prepare(dtype) first."
             raise RuntimeError(msg)

@@ -14,7 +14,14 @@ from tiatoolbox_amd.models.engine.patch_predictor import PatchPredictor
 
 
 class DeepFeatureExtractor(PatchPredictor):
-    """Patch / WSI feature extractor: ``run()`` returns ``{"probabilities": features[, "coordinates"]}``."""
+    """Patch / WSI feature extractor: ``run()`` returns ``{"probabilities": features[, "coordinates"]}``.
+
+    The run kwargs are :class:`PatchPredictor`'s.  ``compute_dtype``: "float32" | "float16" | "bfloat16"; for Vision Transformer backbones
+    on a CUDA device also "float8_e4m3" (the bfloat16 graph with the qkv / fc1 / fc2 Linear layers on the FP8 GEMM) and "bfloat16x3"
+    (the hand-written graph in float32: every Linear on the split-bf16 GEMM, attention on the float32 MFMA kernel -- float32-class
+    features, where "float32" itself keeps the torch module on library GEMMs); both are a ``ValueError`` anywhere else.
+    ``residual_dtype``: ``None`` | "float32", for the same backbones in "float16" / "bfloat16" (not beside "bfloat16x3", whose stream
+    is float32 already)."""
 
     def __init__(self, model, batch_size: int = 8, num_workers: int = 0, weights=None, *,
                  device: str = "cpu", verbose: bool = True) -> None:

@@ -46,13 +46,26 @@ _RESID_COVERS = ("residual_dtype=\"float32\" covers Vision Transformer models th
                  "LayerNorm); residual_dtype=None is the default")
 
 
+# compute_dtype="bfloat16x3": the float32 route of the Vision Transformer graph -- float32 activations, residual stream and row
+# arithmetic, every Linear on the split-bf16 GEMM (three bf16 parts per float32 operand, float32 accumulation), attention on the
+# float32 MFMA kernel (architecture/vit_fused.py).  An option of the GRAPH with a float32 carrier, as FP8_COMPUTE is one
+# with a bfloat16 carrier; compute_dtype="float32" stays the torch module.
+SPLIT_COMPUTE = "bfloat16x3"
+_SPLIT_COVERS = ("compute_dtype=\"bfloat16x3\" covers Vision Transformer models that FusedViT accepts (TimmBackbone / TimmModel: float32 "
+                 "activations with every Linear on the split-bf16 GEMM and attention on the float32 MFMA kernel) on a CUDA device, "
+                 "without residual_dtype (its residual stream is float32 already)")
+
+
 def _compute_name(compute_dtype) -> str:
     return str(compute_dtype).replace("torch.", "")
 
 
 def _carrier_dtype(compute_dtype) -> torch.dtype:
-    """The dtype of the activations (and of the cast model copy) for a ``compute_dtype``: bfloat16 under ``"float8_e4m3"``."""
+    """The dtype of the activations (and of the cast model copy) for a ``compute_dtype``: bfloat16 under ``"float8_e4m3"``, float32
+    under ``"bfloat16x3"``."""
     name = _compute_name(compute_dtype)
+    if name == SPLIT_COMPUTE:
+        return torch.float32
     return torch.bfloat16 if name == FP8_COMPUTE else _DTYPES[name]
 
 
@@ -462,6 +475,16 @@ class EngineABC:
             algo = "winograd"
         fp8 = _compute_name(self.compute_dtype) == FP8_COMPUTE
         resid = getattr(self, "residual_dtype", None)
+        split = _compute_name(self.compute_dtype) == SPLIT_COMPUTE
+        if split:  # the rule of the FP8 option: what this one does not cover is refused, never run in another precision
+            from tiatoolbox_amd.models.architecture.vit import VisionTransformer as _ViT
+
+            if (torch.device(self.device).type != "cuda" or not isinstance(getattr(self.model, "feat_extract", None), _ViT)
+                    or resid is not None):
+                self.compute_dtype, self.residual_dtype = "float32", None  # (run kwargs persist: the rejected values are not left behind)
+                msg = f"{_SPLIT_COVERS}; got {type(self.model).__name__} on {self.device} with residual_dtype={resid!r}."
+                raise ValueError(msg)
+            dtype = torch.float32
         if resid is not None:  # the same rule: what the option does not cover is refused, never run in another precision
             from tiatoolbox_amd.models.architecture.vit import VisionTransformer as _ViT
 
@@ -481,7 +504,8 @@ class EngineABC:
             dtype = torch.bfloat16
         if dtype == torch.float32 and torch.device(self.device).type != "cuda":
             return self.model
-        key = (dtype, str(self.device), id(self.model), self.fold_batchnorm, _weights_version(self.model), algo, fp8, resid)
+        key = (dtype, str(self.device), id(self.model), self.fold_batchnorm, _weights_version(self.model), algo,
+               SPLIT_COMPUTE if split else fp8, resid)
         if self._fast_key != key:
             import copy
 
@@ -493,9 +517,10 @@ class EngineABC:
                 # Vision Transformer backbones (TimmBackbone) and classifiers (TimmModel: FusedViTClassifier, the same graph plus the
                 # head kernel).  GPU, fp16 / bf16: FusedViT -- every Linear on the half MFMA GEMM,
                 # attention, LayerNorm, GELU / SwiGLU and token assembly on their own kernels (architecture/vit_fused.py; `prepare(dtype)`
-                # below).  GPU, float32: there is no float32 attention kernel, the torch module runs on the library's GEMMs -- never
-                # silently.  CPU: the torch module.  `conv_algo` has nothing to choose here.
-                if on_gpu and dtype != torch.float32:
+                # below).  GPU, "bfloat16x3": the same graph in float32 on the split-bf16 GEMM and the float32 attention kernel.  GPU,
+                # "float32": the torch module runs on the library's GEMMs -- never silently.  CPU: the torch module.  `conv_algo` has
+                # nothing to choose here.
+                if on_gpu and (dtype != torch.float32 or split):
                     from tiatoolbox_amd.models.architecture.unet_fused import UnsupportedLayerError
                     from tiatoolbox_amd.models.architecture.vit_fused import FusedViT
 
@@ -509,9 +534,9 @@ class EngineABC:
                         else:
                             m.feat_extract = FusedViT(m.feat_extract)
                     except UnsupportedLayerError as exc:  # (the constructor's own refusal; any other error is a bug and propagates)
-                        if fp8:
+                        if fp8 or split:
                             self.compute_dtype = "float32"
-                            msg = f"{_FP8_COVERS}; {type(self.model).__name__}: {exc}"
+                            msg = f"{_SPLIT_COVERS if split else _FP8_COVERS}; {type(self.model).__name__}: {exc}"
                             raise ValueError(msg) from exc
                         if resid is not None:
                             self.residual_dtype = None
@@ -520,9 +545,10 @@ class EngineABC:
                         logger.warning("%s: %s  Running the torch module in %s instead: its matrix products are library (hipBLASLt / "
                                        "rocBLAS) GEMMs.", type(self.model).__name__, exc, dtype)
                 elif on_gpu:
-                    logger.warning("%s: the hand-written Vision Transformer kernels run in fp16 / bf16 only; compute_dtype=\"float32\" "
-                                   "runs the torch module on library (hipBLASLt / rocBLAS) GEMMs.  Pass compute_dtype=\"bfloat16\" for "
-                                   "the hand-written path.", type(self.model).__name__)
+                    logger.warning("%s: the hand-written Vision Transformer kernels run in fp16 / bf16 or, in float32, under "
+                                   "compute_dtype=\"bfloat16x3\"; compute_dtype=\"float32\" runs the torch module on library (hipBLASLt / "
+                                   "rocBLAS) GEMMs.  Pass compute_dtype=\"bfloat16\" (or \"bfloat16x3\") for the hand-written path.",
+                                   type(self.model).__name__)
             elif self.fold_batchnorm and hasattr(m, "feat_extract"):
                 from tiatoolbox_amd.models.architecture.fused import fuse_cnn_model
                 from tiatoolbox_amd.models.architecture.resnet import BasicBlock, Bottleneck
@@ -583,6 +609,8 @@ class EngineABC:
                     if type(mod).__name__ == "MfmaResNet":
                         mod.set_conv_algo(algo)  # run kwarg `conv_algo="winograd"`: opt-in float32 Winograd for the 3x3 / stride-1 layers
                         mod.prepare(dtype)
+                    elif split and type(mod).__name__ == "FusedViT":
+                        mod.prepare(torch.float32, linear_dtype=SPLIT_COMPUTE)  # three bf16 planes per Linear; float32 everywhere else
                     elif type(mod).__name__ in ("FusedUNet", "FusedPlainUNet", "FusedHoVerNet", "FusedViT") and dtype != torch.float32:
                         if fp8 and type(mod).__name__ == "FusedViT":
                             mod.prepare(dtype, linear_dtype=FP8_COMPUTE)  # qkv / fc1 / fc2 quantised per output channel as well

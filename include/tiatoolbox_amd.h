@@ -49,7 +49,9 @@ extern "C" {
  * classifiers from uint8 patches to probabilities); tia_linear_fp8_rows, tia_linear_fp8_pack_weights, tia_linear_fp8_serves,
  * tia_layernorm_rows_q8, tia_gelu_rows_q8, tia_swiglu_rows_q8 (the Vision Transformer linear layers on the FP8 matrix instruction); tia_add_layernorm_rows_f32,
  * tia_vit_assemble_rows_f32, tia_vit_cls_mean_pool_f32 (the same graph with a float32 residual stream); tia_mha_fwd_f32,
- * tia_gelu_rows_f32, tia_swiglu_rows_f32, tia_vit_patchify_f32, tia_vit_assemble_f32 (the float32 route of that graph). */
+ * tia_gelu_rows_f32, tia_swiglu_rows_f32, tia_vit_patchify_f32, tia_vit_assemble_f32 (the float32 route of that graph);
+ * tia_linear_int8_rows, tia_linear_int8_pack_weights, tia_linear_int8_serves, tia_layernorm_rows_qi8, tia_gelu_rows_qi8,
+ * tia_swiglu_rows_qi8 (the Vision Transformer linear layers on the INT8 matrix instruction). */
 #define TIA_ABI_VERSION 6
 int tia_abi_version(void);
 
@@ -1076,6 +1078,50 @@ int tia_layernorm_rows_q8(const void* d_x, int64_t row_stride, const float* d_ga
                           float* d_scale, int64_t rows, int64_t c, int32_t dtype, void* stream);
 int tia_gelu_rows_q8(const void* d_x, void* d_q, float* d_scale, int64_t rows, int64_t hidden, int32_t dtype, void* stream);
 int tia_swiglu_rows_q8(const void* d_x, void* d_q, float* d_scale, int64_t rows, int64_t hidden, int32_t dtype, void* stream);
+
+/* =======================================================================================
+ * Vision Transformer linear layers on the INT8 matrix instruction (vit_fused.py, linear_dtype="int8").
+ * Additive, same version (6); the contract of the family above (16-byte aligned pointers, nothing launched on an error).
+ *
+ * The numeric contract -- W8A8, symmetric, one scale per token and one per output channel:
+ *   a row        v[0..K) float32: amax = max |v|; inv = 127 / amax and s = amax / 127, one float32 division each (amax == 0:
+ *                inv = s = 1); q[k] = clamp(rne(v[k] * inv), -127, 127), the product in float32, rounding to nearest even.  The
+ *                code -128 is never produced.  Stored as q (K bytes of int8) and s (one float32).
+ *   non-finite   the row maximum propagates NaN.  A row holding NaN has s = NaN, a row holding +-inf (and no NaN) has s = +inf;
+ *                a NaN product v[k] * inv gives the code 0, so every code stays inside [-127, 127].  Every output of that token
+ *                is then non-finite, never a finite wrong value; other tokens are untouched.
+ *   weights      one row per output channel, quantised once from the float32 weights (after the LayerScale fold and the SwiGLU
+ *                padding: where the FP8 route quantises).
+ *   activations  one row per token, quantised from the float32 value the producing kernel holds, before any rounding to half.
+ *   GEMM         acc[r,o] = sum_k qa[r,k] qw[o,k] exactly, in int32: the result does not depend on summation order, tiling or run.
+ *                K <= 65536 keeps K 127^2 inside int32; a larger K is TIA_ESIZE.
+ *                y[r,o] = half_rne(float(acc) * sa[r] * sw[o] + bias[o] (+ float32(residual[r,o]))); float(acc) is the
+ *                round-to-nearest-even conversion (exact below 2^24), the float32 epilogue is tia_linear_fp8_rows's.
+ *                v_mfma_i32_16x16x64_i8, two instructions per 128-deep K-step.
+ * ===================================================================================== */
+
+/* The GEMM.  d_a [rows,K] int8 codes with d_sa [rows]; d_w [N,K] int8 codes with d_sw [N] (tia_linear_int8_pack_weights);
+ * d_bias [N] float32 or NULL; d_residual [rows,N] of `dtype` or NULL; d_y [rows,N] of `dtype` (TIA_DT_F16 | TIA_DT_BF16).
+ * K % 128 == 0, K <= 65536 and N % 16 == 0 (else TIA_ESIZE), any rows >= 1 (rows <= 0: TIA_EINVAL). */
+int tia_linear_int8_rows(const void* d_a, const float* d_sa, const void* d_w, const float* d_sw, const float* d_bias,
+                         const void* d_residual, void* d_y, int64_t rows, int64_t n, int64_t k, int32_t dtype, void* stream);
+
+/* Weights for tia_linear_int8_rows from float32 d_w [N,K] (nn.Linear's own layout): d_q [N,K] codes, d_scale [N], quantised per
+ * output channel on the device by the recipe above.  The shape limits of the GEMM. */
+int tia_linear_int8_pack_weights(const float* d_w, int64_t n, int64_t k, void* d_q, float* d_scale, void* stream);
+
+/* Host-only: 1 when tia_linear_int8_rows takes (and the graph routes) a layer of this shape, 0 when the layer stays on the half
+ * GEMM (a size outside the kernel's), TIA_EINVAL for a non-positive size.  No device call. */
+int tia_linear_int8_serves(int64_t rows, int64_t n, int64_t k);
+
+/* The quantising producers: the arithmetic of tia_layernorm_rows_h / tia_gelu_rows_h / tia_swiglu_rows_h up to the float32
+ * value, which is then quantised per row by the INT8 recipe above.  d_q [rows, c | hidden] int8 codes, d_scale [rows] float32.
+ * c, hidden % 16 == 0 and <= 8192 (else TIA_ESIZE).  tia_swiglu_rows_qi8 reads d_x [rows, 2 hidden], the first half the gate;
+ * a zero gate and value (a pad lane) gives code 0. */
+int tia_layernorm_rows_qi8(const void* d_x, int64_t row_stride, const float* d_gamma, const float* d_beta, float eps, void* d_q,
+                           float* d_scale, int64_t rows, int64_t c, int32_t dtype, void* stream);
+int tia_gelu_rows_qi8(const void* d_x, void* d_q, float* d_scale, int64_t rows, int64_t hidden, int32_t dtype, void* stream);
+int tia_swiglu_rows_qi8(const void* d_x, void* d_q, float* d_scale, int64_t rows, int64_t hidden, int32_t dtype, void* stream);
 
 /* =======================================================================================
  * The float32 route of the Vision Transformer graph (vit_fused.py, prepare(torch.float32, linear_dtype="bfloat16x3"), the engines'

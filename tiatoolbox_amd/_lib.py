@@ -172,6 +172,12 @@ _SIGNATURES = {
     "tia_layernorm_rows_q8": ([_P, _I64, _P, _P, C.c_float, _P, _P, _I64, _I64, _I32, _P], C.c_int),
     "tia_gelu_rows_q8": ([_P, _P, _P, _I64, _I64, _I32, _P], C.c_int),
     "tia_swiglu_rows_q8": ([_P, _P, _P, _I64, _I64, _I32, _P], C.c_int),
+    "tia_linear_int8_rows": ([_P, _P, _P, _P, _P, _P, _P, _I64, _I64, _I64, _I32, _P], C.c_int),
+    "tia_linear_int8_pack_weights": ([_P, _I64, _I64, _P, _P, _P], C.c_int),
+    "tia_linear_int8_serves": ([_I64, _I64, _I64], C.c_int),
+    "tia_layernorm_rows_qi8": ([_P, _I64, _P, _P, C.c_float, _P, _P, _I64, _I64, _I32, _P], C.c_int),
+    "tia_gelu_rows_qi8": ([_P, _P, _P, _I64, _I64, _I32, _P], C.c_int),
+    "tia_swiglu_rows_qi8": ([_P, _P, _P, _I64, _I64, _I32, _P], C.c_int),
     "tia_mha_fwd_f32": ([_P, _P, _I64, _I64, _I64, _I64, C.c_float, _I32, _P], C.c_int),
     "tia_gelu_rows_f32": ([_P, _I64, _P], C.c_int),
     "tia_swiglu_rows_f32": ([_P, _P, _I64, _I64, _P], C.c_int),

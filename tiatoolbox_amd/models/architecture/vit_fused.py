@@ -53,6 +53,12 @@ matrix instruction) and steps 1, 5 and 7 on their quantising forms (``tia_layern
 ``tia_swiglu_rows_q8``: codes and one scale per token from the float32 value, no extra pass).  The carrier stays bfloat16; attention,
 ``proj``, the patch embedding and the ends of the graph are unchanged.  :func:`quantize_rows_e4m3` states the recipe; DESIGN 4.34.
 
+``prepare(torch.bfloat16, linear_dtype="int8")`` (the engines' ``compute_dtype="int8"``) routes the same three layers to the INT8 GEMM
+``tia_linear_int8_rows`` (W8A8 on ``v_mfma_i32_16x16x64_i8``, one scale per token and per output channel, exact int32 accumulation)
+and the same three steps to ``tia_layernorm_rows_qi8`` / ``tia_gelu_rows_qi8`` / ``tia_swiglu_rows_qi8``.  A uniform 8-bit grid in
+place of e4m3's 3-bit mantissa: closer than FP8 on rows without extreme outliers, worse with an outlier channel.
+:func:`quantize_rows_int8` states the recipe; DESIGN 4.38.
+
 ``prepare(torch.float32, linear_dtype="bfloat16x3")`` (the engines' ``compute_dtype="bfloat16x3"``) is the float32 route of the same
 graph: activations, residual stream and row arithmetic in float32; every Linear on ``tia_conv2d_bf16x3_nhwc_f32`` (both operands
 split into three bf16 numbers, six exact products per float32 product, float32 accumulation; the weights split once with
@@ -473,7 +479,7 @@ E4M3_MAX = 448.0            # largest finite value of OCP e4m3fn
 
 class QuantRows(NamedTuple):
     """Rows quantised by :func:`quantize_rows_e4m3`'s recipe: ``codes [..., K]`` (e4m3fn bytes as uint8) and ``scales`` (float32, one
-    per row, flat)."""
+    per row, flat) -- or by :func:`quantize_rows_int8`'s, with ``torch.int8`` codes: the dtype of ``codes`` tells the two apart."""
 
     codes: torch.Tensor
     scales: torch.Tensor
@@ -614,6 +620,139 @@ class _LinearFp8:
 
     def __call__(self, a: QuantRows, residual: torch.Tensor | None = None) -> torch.Tensor:
         return hip_linear_fp8_rows(a, self.packed, self.bias32, residual, dtype=self.dtype)
+
+
+INT8_LINEAR = "int8"  # the other quantised `linear_dtype` of `FusedViT.prepare` (and the engines' `compute_dtype` that selects it)
+INT8_MAX = 127.0      # the symmetric code range: -128 is never produced
+
+
+def quantize_rows_int8(v: torch.Tensor) -> tuple[torch.Tensor, torch.Tensor]:
+    """The INT8 route's recipe for one row ``v[..., :]`` of float32 values, in torch operations (the statement the kernels of
+    ``vit_int8.hip`` are tested against): ``amax = max |v|`` (a NaN in the row makes it NaN); ``inv = 127 / amax`` and
+    ``s = amax / 127``, one float32 division each (``amax == 0``: ``inv = s = 1``); ``q = clamp(rne(v * inv), -127, 127)`` with the
+    product in float32 and rounding to nearest even; a NaN product is code 0.  A row holding NaN so gets ``s = NaN``, a row holding
+    ``+-inf`` ``s = inf``, and either way codes inside ``[-127, 127]``.
+    Returns ``(q [..., K] torch.int8, s [...] float32)``; ``q.float() * s[..., None]`` is the dequantised row."""
+    v = v.to(torch.float32)
+    amax = v.abs().amax(dim=-1, keepdim=True)
+    top, one = torch.tensor(INT8_MAX, dtype=torch.float32, device=v.device), torch.ones((), dtype=torch.float32, device=v.device)
+    inv = torch.where(amax == 0, one, top / amax)
+    s = torch.where(amax == 0, one, amax / top)
+    q = torch.round(v * inv)
+    q = torch.where(torch.isnan(q), torch.zeros_like(q), q).clamp(-INT8_MAX, INT8_MAX).to(torch.int8)
+    return q, s.squeeze(-1)
+
+
+def linear_int8_serves(cout: int, cin: int) -> bool:
+    """Whether a ``cin -> cout`` Linear goes to the INT8 GEMM (``tia_linear_int8_serves``, answered on the host)."""
+    from tiatoolbox_amd import _lib
+
+    return _lib.load().tia_linear_int8_serves(1, cout, cin) == 1
+
+
+def pack_linear_weights_int8(weight: torch.Tensor) -> QuantRows:
+    """Float32 ``[cout, cin]`` -> ``tia_linear_int8_rows``'s weight operand: ``torch.int8`` codes ``[cout, cin]`` and one scale per
+    output channel, quantised on the device (``tia_linear_int8_pack_weights``)."""
+    from tiatoolbox_amd import _lib
+
+    w = weight.detach().to(torch.float32).contiguous()
+    if not w.is_cuda or w.dim() != 2:  # noqa: PLR2004
+        msg = f"pack_linear_weights_int8 packs CUDA weights [cout, cin]; got {tuple(w.shape)} on {w.device}."
+        raise ValueError(msg)
+    cout, cin = w.shape
+    codes = torch.empty((cout, cin), dtype=torch.int8, device=w.device)
+    scales = torch.empty((cout,), dtype=torch.float32, device=w.device)
+    with torch.cuda.device(w.device):
+        rc = _lib.load().tia_linear_int8_pack_weights(w.data_ptr(), cout, cin, codes.data_ptr(), scales.data_ptr(), _lib.current_stream())
+    _lib.check(rc, "tia_linear_int8_pack_weights")
+    return QuantRows(codes, scales)
+
+
+def hip_linear_int8_rows(a: QuantRows, w: QuantRows, bias: torch.Tensor | None, residual: torch.Tensor | None = None, *,
+                         dtype: torch.dtype) -> torch.Tensor:
+    """``half_rne(float(acc) * sa * sw + bias (+ residual))`` of quantised tokens ``[n, S, cin]`` and weights ``[cout, cin]``, both
+    ``torch.int8`` codes (the FP8 route's uint8 codes are refused): ``tia_linear_int8_rows`` -> ``[n, S, cout]`` of ``dtype``."""
+    from tiatoolbox_amd import _lib
+
+    if a.codes.dtype != torch.int8 or w.codes.dtype != torch.int8:  # (before anything else: FP8 codes are another number format)
+        msg = (f"hip_linear_int8_rows takes torch.int8 codes (quantize_rows_int8's recipe) for tokens and weights; got {a.codes.dtype} "
+               f"beside {w.codes.dtype}.")
+        raise ValueError(msg)
+    n, s, cin = a.codes.shape
+    cout = w.codes.shape[0]
+    if not (a.codes.is_cuda and a.codes.is_contiguous() and w.codes.shape[1] == cin and a.scales.dtype == torch.float32
+            and a.scales.numel() == n * s and dtype in _HALF and (bias is None or bias.dtype == torch.float32)):
+        msg = (f"hip_linear_int8_rows takes int8 CUDA codes [n, S, cin] with n * S float32 scales, weights [cout, cin] and a float32 bias; "
+               f"got {tuple(a.codes.shape)}, {a.codes.dtype} beside {tuple(w.codes.shape)}, {w.codes.dtype} for {dtype}.")
+        raise ValueError(msg)
+    if residual is not None:
+        _half_tokens("hip_linear_int8_rows (residual)", residual, cout)
+        if residual.dtype != dtype or tuple(residual.shape[:2]) != (n, s):
+            msg = f"hip_linear_int8_rows: residual {tuple(residual.shape)}, {residual.dtype} beside tokens {(n, s, cin)} for {dtype}."
+            raise ValueError(msg)
+    y = torch.empty((n, s, cout), dtype=dtype, device=a.codes.device)
+    with torch.cuda.device(y.device):
+        rc = _lib.load().tia_linear_int8_rows(a.codes.data_ptr(), a.scales.data_ptr(), w.codes.data_ptr(), w.scales.data_ptr(), _ptr(bias),
+                                              _ptr(residual), y.data_ptr(), n * s, cout, cin, _DT[dtype], _lib.current_stream())
+    _lib.check(rc, "tia_linear_int8_rows")
+    return y
+
+
+def hip_layernorm_rows_qi8(x: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, *, eps: float) -> QuantRows:
+    """LayerNorm of every row of ``[n, S, D]`` tokens, quantised to int8 from its float32 values (``tia_layernorm_rows_qi8``)."""
+    from tiatoolbox_amd import _lib
+
+    _half_tokens("hip_layernorm_rows_qi8", x, gamma.numel())
+    if x.dim() != 3 or gamma.dtype != torch.float32 or beta.dtype != torch.float32 or beta.numel() != gamma.numel():  # noqa: PLR2004
+        msg = f"hip_layernorm_rows_qi8 takes [n, S, D] tokens and a float32 affine of D values; got {tuple(x.shape)}, {tuple(gamma.shape)}."
+        raise ValueError(msg)
+    n, s, d = x.shape
+    codes = torch.empty((n, s, d), dtype=torch.int8, device=x.device)
+    scales = torch.empty((n * s,), dtype=torch.float32, device=x.device)
+    with torch.cuda.device(x.device):
+        rc = _lib.load().tia_layernorm_rows_qi8(x.data_ptr(), d, gamma.data_ptr(), beta.data_ptr(), float(eps), codes.data_ptr(),
+                                                scales.data_ptr(), n * s, d, _DT[x.dtype], _lib.current_stream())
+    _lib.check(rc, "tia_layernorm_rows_qi8")
+    return QuantRows(codes, scales)
+
+
+def hip_act_rows_qi8(x: torch.Tensor, *, swiglu: bool) -> QuantRows:
+    """The activation between ``fc1`` and ``fc2`` on ``[n, S, H]`` (exact GELU) or ``[n, S, 2H]`` (packed SwiGLU, the first half the
+    gate) tokens, quantised to int8 from its float32 values: ``[n, S, H]`` codes (``tia_gelu_rows_qi8`` / ``tia_swiglu_rows_qi8``)."""
+    from tiatoolbox_amd import _lib
+
+    _half_tokens("hip_act_rows_qi8", x)
+    if x.dim() != 3 or (swiglu and x.shape[-1] % 2 != 0):  # noqa: PLR2004
+        msg = f"hip_act_rows_qi8 takes [n, S, H] (GELU) or [n, S, 2H] (SwiGLU) tokens; got {tuple(x.shape)}."
+        raise ValueError(msg)
+    n, s, c = x.shape
+    hidden = c // 2 if swiglu else c
+    codes = torch.empty((n, s, hidden), dtype=torch.int8, device=x.device)
+    scales = torch.empty((n * s,), dtype=torch.float32, device=x.device)
+    lib = _lib.load()
+    entry, what = (lib.tia_swiglu_rows_qi8, "tia_swiglu_rows_qi8") if swiglu else (lib.tia_gelu_rows_qi8, "tia_gelu_rows_qi8")
+    with torch.cuda.device(x.device):
+        rc = entry(x.data_ptr(), codes.data_ptr(), scales.data_ptr(), n * s, hidden, _DT[x.dtype], _lib.current_stream())
+    _lib.check(rc, what)
+    return QuantRows(codes, scales)
+
+
+class _LinearInt8:
+    """One GEMM of the graph on the INT8 kernel: weights quantised per output channel in ``prepare`` from the float32 (folded, padded)
+    ones, the float32 bias throughout; called on int8 :class:`QuantRows` from a quantising producer."""
+
+    def __init__(self, name: str, weight: torch.Tensor, bias: torch.Tensor) -> None:
+        self.name, self.weight32, self.bias32 = name, weight, bias
+        self.cout, self.cin = weight.shape
+        self.packed: QuantRows | None = None
+        self.dtype: torch.dtype | None = None
+
+    def prepare(self, dtype: torch.dtype) -> None:
+        self.packed, self.dtype = pack_linear_weights_int8(self.weight32), dtype
+        self.weight32 = None
+
+    def __call__(self, a: QuantRows, residual: torch.Tensor | None = None) -> torch.Tensor:
+        return hip_linear_int8_rows(a, self.packed, self.bias32, residual, dtype=self.dtype)
 
 
 class _Linear:
@@ -894,6 +1033,12 @@ class FusedViT(nn.Module):
         quantising form.  A layer off that kernel's shapes stays on the half kernel (one ``info`` line names them); ``attn.proj``,
         the patch embedding, attention, the residual stream and the final norm are the half graph's, unchanged.
 
+        ``linear_dtype="int8"`` (bfloat16 carrier only) is the same routing on the INT8 GEMM (``tia_linear_int8_rows``: W8A8, one
+        scale per token and per output channel, an exact int32 accumulator; the contract is in ``include/tiatoolbox_amd.h`` and
+        DESIGN 4.38) with the ``_qi8`` producers; its codes are ``torch.int8`` tensors, the FP8 route's ``torch.uint8``, and neither
+        layer takes the other's.  A float16 carrier, a ``residual_dtype`` beside it and a float32 carrier are refused, each with a
+        message of its own, before any device work.
+
         ``residual_dtype="float32"`` keeps the residual stream ``x`` in float32 from token assembly to the final norm, as the float32
         module under ``torch.autocast`` does: ``proj`` and ``fc2`` write half branches without a residual, and one pass
         (``tia_add_layernorm_rows_f32``) adds the branch to ``x`` in float32 and normalises the sum.  ``None`` (the
@@ -915,6 +1060,11 @@ class FusedViT(nn.Module):
             self._route_split()
             self.linear_dtype = SPLIT_LINEAR
             return
+        if linear_dtype == INT8_LINEAR and dtype == torch.float32:  # (the new option's own refusals; the pinned ones follow unchanged)
+            msg = (f"FusedViT.prepare: linear_dtype={INT8_LINEAR!r} quantises the bfloat16 graph's qkv / fc1 / fc2 layers and has no float32 "
+                   f"carrier; call prepare(torch.bfloat16, linear_dtype={INT8_LINEAR!r}), or prepare(torch.float32, "
+                   f"linear_dtype={SPLIT_LINEAR!r}) for the float32 route.")
+            raise ValueError(msg)
         if dtype not in _HALF:
             msg = (f"FusedViT runs in float16 or bfloat16, or in float32 with linear_dtype={SPLIT_LINEAR!r} and nothing else (the float32 "
                    f"route); got {dtype} with linear_dtype={linear_dtype!r}, residual_dtype={residual_dtype!r}.")
@@ -931,11 +1081,22 @@ class FusedViT(nn.Module):
             if residual_dtype != RESIDUAL_F32:
                 msg = f"FusedViT.prepare: residual_dtype is None (the stream in `dtype`) or {RESIDUAL_F32!r}; got {residual_dtype!r}."
                 raise ValueError(msg)
+            if linear_dtype == INT8_LINEAR:
+                msg = (f"FusedViT.prepare: linear_dtype={INT8_LINEAR!r} runs on the bfloat16 residual stream only: there is no "
+                       f"tia_layernorm_rows_qi8 that reads a float32 stream, so residual_dtype={residual_dtype!r} is refused beside it; "
+                       "choose one.")
+                raise ValueError(msg)
             if linear_dtype is not None:
                 msg = (f"FusedViT.prepare: residual_dtype={RESIDUAL_F32!r} beside linear_dtype={linear_dtype!r} needs a float32-input "
                        "quantising LayerNorm (a tia_layernorm_rows_q8 that reads the float32 stream), which does not exist; choose one.")
                 raise ValueError(msg)
-        if linear_dtype is not None:
+        if linear_dtype == INT8_LINEAR:
+            if dtype != torch.bfloat16:
+                msg = (f"FusedViT.prepare: linear_dtype={INT8_LINEAR!r} runs on the bfloat16 carrier only (an fp16 carrier is not built); "
+                       f"got {dtype}.")
+                raise ValueError(msg)
+            self._route_int8()
+        elif linear_dtype is not None:
             if linear_dtype != FP8_LINEAR:
                 msg = f"FusedViT.prepare: linear_dtype is None or {FP8_LINEAR!r}; got {linear_dtype!r}."
                 raise ValueError(msg)
@@ -972,6 +1133,29 @@ class FusedViT(nn.Module):
 
             logging.getLogger("tiatoolbox_amd").info(
                 "FusedViT: the FP8 GEMM takes cin %% 128 == 0 and cout %% 16 == 0; %d layer(s) stay on the half kernel: %s.", len(kept),
+                ", ".join(kept))
+
+    def _route_int8(self) -> None:
+        """``qkv`` / ``fc1`` / ``fc2`` of every block to :class:`_LinearInt8` where ``tia_linear_int8_serves`` takes the shape; the
+        padding of a packed SwiGLU half to the kernel's multiple of 128 is ``_route_fp8``'s."""
+        kept: list[str] = []
+        for layer in self.layers:
+            fc1, fc2 = layer["fc1"], layer["fc2"]
+            target = -(-fc2.cin // 128) * 128
+            if self.swiglu and target != fc2.cin and fc2.cin >= SWIGLU_PAD_FLOOR:
+                fc1_w, fc1_b, fc2_w = pad_swiglu_to(fc1.weight32, fc1.bias32, fc2.weight32, target)
+                layer["fc1"], layer["fc2"] = _Linear(fc1.name, fc1_w, fc1_b), _Linear(fc2.name, fc2_w, fc2.bias32)
+            for name in ("qkv", "fc1", "fc2"):
+                lin = layer[name]
+                if linear_int8_serves(lin.cout, lin.cin):
+                    layer[name] = _LinearInt8(lin.name, lin.weight32, lin.bias32)
+                else:
+                    kept.append(f"{lin.name} ({lin.cin} -> {lin.cout})")
+        if kept:
+            import logging
+
+            logging.getLogger("tiatoolbox_amd").info(
+                "FusedViT: the INT8 GEMM takes cin %% 128 == 0 and cout %% 16 == 0; %d layer(s) stay on the half kernel: %s.", len(kept),
                 ", ".join(kept))
 
     def _route_split(self) -> None:
@@ -1118,9 +1302,11 @@ class FusedViT(nn.Module):
         else:
             x = hip_vit_assemble_tokens_h(tok, self._cls32, pos)
         s = x.shape[1]
-        def norm_for(linear: _Linear | _LinearFp8, norm: tuple[torch.Tensor, torch.Tensor]) -> torch.Tensor | QuantRows:
+        def norm_for(linear: _Linear | _LinearFp8 | _LinearInt8, norm: tuple[torch.Tensor, torch.Tensor]) -> torch.Tensor | QuantRows:
             if isinstance(linear, _LinearFp8):  # the same pass over x, codes + scales out
                 return hip_layernorm_rows_q8(x, *norm, eps=LN_EPS)
+            if isinstance(linear, _LinearInt8):
+                return hip_layernorm_rows_qi8(x, *norm, eps=LN_EPS)
             return hip_layernorm_rows_h(x, *norm, eps=LN_EPS, rows=n * s, row_stride=d).view(n, s, d)
 
         for layer in self.layers:
@@ -1129,6 +1315,8 @@ class FusedViT(nn.Module):
             a = layer["fc1"](norm_for(layer["fc1"], layer["norm2"]))
             if isinstance(layer["fc2"], _LinearFp8):
                 a = hip_act_rows_q8(a, swiglu=self.swiglu)
+            elif isinstance(layer["fc2"], _LinearInt8):
+                a = hip_act_rows_qi8(a, swiglu=self.swiglu)
             else:
                 a = hip_swiglu_rows_h(a) if self.swiglu else hip_gelu_rows_h_(a)
             x = layer["fc2"](a, residual=x)

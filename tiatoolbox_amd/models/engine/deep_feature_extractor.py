@@ -17,9 +17,12 @@ class DeepFeatureExtractor(PatchPredictor):
     """Patch / WSI feature extractor: ``run()`` returns ``{"probabilities": features[, "coordinates"]}``.
 
     The run kwargs are :class:`PatchPredictor`'s.  ``compute_dtype``: "float32" | "float16" | "bfloat16"; for Vision Transformer backbones
-    on a CUDA device also "float8_e4m3" (the bfloat16 graph with the qkv / fc1 / fc2 Linear layers on the FP8 GEMM) and "bfloat16x3"
+    on a CUDA device also "float8_e4m3" (the bfloat16 graph with the qkv / fc1 / fc2 Linear layers on the FP8 GEMM), "int8" (the same
+    layers on the INT8 GEMM: W8A8 with one scale per token and per output channel; closer to float32 than FP8 where the activations
+    have no outlier channel, further where they have one, and unmeasured on real checkpoints: compare "int8", "float8_e4m3" and
+    "bfloat16" on your own; not beside ``residual_dtype``) and "bfloat16x3"
     (the hand-written graph in float32: every Linear on the split-bf16 GEMM, attention on the float32 MFMA kernel -- float32-class
-    features, where "float32" itself keeps the torch module on library GEMMs); both are a ``ValueError`` anywhere else.
+    features, where "float32" itself keeps the torch module on library GEMMs); each is a ``ValueError`` anywhere else.
     ``residual_dtype``: ``None`` | "float32", for the same backbones in "float16" / "bfloat16" (not beside "bfloat16x3", whose stream
     is float32 already)."""
 

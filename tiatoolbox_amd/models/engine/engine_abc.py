@@ -56,17 +56,26 @@ _SPLIT_COVERS = ("compute_dtype=\"bfloat16x3\" covers Vision Transformer models 
                  "without residual_dtype (its residual stream is float32 already)")
 
 
+# compute_dtype="int8": the same graph with the qkv / fc1 / fc2 Linear layers on the INT8 matrix instruction (W8A8, one scale per token
+# and per output channel, exact int32 accumulation; architecture/vit_fused.py).  An option of the GRAPH on the bfloat16
+# carrier, with FP8_COMPUTE's rule: what it does not cover is refused, never run in another precision.
+INT8_COMPUTE = "int8"
+_INT8_COVERS = ("compute_dtype=\"int8\" covers Vision Transformer models that FusedViT accepts (TimmBackbone / TimmModel: the qkv, fc1 "
+                "and fc2 Linear layers on the INT8 GEMM, everything else in bfloat16) on a CUDA device, without residual_dtype (there is "
+                "no float32-input quantising LayerNorm)")
+
+
 def _compute_name(compute_dtype) -> str:
     return str(compute_dtype).replace("torch.", "")
 
 
 def _carrier_dtype(compute_dtype) -> torch.dtype:
-    """The dtype of the activations (and of the cast model copy) for a ``compute_dtype``: bfloat16 under ``"float8_e4m3"``, float32
-    under ``"bfloat16x3"``."""
+    """The dtype of the activations (and of the cast model copy) for a ``compute_dtype``: bfloat16 under ``"float8_e4m3"`` and ``"int8"``,
+    float32 under ``"bfloat16x3"``."""
     name = _compute_name(compute_dtype)
     if name == SPLIT_COMPUTE:
         return torch.float32
-    return torch.bfloat16 if name == FP8_COMPUTE else _DTYPES[name]
+    return torch.bfloat16 if name in (FP8_COMPUTE, INT8_COMPUTE) else _DTYPES[name]
 
 
 def _clear_last_hip_error() -> int:
@@ -476,6 +485,16 @@ class EngineABC:
         fp8 = _compute_name(self.compute_dtype) == FP8_COMPUTE
         resid = getattr(self, "residual_dtype", None)
         split = _compute_name(self.compute_dtype) == SPLIT_COMPUTE
+        int8 = _compute_name(self.compute_dtype) == INT8_COMPUTE
+        if int8:  # the rule of the FP8 option: what this one does not cover is refused, never run in another precision
+            from tiatoolbox_amd.models.architecture.vit import VisionTransformer as _ViT
+
+            if (torch.device(self.device).type != "cuda" or not isinstance(getattr(self.model, "feat_extract", None), _ViT)
+                    or resid is not None):
+                self.compute_dtype, self.residual_dtype = "float32", None  # (run kwargs persist: the rejected values are not left behind)
+                msg = f"{_INT8_COVERS}; got {type(self.model).__name__} on {self.device} with residual_dtype={resid!r}."
+                raise ValueError(msg)
+            dtype = torch.bfloat16
         if split:  # the rule of the FP8 option: what this one does not cover is refused, never run in another precision
             from tiatoolbox_amd.models.architecture.vit import VisionTransformer as _ViT
 
@@ -505,7 +524,7 @@ class EngineABC:
         if dtype == torch.float32 and torch.device(self.device).type != "cuda":
             return self.model
         key = (dtype, str(self.device), id(self.model), self.fold_batchnorm, _weights_version(self.model), algo,
-               SPLIT_COMPUTE if split else fp8, resid)
+               SPLIT_COMPUTE if split else (INT8_COMPUTE if int8 else fp8), resid)
         if self._fast_key != key:
             import copy
 
@@ -534,6 +553,10 @@ class EngineABC:
                         else:
                             m.feat_extract = FusedViT(m.feat_extract)
                     except UnsupportedLayerError as exc:  # (the constructor's own refusal; any other error is a bug and propagates)
+                        if int8:
+                            self.compute_dtype, self.residual_dtype = "float32", None
+                            msg = f"{_INT8_COVERS}; {type(self.model).__name__}: {exc}"
+                            raise ValueError(msg) from exc
                         if fp8 or split:
                             self.compute_dtype = "float32"
                             msg = f"{_SPLIT_COVERS if split else _FP8_COVERS}; {type(self.model).__name__}: {exc}"
@@ -612,7 +635,9 @@ class EngineABC:
                     elif split and type(mod).__name__ == "FusedViT":
                         mod.prepare(torch.float32, linear_dtype=SPLIT_COMPUTE)  # three bf16 planes per Linear; float32 everywhere else
                     elif type(mod).__name__ in ("FusedUNet", "FusedPlainUNet", "FusedHoVerNet", "FusedViT") and dtype != torch.float32:
-                        if fp8 and type(mod).__name__ == "FusedViT":
+                        if int8 and type(mod).__name__ == "FusedViT":
+                            mod.prepare(dtype, linear_dtype=INT8_COMPUTE)  # qkv / fc1 / fc2 as W8A8 int8, per token x per output channel
+                        elif fp8 and type(mod).__name__ == "FusedViT":
                             mod.prepare(dtype, linear_dtype=FP8_COMPUTE)  # qkv / fc1 / fc2 quantised per output channel as well
                         elif resid is not None and type(mod).__name__ == "FusedViT":
                             mod.prepare(dtype, residual_dtype=resid)  # the float32 residual stream (architecture/vit_fused.py)

@@ -16,7 +16,9 @@ class PatchPredictor(EngineABC):
     """Patch-level prediction: ``probabilities`` (optional) + ``predictions`` (ref. :88-679).
 
     Extra run-time kwargs on MI355X: ``compute_dtype`` ("float32" | "float16" | "bfloat16"; for Vision Transformer models on a CUDA
-    device also "float8_e4m3": the bfloat16 graph with the qkv / fc1 / fc2 Linear layers on the FP8 GEMM, and "bfloat16x3": the same
+    device also "float8_e4m3": the bfloat16 graph with the qkv / fc1 / fc2 Linear layers on the FP8 GEMM, "int8": the same layers on the
+    INT8 GEMM (W8A8, one scale per token and per output channel; closer than FP8 on activations without outlier channels, worse with
+    one -- compare both with "bfloat16" on your own checkpoint; not beside ``residual_dtype``), and "bfloat16x3": the same
     graph in float32 with every Linear on the split-bf16 GEMM and attention on the float32 MFMA kernel; a ``ValueError`` elsewhere),
     ``residual_dtype`` (``None`` | "float32": Vision Transformer models on a CUDA device in "float16" / "bfloat16" keep their residual
     stream in float32, as the float32 module under ``torch.autocast`` does; a ``ValueError`` elsewhere) and ``stain_normalizer`` (a fitted :class:`~tiatoolbox_amd.tools.stainnorm.StainNormalizer`; shorthand

@@ -1,13 +1,14 @@
 """Compare the gfx950 device code of HIP sources between two git revisions.
 
-    python scripts/isa_compare.py PARENT HEAD conv_mfma.hip conv_mfma_h.hip ... [--out report.txt]
+    python scripts/isa_compare.py PARENT HEAD conv_mfma.hip conv_mfma_h.hip ... [--alias OLD=NEW ...] [--out report.txt]
 
 For each revision ``tiatoolbox_amd/csrc`` and ``include`` are extracted into a temporary directory (``HEAD`` may be the word
 ``WORKTREE``: the files as they are on disk), every listed file is compiled with ``build.HIPCC_FLAGS`` plus
 ``--cuda-device-only -S``, and per kernel the report says whether the instruction stream is the same -- labels renumbered in
 order of appearance, comments and assembler directives dropped -- and prints the register, spill, LDS, scratch and kernarg
-figures of the code object's metadata.  Kernels are matched by their demangled signature without namespaces.  A kernel that
-differs gets its per-mnemonic instruction counts compared and the extent of the differing lines printed, as they are and with
+figures of the code object's metadata.  Kernels are matched by their demangled signature without namespaces; ``--alias OLD=NEW``
+(repeatable) replaces the substring ``OLD`` by ``NEW`` in the parent's signatures first, for kernels that the head renames.  A kernel
+that differs gets its per-mnemonic instruction counts compared and the extent of the differing lines printed, as they are and with
 register numbers masked (what is left then is reordering and real instruction changes).  The comparison is generic: no
 instruction is looked for in particular.
 """
@@ -16,6 +17,7 @@ from __future__ import annotations
 
 import argparse
 import difflib
+import functools
 import re
 import shutil
 import subprocess
@@ -131,8 +133,11 @@ def main() -> int:
     ap.add_argument("files", nargs="+", help="names of .hip files in tiatoolbox_amd/csrc")
     ap.add_argument("--variant", action="append", default=[], metavar="FILE:DEFINE",
                     help="also compile FILE of the head with -DDEFINE (developer builds: compile only)")
+    ap.add_argument("--alias", action="append", default=[], metavar="OLD=NEW",
+                    help="replace the substring OLD by NEW in the parent's demangled signatures before matching (renamed kernels)")
     ap.add_argument("--out", type=Path)
     args = ap.parse_args()
+    aliases = [a.split("=", 1) for a in args.alias]
     report: list[str] = []
     differences = 0
     with tempfile.TemporaryDirectory() as tmp:
@@ -148,10 +153,13 @@ def main() -> int:
             ok = list(pool.map(lambda v: bool(compile_asm(trees["head"], v[0], (v[1],))), variants))
     report.append(f"device code, {args.parent} (parent) against {args.head} (head)")
     report.append("flags: " + " ".join([*HIPCC_FLAGS, *EXTRA]))
+    report += [f"alias: {old} -> {new}" for old, new in aliases]
     for f in args.files:
         (ps, pm, pother), (hs, hm, hother) = parse(asms[("parent", f)]), parse(asms[("head", f)])
         names = demangle(sorted(set(ps) | set(hs)))
-        ps, pm, hs, hm = ({names[k]: v for k, v in d.items()} for d in (ps, pm, hs, hm))
+        renamed = {k: functools.reduce(lambda n, a: n.replace(*a), aliases, names[k]) for k in ps}
+        ps, pm = ({renamed[k]: v for k, v in d.items()} for d in (ps, pm))
+        hs, hm = ({names[k]: v for k, v in d.items()} for d in (hs, hm))
         report.append("")
         report.append(f"{f}: {len(ps)} kernels at the parent, {len(hs)} at the head; other device functions: {pother} / {hother}")
         for sym in sorted(set(ps) | set(hs)):

@@ -85,11 +85,11 @@ def test_fp8_forward_launches_the_fp8_kernels_and_no_library():
         swiglu(x14)
         kernels = _device_kernels(lambda: fused(x))
         kernels_swiglu = _device_kernels(lambda: swiglu(x14))
-    for wanted in ("linear_fp8_rows_kernel", "layernorm_rows_q8_kernel", "act_rows_q8_kernel", "mha_fwd_h_kernel", "conv_mfma_h"):
+    for wanted in ("linear_rows_kernel<tia::q8::E4m3", "layernorm_rows_kernel<tia::q8::E4m3", "act_rows_kernel<tia::q8::E4m3", "mha_fwd_h_kernel", "conv_mfma_h"):
         assert any(wanted in k for k in kernels), (wanted, kernels)
         assert any(wanted in k for k in kernels_swiglu), (wanted, kernels_swiglu)
     # the GELU and the SwiGLU form of the activation producer are two instantiations of one kernel template
-    assert {k for k in kernels if "act_rows_q8_kernel" in k} != {k for k in kernels_swiglu if "act_rows_q8_kernel" in k}
+    assert {k for k in kernels if "act_rows_kernel<tia::q8::E4m3" in k} != {k for k in kernels_swiglu if "act_rows_kernel<tia::q8::E4m3" in k}
     for ks in (kernels, kernels_swiglu):  # every FP8 layer's producer is the quantising one: no half LayerNorm / activation pass
         assert not {k for k in ks if "gelu_rows_h_kernel" in k or "swiglu_rows_h_kernel" in k}, ks
         assert not {k for k in ks if _banned(k)}, ks
@@ -114,8 +114,8 @@ def test_a_layer_off_the_fp8_shapes_stays_on_the_half_kernel(caplog):
     x = torch.randn((2, 3, 32, 32), generator=torch.Generator().manual_seed(2))
     with torch.inference_mode():
         kernels = _device_kernels(lambda: fused(x.cuda().to(BF16)))
-    assert any("gelu_rows_h_kernel" in k for k in kernels) and not any("act_rows_q8_kernel" in k for k in kernels), kernels
-    assert any("linear_fp8_rows_kernel" in k for k in kernels) and any("layernorm_rows_q8_kernel" in k for k in kernels), kernels
+    assert any("gelu_rows_h_kernel" in k for k in kernels) and not any("act_rows_kernel<tia::q8::E4m3" in k for k in kernels), kernels
+    assert any("linear_rows_kernel<tia::q8::E4m3" in k for k in kernels) and any("layernorm_rows_kernel<tia::q8::E4m3" in k for k in kernels), kernels
     # the yardstick for this model quantises what the graph quantises: qkv and fc1 only
     with torch.inference_mode():
         ref = vit(x)
@@ -214,7 +214,7 @@ def test_patch_predictor_runs_a_timm_model_in_fp8(caplog):
     _rule(out["probabilities"], yard, ref, "PatchPredictor TimmModel vit_small float8_e4m3")
     assert float(np.abs(out["probabilities"].sum(-1) - 1).max()) <= 1e-6
     kernels = _device_kernels(lambda: eng.infer_patches(eng.dataloader))
-    for wanted in ("vit_patchify_norm_u8_h_kernel", "linear_fp8_rows_kernel", "layernorm_rows_q8_kernel", "act_rows_q8_kernel",
+    for wanted in ("vit_patchify_norm_u8_h_kernel", "linear_rows_kernel<tia::q8::E4m3", "layernorm_rows_kernel<tia::q8::E4m3", "act_rows_kernel<tia::q8::E4m3",
                    "linear_softmax_rows_f32_kernel"):
         assert any(wanted in k for k in kernels), (wanted, kernels)
     assert not {k for k in kernels if _banned(k)}, kernels

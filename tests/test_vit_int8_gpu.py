@@ -110,12 +110,12 @@ def test_int8_forward_launches_the_int8_kernels_and_no_library():
         swiglu(x14)
         kernels = _device_kernels(lambda: fused(x))
         kernels_swiglu = _device_kernels(lambda: swiglu(x14))
-    for wanted in ("linear_int8_rows_kernel", "layernorm_rows_qi8_kernel", "act_rows_qi8_kernel", "mha_fwd_h_kernel", "conv_mfma_h"):
+    for wanted in ("linear_rows_kernel<tia::q8::Int8", "layernorm_rows_kernel<tia::q8::Int8", "act_rows_kernel<tia::q8::Int8", "mha_fwd_h_kernel", "conv_mfma_h"):
         assert any(wanted in k for k in kernels), (wanted, kernels)
         assert any(wanted in k for k in kernels_swiglu), (wanted, kernels_swiglu)
-    assert {k for k in kernels if "act_rows_qi8_kernel" in k} != {k for k in kernels_swiglu if "act_rows_qi8_kernel" in k}
+    assert {k for k in kernels if "act_rows_kernel<tia::q8::Int8" in k} != {k for k in kernels_swiglu if "act_rows_kernel<tia::q8::Int8" in k}
     for ks in (kernels, kernels_swiglu):  # every INT8 layer's producer is the quantising one; nothing of the FP8 route runs
-        assert not {k for k in ks if "gelu_rows_h_kernel" in k or "swiglu_rows_h_kernel" in k or "fp8" in k or "_q8_kernel" in k}, ks
+        assert not {k for k in ks if "gelu_rows_h_kernel" in k or "swiglu_rows_h_kernel" in k or "fp8" in k or "tia::q8::E4m3" in k}, ks
         assert not {k for k in ks if _banned(k)}, ks
 
 
@@ -135,8 +135,8 @@ def test_a_layer_off_the_int8_shapes_stays_on_the_half_kernel(caplog):
     x = torch.randn((2, 3, 32, 32), generator=torch.Generator().manual_seed(2))
     with torch.inference_mode():
         kernels = _device_kernels(lambda: fused(x.cuda().to(BF16)))
-    assert any("gelu_rows_h_kernel" in k for k in kernels) and not any("act_rows_qi8_kernel" in k for k in kernels), kernels
-    assert any("linear_int8_rows_kernel" in k for k in kernels) and any("layernorm_rows_qi8_kernel" in k for k in kernels), kernels
+    assert any("gelu_rows_h_kernel" in k for k in kernels) and not any("act_rows_kernel<tia::q8::Int8" in k for k in kernels), kernels
+    assert any("linear_rows_kernel<tia::q8::Int8" in k for k in kernels) and any("layernorm_rows_kernel<tia::q8::Int8" in k for k in kernels), kernels
     _parity_int8(vit, x, "mlp_dim 576 (fc2 on the half kernel)", layers=("qkv", "fc1"))  # the yardstick quantises what the graph does
 
 
@@ -186,7 +186,7 @@ def test_feature_extractor_runs_int8_from_uint8_patches(caplog):
         yard = fake_quantised_module(copy.deepcopy(cpu.model).cuda())(x).float().cpu().numpy()
     _rule(got, yard, ref, "DeepFeatureExtractor vit_small int8")
     kernels = _device_kernels(lambda: eng.infer_patches(eng.dataloader))
-    for wanted in ("vit_patchify_norm_u8_h_kernel", "linear_int8_rows_kernel", "layernorm_rows_qi8_kernel", "act_rows_qi8_kernel"):
+    for wanted in ("vit_patchify_norm_u8_h_kernel", "linear_rows_kernel<tia::q8::Int8", "layernorm_rows_kernel<tia::q8::Int8", "act_rows_kernel<tia::q8::Int8"):
         assert any(wanted in k for k in kernels), (wanted, kernels)
     assert not {k for k in kernels if _banned(k)}, kernels
     # the cache tells the option from FP8 and from plain bfloat16: other copies, and back again to the same bits
@@ -231,7 +231,7 @@ def test_patch_predictor_runs_a_timm_model_in_int8(caplog):
     _rule(out["probabilities"], yard, ref, "PatchPredictor TimmModel vit_small int8")
     assert float(np.abs(out["probabilities"].sum(-1) - 1).max()) <= 1e-6
     kernels = _device_kernels(lambda: eng.infer_patches(eng.dataloader))
-    for wanted in ("vit_patchify_norm_u8_h_kernel", "linear_int8_rows_kernel", "layernorm_rows_qi8_kernel", "act_rows_qi8_kernel",
+    for wanted in ("vit_patchify_norm_u8_h_kernel", "linear_rows_kernel<tia::q8::Int8", "layernorm_rows_kernel<tia::q8::Int8", "act_rows_kernel<tia::q8::Int8",
                    "linear_softmax_rows_f32_kernel"):
         assert any(wanted in k for k in kernels), (wanted, kernels)
     assert not {k for k in kernels if _banned(k)}, kernels

@@ -9,6 +9,7 @@
 // access (8 halves), float32 arithmetic with every step rounded on its own (contraction off: the order of the unfused torch
 // ops), ONE round-to-nearest-even to half at the end, 64-bit element offsets (a tensor may exceed 2^31 bytes).
 #include "conv_device.hpp"
+#include "half_rows.hpp"
 #include "stream_glue.hpp"
 #include "wide_io.hpp"
 
@@ -19,25 +20,6 @@ namespace {
 using namespace tia;
 
 constexpr int ET = 256;
-
-template <bool BF>
-__device__ __forceinline__ void unpack8(const v4u& v, float (&f)[8]) {
-    const unsigned w[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        f[2 * i] = half_to_f32<BF>((unsigned short)(w[i] & 0xffffu));
-        f[2 * i + 1] = half_to_f32<BF>((unsigned short)(w[i] >> 16));
-    }
-}
-template <bool BF>
-__device__ __forceinline__ v4u pack8(const float (&f)[8]) {
-    unsigned w[4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) w[i] = (unsigned)f32_to_half<BF>(f[2 * i]) | ((unsigned)f32_to_half<BF>(f[2 * i + 1]) << 16);
-    v4u v;
-    v.x = w[0], v.y = w[1], v.z = w[2], v.w = w[3];
-    return v;
-}
 
 // the 16-byte vector of 8 halves as stream_glue.hpp's kernels take it
 template <bool BF>

@@ -3,6 +3,7 @@
 //                          (ToTensor + Normalize(mean, std), worked out once on the host) -- a gather, no arithmetic
 //   linear_softmax_rows  : p[r, :] = softmax(x[r, :f] . W^T + b) on the graph's float32 features, float32 throughout
 // 64-bit element offsets; nothing here depends on the grid, so a row's (a patch's) result is the same in any batch.
+#include "half_rows.hpp"
 #include "wide_io.hpp"
 
 namespace {
@@ -77,17 +78,6 @@ __global__ __launch_bounds__(ET) void vit_patchify_norm_u8_h_kernel(const unsign
         o.w = (unsigned)hv[6] | ((unsigned)hv[7] << 16);
         out[i] = o;
     }
-}
-
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);
-    return v;
-}
-__device__ __forceinline__ float wave_max(float v) {
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) v = fmaxf(v, __shfl_xor(v, m, 64));
-    return v;
 }
 
 // One wave per row, four rows per workgroup, no LDS.  Four classes at a time: lane l multiplies the 16-byte vectors l, l + 64, ... of

@@ -56,6 +56,7 @@
 // p = exp2(-inf) = 0 exactly, and since every tile the loop visits holds at least one real key (k0 < s) the new maximum is finite from
 // the first tile on: m_old - m_new is -inf - finite there, never inf - inf.  Query rows >= s compute on zeros and are not stored.
 #include "conv_device.hpp"
+#include "half_rows.hpp"
 #include "wide_io.hpp"
 
 namespace {
@@ -202,14 +203,6 @@ __global__ __launch_bounds__(AT) void mha_fwd_f32_kernel(const float* __restrict
 __device__ __forceinline__ float gelu_f32(float x) {
     const float t = x * 0.70710678118654752440f;
     return x >= 0.0f ? 0.5f * x * (1.0f + erff(t)) : 0.5f * x * erfcf(-t);
-}
-
-// silu(t) = t / (1 + exp(-t)) through e = exp(-|t|) in (0, 1]: silu_f32 of vit_rows.hip, operation for operation (no exponential
-// overflows: a gate of -100 gives the tiny value it should or a signed zero, never inf / inf).
-__device__ __forceinline__ float silu_f32(float t) {
-    const float e = expf(-fabsf(t));
-    const float num = t >= 0.0f ? t : t * e;
-    return num / (1.0f + e);
 }
 
 __global__ __launch_bounds__(ET) void gelu_rows_f32_kernel(f32x4* __restrict__ x, long vectors) {

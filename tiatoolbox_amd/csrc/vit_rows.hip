@@ -11,6 +11,7 @@
 //   cls_mean_pool    : out[b] = cat(LN(x[b, 0]), mean_{i >= skip} LN(x[b, i]))     float32 out, one workgroup per image
 // 16 bytes per lane and access (8 halves), float32 arithmetic, ONE round-to-nearest-even on the way out, 64-bit element offsets.
 #include "conv_device.hpp"
+#include "half_rows.hpp"
 #include "wide_io.hpp"
 
 namespace {
@@ -18,35 +19,6 @@ namespace {
 using namespace tia;
 
 constexpr int ET = 256;
-
-template <bool BF>
-__device__ __forceinline__ void unpack8(const v4u& v, float (&f)[8]) {
-    const unsigned w[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        f[2 * i] = half_to_f32<BF>((unsigned short)(w[i] & 0xffffu));
-        f[2 * i + 1] = half_to_f32<BF>((unsigned short)(w[i] >> 16));
-    }
-}
-template <bool BF>
-__device__ __forceinline__ v4u pack8(const float (&f)[8]) {
-    v4u v;
-    v.x = (unsigned)f32_to_half<BF>(f[0]) | ((unsigned)f32_to_half<BF>(f[1]) << 16);
-    v.y = (unsigned)f32_to_half<BF>(f[2]) | ((unsigned)f32_to_half<BF>(f[3]) << 16);
-    v.z = (unsigned)f32_to_half<BF>(f[4]) | ((unsigned)f32_to_half<BF>(f[5]) << 16);
-    v.w = (unsigned)f32_to_half<BF>(f[6]) | ((unsigned)f32_to_half<BF>(f[7]) << 16);
-    return v;
-}
-__device__ __forceinline__ void load8_f32(const float* p, float (&f)[8]) {
-    const float4 a = *reinterpret_cast<const float4*>(p), b = *reinterpret_cast<const float4*>(p + 4);
-    f[0] = a.x, f[1] = a.y, f[2] = a.z, f[3] = a.w, f[4] = b.x, f[5] = b.y, f[6] = b.z, f[7] = b.w;
-}
-
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);
-    return v;
-}
 
 // One wave per row, the row in registers (VPL 16-byte vectors per lane, c <= 512 VPL): one read of x, the mean, then the variance
 // of the CENTRED values (not E[x^2] - mean^2, which cancels for rows with a large mean), both folded over the wave by lane
@@ -156,15 +128,6 @@ __global__ __launch_bounds__(ET) void vit_assemble_tokens_h_kernel(const v4u* __
         for (int k = 0; k < 8; ++k) a[k] += ps[k];
         out[i] = pack8<BF>(a);
     }
-}
-
-// silu(t) = t / (1 + exp(-t)), written so that no exponential overflows: with e = exp(-|t|) in (0, 1] it is t / (1 + e) for t >= 0
-// and t e / (1 + e) for t < 0 -- a gate of -100 gives the tiny value it should (or a signed zero), never inf / inf.  expf and the
-// division are the correctly rounded ones (no fast-math): a few float32 units in all.
-__device__ __forceinline__ float silu_f32(float t) {
-    const float e = expf(-fabsf(t));
-    const float num = t >= 0.0f ? t : t * e;
-    return num / (1.0f + e);
 }
 
 // One thread per 8 outputs: the gate vector at [r, 8 j] and the value vector at [r, H + 8 j], both 16-byte loads (H % 8 == 0 makes

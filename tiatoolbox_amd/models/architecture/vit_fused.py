@@ -500,95 +500,159 @@ def quantize_rows_e4m3(v: torch.Tensor) -> tuple[torch.Tensor, torch.Tensor]:
     return q, s.squeeze(-1)
 
 
-def linear_fp8_serves(cout: int, cin: int) -> bool:
-    """Whether a ``cin -> cout`` Linear goes to the FP8 GEMM (``tia_linear_fp8_serves``, answered on the host)."""
+class _QuantFormat(NamedTuple):
+    """One 8-bit format of the quantised linear layers: its name in messages, the dtype of its codes, its ``linear_dtype`` and the
+    module-level names of its five wrappers.  The wrappers' messages carry these names, and the graph finds a wrapper through ``fn``
+    when it calls it: by its name in this module, so that a replaced module attribute is what runs."""
+
+    name: str
+    codes: torch.dtype
+    linear_dtype: str
+    serves: str
+    pack: str
+    linear: str
+    layernorm: str
+    act: str
+
+    def fn(self, which: str):  # noqa: ANN201
+        return globals()[getattr(self, which)]
+
+
+def _linear_serves(entry: str, cout: int, cin: int) -> bool:
     from tiatoolbox_amd import _lib
 
-    return _lib.load().tia_linear_fp8_serves(1, cout, cin) == 1
+    return getattr(_lib.load(), entry)(1, cout, cin) == 1
+
+
+def _pack_linear_weights(fmt: _QuantFormat, entry: str, weight: torch.Tensor) -> QuantRows:
+    from tiatoolbox_amd import _lib
+
+    w = weight.detach().to(torch.float32).contiguous()
+    if not w.is_cuda or w.dim() != 2:  # noqa: PLR2004
+        msg = f"{fmt.pack} packs CUDA weights [cout, cin]; got {tuple(w.shape)} on {w.device}."
+        raise ValueError(msg)
+    cout, cin = w.shape
+    codes = torch.empty((cout, cin), dtype=fmt.codes, device=w.device)
+    scales = torch.empty((cout,), dtype=torch.float32, device=w.device)
+    with torch.cuda.device(w.device):
+        rc = getattr(_lib.load(), entry)(w.data_ptr(), cout, cin, codes.data_ptr(), scales.data_ptr(), _lib.current_stream())
+    _lib.check(rc, entry)
+    return QuantRows(codes, scales)
+
+
+def _linear_quant_rows(fmt: _QuantFormat, entry: str, a: QuantRows, w: QuantRows, bias: torch.Tensor | None,
+                       residual: torch.Tensor | None, dtype: torch.dtype) -> torch.Tensor:
+    from tiatoolbox_amd import _lib
+
+    n, s, cin = a.codes.shape
+    cout = w.codes.shape[0]
+    if not (a.codes.is_cuda and a.codes.dtype == fmt.codes and a.codes.is_contiguous() and w.codes.dtype == fmt.codes
+            and w.codes.shape[1] == cin and a.scales.dtype == torch.float32 and a.scales.numel() == n * s and dtype in _HALF
+            and (bias is None or bias.dtype == torch.float32)):
+        msg = (f"{fmt.linear} takes {str(fmt.codes).removeprefix('torch.')} CUDA codes [n, S, cin] with n * S float32 scales, weights "
+               f"[cout, cin] and a float32 bias; "
+               f"got {tuple(a.codes.shape)}, {a.codes.dtype} beside {tuple(w.codes.shape)}, {w.codes.dtype} for {dtype}.")
+        raise ValueError(msg)
+    if residual is not None:
+        _half_tokens(f"{fmt.linear} (residual)", residual, cout)
+        if residual.dtype != dtype or tuple(residual.shape[:2]) != (n, s):
+            msg = f"{fmt.linear}: residual {tuple(residual.shape)}, {residual.dtype} beside tokens {(n, s, cin)} for {dtype}."
+            raise ValueError(msg)
+    y = torch.empty((n, s, cout), dtype=dtype, device=a.codes.device)
+    with torch.cuda.device(y.device):
+        rc = getattr(_lib.load(), entry)(a.codes.data_ptr(), a.scales.data_ptr(), w.codes.data_ptr(), w.scales.data_ptr(), _ptr(bias),
+                                         _ptr(residual), y.data_ptr(), n * s, cout, cin, _DT[dtype], _lib.current_stream())
+    _lib.check(rc, entry)
+    return y
+
+
+def _layernorm_quant_rows(fmt: _QuantFormat, entry: str, x: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, eps: float) -> QuantRows:
+    from tiatoolbox_amd import _lib
+
+    _half_tokens(fmt.layernorm, x, gamma.numel())
+    if x.dim() != 3 or gamma.dtype != torch.float32 or beta.dtype != torch.float32 or beta.numel() != gamma.numel():  # noqa: PLR2004
+        msg = f"{fmt.layernorm} takes [n, S, D] tokens and a float32 affine of D values; got {tuple(x.shape)}, {tuple(gamma.shape)}."
+        raise ValueError(msg)
+    n, s, d = x.shape
+    codes = torch.empty((n, s, d), dtype=fmt.codes, device=x.device)
+    scales = torch.empty((n * s,), dtype=torch.float32, device=x.device)
+    with torch.cuda.device(x.device):
+        rc = getattr(_lib.load(), entry)(x.data_ptr(), d, gamma.data_ptr(), beta.data_ptr(), float(eps), codes.data_ptr(),
+                                         scales.data_ptr(), n * s, d, _DT[x.dtype], _lib.current_stream())
+    _lib.check(rc, entry)
+    return QuantRows(codes, scales)
+
+
+def _act_quant_rows(fmt: _QuantFormat, gelu_entry: str, swiglu_entry: str, x: torch.Tensor, swiglu: bool) -> QuantRows:  # noqa: FBT001
+    from tiatoolbox_amd import _lib
+
+    _half_tokens(fmt.act, x)
+    if x.dim() != 3 or (swiglu and x.shape[-1] % 2 != 0):  # noqa: PLR2004
+        msg = f"{fmt.act} takes [n, S, H] (GELU) or [n, S, 2H] (SwiGLU) tokens; got {tuple(x.shape)}."
+        raise ValueError(msg)
+    n, s, c = x.shape
+    hidden = c // 2 if swiglu else c
+    codes = torch.empty((n, s, hidden), dtype=fmt.codes, device=x.device)
+    scales = torch.empty((n * s,), dtype=torch.float32, device=x.device)
+    entry = swiglu_entry if swiglu else gelu_entry
+    launch = getattr(_lib.load(), entry)
+    with torch.cuda.device(x.device):
+        rc = launch(x.data_ptr(), codes.data_ptr(), scales.data_ptr(), n * s, hidden, _DT[x.dtype], _lib.current_stream())
+    _lib.check(rc, entry)
+    return QuantRows(codes, scales)
+
+
+class _LinearQuant:
+    """One GEMM of the graph on a quantised kernel of format ``fmt``: weights quantised per output channel in ``prepare`` from the
+    float32 (folded, padded) ones, the float32 bias throughout; called on :class:`QuantRows` from a quantising producer."""
+
+    fmt: _QuantFormat
+
+    def __init__(self, name: str, weight: torch.Tensor, bias: torch.Tensor) -> None:
+        self.name, self.weight32, self.bias32 = name, weight, bias
+        self.cout, self.cin = weight.shape
+        self.packed: QuantRows | None = None
+        self.dtype: torch.dtype | None = None
+
+    def prepare(self, dtype: torch.dtype) -> None:
+        self.packed, self.dtype = self.fmt.fn("pack")(self.weight32), dtype
+        self.weight32 = None
+
+    def __call__(self, a: QuantRows, residual: torch.Tensor | None = None) -> torch.Tensor:
+        return self.fmt.fn("linear")(a, self.packed, self.bias32, residual, dtype=self.dtype)
+
+
+_FP8 = _QuantFormat("FP8", torch.uint8, FP8_LINEAR, "linear_fp8_serves", "pack_linear_weights_fp8", "hip_linear_fp8_rows",
+                    "hip_layernorm_rows_q8", "hip_act_rows_q8")
+
+
+def linear_fp8_serves(cout: int, cin: int) -> bool:
+    """Whether a ``cin -> cout`` Linear goes to the FP8 GEMM (``tia_linear_fp8_serves``, answered on the host)."""
+    return _linear_serves("tia_linear_fp8_serves", cout, cin)
 
 
 def pack_linear_weights_fp8(weight: torch.Tensor) -> QuantRows:
     """Float32 ``[cout, cin]`` -> ``tia_linear_fp8_rows``'s weight operand: codes ``[cout, cin]`` and one scale per output channel,
     quantised on the device (``tia_linear_fp8_pack_weights``)."""
-    from tiatoolbox_amd import _lib
-
-    w = weight.detach().to(torch.float32).contiguous()
-    if not w.is_cuda or w.dim() != 2:  # noqa: PLR2004
-        msg = f"pack_linear_weights_fp8 packs CUDA weights [cout, cin]; got {tuple(w.shape)} on {w.device}."
-        raise ValueError(msg)
-    cout, cin = w.shape
-    codes = torch.empty((cout, cin), dtype=torch.uint8, device=w.device)
-    scales = torch.empty((cout,), dtype=torch.float32, device=w.device)
-    with torch.cuda.device(w.device):
-        rc = _lib.load().tia_linear_fp8_pack_weights(w.data_ptr(), cout, cin, codes.data_ptr(), scales.data_ptr(), _lib.current_stream())
-    _lib.check(rc, "tia_linear_fp8_pack_weights")
-    return QuantRows(codes, scales)
+    return _pack_linear_weights(_FP8, "tia_linear_fp8_pack_weights", weight)
 
 
 def hip_linear_fp8_rows(a: QuantRows, w: QuantRows, bias: torch.Tensor | None, residual: torch.Tensor | None = None, *,
                         dtype: torch.dtype) -> torch.Tensor:
     """``half_rne(acc * sa * sw + bias (+ residual))`` of quantised tokens ``[n, S, cin]`` and weights ``[cout, cin]``:
     ``tia_linear_fp8_rows`` -> ``[n, S, cout]`` of ``dtype``."""
-    from tiatoolbox_amd import _lib
-
-    n, s, cin = a.codes.shape
-    cout = w.codes.shape[0]
-    if not (a.codes.is_cuda and a.codes.dtype == torch.uint8 and a.codes.is_contiguous() and w.codes.dtype == torch.uint8
-            and w.codes.shape[1] == cin and a.scales.dtype == torch.float32 and a.scales.numel() == n * s and dtype in _HALF
-            and (bias is None or bias.dtype == torch.float32)):
-        msg = (f"hip_linear_fp8_rows takes uint8 CUDA codes [n, S, cin] with n * S float32 scales, weights [cout, cin] and a float32 bias; "
-               f"got {tuple(a.codes.shape)}, {a.codes.dtype} beside {tuple(w.codes.shape)}, {w.codes.dtype} for {dtype}.")
-        raise ValueError(msg)
-    if residual is not None:
-        _half_tokens("hip_linear_fp8_rows (residual)", residual, cout)
-        if residual.dtype != dtype or tuple(residual.shape[:2]) != (n, s):
-            msg = f"hip_linear_fp8_rows: residual {tuple(residual.shape)}, {residual.dtype} beside tokens {(n, s, cin)} for {dtype}."
-            raise ValueError(msg)
-    y = torch.empty((n, s, cout), dtype=dtype, device=a.codes.device)
-    with torch.cuda.device(y.device):
-        rc = _lib.load().tia_linear_fp8_rows(a.codes.data_ptr(), a.scales.data_ptr(), w.codes.data_ptr(), w.scales.data_ptr(), _ptr(bias),
-                                             _ptr(residual), y.data_ptr(), n * s, cout, cin, _DT[dtype], _lib.current_stream())
-    _lib.check(rc, "tia_linear_fp8_rows")
-    return y
+    return _linear_quant_rows(_FP8, "tia_linear_fp8_rows", a, w, bias, residual, dtype)
 
 
 def hip_layernorm_rows_q8(x: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, *, eps: float) -> QuantRows:
     """LayerNorm of every row of ``[n, S, D]`` tokens, quantised from its float32 values (``tia_layernorm_rows_q8``)."""
-    from tiatoolbox_amd import _lib
-
-    _half_tokens("hip_layernorm_rows_q8", x, gamma.numel())
-    if x.dim() != 3 or gamma.dtype != torch.float32 or beta.dtype != torch.float32 or beta.numel() != gamma.numel():  # noqa: PLR2004
-        msg = f"hip_layernorm_rows_q8 takes [n, S, D] tokens and a float32 affine of D values; got {tuple(x.shape)}, {tuple(gamma.shape)}."
-        raise ValueError(msg)
-    n, s, d = x.shape
-    codes = torch.empty((n, s, d), dtype=torch.uint8, device=x.device)
-    scales = torch.empty((n * s,), dtype=torch.float32, device=x.device)
-    with torch.cuda.device(x.device):
-        rc = _lib.load().tia_layernorm_rows_q8(x.data_ptr(), d, gamma.data_ptr(), beta.data_ptr(), float(eps), codes.data_ptr(),
-                                               scales.data_ptr(), n * s, d, _DT[x.dtype], _lib.current_stream())
-    _lib.check(rc, "tia_layernorm_rows_q8")
-    return QuantRows(codes, scales)
+    return _layernorm_quant_rows(_FP8, "tia_layernorm_rows_q8", x, gamma, beta, eps)
 
 
 def hip_act_rows_q8(x: torch.Tensor, *, swiglu: bool) -> QuantRows:
     """The activation between ``fc1`` and ``fc2`` on ``[n, S, H]`` (exact GELU) or ``[n, S, 2H]`` (packed SwiGLU, the first half the
     gate) tokens, quantised from its float32 values: ``[n, S, H]`` codes (``tia_gelu_rows_q8`` / ``tia_swiglu_rows_q8``)."""
-    from tiatoolbox_amd import _lib
-
-    _half_tokens("hip_act_rows_q8", x)
-    if x.dim() != 3 or (swiglu and x.shape[-1] % 2 != 0):  # noqa: PLR2004
-        msg = f"hip_act_rows_q8 takes [n, S, H] (GELU) or [n, S, 2H] (SwiGLU) tokens; got {tuple(x.shape)}."
-        raise ValueError(msg)
-    n, s, c = x.shape
-    hidden = c // 2 if swiglu else c
-    codes = torch.empty((n, s, hidden), dtype=torch.uint8, device=x.device)
-    scales = torch.empty((n * s,), dtype=torch.float32, device=x.device)
-    lib = _lib.load()
-    entry, what = (lib.tia_swiglu_rows_q8, "tia_swiglu_rows_q8") if swiglu else (lib.tia_gelu_rows_q8, "tia_gelu_rows_q8")
-    with torch.cuda.device(x.device):
-        rc = entry(x.data_ptr(), codes.data_ptr(), scales.data_ptr(), n * s, hidden, _DT[x.dtype], _lib.current_stream())
-    _lib.check(rc, what)
-    return QuantRows(codes, scales)
+    return _act_quant_rows(_FP8, "tia_gelu_rows_q8", "tia_swiglu_rows_q8", x, swiglu)
 
 
 def pad_swiglu_to(fc1_w: torch.Tensor, fc1_b: torch.Tensor, fc2_w: torch.Tensor, target: int) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
@@ -604,22 +668,10 @@ def pad_swiglu_to(fc1_w: torch.Tensor, fc1_b: torch.Tensor, fc2_w: torch.Tensor,
     return fc1_w, fc1_b, torch.nn.functional.pad(fc2_w, (0, pad)).contiguous()
 
 
-class _LinearFp8:
-    """One GEMM of the graph on the FP8 kernel: weights quantised per output channel in ``prepare`` from the float32 (folded, padded)
-    ones, the float32 bias throughout; called on :class:`QuantRows` from a quantising producer."""
+class _LinearFp8(_LinearQuant):
+    """:class:`_LinearQuant` on the FP8 kernel."""
 
-    def __init__(self, name: str, weight: torch.Tensor, bias: torch.Tensor) -> None:
-        self.name, self.weight32, self.bias32 = name, weight, bias
-        self.cout, self.cin = weight.shape
-        self.packed: QuantRows | None = None
-        self.dtype: torch.dtype | None = None
-
-    def prepare(self, dtype: torch.dtype) -> None:
-        self.packed, self.dtype = pack_linear_weights_fp8(self.weight32), dtype
-        self.weight32 = None
-
-    def __call__(self, a: QuantRows, residual: torch.Tensor | None = None) -> torch.Tensor:
-        return hip_linear_fp8_rows(a, self.packed, self.bias32, residual, dtype=self.dtype)
+    fmt = _FP8
 
 
 INT8_LINEAR = "int8"  # the other quantised `linear_dtype` of `FusedViT.prepare` (and the engines' `compute_dtype` that selects it)
@@ -643,116 +695,47 @@ def quantize_rows_int8(v: torch.Tensor) -> tuple[torch.Tensor, torch.Tensor]:
     return q, s.squeeze(-1)
 
 
+_INT8 = _QuantFormat("INT8", torch.int8, INT8_LINEAR, "linear_int8_serves", "pack_linear_weights_int8", "hip_linear_int8_rows",
+                     "hip_layernorm_rows_qi8", "hip_act_rows_qi8")
+
+
 def linear_int8_serves(cout: int, cin: int) -> bool:
     """Whether a ``cin -> cout`` Linear goes to the INT8 GEMM (``tia_linear_int8_serves``, answered on the host)."""
-    from tiatoolbox_amd import _lib
-
-    return _lib.load().tia_linear_int8_serves(1, cout, cin) == 1
+    return _linear_serves("tia_linear_int8_serves", cout, cin)
 
 
 def pack_linear_weights_int8(weight: torch.Tensor) -> QuantRows:
     """Float32 ``[cout, cin]`` -> ``tia_linear_int8_rows``'s weight operand: ``torch.int8`` codes ``[cout, cin]`` and one scale per
     output channel, quantised on the device (``tia_linear_int8_pack_weights``)."""
-    from tiatoolbox_amd import _lib
-
-    w = weight.detach().to(torch.float32).contiguous()
-    if not w.is_cuda or w.dim() != 2:  # noqa: PLR2004
-        msg = f"pack_linear_weights_int8 packs CUDA weights [cout, cin]; got {tuple(w.shape)} on {w.device}."
-        raise ValueError(msg)
-    cout, cin = w.shape
-    codes = torch.empty((cout, cin), dtype=torch.int8, device=w.device)
-    scales = torch.empty((cout,), dtype=torch.float32, device=w.device)
-    with torch.cuda.device(w.device):
-        rc = _lib.load().tia_linear_int8_pack_weights(w.data_ptr(), cout, cin, codes.data_ptr(), scales.data_ptr(), _lib.current_stream())
-    _lib.check(rc, "tia_linear_int8_pack_weights")
-    return QuantRows(codes, scales)
+    return _pack_linear_weights(_INT8, "tia_linear_int8_pack_weights", weight)
 
 
 def hip_linear_int8_rows(a: QuantRows, w: QuantRows, bias: torch.Tensor | None, residual: torch.Tensor | None = None, *,
                          dtype: torch.dtype) -> torch.Tensor:
     """``half_rne(float(acc) * sa * sw + bias (+ residual))`` of quantised tokens ``[n, S, cin]`` and weights ``[cout, cin]``, both
     ``torch.int8`` codes (the FP8 route's uint8 codes are refused): ``tia_linear_int8_rows`` -> ``[n, S, cout]`` of ``dtype``."""
-    from tiatoolbox_amd import _lib
-
     if a.codes.dtype != torch.int8 or w.codes.dtype != torch.int8:  # (before anything else: FP8 codes are another number format)
         msg = (f"hip_linear_int8_rows takes torch.int8 codes (quantize_rows_int8's recipe) for tokens and weights; got {a.codes.dtype} "
                f"beside {w.codes.dtype}.")
         raise ValueError(msg)
-    n, s, cin = a.codes.shape
-    cout = w.codes.shape[0]
-    if not (a.codes.is_cuda and a.codes.is_contiguous() and w.codes.shape[1] == cin and a.scales.dtype == torch.float32
-            and a.scales.numel() == n * s and dtype in _HALF and (bias is None or bias.dtype == torch.float32)):
-        msg = (f"hip_linear_int8_rows takes int8 CUDA codes [n, S, cin] with n * S float32 scales, weights [cout, cin] and a float32 bias; "
-               f"got {tuple(a.codes.shape)}, {a.codes.dtype} beside {tuple(w.codes.shape)}, {w.codes.dtype} for {dtype}.")
-        raise ValueError(msg)
-    if residual is not None:
-        _half_tokens("hip_linear_int8_rows (residual)", residual, cout)
-        if residual.dtype != dtype or tuple(residual.shape[:2]) != (n, s):
-            msg = f"hip_linear_int8_rows: residual {tuple(residual.shape)}, {residual.dtype} beside tokens {(n, s, cin)} for {dtype}."
-            raise ValueError(msg)
-    y = torch.empty((n, s, cout), dtype=dtype, device=a.codes.device)
-    with torch.cuda.device(y.device):
-        rc = _lib.load().tia_linear_int8_rows(a.codes.data_ptr(), a.scales.data_ptr(), w.codes.data_ptr(), w.scales.data_ptr(), _ptr(bias),
-                                              _ptr(residual), y.data_ptr(), n * s, cout, cin, _DT[dtype], _lib.current_stream())
-    _lib.check(rc, "tia_linear_int8_rows")
-    return y
+    return _linear_quant_rows(_INT8, "tia_linear_int8_rows", a, w, bias, residual, dtype)
 
 
 def hip_layernorm_rows_qi8(x: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, *, eps: float) -> QuantRows:
     """LayerNorm of every row of ``[n, S, D]`` tokens, quantised to int8 from its float32 values (``tia_layernorm_rows_qi8``)."""
-    from tiatoolbox_amd import _lib
-
-    _half_tokens("hip_layernorm_rows_qi8", x, gamma.numel())
-    if x.dim() != 3 or gamma.dtype != torch.float32 or beta.dtype != torch.float32 or beta.numel() != gamma.numel():  # noqa: PLR2004
-        msg = f"hip_layernorm_rows_qi8 takes [n, S, D] tokens and a float32 affine of D values; got {tuple(x.shape)}, {tuple(gamma.shape)}."
-        raise ValueError(msg)
-    n, s, d = x.shape
-    codes = torch.empty((n, s, d), dtype=torch.int8, device=x.device)
-    scales = torch.empty((n * s,), dtype=torch.float32, device=x.device)
-    with torch.cuda.device(x.device):
-        rc = _lib.load().tia_layernorm_rows_qi8(x.data_ptr(), d, gamma.data_ptr(), beta.data_ptr(), float(eps), codes.data_ptr(),
-                                                scales.data_ptr(), n * s, d, _DT[x.dtype], _lib.current_stream())
-    _lib.check(rc, "tia_layernorm_rows_qi8")
-    return QuantRows(codes, scales)
+    return _layernorm_quant_rows(_INT8, "tia_layernorm_rows_qi8", x, gamma, beta, eps)
 
 
 def hip_act_rows_qi8(x: torch.Tensor, *, swiglu: bool) -> QuantRows:
     """The activation between ``fc1`` and ``fc2`` on ``[n, S, H]`` (exact GELU) or ``[n, S, 2H]`` (packed SwiGLU, the first half the
     gate) tokens, quantised to int8 from its float32 values: ``[n, S, H]`` codes (``tia_gelu_rows_qi8`` / ``tia_swiglu_rows_qi8``)."""
-    from tiatoolbox_amd import _lib
-
-    _half_tokens("hip_act_rows_qi8", x)
-    if x.dim() != 3 or (swiglu and x.shape[-1] % 2 != 0):  # noqa: PLR2004
-        msg = f"hip_act_rows_qi8 takes [n, S, H] (GELU) or [n, S, 2H] (SwiGLU) tokens; got {tuple(x.shape)}."
-        raise ValueError(msg)
-    n, s, c = x.shape
-    hidden = c // 2 if swiglu else c
-    codes = torch.empty((n, s, hidden), dtype=torch.int8, device=x.device)
-    scales = torch.empty((n * s,), dtype=torch.float32, device=x.device)
-    lib = _lib.load()
-    entry, what = (lib.tia_swiglu_rows_qi8, "tia_swiglu_rows_qi8") if swiglu else (lib.tia_gelu_rows_qi8, "tia_gelu_rows_qi8")
-    with torch.cuda.device(x.device):
-        rc = entry(x.data_ptr(), codes.data_ptr(), scales.data_ptr(), n * s, hidden, _DT[x.dtype], _lib.current_stream())
-    _lib.check(rc, what)
-    return QuantRows(codes, scales)
+    return _act_quant_rows(_INT8, "tia_gelu_rows_qi8", "tia_swiglu_rows_qi8", x, swiglu)
 
 
-class _LinearInt8:
-    """One GEMM of the graph on the INT8 kernel: weights quantised per output channel in ``prepare`` from the float32 (folded, padded)
-    ones, the float32 bias throughout; called on int8 :class:`QuantRows` from a quantising producer."""
+class _LinearInt8(_LinearQuant):
+    """:class:`_LinearQuant` on the INT8 kernel, called on int8 :class:`QuantRows`."""
 
-    def __init__(self, name: str, weight: torch.Tensor, bias: torch.Tensor) -> None:
-        self.name, self.weight32, self.bias32 = name, weight, bias
-        self.cout, self.cin = weight.shape
-        self.packed: QuantRows | None = None
-        self.dtype: torch.dtype | None = None
-
-    def prepare(self, dtype: torch.dtype) -> None:
-        self.packed, self.dtype = pack_linear_weights_int8(self.weight32), dtype
-        self.weight32 = None
-
-    def __call__(self, a: QuantRows, residual: torch.Tensor | None = None) -> torch.Tensor:
-        return hip_linear_int8_rows(a, self.packed, self.bias32, residual, dtype=self.dtype)
+    fmt = _INT8
 
 
 class _Linear:
@@ -1112,32 +1095,20 @@ class FusedViT(nn.Module):
         self.residual_dtype = residual_dtype
 
     def _route_fp8(self) -> None:
-        """``qkv`` / ``fc1`` / ``fc2`` of every block to :class:`_LinearFp8` where ``tia_linear_fp8_serves`` takes the shape.  A packed
-        SwiGLU half off the kernel's multiple of 128 is first padded up to it with ``pad_swiglu``'s exact zero lanes (at or above
-        ``SWIGLU_PAD_FLOOR`` only, as there)."""
-        kept: list[str] = []
-        for layer in self.layers:
-            fc1, fc2 = layer["fc1"], layer["fc2"]
-            target = -(-fc2.cin // 128) * 128
-            if self.swiglu and target != fc2.cin and fc2.cin >= SWIGLU_PAD_FLOOR:
-                fc1_w, fc1_b, fc2_w = pad_swiglu_to(fc1.weight32, fc1.bias32, fc2.weight32, target)
-                layer["fc1"], layer["fc2"] = _Linear(fc1.name, fc1_w, fc1_b), _Linear(fc2.name, fc2_w, fc2.bias32)
-            for name in ("qkv", "fc1", "fc2"):
-                lin = layer[name]
-                if linear_fp8_serves(lin.cout, lin.cin):
-                    layer[name] = _LinearFp8(lin.name, lin.weight32, lin.bias32)
-                else:
-                    kept.append(f"{lin.name} ({lin.cin} -> {lin.cout})")
-        if kept:
-            import logging
-
-            logging.getLogger("tiatoolbox_amd").info(
-                "FusedViT: the FP8 GEMM takes cin %% 128 == 0 and cout %% 16 == 0; %d layer(s) stay on the half kernel: %s.", len(kept),
-                ", ".join(kept))
+        """``qkv`` / ``fc1`` / ``fc2`` of every block to :class:`_LinearFp8` where ``tia_linear_fp8_serves`` takes the shape
+        (``_route_quant``)."""
+        self._route_quant(_LinearFp8)
 
     def _route_int8(self) -> None:
-        """``qkv`` / ``fc1`` / ``fc2`` of every block to :class:`_LinearInt8` where ``tia_linear_int8_serves`` takes the shape; the
-        padding of a packed SwiGLU half to the kernel's multiple of 128 is ``_route_fp8``'s."""
+        """``qkv`` / ``fc1`` / ``fc2`` of every block to :class:`_LinearInt8` where ``tia_linear_int8_serves`` takes the shape
+        (``_route_quant``)."""
+        self._route_quant(_LinearInt8)
+
+    def _route_quant(self, linear_cls: type[_LinearQuant]) -> None:
+        """``qkv`` / ``fc1`` / ``fc2`` of every block to ``linear_cls`` where its format's ``serves`` takes the shape.  A packed SwiGLU
+        half off the kernels' multiple of 128 is first padded up to it with ``pad_swiglu``'s exact zero lanes (at or above
+        ``SWIGLU_PAD_FLOOR`` only, as there)."""
+        fmt = linear_cls.fmt
         kept: list[str] = []
         for layer in self.layers:
             fc1, fc2 = layer["fc1"], layer["fc2"]
@@ -1147,16 +1118,16 @@ class FusedViT(nn.Module):
                 layer["fc1"], layer["fc2"] = _Linear(fc1.name, fc1_w, fc1_b), _Linear(fc2.name, fc2_w, fc2.bias32)
             for name in ("qkv", "fc1", "fc2"):
                 lin = layer[name]
-                if linear_int8_serves(lin.cout, lin.cin):
-                    layer[name] = _LinearInt8(lin.name, lin.weight32, lin.bias32)
+                if fmt.fn("serves")(lin.cout, lin.cin):
+                    layer[name] = linear_cls(lin.name, lin.weight32, lin.bias32)
                 else:
                     kept.append(f"{lin.name} ({lin.cin} -> {lin.cout})")
         if kept:
             import logging
 
             logging.getLogger("tiatoolbox_amd").info(
-                "FusedViT: the INT8 GEMM takes cin %% 128 == 0 and cout %% 16 == 0; %d layer(s) stay on the half kernel: %s.", len(kept),
-                ", ".join(kept))
+                f"FusedViT: the {fmt.name} GEMM takes cin %% 128 == 0 and cout %% 16 == 0; %d layer(s) stay on the half kernel: %s.",  # noqa: G004
+                len(kept), ", ".join(kept))
 
     def _route_split(self) -> None:
         """Every GEMM of the graph to :class:`_LinearF32`, packed.  A packed SwiGLU whose ``fc1`` is off the split kernel's multiple
@@ -1302,21 +1273,17 @@ class FusedViT(nn.Module):
         else:
             x = hip_vit_assemble_tokens_h(tok, self._cls32, pos)
         s = x.shape[1]
-        def norm_for(linear: _Linear | _LinearFp8 | _LinearInt8, norm: tuple[torch.Tensor, torch.Tensor]) -> torch.Tensor | QuantRows:
-            if isinstance(linear, _LinearFp8):  # the same pass over x, codes + scales out
-                return hip_layernorm_rows_q8(x, *norm, eps=LN_EPS)
-            if isinstance(linear, _LinearInt8):
-                return hip_layernorm_rows_qi8(x, *norm, eps=LN_EPS)
+        def norm_for(linear: _Linear | _LinearQuant, norm: tuple[torch.Tensor, torch.Tensor]) -> torch.Tensor | QuantRows:
+            if isinstance(linear, _LinearQuant):  # the same pass over x, codes + scales out
+                return linear.fmt.fn("layernorm")(x, *norm, eps=LN_EPS)
             return hip_layernorm_rows_h(x, *norm, eps=LN_EPS, rows=n * s, row_stride=d).view(n, s, d)
 
         for layer in self.layers:
             a = hip_mha_fwd_h(layer["qkv"](norm_for(layer["qkv"], layer["norm1"])), self.num_heads, self.scale)
             x = layer["proj"](a, residual=x)
             a = layer["fc1"](norm_for(layer["fc1"], layer["norm2"]))
-            if isinstance(layer["fc2"], _LinearFp8):
-                a = hip_act_rows_q8(a, swiglu=self.swiglu)
-            elif isinstance(layer["fc2"], _LinearInt8):
-                a = hip_act_rows_qi8(a, swiglu=self.swiglu)
+            if isinstance(layer["fc2"], _LinearQuant):
+                a = layer["fc2"].fmt.fn("act")(a, swiglu=self.swiglu)
             else:
                 a = hip_swiglu_rows_h(a) if self.swiglu else hip_gelu_rows_h_(a)
             x = layer["fc2"](a, residual=x)

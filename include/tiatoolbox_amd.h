@@ -656,7 +656,7 @@ int tia_conv3x3_wino_form(int64_t n, int64_t h, int64_t w, int64_t cin, int64_t 
  * (conv3x3_wino_bf16x3.hip; additive, same version 6): float32 in, float32 accumulate, V = B^T d B in float32 and U = G g G^T
  * rounded once to float32 exactly as in tia_conv3x3_wino_nhwc_f32; only the multiplication differs (six exact bf16 products per
  * float32 product, another summation order).  Contract, checks and return codes of tia_conv3x3_wino_nhwc_f32; cin % 16 == 0,
- * cout % 64 == 0; blocks of 16 x 16 outputs for every map size.
+ * cout % 64 == 0; blocks of 16 x 16 outputs, or of four images for maps of at most 8 x 8 outputs (bit-identical results).
  *   tia_conv_pack_weights_wino_bf16x3: d_parts [3][cout][cin][4][4] float32 holding bf16 VALUES (the planes hi, mid, lo of
  *   U[o][c][i][j]; the split and its check are the caller's, fused.pack_conv_weights_wino_split) -> 48 * cin * cout bf16 in the
  *   kernel's stage layout [cin/16][2 jh][cout/64][8 positions 2 i + jl][3 planes][2 k-chunks][64 cout][8 channels]
@@ -664,12 +664,18 @@ int tia_conv3x3_wino_form(int64_t n, int64_t h, int64_t w, int64_t cin, int64_t 
  *   tia_conv3x3_wino_bf16x3_serves: host-only route query (no launch) -- 1 where the fused resnet blocks take this form for a
  *   "same"-padded 3x3 / stride-1 layer under conv_algo="auto" (the layer classes that measured faster than the float32 form
  *   serving them, see the table at its definition), 0 otherwise; the negative code of tia_conv3x3_wino_form for shapes no
- *   Winograd form serves. */
+ *   Winograd form serves.  It answers for the classes that run on 16 x 16 blocks only.
+ *   tia_conv3x3_wino_bf16x3_form (additive, same version 6): the route query the fused resnet blocks go by -- 1 where
+ *   tia_conv3x3_wino_bf16x3_serves answers 1, 2 for the layer class taken on blocks of FOUR images of at most 8 x 8 outputs
+ *   (tia_conv3x3_wino_bf16x3_nhwc_f32 takes that geometry by itself for such maps), 0 otherwise, negative as above;
+ *   0 under the developer switch TIA_WINO_NO_SPLIT, and never 2 under TIA_WINO_SPLIT_NO_W8, which keeps the kernel on 16 x 16
+ *   blocks for every map (both with TIA_DEV=1). */
 int tia_conv_pack_weights_wino_bf16x3(const float* d_parts, int64_t cout, int64_t cin, void* d_packed, void* stream);
 int tia_conv3x3_wino_bf16x3_nhwc_f32(const float* d_x, const void* d_u_packed3, const float* d_bias, const float* d_residual,
                                      float* d_y, int64_t n, int64_t h, int64_t w, int64_t cin, int64_t cout, int64_t pad_top,
                                      int64_t pad_left, int64_t ho, int64_t wo, int32_t relu, void* stream);
 int tia_conv3x3_wino_bf16x3_serves(int64_t n, int64_t h, int64_t w, int64_t cin, int64_t cout, int64_t pad);
+int tia_conv3x3_wino_bf16x3_form(int64_t n, int64_t h, int64_t w, int64_t cin, int64_t cout, int64_t pad);
 
 /* Host-only query (no launch): which kernel tia_conv2d_nhwc_f32[_ex] runs a float32 convolution of this shape on --
  * 0: conv_mfma_f32_kernel (register-staged 128-pixel slices), 1: conv3x3_spatial_kernel (tap reuse; tia_conv3x3_geometry says

@@ -1,7 +1,10 @@
 """Winograd F(2x2, 3x3), F(4x2, 3x3) and the split-operand F(2x2, 3x3) (bf16 matrix cores) vs the direct tap-reuse kernel, per
 3x3 / stride-1 layer of resnet18 at a batch and patch size, and the whole trunk; per form the best of three interleaved warmed-up rounds, their
 spread, and the error of two images against a float64 convolution.  usage: perf_wino.py [batch=1024] [patch=256]  (HIP events on the launch stream; TFLOP/s are DIRECT-convolution flops / time,
-i.e. 'effective' for the Winograd rows, whose executed MFMA flops are 16/36 (F(2x2)) and 24/72 (F(4x2)) of that -- printed as `exec`)."""
+i.e. 'effective' for the Winograd rows, whose executed MFMA flops are 16/36 (F(2x2)) and 24/72 (F(4x2)) of that -- printed as `exec`).
+On maps of at most 8 x 8 the split column is the four-images-per-block geometry (W8), labelled so; with
+``TIA_DEV=1 TIA_WINO_SPLIT_NO_W8=1`` in the environment it is the 16 x 16-block geometry on those rows as well."""
+import os
 import sys
 from pathlib import Path
 
@@ -33,6 +36,8 @@ def main():
     tot_d = tot_w = tot_4 = tot_s = 0.0
     for c, div, count in ((64, 4, 4), (128, 8, 3), (256, 16, 3), (512, 32, 3)):
         hw = patch // div
+        w8 = hw <= 8 and not (os.environ.get("TIA_DEV", "")[:1] == "1" and "TIA_WINO_SPLIT_NO_W8" in os.environ)
+        split_name = "split F(2x2) W8 (four images per block)" if w8 else "split F(2x2)"
         conv = torch.nn.Conv2d(c, c, 3, padding=1).cuda()
         x = torch.randn((n, c, hw, hw), device="cuda", generator=g).contiguous(memory_format=torch.channels_last)
         res = torch.randn_like(x)
@@ -68,7 +73,7 @@ def main():
         print(f"3x3 {c:3d}->{c:3d} @{hw:3d} n={n}: direct {td:6.3f} ms {flops / td / 1e9:6.1f} TF/s | winograd {tw:6.3f} ms "
               f"{flops / tw / 1e9:6.1f} TF/s effective, {flops * 16 / 36 / tw / 1e9:6.1f} exec | x{td / tw:4.2f} | max rel diff {rel:.1e} || F(4x2) "
               f"{t4:6.3f} ms {flops / t4 / 1e9:6.1f} TF/s effective, {flops * 24 / 72 / t4 / 1e9:6.1f} exec | x{tw / t4:4.2f} vs F(2x2) | "
-              f"max rel diff {rel4:.1e} || split F(2x2) {ts:6.3f} ms {flops / ts / 1e9:6.1f} TF/s effective | x{tw / ts:4.2f} vs F(2x2), x{t4 / ts:4.2f} vs F(4x2) | "
+              f"max rel diff {rel4:.1e} || {split_name} {ts:6.3f} ms {flops / ts / 1e9:6.1f} TF/s effective | x{tw / ts:4.2f} vs F(2x2), x{t4 / ts:4.2f} vs F(4x2) | "
               f"spread of the rounds: direct {sp[0]:.1f} %, F(2x2) {sp[1]:.1f} %, F(4x2) {sp[2]:.1f} %, split {sp[3]:.1f} % | "
               f"error vs float64: F(2x2) {e64[0]:.1e}, F(4x2) {e64[1]:.1e}, split {e64[2]:.1e}", flush=True)
     if pmc:

@@ -13,8 +13,9 @@
 // 18 x 18 patch of a 16-channel slice arrives by LDS-DMA in the pair layout (two buffers of 24 KB); persistent item walk with the
 // next item's first operands requested behind the current item's last steps; the epilogue (column transform in registers, row
 // transform through the exchange area, + bias + residual, ReLU, 16-byte stores) takes the accumulators as they are: the C / D
-// layout of v_mfma_f32_32x32x16_bf16 is that of v_mfma_f32_32x32x2_f32.  Any map size is served by these blocks (maps of at
-// most 8 x 8 fill a quarter of one; the route query keeps such layers on the float32 forms).
+// layout of v_mfma_f32_32x32x16_bf16 is that of v_mfma_f32_32x32x2_f32.  Any map size is served by these blocks; maps of at
+// most 8 x 8 would fill a quarter of one and go FOUR IMAGES to a block instead (W8 below): the same loop and
+// epilogue around another decode, patch set-up and tile mapping, those of conv3x3_wino.hip's W8.
 //   * a lane's A fragment is row lane & 31 (its tile), k = 8 (lane >> 5) .. + 7: EIGHT channels of the slice, two ds_read_b128 per
 //     patch pixel.  Per slice it reads two patch rows x four columns (16 reads), forms R[c] = d[ra] +- d[rb] (32 adds) and keeps
 //     the four R in registers; V_j = R0 - R2 | R1 + R2 | R2 - R1 | R1 - R3 (8 adds each, unpacked: a packed float32 add beside the
@@ -29,7 +30,8 @@
 //     the next slice's patch; end of a step: s_waitcnt vmcnt(0) lgkmcnt(0) and one barrier.
 //   * LDS: [patch 0][stage 0][patch 1][stage 1] = 24 + 48 + 24 + 48 = 144 KB; the epilogue's 64 KB lie over patch 1 and the
 //     front of stage 1, which the next item requests only behind the epilogue (one barrier); patch 0 and stage 0 hold the next
-//     item's first operands while the epilogue runs.  One workgroup per CU, two waves per SIMD, 256 registers.
+//     item's first operands while the epilogue runs.  One workgroup per CU, two waves per SIMD, 256 registers.  (W8: patches
+//     of 32 KB, 160 KB in all.)
 //
 // Invalid-input domain: as conv_ring_bf16x3.hip -- a non-finite V, or |V| >= 2^127 (2 - 2^-8), makes every output that reads it
 // non-finite, never a finite wrong value; the weights' parts are checked on the host (fused.pack_conv_weights_wino_split).
@@ -62,20 +64,33 @@ struct WinoSplitDims {
 #define WSTAMP(var)
 #endif
 
-// the patch layout of conv3x3_wino.hip's W16 (pairs of pixels at 9 units, row pitch 84 units: its bank analysis holds for the two
-// units 2 hi, 2 hi + 1 a lane reads here -- the unit offset is the same for all lanes of a service group)
-constexpr int TH = 16, TW = 16, PH = 18, PWD = 18, ROW = 84, IMG = 18 * 84;
-constexpr int A_UNITS = (IMG + 63) / 64 * 64;  // 1536 patch units of 16 bytes: three whole DMA rounds of 512
-constexpr int A_BYTES = A_UNITS * 16;
+// Block geometries: the patch layouts of conv3x3_wino.hip's W16 and W8 (pairs of pixels at 9 units; their bank analysis holds for the
+// two units 2 hi, 2 hi + 1 a lane reads here -- the unit offset is the same for all lanes of a service group).
+//   W16: 16 x 16 outputs of ONE image, patch 18 x 18, row pitch 84 units: 1536 patch units of 16 bytes, three whole DMA rounds of 512;
+//        LDS 24 + 48 + 24 + 48 = 144 KB.  Serves every map size.
+//   W8:  FOUR images of at most 8 x 8 outputs, patch 10 x 10 each, row pitch 50 units, image pitch 512 units: 2048 units, four whole
+//        DMA rounds; LDS 32 + 48 + 32 + 48 = 160 KB, the whole LDS of a CU.  Block pixel = 64 image + 8 y + x; images beyond
+//        the batch and pixels beyond the map read zeros and are never stored.
+struct W16 {
+    static constexpr int G = 1, TH = 16, TW = 16, PH = 18, PWD = 18, ROW = 84, IMG = 18 * 84;
+};
+struct W8 {
+    static constexpr int G = 4, TH = 8, TW = 8, PH = 10, PWD = 10, ROW = 50, IMG = 512;
+};
 constexpr int W_STAGE = 8 * 3 * 2048;          // 8 positions x 3 planes x [2 k-chunks][64 columns][8 bf16]
-constexpr int LDS_BYTES = 2 * A_BYTES + 2 * W_STAGE;
+template <typename GEO>
+constexpr int wino_split_lds_bytes() {
+    return 2 * ((GEO::G * GEO::IMG + 63) / 64 * 64) * 16 + 2 * W_STAGE;
+}
 
-template <bool PERSIST>
+template <typename GEO, bool PERSIST>
 __global__ __launch_bounds__(512, 2) void conv3x3_wino_bf16x3_kernel(const float* __restrict__ x, const void* __restrict__ u,
                                                                      const float* __restrict__ bias, const float* __restrict__ res,
                                                                      float* __restrict__ y, WinoSplitDims d, int relu, int m_tiles,
                                                                      int tiles_x, int tiles_per_image) {
     constexpr int NT = 512, BN = 64, BLOCK_PX = 256;
+    constexpr int TH = GEO::TH, TW = GEO::TW, PH = GEO::PH, PWD = GEO::PWD, ROW = GEO::ROW;
+    constexpr int A_UNITS = (GEO::G * GEO::IMG + 63) / 64 * 64, A_BYTES = A_UNITS * 16, LDS_BYTES = wino_split_lds_bytes<GEO>();
     constexpr int NA = A_UNITS / NT;
     constexpr int NW = W_STAGE / (NT * 16);        // DMA rounds per stage: 6
     constexpr int OFF_W = A_BYTES, OFF_A1 = A_BYTES + W_STAGE, OFF_W1 = OFF_A1 + A_BYTES, OFF_EPI = OFF_A1;
@@ -111,8 +126,8 @@ __global__ __launch_bounds__(512, 2) void conv3x3_wino_bf16x3_kernel(const float
         } else {
             mt_id = xcd_tile(bid, m_tiles), cb = (int)blockIdx.y;
         }
-        img = mt_id / tiles_per_image;
-        const int trem = mt_id - img * tiles_per_image;
+        img = GEO::G == 1 ? mt_id / tiles_per_image : mt_id * GEO::G;  // (W8: the block's first image; its maps start at (0, 0))
+        const int trem = GEO::G == 1 ? mt_id - img * tiles_per_image : 0;
         ty0 = (trem / tiles_x) * TH;
         tx0 = (trem - (trem / tiles_x) * tiles_x) * TW;
     };
@@ -125,19 +140,20 @@ __global__ __launch_bounds__(512, 2) void conv3x3_wino_bf16x3_kernel(const float
     const __amdgpu_buffer_rsrc_t rx = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(x), 0, (int)d.x_bytes, kBufferRsrcFlags);
     const __amdgpu_buffer_rsrc_t ru = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(u), 0, (int)d.u_bytes, kBufferRsrcFlags);
 
-    // patch staging: unit NT r + tid -> row / pixel pair / pixel / unit of the slice (layout above); outside the image or the patch,
-    // and the padding unit of a pair: an out-of-range offset (the DMA writes zeros)
+    // patch staging: unit NT r + tid -> image of the block / row / pixel pair / pixel / unit of the slice (layout above); outside the
+    // batch, the image or the patch, and the padding unit of a pair: an out-of-range offset (the DMA writes zeros)
     int cen[NA];
     auto make_cen = [&] {  // for the item `decode` has just set
 #pragma unroll
         for (int r = 0; r < NA; ++r) {
             const int un = NT * r + tid;
-            const int py = un / ROW, rem = un - py * ROW;
+            const int g = GEO::G == 1 ? 0 : un / GEO::IMG, ug = un - g * GEO::IMG;  // (A_UNITS = G IMG for W8: g < G)
+            const int py = ug / ROW, rem = ug - py * ROW;
             const int pair = rem / 9, r9 = rem - pair * 9;
             const int px = 2 * pair + (r9 >> 2), chunk = r9 == 8 ? 4 : (r9 & 3);
             const int iy = ty0 - d.pad_y + py, ix = tx0 - d.pad_x + px;
-            const bool inside = img < d.n && py < PH && px < PWD && chunk < 4 && (unsigned)iy < (unsigned)d.h && (unsigned)ix < (unsigned)d.w;
-            cen[r] = inside ? ((img * d.h + iy) * d.w + ix) * d.cin * 4 + 16 * chunk : OOB;
+            const bool inside = img + g < d.n && py < PH && px < PWD && chunk < 4 && (unsigned)iy < (unsigned)d.h && (unsigned)ix < (unsigned)d.w;
+            cen[r] = inside ? (((img + g) * d.h + iy) * d.w + ix) * d.cin * 4 + 16 * chunk : OOB;
         }
     };
     make_cen();
@@ -163,7 +179,8 @@ __global__ __launch_bounds__(512, 2) void conv3x3_wino_bf16x3_kernel(const float
     // the lane's tile: MFMA row lane & 31 -> tile 32 wm + (lane & 31), its 4 x 4 input tile starts at patch pixel (2 ty, 2 tx); the
     // lane's k values are channels 8 hi .. 8 hi + 7 = units 2 hi, 2 hi + 1 of a pixel
     const int t = 32 * wm + (lane & 31);
-    const int fa = 2 * (t >> 3) * ROW + (t & 7) * 9 + 2 * hi;
+    const int fa = GEO::G == 1 ? 2 * (t >> 3) * ROW + (t & 7) * 9 + 2 * hi
+                               : (t >> 4) * GEO::IMG + 2 * ((t >> 2) & 3) * ROW + (t & 3) * 9 + 2 * hi;  // (W8: 16 tiles per image)
     // R = d[ra] +- d[rb]: i = 0: d0 - d2, 1: d1 + d2, 2: d2 - d1, 3: d1 - d3
     const int ra_off = (irow == 0 ? 0 : (irow == 2 ? 2 : 1)) * ROW, rb_off = (irow == 0 || irow == 1 ? 2 : (irow == 2 ? 1 : 3)) * ROW;
     const bool plus = irow == 1;
@@ -300,11 +317,12 @@ __global__ __launch_bounds__(512, 2) void conv3x3_wino_bf16x3_kernel(const float
         int mpix[ITER];
         u32x4 rq[ITER][2];
 #pragma unroll
-        for (int it = 0; it < ITER; ++it) {  // block pixel m = (ty0 + m / TW, tx0 + m % TW)
+        for (int it = 0; it < ITER; ++it) {  // block pixel m = image m / (TH TW) of the block, (ty0 + .. / TW, tx0 + .. % TW)
             const int row = (tid + NT * it) / (BN / 8);
-            const int oy = cur_ty0 + row / TW, ox = cur_tx0 + row % TW;
-            const bool live = oy < d.ho && ox < d.wo && cur_img < d.n;
-            mpix[it] = live ? (cur_img * d.ho + oy) * d.wo + ox : -1;
+            const int g = GEO::G == 1 ? 0 : row / (TH * TW), rg = row - g * (TH * TW);
+            const int oy = cur_ty0 + rg / TW, ox = cur_tx0 + rg % TW;
+            const bool live = oy < d.ho && ox < d.wo && cur_img + g < d.n;
+            mpix[it] = live ? ((cur_img + g) * d.ho + oy) * d.wo + ox : -1;
             rq[it][0] = rq[it][1] = u32x4{0u, 0u, 0u, 0u};
             if (res && live) {
                 const u32x4* rp = reinterpret_cast<const u32x4*>(res + (long)mpix[it] * d.cout + col0);
@@ -348,7 +366,7 @@ __global__ __launch_bounds__(512, 2) void conv3x3_wino_bf16x3_kernel(const float
 #pragma unroll
             for (int e = 0; e < 16; ++e) {
                 const int tt = 32 * wm + (e & 3) + 8 * (e >> 2) + 4 * hi;  // MFMA result row -> tile
-                const int m00 = 2 * (tt >> 3) * TW + 2 * (tt & 7);
+                const int m00 = GEO::G == 1 ? 2 * (tt >> 3) * TW + 2 * (tt & 7) : (tt >> 4) * (TH * TW) + 2 * ((tt >> 2) & 3) * TW + 2 * (tt & 3);
 #pragma unroll
                 for (int b = 0; b < 2; ++b)
 #pragma unroll
@@ -439,16 +457,30 @@ int conv3x3_wino_bf16x3_launch(const float* x, const float* u_packed, const floa
                                long h, long w, long cin, long cout, long pad_top, long pad_left, long ho, long wo, int relu,
                                hipStream_t stream) {
     if (!conv3x3_wino_serves(nb, h, w, cin, cout, pad_top, pad_left, ho, wo) || 96L * cin * cout > 0x7fffffffL) return TIA_ESIZE;
-    const long tiles_y = (ho + 15) / 16, tiles_x = (wo + 15) / 16, tiles = nb * tiles_y * tiles_x;
     const WinoSplitDims d{(int)nb, (int)h, (int)w, (int)cin, (int)cout, (int)ho, (int)wo, (int)pad_top, (int)pad_left,
                           (unsigned)(nb * h * w * cin * 4), (unsigned)(96 * cin * cout)};
-    const WinoGrid g = wino_grid(true, tiles, cin, cout);
-    constexpr int lds = LDS_BYTES;
-    const bool ok = g.persist ? launch_dyn_lds<&conv3x3_wino_bf16x3_kernel<true>>(g.grid, dim3(512), lds, stream, x, u_packed, bias, residual, y, d,
+    auto run = [&](auto geo, long tiles_y, long tiles_x, long tiles) {  // `tiles`: pixel blocks of the launch
+        using GEO = decltype(geo);
+        constexpr int lds = wino_split_lds_bytes<GEO>();
+        static_assert(lds <= 160 * 1024, "one workgroup per CU");
+        const WinoGrid g = wino_grid(true, tiles, cin, cout);
+        return g.persist ? launch_dyn_lds<&conv3x3_wino_bf16x3_kernel<GEO, true>>(g.grid, dim3(512), lds, stream, x, u_packed, bias, residual, y, d,
                                                                                  relu, (int)tiles, (int)tiles_x, (int)(tiles_y * tiles_x))
-                              : launch_dyn_lds<&conv3x3_wino_bf16x3_kernel<false>>(g.grid, dim3(512), lds, stream, x, u_packed, bias, residual, y, d,
+                         : launch_dyn_lds<&conv3x3_wino_bf16x3_kernel<GEO, false>>(g.grid, dim3(512), lds, stream, x, u_packed, bias, residual, y, d,
                                                                                   relu, (int)tiles, (int)tiles_x, (int)(tiles_y * tiles_x));
-    return ok ? TIA_OK : TIA_ELAUNCH;
+    };
+    // Maps of at most 8 x 8 outputs go four images per block (conv3x3_wino_run keeps the groups at whole blocks of four).  That form
+    // takes the CU's whole LDS: a device that refuses it is remembered, the refusal is cleared, and the 16 x 16 blocks -- correct for
+    // every map size -- serve instead.  Developer switch (TIA_DEV=1): TIA_WINO_SPLIT_NO_W8 forces 16 x 16 blocks (A/B runs, bit identity).
+    static const bool no_w8 = tia::dev_env("TIA_WINO_SPLIT_NO_W8") != nullptr;
+    static std::atomic<bool> w8_refused{false};
+    if (ho <= 8 && wo <= 8 && !no_w8 && !w8_refused.load(std::memory_order_relaxed)) {
+        if (run(W8{}, 1, 1, (nb + 3) / 4)) return TIA_OK;
+        (void)hipGetLastError();
+        w8_refused.store(true, std::memory_order_relaxed);
+    }
+    const long tiles_y = (ho + 15) / 16, tiles_x = (wo + 15) / 16;
+    return run(W16{}, tiles_y, tiles_x, nb * tiles_y * tiles_x) ? TIA_OK : TIA_ELAUNCH;
 }
 
 }  // namespace
@@ -484,15 +516,41 @@ extern "C" int tia_conv3x3_wino_bf16x3_nhwc_f32(const float* d_x, const void* d_
 // RULE: exactly the three classes measured winning per launch AND in the whole step -- square maps of 64 / 32 / 16
 // pixels a side with 64 / 128 / 256 channels in and out.  The maps of 224^2 patches win per launch (4.87 -> 4.34, 4.44 -> 3.74, 4.23 -> 3.40 ms,
 // profiles/wino_split_perf_4096_224.txt) but their whole step was not measured with them routed: not admitted yet.  48^2 and rectangular
-// maps and other channel counts were not measured; maps of at most 8 x 8 lose.
-// Developer switch (TIA_DEV=1): TIA_WINO_NO_SPLIT makes the answer 0 (A/B runs from one build).
-extern "C" int tia_conv3x3_wino_bf16x3_serves(int64_t n, int64_t h, int64_t w, int64_t cin, int64_t cout, int64_t pad) {
+// maps and other channel counts were not measured; maps of at most 8 x 8 lose on 16 x 16 blocks.
+// Four images per block (W8; scripts/perf_wino.py 4096 256 | 224, profiles/wino_split_w8_perf_4096_*.txt):
+//     map   channels   serves it today        split, four images per block
+//      8^2    512      F(4x2) four images      3.84 -> 3.54  x1.08  [0.2 / 0.6 %]   256^2 patches
+//      7^2    512      F(4x2) four images      3.81 -> 3.48  x1.09  [0.1 / 1.2 %]   224^2 patches
+// RULE for this geometry, the same as above: the 8^2 / 512 class wins per launch AND in the whole step (71.76 .. 71.93 -> 69.25 .. 69.50 ms,
+// DESIGN 4.40 item 4): admitted, answer 2.  The 7^2 / 512 class wins per launch, but the whole step at 224^2 with it routed did not meet
+// the criterion (73.94 .. 74.68 -> 73.32 .. 74.11 ms: inside the spread of the runs): NOT admitted.  Other maps of at most 8 x 8 and other
+// channel counts were not measured.
+// Developer switches (TIA_DEV=1): TIA_WINO_NO_SPLIT makes the answer 0 (A/B runs from one build); TIA_WINO_SPLIT_NO_W8 takes the
+// four-image class out (its layers would run on 16 x 16 blocks, which lose).
+namespace {
+
+// 0 not taken, 1 one of the three classes on 16 x 16 blocks, 2 the class on four-image blocks; negative: no Winograd form serves it
+int wino_split_form(long n, long h, long w, long cin, long cout, long pad) {
     const int form = tia::conv3x3_wino_form(n, h, w, cin, cout, pad);
     if (form < 0) return form;
     static const bool disabled = tia::dev_env("TIA_WINO_NO_SPLIT") != nullptr;
-    if (disabled || pad != 1 || 96L * cin * cout > 0x7fffffffL) return 0;
-    const long tiles = n * ((h + 15) / 16) * ((w + 15) / 16);
+    static const bool no_w8 = tia::dev_env("TIA_WINO_SPLIT_NO_W8") != nullptr;
+    if (disabled || pad != 1 || 96L * cin * cout > 0x7fffffffL || h != w || cin != cout) return 0;
+    const bool small = h <= 8;  // ("same" padding: the output map is the input's)
+    const long tiles = small ? (n + 3) / 4 : n * ((h + 15) / 16) * ((w + 15) / 16);
     if (!tia::wino_grid(true, tiles, cin, cout).persist) return 0;
-    const bool measured = (h == 64 && cin == 64) || (h == 32 && cin == 128) || (h == 16 && cin == 256);
-    return h == w && cin == cout && measured ? 1 : 0;
+    if (small) return !no_w8 && h == 8 && cin == 512 ? 2 : 0;
+    return (h == 64 && cin == 64) || (h == 32 && cin == 128) || (h == 16 && cin == 256) ? 1 : 0;
+}
+
+}  // namespace
+
+extern "C" int tia_conv3x3_wino_bf16x3_form(int64_t n, int64_t h, int64_t w, int64_t cin, int64_t cout, int64_t pad) {
+    return wino_split_form(n, h, w, cin, cout, pad);
+}
+
+// (the query of DESIGN 4.30: the classes on 16 x 16 blocks only -- 0 for the four-image class)
+extern "C" int tia_conv3x3_wino_bf16x3_serves(int64_t n, int64_t h, int64_t w, int64_t cin, int64_t cout, int64_t pad) {
+    const int form = wino_split_form(n, h, w, cin, cout, pad);
+    return form < 0 ? form : (form == 1 ? 1 : 0);
 }

@@ -705,10 +705,18 @@ def pack_conv_weights_wino_split(conv: nn.Conv2d) -> torch.Tensor | None:
 @functools.lru_cache(maxsize=256)
 def wino_split_serves(n: int, h: int, w: int, cin: int, cout: int, pad: int) -> bool:
     """Whether the fused resnet blocks run this "same"-padded 3x3 / stride-1 layer on the split-operand Winograd form under
-    ``conv_algo="auto"`` (``tia_conv3x3_wino_bf16x3_serves``, a host-only query)."""
+    ``conv_algo="auto"``: :func:`wino_split_form` answers 1 (16 x 16 blocks) or 2 (four images of at most 8 x 8 per block)."""
+    return wino_split_form(n, h, w, cin, cout, pad) > 0
+
+
+@functools.lru_cache(maxsize=256)
+def wino_split_form(n: int, h: int, w: int, cin: int, cout: int, pad: int) -> int:
+    """The route query of the split-operand Winograd form (``tia_conv3x3_wino_bf16x3_form``, host-only): 0 not taken, 1 a layer class
+    on 16 x 16 blocks, 2 the class on blocks of four images (the kernel picks the geometry by the map size); negative for shapes no
+    Winograd form serves."""
     from tiatoolbox_amd import _lib
 
-    return _lib.load().tia_conv3x3_wino_bf16x3_serves(n, h, w, cin, cout, pad) == 1
+    return int(_lib.load().tia_conv3x3_wino_bf16x3_form(n, h, w, cin, cout, pad))
 
 
 @functools.lru_cache(maxsize=256)

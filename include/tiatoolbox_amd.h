@@ -51,7 +51,9 @@ extern "C" {
  * tia_vit_assemble_rows_f32, tia_vit_cls_mean_pool_f32 (the same graph with a float32 residual stream); tia_mha_fwd_f32,
  * tia_gelu_rows_f32, tia_swiglu_rows_f32, tia_vit_patchify_f32, tia_vit_assemble_f32 (the float32 route of that graph);
  * tia_linear_int8_rows, tia_linear_int8_pack_weights, tia_linear_int8_serves, tia_layernorm_rows_qi8, tia_gelu_rows_qi8,
- * tia_swiglu_rows_qi8 (the Vision Transformer linear layers on the INT8 matrix instruction). */
+ * tia_swiglu_rows_qi8 (the Vision Transformer linear layers on the INT8 matrix instruction); tia_gelu_rows_qi8_smooth,
+ * tia_swiglu_rows_qi8_smooth, tia_layernorm_rows_absmax_h, tia_gelu_rows_absmax_h, tia_swiglu_rows_absmax_h (per-input-channel
+ * smoothing of those layers and its calibration statistics). */
 #define TIA_ABI_VERSION 6
 int tia_abi_version(void);
 
@@ -1128,6 +1130,42 @@ int tia_layernorm_rows_qi8(const void* d_x, int64_t row_stride, const float* d_g
                            float* d_scale, int64_t rows, int64_t c, int32_t dtype, void* stream);
 int tia_gelu_rows_qi8(const void* d_x, void* d_q, float* d_scale, int64_t rows, int64_t hidden, int32_t dtype, void* stream);
 int tia_swiglu_rows_qi8(const void* d_x, void* d_q, float* d_scale, int64_t rows, int64_t hidden, int32_t dtype, void* stream);
+
+/* ---------------------------------------------------------------------------------------
+ * Per-input-channel smoothing of the INT8 layers (vit_fused.py, prepare(..., linear_dtype="int8", smoothing=scales), the engines'
+ * int8_smoothing).  Additive, same version (6); opt-in: nothing above changes.
+ *
+ * The recipe -- for a layer y = x W^T + b that the graph routes to tia_linear_int8_rows (attn.qkv, mlp.fc1, mlp.fc2) and input
+ * channel j:
+ *   a[j]   the calibrated abs-max, over every token of the calibration set, of the float32 value the producing kernel holds for
+ *          channel j (the LayerNorm output for qkv and fc1, the GELU / SwiGLU output for fc2): the statistics entries below
+ *   w[j]   max_o |W[o,j]| of the float32 weights that are packed (after the LayerScale fold and the SwiGLU padding)
+ *   s[j]   2^clamp(round(alpha log2 a[j] - (1 - alpha) log2 w[j]), -24, 24), evaluated in float64 on the host, alpha in (0, 1];
+ *          s[j] = 1 where a[j] == 0 or w[j] == 0 (the SwiGLU pad lanes among them).  A non-finite a[j] is refused.
+ * A power of two makes x / s and W s exact in float32: smoothing adds no rounding of its own, x W^T is unchanged as a real-valued
+ * function, and all-ones scales reproduce the unsmoothed graph bit for bit.
+ *   weights   W'[o,j] = W[o,j] s[j] in float32, then tia_linear_int8_pack_weights
+ *   qkv, fc1  the float32 LayerNorm affine is folded on the host, gamma' = gamma / s and beta' = beta / s, and
+ *             tia_layernorm_rows_qi8 runs with the folded pair
+ *   fc2       tia_gelu_rows_qi8_smooth / tia_swiglu_rows_qi8_smooth multiply the float32 value by inv_smooth[j] = 1 / s[j] (one
+ *             float32 multiplication per element) before the row maximum and the codes
+ * ------------------------------------------------------------------------------------- */
+
+/* tia_gelu_rows_qi8 / tia_swiglu_rows_qi8 with d_inv_smooth [hidden] float32 (16-byte aligned, non-NULL) applied to the float32
+ * value before it is quantised; the sizes, the errors and the NaN / inf contract of those entries.  A pad lane stays code 0. */
+int tia_gelu_rows_qi8_smooth(const void* d_x, const float* d_inv_smooth, void* d_q, float* d_scale, int64_t rows, int64_t hidden,
+                             int32_t dtype, void* stream);
+int tia_swiglu_rows_qi8_smooth(const void* d_x, const float* d_inv_smooth, void* d_q, float* d_scale, int64_t rows, int64_t hidden,
+                               int32_t dtype, void* stream);
+
+/* The calibration statistics: the arithmetic of the _qi8 producers up to the float32 value v, then
+ * d_amax[j] = max(d_amax[j], max_r |v[r,j]|) for every column j.  d_amax [c | hidden] float32: the caller zeroes it, and the result
+ * accumulates over calls.  Magnitudes are compared as the bit patterns of non-negative floats: a NaN sorts above +inf and stays in
+ * its column (and only there).  The sizes and errors of the _qi8 entries; nothing is launched on an error.  Run once per model. */
+int tia_layernorm_rows_absmax_h(const void* d_x, int64_t row_stride, const float* d_gamma, const float* d_beta, float eps,
+                                float* d_amax, int64_t rows, int64_t c, int32_t dtype, void* stream);
+int tia_gelu_rows_absmax_h(const void* d_x, float* d_amax, int64_t rows, int64_t hidden, int32_t dtype, void* stream);
+int tia_swiglu_rows_absmax_h(const void* d_x, float* d_amax, int64_t rows, int64_t hidden, int32_t dtype, void* stream);
 
 /* =======================================================================================
  * The float32 route of the Vision Transformer graph (vit_fused.py, prepare(torch.float32, linear_dtype="bfloat16x3"), the engines'

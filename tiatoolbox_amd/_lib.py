@@ -179,6 +179,11 @@ _SIGNATURES = {
     "tia_layernorm_rows_qi8": ([_P, _I64, _P, _P, C.c_float, _P, _P, _I64, _I64, _I32, _P], C.c_int),
     "tia_gelu_rows_qi8": ([_P, _P, _P, _I64, _I64, _I32, _P], C.c_int),
     "tia_swiglu_rows_qi8": ([_P, _P, _P, _I64, _I64, _I32, _P], C.c_int),
+    "tia_gelu_rows_qi8_smooth": ([_P, _P, _P, _P, _I64, _I64, _I32, _P], C.c_int),
+    "tia_swiglu_rows_qi8_smooth": ([_P, _P, _P, _P, _I64, _I64, _I32, _P], C.c_int),
+    "tia_layernorm_rows_absmax_h": ([_P, _I64, _P, _P, C.c_float, _P, _I64, _I64, _I32, _P], C.c_int),
+    "tia_gelu_rows_absmax_h": ([_P, _P, _I64, _I64, _I32, _P], C.c_int),
+    "tia_swiglu_rows_absmax_h": ([_P, _P, _I64, _I64, _I32, _P], C.c_int),
     "tia_mha_fwd_f32": ([_P, _P, _I64, _I64, _I64, _I64, C.c_float, _I32, _P], C.c_int),
     "tia_gelu_rows_f32": ([_P, _I64, _P], C.c_int),
     "tia_swiglu_rows_f32": ([_P, _P, _I64, _I64, _P], C.c_int),

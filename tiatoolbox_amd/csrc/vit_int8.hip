@@ -55,6 +55,108 @@ struct Int8 {
     }
 };
 
+namespace {
+
+// ---- calibration statistics -----------------------------------------------------------------------------------------------------
+// amax[j] = max(amax[j], max over rows |v[r, j]|) of the float32 values v a producer above holds.  Magnitudes travel as the bit
+// pattern of |v|, compared as unsigned integers: the order of the non-negative floats, with every NaN above +inf, so a NaN in a column
+// stays there.  A workgroup keeps the column maxima of all the rows it visits in LDS (vector v of a row at [j][v], so that a wave's
+// 64 lanes touch 64 consecutive words) and ends with one atomic maximum per column that saw anything but zeros.
+constexpr int ABSMAX_BLOCKS = 1024;  // at most this many workgroups; a wave strides over the rows
+
+__device__ __forceinline__ void column_max_clear(unsigned* cm, int c) {
+    for (int i = threadIdx.x; i < c; i += ET) cm[i] = 0u;
+    __syncthreads();
+}
+
+template <int VPL>
+__device__ __forceinline__ void column_max_row(const float (&f)[VPL][8], int lane, int cv, unsigned* cm) {
+#pragma unroll
+    for (int i = 0; i < VPL; ++i) {
+        const int v = lane + 64 * i;
+        if (v < cv) {
+#pragma unroll
+            for (int j = 0; j < 8; ++j) atomicMax(cm + j * cv + v, __float_as_uint(f[i][j]) & 0x7fffffffu);
+        }
+    }
+}
+
+__device__ __forceinline__ void column_max_flush(const unsigned* cm, int c, unsigned* __restrict__ amax) {
+    __syncthreads();
+    const int cv = c >> 3;
+    for (int col = threadIdx.x; col < c; col += ET) {
+        const unsigned m = cm[(col & 7) * cv + (col >> 3)];
+        if (m != 0u) atomicMax(amax + col, m);
+    }
+}
+
+template <bool BF, int VPL>
+__global__ __launch_bounds__(ET) void layernorm_rows_absmax_kernel(const unsigned short* __restrict__ x, long stride,
+                                                                    const float* __restrict__ gamma, const float* __restrict__ beta,
+                                                                    float eps, long rows, int c, unsigned* __restrict__ amax) {
+    __shared__ unsigned cm[VPL * 512];
+    column_max_clear(cm, c);
+    const int lane = threadIdx.x & 63;
+    for (long row = (long)blockIdx.x * (ET / 64) + (threadIdx.x >> 6); row < rows; row += (long)gridDim.x * (ET / 64)) {
+        float f[VPL][8];
+        layernorm_row_values<BF, VPL>(x + row * stride, gamma, beta, eps, c, lane, f);
+        column_max_row<VPL>(f, lane, c >> 3, cm);
+    }
+    column_max_flush(cm, c, amax);
+}
+
+template <bool BF, bool SWIGLU, int VPL>
+__global__ __launch_bounds__(ET) void act_rows_absmax_kernel(const unsigned short* __restrict__ x, long rows, int hidden,
+                                                              unsigned* __restrict__ amax) {
+    __shared__ unsigned cm[VPL * 512];
+    column_max_clear(cm, hidden);
+    const int lane = threadIdx.x & 63;
+    for (long row = (long)blockIdx.x * (ET / 64) + (threadIdx.x >> 6); row < rows; row += (long)gridDim.x * (ET / 64)) {
+        float f[VPL][8];
+        act_row_values<BF, SWIGLU, VPL>(x + row * (SWIGLU ? 2L : 1L) * hidden, hidden, lane, f);
+        column_max_row<VPL>(f, lane, hidden >> 3, cm);
+    }
+    column_max_flush(cm, hidden, amax);
+}
+
+inline unsigned absmax_blocks(int64_t rows) {
+    const int64_t blocks = (rows + ET / 64 - 1) / (ET / 64);
+    return (unsigned)(blocks < ABSMAX_BLOCKS ? blocks : ABSMAX_BLOCKS);
+}
+
+inline int layernorm_rows_absmax(const void* d_x, int64_t row_stride, const float* d_gamma, const float* d_beta, float eps, float* d_amax,
+                                 int64_t rows, int64_t c, int32_t dtype, void* stream) {
+    if (!d_x || !d_gamma || !d_beta || !d_amax || rows <= 0 || c <= 0 || !(eps >= 0.0f)) return TIA_EINVAL;
+    if (!is_half(dtype)) return TIA_EINVAL;
+    if ((c & 15) != 0 || c > 8192) return TIA_ESIZE;
+    if (row_stride < c || (row_stride & 7) != 0) return TIA_EINVAL;
+    if (misaligned({d_x, d_gamma, d_beta, d_amax})) return TIA_EINVAL;
+    if (rows > (int64_t(1) << 40)) return TIA_ESIZE;
+    for_row_width(dtype, c, [&](auto bf, auto vpl) {
+        hipLaunchKernelGGL((layernorm_rows_absmax_kernel<decltype(bf)::value, decltype(vpl)::value>), dim3(absmax_blocks(rows)), dim3(ET), 0,
+                           (hipStream_t)stream, static_cast<const unsigned short*>(d_x), (long)row_stride, d_gamma, d_beta, eps, (long)rows,
+                           (int)c, reinterpret_cast<unsigned*>(d_amax));
+    });
+    return launched();
+}
+
+template <bool SWIGLU>
+int act_rows_absmax(const void* d_x, float* d_amax, int64_t rows, int64_t hidden, int32_t dtype, void* stream) {
+    if (!d_x || !d_amax || rows <= 0 || hidden <= 0) return TIA_EINVAL;
+    if (!is_half(dtype)) return TIA_EINVAL;
+    if ((hidden & 15) != 0 || hidden > 8192) return TIA_ESIZE;
+    if (misaligned({d_x, d_amax})) return TIA_EINVAL;
+    if (rows > (int64_t(1) << 40)) return TIA_ESIZE;
+    for_row_width(dtype, hidden, [&](auto bf, auto vpl) {
+        hipLaunchKernelGGL((act_rows_absmax_kernel<decltype(bf)::value, SWIGLU, decltype(vpl)::value>), dim3(absmax_blocks(rows)), dim3(ET), 0,
+                           (hipStream_t)stream, static_cast<const unsigned short*>(d_x), (long)rows, (int)hidden,
+                           reinterpret_cast<unsigned*>(d_amax));
+    });
+    return launched();
+}
+
+}  // namespace
+
 }  // namespace tia::q8
 
 using tia::q8::Int8;
@@ -81,4 +183,29 @@ extern "C" int tia_gelu_rows_qi8(const void* d_x, void* d_q, float* d_scale, int
 
 extern "C" int tia_swiglu_rows_qi8(const void* d_x, void* d_q, float* d_scale, int64_t rows, int64_t hidden, int32_t dtype, void* stream) {
     return tia::q8::act_rows<Int8, true>(d_x, d_q, d_scale, rows, hidden, dtype, stream);
+}
+
+// ---- per-input-channel smoothing of fc2's input, and the calibration statistics of all three producer sites --------
+
+extern "C" int tia_gelu_rows_qi8_smooth(const void* d_x, const float* d_inv_smooth, void* d_q, float* d_scale, int64_t rows,
+                                         int64_t hidden, int32_t dtype, void* stream) {
+    return tia::q8::act_rows_smooth<Int8, false>(d_x, d_inv_smooth, d_q, d_scale, rows, hidden, dtype, stream);
+}
+
+extern "C" int tia_swiglu_rows_qi8_smooth(const void* d_x, const float* d_inv_smooth, void* d_q, float* d_scale, int64_t rows,
+                                           int64_t hidden, int32_t dtype, void* stream) {
+    return tia::q8::act_rows_smooth<Int8, true>(d_x, d_inv_smooth, d_q, d_scale, rows, hidden, dtype, stream);
+}
+
+extern "C" int tia_layernorm_rows_absmax_h(const void* d_x, int64_t row_stride, const float* d_gamma, const float* d_beta, float eps,
+                                           float* d_amax, int64_t rows, int64_t c, int32_t dtype, void* stream) {
+    return tia::q8::layernorm_rows_absmax(d_x, row_stride, d_gamma, d_beta, eps, d_amax, rows, c, dtype, stream);
+}
+
+extern "C" int tia_gelu_rows_absmax_h(const void* d_x, float* d_amax, int64_t rows, int64_t hidden, int32_t dtype, void* stream) {
+    return tia::q8::act_rows_absmax<false>(d_x, d_amax, rows, hidden, dtype, stream);
+}
+
+extern "C" int tia_swiglu_rows_absmax_h(const void* d_x, float* d_amax, int64_t rows, int64_t hidden, int32_t dtype, void* stream) {
+    return tia::q8::act_rows_absmax<true>(d_x, d_amax, rows, hidden, dtype, stream);
 }

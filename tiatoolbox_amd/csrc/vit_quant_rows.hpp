@@ -184,18 +184,12 @@ __device__ __forceinline__ void quantise_row(const float (&f)[VPL][8], int lane,
     if (lane == 0) *srow = s;
 }
 
-// One wave per row, the row in registers (layernorm_rows_h_kernel's form and arithmetic: the mean, then the variance of the centred
-// values, the affine as one fmaf), four rows per workgroup; what would be rounded to half there is quantised here.
-template <class F, bool BF, int VPL>
-__global__ __launch_bounds__(ET) void layernorm_rows_kernel(const unsigned short* __restrict__ x, long stride, const float* __restrict__ gamma,
-                                                             const float* __restrict__ beta, float eps, long rows, int c,
-                                                             typename F::code_t* __restrict__ q, float* __restrict__ s) {
-    const int lane = threadIdx.x & 63;
-    const long row = (long)blockIdx.x * (ET / 64) + (threadIdx.x >> 6);
-    if (row >= rows) return;  // whole waves leave: the exchanges below stay inside a wave
+// The float32 values of one LayerNorm row in a wave's registers (layernorm_rows_h_kernel's form and arithmetic: the mean, then the
+// variance of the centred values, the affine as one fmaf): f holds this lane's vectors lane + 64 i, below cv = c / 8.
+template <bool BF, int VPL>
+__device__ __forceinline__ void layernorm_row_values(const unsigned short* __restrict__ xr, const float* __restrict__ gamma,
+                                                     const float* __restrict__ beta, float eps, int c, int lane, float (&f)[VPL][8]) {
     const int cv = c >> 3;
-    const unsigned short* xr = x + row * stride;
-    float f[VPL][8];
     float sum = 0.0f;
 #pragma unroll
     for (int i = 0; i < VPL; ++i) {
@@ -229,19 +223,26 @@ __global__ __launch_bounds__(ET) void layernorm_rows_kernel(const unsigned short
             for (int j = 0; j < 8; ++j) f[i][j] = fmaf(f[i][j] * rstd, gm[j], bt[j]);
         }
     }
-    quantise_row<F, VPL>(f, lane, cv, q + row * (long)c, s + row);
 }
 
-// The activation between fc1 and fc2, one wave per row of `hidden` outputs.  SWIGLU: the input row is [gate H | value H].
-template <class F, bool BF, bool SWIGLU, int VPL>
-__global__ __launch_bounds__(ET) void act_rows_kernel(const unsigned short* __restrict__ x, long rows, int hidden,
-                                                       typename F::code_t* __restrict__ q, float* __restrict__ s) {
+// One wave per row, the row in registers, four rows per workgroup; what layernorm_rows_h_kernel would round to half is quantised here.
+template <class F, bool BF, int VPL>
+__global__ __launch_bounds__(ET) void layernorm_rows_kernel(const unsigned short* __restrict__ x, long stride, const float* __restrict__ gamma,
+                                                             const float* __restrict__ beta, float eps, long rows, int c,
+                                                             typename F::code_t* __restrict__ q, float* __restrict__ s) {
     const int lane = threadIdx.x & 63;
     const long row = (long)blockIdx.x * (ET / 64) + (threadIdx.x >> 6);
-    if (row >= rows) return;
-    const int cv = hidden >> 3;
-    const unsigned short* xr = x + row * (SWIGLU ? 2L : 1L) * hidden;
+    if (row >= rows) return;  // whole waves leave: the exchanges below stay inside a wave
     float f[VPL][8];
+    layernorm_row_values<BF, VPL>(x + row * stride, gamma, beta, eps, c, lane, f);
+    quantise_row<F, VPL>(f, lane, c >> 3, q + row * (long)c, s + row);
+}
+
+// The float32 values of the activation between fc1 and fc2 for one row of `hidden` outputs.  SWIGLU: the input row is
+// [gate H | value H].
+template <bool BF, bool SWIGLU, int VPL>
+__device__ __forceinline__ void act_row_values(const unsigned short* __restrict__ xr, int hidden, int lane, float (&f)[VPL][8]) {
+    const int cv = hidden >> 3;
 #pragma unroll
     for (int i = 0; i < VPL; ++i) {
         const int v = lane + 64 * i;
@@ -256,6 +257,42 @@ __global__ __launch_bounds__(ET) void act_rows_kernel(const unsigned short* __re
 #pragma unroll
                 for (int j = 0; j < 8; ++j) f[i][j] = 0.5f * f[i][j] * (1.0f + erff(f[i][j] * 0.70710678118654752440f));
             }
+        }
+    }
+}
+
+// The activation, one wave per row, quantised.
+template <class F, bool BF, bool SWIGLU, int VPL>
+__global__ __launch_bounds__(ET) void act_rows_kernel(const unsigned short* __restrict__ x, long rows, int hidden,
+                                                       typename F::code_t* __restrict__ q, float* __restrict__ s) {
+    const int lane = threadIdx.x & 63;
+    const long row = (long)blockIdx.x * (ET / 64) + (threadIdx.x >> 6);
+    if (row >= rows) return;
+    float f[VPL][8];
+    act_row_values<BF, SWIGLU, VPL>(x + row * (SWIGLU ? 2L : 1L) * hidden, hidden, lane, f);
+    quantise_row<F, VPL>(f, lane, hidden >> 3, q + row * (long)hidden, s + row);
+}
+
+// The same with per-input-channel smoothing: every float32 value is multiplied by inv_smooth[channel] -- one float32
+// multiplication, exact for the power-of-two scales the graph makes -- before the row maximum and the codes.
+template <class F, bool BF, bool SWIGLU, int VPL>
+__global__ __launch_bounds__(ET) void act_rows_smooth_kernel(const unsigned short* __restrict__ x, const float* __restrict__ inv_smooth,
+                                                              long rows, int hidden, typename F::code_t* __restrict__ q,
+                                                              float* __restrict__ s) {
+    const int lane = threadIdx.x & 63;
+    const long row = (long)blockIdx.x * (ET / 64) + (threadIdx.x >> 6);
+    if (row >= rows) return;
+    const int cv = hidden >> 3;
+    float f[VPL][8];
+    act_row_values<BF, SWIGLU, VPL>(x + row * (SWIGLU ? 2L : 1L) * hidden, hidden, lane, f);
+#pragma unroll
+    for (int i = 0; i < VPL; ++i) {
+        const int v = lane + 64 * i;
+        if (v < cv) {
+            float sm[8];
+            load8_f32(inv_smooth + 8 * v, sm);
+#pragma unroll
+            for (int j = 0; j < 8; ++j) f[i][j] *= sm[j];
         }
     }
     quantise_row<F, VPL>(f, lane, cv, q + row * (long)hidden, s + row);
@@ -390,6 +427,23 @@ int act_rows(const void* d_x, void* d_q, float* d_scale, int64_t rows, int64_t h
         hipLaunchKernelGGL((act_rows_kernel<F, decltype(bf)::value, SWIGLU, decltype(vpl)::value>), dim3((unsigned)blocks), dim3(ET), 0, (hipStream_t)stream,
                            static_cast<const unsigned short*>(d_x), (long)rows, (int)hidden, static_cast<typename F::code_t*>(d_q),
                            d_scale);
+    });
+    return launched();
+}
+
+template <class F, bool SWIGLU>
+int act_rows_smooth(const void* d_x, const float* d_inv_smooth, void* d_q, float* d_scale, int64_t rows, int64_t hidden, int32_t dtype,
+                    void* stream) {
+    if (!d_x || !d_inv_smooth || !d_q || !d_scale || rows <= 0 || hidden <= 0) return TIA_EINVAL;
+    if (!is_half(dtype)) return TIA_EINVAL;
+    if ((hidden & 15) != 0 || hidden > 8192) return TIA_ESIZE;
+    if (misaligned({d_x, d_inv_smooth, d_q, d_scale})) return TIA_EINVAL;
+    const long blocks = (rows + ET / 64 - 1) / (ET / 64);
+    if (blocks > 0x7fffffffL) return TIA_ESIZE;
+    for_row_width(dtype, hidden, [&](auto bf, auto vpl) {
+        hipLaunchKernelGGL((act_rows_smooth_kernel<F, decltype(bf)::value, SWIGLU, decltype(vpl)::value>), dim3((unsigned)blocks), dim3(ET), 0,
+                           (hipStream_t)stream, static_cast<const unsigned short*>(d_x), d_inv_smooth, (long)rows, (int)hidden,
+                           static_cast<typename F::code_t*>(d_q), d_scale);
     });
     return launched();
 }

@@ -57,7 +57,11 @@ matrix instruction) and steps 1, 5 and 7 on their quantising forms (``tia_layern
 ``tia_linear_int8_rows`` (W8A8 on ``v_mfma_i32_16x16x64_i8``, one scale per token and per output channel, exact int32 accumulation)
 and the same three steps to ``tia_layernorm_rows_qi8`` / ``tia_gelu_rows_qi8`` / ``tia_swiglu_rows_qi8``.  A uniform 8-bit grid in
 place of e4m3's 3-bit mantissa: closer than FP8 on rows without extreme outliers, worse with an outlier channel.
-:func:`quantize_rows_int8` states the recipe; DESIGN 4.38.
+:func:`quantize_rows_int8` states the recipe; DESIGN 4.38.  ``smoothing=scales`` beside it (the engines' ``int8_smoothing`` /
+``int8_calibration``) divides each routed layer's input by a power of two per channel and multiplies the weight column by it
+(:func:`int8_smoothing_scales` states the recipe, :func:`calibrate_int8_smoothing` measures the statistics on the bfloat16 graph with
+``tia_*_rows_absmax_h``): folded into the LayerNorm affine for ``qkv`` / ``fc1``, ``tia_gelu_rows_qi8_smooth`` /
+``tia_swiglu_rows_qi8_smooth`` in front of ``fc2``; DESIGN 4.41.
 
 ``prepare(torch.float32, linear_dtype="bfloat16x3")`` (the engines' ``compute_dtype="bfloat16x3"``) is the float32 route of the same
 graph: activations, residual stream and row arithmetic in float32; every Linear on ``tia_conv2d_bf16x3_nhwc_f32`` (both operands
@@ -732,10 +736,134 @@ def hip_act_rows_qi8(x: torch.Tensor, *, swiglu: bool) -> QuantRows:
     return _act_quant_rows(_INT8, "tia_gelu_rows_qi8", "tia_swiglu_rows_qi8", x, swiglu)
 
 
+def _smooth_vector(name: str, what: str, v: torch.Tensor, x: torch.Tensor, width: int) -> None:
+    if not (v.is_cuda and v.device == x.device and v.dtype == torch.float32 and v.dim() == 1 and v.numel() == width and v.is_contiguous()):
+        msg = f"{name} takes {what} as {width} contiguous float32 values on {x.device}; got {tuple(v.shape)}, {v.dtype} on {v.device}."
+        raise ValueError(msg)
+
+
+def hip_act_rows_qi8_smooth(x: torch.Tensor, inv_smooth: torch.Tensor, *, swiglu: bool) -> QuantRows:
+    """:func:`hip_act_rows_qi8` with the float32 activation multiplied by ``inv_smooth[channel]`` (float32 ``[H]``) before the row
+    maximum and the codes (``tia_gelu_rows_qi8_smooth`` / ``tia_swiglu_rows_qi8_smooth``): ``fc2``'s producer under smoothing."""
+    from tiatoolbox_amd import _lib
+
+    name = "hip_act_rows_qi8_smooth"
+    _half_tokens(name, x)
+    if x.dim() != 3 or (swiglu and x.shape[-1] % 2 != 0):  # noqa: PLR2004
+        msg = f"{name} takes [n, S, H] (GELU) or [n, S, 2H] (SwiGLU) tokens; got {tuple(x.shape)}."
+        raise ValueError(msg)
+    n, s, c = x.shape
+    hidden = c // 2 if swiglu else c
+    _smooth_vector(name, "inv_smooth", inv_smooth, x, hidden)
+    codes = torch.empty((n, s, hidden), dtype=torch.int8, device=x.device)
+    scales = torch.empty((n * s,), dtype=torch.float32, device=x.device)
+    entry = "tia_swiglu_rows_qi8_smooth" if swiglu else "tia_gelu_rows_qi8_smooth"
+    with torch.cuda.device(x.device):
+        rc = getattr(_lib.load(), entry)(x.data_ptr(), inv_smooth.data_ptr(), codes.data_ptr(), scales.data_ptr(), n * s, hidden,
+                                         _DT[x.dtype], _lib.current_stream())
+    _lib.check(rc, entry)
+    return QuantRows(codes, scales)
+
+
+def hip_layernorm_rows_absmax_h(x: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, amax: torch.Tensor, *, eps: float) -> torch.Tensor:
+    """``amax[j] = max(amax[j], max |LayerNorm(x)[.., j]|)`` over every row of ``[n, S, D]`` tokens, of the float32 values
+    :func:`hip_layernorm_rows_qi8` quantises (``tia_layernorm_rows_absmax_h``).  ``amax`` (float32 ``[D]``, zeroed by the caller) is
+    updated in place and returned; a NaN stays in its column."""
+    from tiatoolbox_amd import _lib
+
+    name = "hip_layernorm_rows_absmax_h"
+    _half_tokens(name, x, gamma.numel())
+    if x.dim() != 3 or gamma.dtype != torch.float32 or beta.dtype != torch.float32 or beta.numel() != gamma.numel():  # noqa: PLR2004
+        msg = f"{name} takes [n, S, D] tokens and a float32 affine of D values; got {tuple(x.shape)}, {tuple(gamma.shape)}."
+        raise ValueError(msg)
+    n, s, d = x.shape
+    _smooth_vector(name, "amax", amax, x, d)
+    with torch.cuda.device(x.device):
+        rc = _lib.load().tia_layernorm_rows_absmax_h(x.data_ptr(), d, gamma.data_ptr(), beta.data_ptr(), float(eps), amax.data_ptr(), n * s, d,
+                                                     _DT[x.dtype], _lib.current_stream())
+    _lib.check(rc, "tia_layernorm_rows_absmax_h")
+    return amax
+
+
+def hip_act_rows_absmax_h(x: torch.Tensor, amax: torch.Tensor, *, swiglu: bool) -> torch.Tensor:
+    """The same statistics of the float32 values :func:`hip_act_rows_qi8` quantises, on ``[n, S, H]`` (exact GELU) or ``[n, S, 2H]``
+    (packed SwiGLU) tokens: ``amax`` float32 ``[H]`` (``tia_gelu_rows_absmax_h`` / ``tia_swiglu_rows_absmax_h``)."""
+    from tiatoolbox_amd import _lib
+
+    name = "hip_act_rows_absmax_h"
+    _half_tokens(name, x)
+    if x.dim() != 3 or (swiglu and x.shape[-1] % 2 != 0):  # noqa: PLR2004
+        msg = f"{name} takes [n, S, H] (GELU) or [n, S, 2H] (SwiGLU) tokens; got {tuple(x.shape)}."
+        raise ValueError(msg)
+    n, s, c = x.shape
+    hidden = c // 2 if swiglu else c
+    _smooth_vector(name, "amax", amax, x, hidden)
+    entry = "tia_swiglu_rows_absmax_h" if swiglu else "tia_gelu_rows_absmax_h"
+    with torch.cuda.device(x.device):
+        rc = getattr(_lib.load(), entry)(x.data_ptr(), amax.data_ptr(), n * s, hidden, _DT[x.dtype], _lib.current_stream())
+    _lib.check(rc, entry)
+    return amax
+
+
+SMOOTH_EXP_MAX = 24  # the smoothing scales are 2^e with |e| <= 24
+
+
+def int8_smoothing_scales(amax_x: torch.Tensor, amax_w: torch.Tensor, alpha: float = 0.5) -> torch.Tensor:
+    """The smoothing scale of every input channel of one INT8 layer (SmoothQuant's balance between activation and weight ranges, on
+    powers of two): ``s[j] = 2^clamp(round(alpha log2 a[j] - (1 - alpha) log2 w[j]), -24, 24)`` in float64, with
+    ``a = amax_x`` the calibrated abs-max of the layer's float32 input per channel and ``w = amax_w = max_o |W[o, j]|`` of the
+    float32 weights that are packed; ``s[j] = 1`` where ``a[j] == 0`` or ``w[j] == 0`` (a SwiGLU pad lane).  A power of two makes
+    ``x / s`` and ``W * s`` exact in float32.  ``alpha`` in (0, 1]; a non-finite ``amax_x`` is a ``ValueError`` (the calibration data
+    produced non-finite activations).  Returns float32 ``[K]`` on the CPU."""
+    alpha = _checked_alpha(alpha)
+    a, w = amax_x.detach().double().cpu().reshape(-1), amax_w.detach().double().cpu().reshape(-1)
+    if a.numel() != w.numel():
+        msg = f"int8_smoothing_scales: {a.numel()} activation maxima beside {w.numel()} weight columns."
+        raise ValueError(msg)
+    if not bool(torch.isfinite(a).all()) or bool((a < 0).any()):
+        msg = (f"int8_smoothing_scales: {int((~torch.isfinite(a)).sum())} of {a.numel()} calibrated activation maxima are not finite "
+               "(the calibration data produced non-finite activations).")
+        raise ValueError(msg)
+    if not bool(torch.isfinite(w).all()) or bool((w < 0).any()):
+        msg = "int8_smoothing_scales: the weight column maxima must be finite and non-negative."
+        raise ValueError(msg)
+    live = (a > 0) & (w > 0)
+    one = torch.ones_like(a)
+    e = alpha * torch.log2(torch.where(live, a, one)) - (1.0 - alpha) * torch.log2(torch.where(live, w, one))
+    e = torch.round(e).clamp(-SMOOTH_EXP_MAX, SMOOTH_EXP_MAX)
+    return torch.where(live, torch.exp2(e), one).to(torch.float32)
+
+
+def _checked_alpha(alpha) -> float:  # noqa: ANN001
+    if isinstance(alpha, bool) or not isinstance(alpha, (int, float)) or not 0.0 < float(alpha) <= 1.0:
+        msg = f"int8 smoothing: alpha lies in (0, 1] (0.5 balances activations and weights); got {alpha!r}."
+        raise ValueError(msg)
+    return float(alpha)
+
+
+def _checked_smoothing_scale(name: str, s: torch.Tensor, width: int) -> torch.Tensor:
+    """One layer's entry of a ``smoothing`` dict as float32 ``[width]`` on the CPU, or the ``ValueError`` that names it."""
+    if not isinstance(s, torch.Tensor) or s.dim() != 1 or s.numel() != width or not s.is_floating_point():
+        got = f"{tuple(s.shape)}, {s.dtype}" if isinstance(s, torch.Tensor) else type(s).__name__
+        msg = f"FusedViT.prepare: smoothing[{name!r}] must hold one floating-point scale per input channel, [{width}]; got {got}."
+        raise ValueError(msg)
+    s = s.detach().to(torch.float32).cpu().contiguous()
+    mantissa, _ = torch.frexp(s)
+    bad = ~(torch.isfinite(s) & (s > 0) & (mantissa == 0.5))  # noqa: PLR2004
+    if bool(bad.any()):
+        j = int(torch.nonzero(bad)[0])
+        msg = (f"FusedViT.prepare: smoothing[{name!r}] must hold finite positive powers of two (they keep x / s and W * s exact); "
+               f"channel {j} is {float(s[j])!r} ({int(bad.sum())} such of {width}).")
+        raise ValueError(msg)
+    return s
+
+
 class _LinearInt8(_LinearQuant):
-    """:class:`_LinearQuant` on the INT8 kernel, called on int8 :class:`QuantRows`."""
+    """:class:`_LinearQuant` on the INT8 kernel, called on int8 :class:`QuantRows`.  ``inv_smooth`` (float32 ``[cin]``) is set on an
+    ``fc2`` whose producer applies the layer's smoothing scales (``hip_act_rows_qi8_smooth``)."""
 
     fmt = _INT8
+    inv_smooth: torch.Tensor | None = None
 
 
 class _Linear:
@@ -1004,8 +1132,12 @@ class FusedViT(nn.Module):
         self.half_dtype: torch.dtype | None = None
         self.linear_dtype: str | None = None
         self.residual_dtype: str | None = None
+        self.smoothing: dict[str, torch.Tensor] | None = None  # the per-input-channel scales `prepare` applied (layer name -> [cin])
+        self._taps: dict[str, torch.Tensor] | None = None      # calibration: layer name -> abs-max of its float32 input, per channel
+        self._amax_w: dict[str, torch.Tensor] = {}             # calibration: layer name -> max_o |W[o, j]| of the weights to pack
 
-    def prepare(self, dtype: torch.dtype, linear_dtype: str | None = None, residual_dtype: str | None = None) -> None:
+    def prepare(self, dtype: torch.dtype, linear_dtype: str | None = None, residual_dtype: str | None = None,
+                smoothing: dict[str, torch.Tensor] | None = None) -> None:
         """Pack every GEMM's float32 (folded) weights for ``tia_conv2d_nhwc_h`` in ``dtype`` (rounded once, after the folding): call
         this on the device, BEFORE ``.to(dtype)``.  Biases, LayerNorm affines, the class token and the position table stay float32
         in plain attributes that the cast does not reach.
@@ -1022,6 +1154,15 @@ class FusedViT(nn.Module):
         layer takes the other's.  A float16 carrier, a ``residual_dtype`` beside it and a float32 carrier are refused, each with a
         message of its own, before any device work.
 
+        ``smoothing=scales`` beside ``linear_dtype="int8"`` (``scales`` from :func:`calibrate_int8_smoothing`, layer
+        name -> float32 ``[cin]`` powers of two) divides the input of every routed layer by ``s`` per channel and multiplies its
+        weight columns by ``s`` in float32 before they are packed -- both exact, so the layer's real-valued function is unchanged
+        while an outlier channel no longer sets the token's scale.  For ``qkv`` / ``fc1`` the division is folded into the float32
+        LayerNorm affine; ``fc2``'s producer becomes ``hip_act_rows_qi8_smooth``.  ``None`` is the unsmoothed path; all-ones scales
+        reproduce it bit for bit.  Beside any other ``linear_dtype``, with a key missing for a routed layer, a wrong length or a scale
+        that is no finite positive power of two it is a ``ValueError``, raised before anything is padded or packed; keys of layers
+        that stay on the half kernel are ignored with one ``info`` line.  ``self.smoothing`` holds what was applied.
+
         ``residual_dtype="float32"`` keeps the residual stream ``x`` in float32 from token assembly to the final norm, as the float32
         module under ``torch.autocast`` does: ``proj`` and ``fc2`` write half branches without a residual, and one pass
         (``tia_add_layernorm_rows_f32``) adds the branch to ``x`` in float32 and normalises the sum.  ``None`` (the
@@ -1036,6 +1177,11 @@ class FusedViT(nn.Module):
         ``info`` line names them); a packed SwiGLU whose ``fc1`` is off the multiple is first padded with exact zero lanes.
         ``half_dtype`` stays ``None``.  ``torch.float32`` without that keyword, with ``"float8_e4m3"`` or with ``residual_dtype`` is
         refused as before; ``"bfloat16x3"`` with a half ``dtype`` is refused too."""
+        if smoothing is not None and linear_dtype != INT8_LINEAR:
+            msg = (f"FusedViT.prepare: smoothing= scales the inputs and weight columns of the layers on the INT8 GEMM and goes with "
+                   f"linear_dtype={INT8_LINEAR!r} only (the FP8 route's floating grid does not need it, the half and float32 routes do "
+                   f"not quantise); got linear_dtype={linear_dtype!r}.")
+            raise ValueError(msg)
         if linear_dtype == SPLIT_LINEAR and dtype == torch.float32 and residual_dtype is None:
             if self.half_dtype is not None or self.linear_dtype is not None:
                 msg = "FusedViT.prepare packs once, from the float32 weights; build a new FusedViT for another dtype."
@@ -1078,7 +1224,7 @@ class FusedViT(nn.Module):
                 msg = (f"FusedViT.prepare: linear_dtype={INT8_LINEAR!r} runs on the bfloat16 carrier only (an fp16 carrier is not built); "
                        f"got {dtype}.")
                 raise ValueError(msg)
-            self._route_int8()
+            self._route_int8(smoothing)
         elif linear_dtype is not None:
             if linear_dtype != FP8_LINEAR:
                 msg = f"FusedViT.prepare: linear_dtype is None or {FP8_LINEAR!r}; got {linear_dtype!r}."
@@ -1099,29 +1245,82 @@ class FusedViT(nn.Module):
         (``_route_quant``)."""
         self._route_quant(_LinearFp8)
 
-    def _route_int8(self) -> None:
+    def _route_int8(self, smoothing: dict[str, torch.Tensor] | None = None) -> None:
         """``qkv`` / ``fc1`` / ``fc2`` of every block to :class:`_LinearInt8` where ``tia_linear_int8_serves`` takes the shape
-        (``_route_quant``)."""
-        self._route_quant(_LinearInt8)
+        (``_route_quant``), with the ``smoothing`` scales applied where given."""
+        self._route_quant(_LinearInt8, smoothing)
 
-    def _route_quant(self, linear_cls: type[_LinearQuant]) -> None:
-        """``qkv`` / ``fc1`` / ``fc2`` of every block to ``linear_cls`` where its format's ``serves`` takes the shape.  A packed SwiGLU
-        half off the kernels' multiple of 128 is first padded up to it with ``pad_swiglu``'s exact zero lanes (at or above
-        ``SWIGLU_PAD_FLOOR`` only, as there)."""
-        fmt = linear_cls.fmt
-        kept: list[str] = []
+    def _quant_padded_half(self, fc2: _Linear) -> int | None:
+        """The width the quantised routes pad a packed SwiGLU half to (the kernels' multiple of 128), or ``None`` where they leave
+        it: at or above ``SWIGLU_PAD_FLOOR`` only, as ``pad_swiglu`` does."""
+        target = -(-fc2.cin // 128) * 128
+        return target if self.swiglu and target != fc2.cin and fc2.cin >= SWIGLU_PAD_FLOOR else None
+
+    def _pad_swiglu_for_quant(self) -> None:
         for layer in self.layers:
             fc1, fc2 = layer["fc1"], layer["fc2"]
-            target = -(-fc2.cin // 128) * 128
-            if self.swiglu and target != fc2.cin and fc2.cin >= SWIGLU_PAD_FLOOR:
+            target = self._quant_padded_half(fc2)
+            if target is not None:
                 fc1_w, fc1_b, fc2_w = pad_swiglu_to(fc1.weight32, fc1.bias32, fc2.weight32, target)
                 layer["fc1"], layer["fc2"] = _Linear(fc1.name, fc1_w, fc1_b), _Linear(fc2.name, fc2_w, fc2.bias32)
+
+    def _checked_smoothing(self, fmt: _QuantFormat, smoothing: dict[str, torch.Tensor]) -> dict[str, torch.Tensor]:
+        """The entries of ``smoothing`` for the layers ``_route_quant`` will route, checked, as float32 CPU tensors -- worked out from
+        the shapes alone, before anything is padded or packed."""
+        if not isinstance(smoothing, dict):
+            msg = (f"FusedViT.prepare: smoothing is a dict of layer name -> scales [cin] (calibrate_int8_smoothing's result); got "
+                   f"{type(smoothing).__name__}.")
+            raise ValueError(msg)
+        scales: dict[str, torch.Tensor] = {}
+        for layer in self.layers:
+            half = self._quant_padded_half(layer["fc2"])
+            for name in ("qkv", "fc1", "fc2"):
+                lin = layer[name]
+                cout = 2 * half if half is not None and name == "fc1" else lin.cout
+                cin = half if half is not None and name == "fc2" else lin.cin
+                if not fmt.fn("serves")(cout, cin):
+                    continue
+                if lin.name not in smoothing:
+                    msg = (f"FusedViT.prepare: smoothing has no scales for `{lin.name}` ({cin} -> {cout}), which goes on the {fmt.name} "
+                           f"GEMM; calibrate_int8_smoothing returns one entry per routed layer.")
+                    raise ValueError(msg)
+                scales[lin.name] = _checked_smoothing_scale(lin.name, smoothing[lin.name], cin)
+        ignored = sorted(str(k) for k in smoothing if k not in scales)
+        if ignored:
+            import logging
+
+            logging.getLogger("tiatoolbox_amd").info(
+                "FusedViT: smoothing scales of %d layer(s) that stay on the half kernel (neither smoothed nor quantised) are ignored: %s.",
+                len(ignored), ", ".join(ignored))
+        return scales
+
+    def _route_quant(self, linear_cls: type[_LinearQuant], smoothing: dict[str, torch.Tensor] | None = None) -> None:
+        """``qkv`` / ``fc1`` / ``fc2`` of every block to ``linear_cls`` where its format's ``serves`` takes the shape.  A packed SwiGLU
+        half off the kernels' multiple of 128 is first padded up to it with ``pad_swiglu``'s exact zero lanes (at or above
+        ``SWIGLU_PAD_FLOOR`` only, as there).  With ``smoothing``, a routed layer's weight columns are multiplied by its scales ``s``
+        in float32 (exact: powers of two) and its input divided by them: folded into the LayerNorm affine in front of ``qkv`` /
+        ``fc1`` (``gamma / s``, ``beta / s``), handed to ``fc2``'s producer as ``inv_smooth = 1 / s``."""
+        fmt = linear_cls.fmt
+        scales = self._checked_smoothing(fmt, smoothing) if smoothing is not None else None
+        kept: list[str] = []
+        self._pad_swiglu_for_quant()
+        for layer in self.layers:
             for name in ("qkv", "fc1", "fc2"):
                 lin = layer[name]
                 if fmt.fn("serves")(lin.cout, lin.cin):
-                    layer[name] = linear_cls(lin.name, lin.weight32, lin.bias32)
+                    weight, inv = lin.weight32, None
+                    if scales is not None:
+                        s = scales[lin.name].to(weight.device)
+                        weight, inv = weight * s, (1.0 / s).contiguous()
+                        if name != "fc2":
+                            norm = "norm1" if name == "qkv" else "norm2"
+                            layer[norm] = tuple((t * inv).contiguous() for t in layer[norm])
+                    layer[name] = linear_cls(lin.name, weight, lin.bias32)
+                    if inv is not None and name == "fc2":
+                        layer[name].inv_smooth = inv
                 else:
                     kept.append(f"{lin.name} ({lin.cin} -> {lin.cout})")
+        self.smoothing = scales
         if kept:
             import logging
 
@@ -1156,6 +1355,41 @@ class FusedViT(nn.Module):
             logging.getLogger("tiatoolbox_amd").info(
                 "FusedViT: the split-bf16 GEMM takes cin %% 16 == 0, cout %% 128 == 0 and weights with an exact split into normal bf16 "
                 "numbers; %d layer(s) run on the float32 GEMM (tia_conv2d_nhwc_f32): %s.", len(kept), ", ".join(kept))
+
+    def begin_int8_calibration(self) -> None:
+        """Make this (unprepared) graph the calibration graph of :func:`calibrate_int8_smoothing`: the bfloat16 hand-written graph
+        (``prepare(torch.bfloat16)``) with the INT8 route's SwiGLU padding, whose forward also accumulates, for every layer the INT8
+        GEMM will serve, the per-channel abs-max of the float32 value its producer holds (``hip_layernorm_rows_absmax_h`` /
+        ``hip_act_rows_absmax_h``).  The weight column maxima are taken here, from the float32 weights ``prepare`` would pack."""
+        if self.half_dtype is not None or self.linear_dtype is not None:
+            msg = "FusedViT.begin_int8_calibration starts from the float32 weights: build a new FusedViT (prepare packs once)."
+            raise ValueError(msg)
+        self._pad_swiglu_for_quant()
+        taps: dict[str, torch.Tensor] = {}
+        for layer in self.layers:
+            for name in ("qkv", "fc1", "fc2"):
+                lin = layer[name]
+                if _INT8.fn("serves")(lin.cout, lin.cin):
+                    self._amax_w[lin.name] = lin.weight32.abs().amax(dim=0).cpu()
+                    taps[lin.name] = torch.zeros(lin.cin, dtype=torch.float32, device=lin.weight32.device)
+        self.prepare(torch.bfloat16)
+        self._taps = taps
+
+    def int8_calibration_scales(self, alpha: float = 0.5) -> dict[str, torch.Tensor]:
+        """:func:`int8_smoothing_scales` of every tapped layer from what the forwards since ``begin_int8_calibration`` have seen."""
+        alpha = _checked_alpha(alpha)
+        if not self._taps:
+            msg = ("FusedViT.int8_calibration_scales: no layer of this model goes on the INT8 GEMM (or begin_int8_calibration was not "
+                   "called): there is nothing to smooth.")
+            raise ValueError(msg)
+        scales = {}
+        for name, tap in self._taps.items():
+            try:
+                scales[name] = int8_smoothing_scales(tap, self._amax_w[name], alpha)
+            except ValueError as exc:
+                msg = f"calibrate_int8_smoothing: `{name}`: {exc}"
+                raise ValueError(msg) from exc
+        return scales
 
     def _forward_f32(self, imgs: torch.Tensor) -> torch.Tensor:
         """The float32 route (``linear_dtype="bfloat16x3"``): the module's block sequence on float32 tensors --
@@ -1273,7 +1507,11 @@ class FusedViT(nn.Module):
         else:
             x = hip_vit_assemble_tokens_h(tok, self._cls32, pos)
         s = x.shape[1]
+        taps = self._taps if self._taps is not None else {}  # (calibration only: the float32 inputs of the layers to smooth)
+
         def norm_for(linear: _Linear | _LinearQuant, norm: tuple[torch.Tensor, torch.Tensor]) -> torch.Tensor | QuantRows:
+            if linear.name in taps:
+                hip_layernorm_rows_absmax_h(x, *norm, taps[linear.name], eps=LN_EPS)
             if isinstance(linear, _LinearQuant):  # the same pass over x, codes + scales out
                 return linear.fmt.fn("layernorm")(x, *norm, eps=LN_EPS)
             return hip_layernorm_rows_h(x, *norm, eps=LN_EPS, rows=n * s, row_stride=d).view(n, s, d)
@@ -1282,7 +1520,11 @@ class FusedViT(nn.Module):
             a = hip_mha_fwd_h(layer["qkv"](norm_for(layer["qkv"], layer["norm1"])), self.num_heads, self.scale)
             x = layer["proj"](a, residual=x)
             a = layer["fc1"](norm_for(layer["fc1"], layer["norm2"]))
-            if isinstance(layer["fc2"], _LinearQuant):
+            if layer["fc2"].name in taps:
+                hip_act_rows_absmax_h(a, taps[layer["fc2"].name], swiglu=self.swiglu)
+            if getattr(layer["fc2"], "inv_smooth", None) is not None:  # smoothing: 1 / s per input channel before the row is quantised
+                a = hip_act_rows_qi8_smooth(a, layer["fc2"].inv_smooth, swiglu=self.swiglu)
+            elif isinstance(layer["fc2"], _LinearQuant):
                 a = layer["fc2"].fmt.fn("act")(a, swiglu=self.swiglu)
             else:
                 a = hip_swiglu_rows_h(a) if self.swiglu else hip_gelu_rows_h_(a)
@@ -1356,6 +1598,15 @@ class FusedViTClassifier(nn.Module):
     def half_dtype(self) -> torch.dtype | None:
         return self.feat_extract.half_dtype
 
+    @property
+    def smoothing(self) -> dict[str, torch.Tensor] | None:
+        return self.feat_extract.smoothing
+
+    def prepare(self, dtype: torch.dtype, linear_dtype: str | None = None, residual_dtype: str | None = None,
+                smoothing: dict[str, torch.Tensor] | None = None) -> None:
+        """``FusedViT.prepare`` of the backbone, every argument passed through (the head stays float32)."""
+        self.feat_extract.prepare(dtype, linear_dtype=linear_dtype, residual_dtype=residual_dtype, smoothing=smoothing)
+
     def _head(self, feat: torch.Tensor) -> torch.Tensor:
         feat = torch.flatten(feat, 1)
         if self.head_kernel:
@@ -1367,3 +1618,39 @@ class FusedViTClassifier(nn.Module):
 
     def forward_uint8(self, x_u8_nhwc: torch.Tensor, table: torch.Tensor) -> torch.Tensor:
         return self._head(self.feat_extract.forward_uint8(x_u8_nhwc, table))
+
+
+def calibrate_int8_smoothing(vit_or_model: nn.Module, batches, *, alpha: float = 0.5) -> dict[str, torch.Tensor]:  # noqa: ANN001
+    """The smoothing scales of ``prepare(torch.bfloat16, linear_dtype="int8", smoothing=...)`` for a loaded model on a CUDA device
+    (a ``VisionTransformer``, or a ``TimmBackbone`` / ``TimmModel`` around one), calibrated on ``batches`` -- one batch or an iterable
+    of them: normalised NCHW float tensors, or uint8 NHWC patches, which go through ``forward_uint8`` with the table of the model's
+    ``preproc_func`` (a ``TimmNormPreproc``) as a run's batches do.
+
+    A temporary :class:`FusedViT` runs the bfloat16 hand-written graph on them (``begin_int8_calibration``); the abs-max kernels tap
+    the LayerNorm in front of ``qkv`` and ``fc1`` and the activation in front of ``fc2`` of every block, and
+    :func:`int8_smoothing_scales` turns the statistics and the weight column maxima into powers of two.  Returns float32 CPU
+    tensors ``[cin]`` under ``blocks.{i}.attn.qkv``, ``blocks.{i}.mlp.fc1`` and ``blocks.{i}.mlp.fc2`` (``fc2`` at its padded
+    width) for the layers the INT8 GEMM serves: a plain dict that ``torch.save`` keeps -- how a deployment pins its calibration.
+    Non-finite activations on the calibration data are a ``ValueError`` that names the layer."""
+    import numpy as np
+
+    alpha = _checked_alpha(alpha)
+    vit = getattr(vit_or_model, "feat_extract", vit_or_model)
+    fused = FusedViT(vit)
+    fused.begin_int8_calibration()
+    device = fused._cls32.device  # noqa: SLF001
+    if isinstance(batches, (torch.Tensor, np.ndarray)):
+        batches = [batches]
+    hook = getattr(vit_or_model, "preproc_func", None)
+    with torch.inference_mode():
+        for batch in batches:
+            t = torch.as_tensor(batch).to(device)
+            if t.dtype == torch.uint8:
+                if not hasattr(hook, "device_table"):
+                    msg = ("calibrate_int8_smoothing: uint8 patches need the model's preproc_func (a TimmNormPreproc, whose table the "
+                           "im2col looks the bytes up in); pass normalised NCHW float batches for a bare VisionTransformer.")
+                    raise ValueError(msg)
+                fused.forward_uint8(t, hook.device_table(device, torch.bfloat16))
+            else:
+                fused(t)
+    return fused.int8_calibration_scales(alpha)

@@ -24,7 +24,12 @@ class DeepFeatureExtractor(PatchPredictor):
     (the hand-written graph in float32: every Linear on the split-bf16 GEMM, attention on the float32 MFMA kernel -- float32-class
     features, where "float32" itself keeps the torch module on library GEMMs); each is a ``ValueError`` anywhere else.
     ``residual_dtype``: ``None`` | "float32", for the same backbones in "float16" / "bfloat16" (not beside "bfloat16x3", whose stream
-    is float32 already)."""
+    is float32 already).
+    ``int8_smoothing=alpha`` (0 < alpha <= 1, usually 0.5) with ``int8_calibration=`` (uint8 or float patches as a run takes them, or
+    the scales dict of ``calibrate_int8_smoothing`` / of an earlier run's ``engine.int8_smoothing_scales``), beside "int8" only:
+    per-input-channel smoothing of the three INT8 layers for checkpoints with outlier channels -- the patches are run once through
+    the bfloat16 graph when the inference copy is built, and a later run with the same alpha and no new calibration reuses the copy.
+    Either kwarg without the other, without "int8" or with alpha outside (0, 1] is a ``ValueError``.  Unmeasured on real checkpoints."""
 
     def __init__(self, model, batch_size: int = 8, num_workers: int = 0, weights=None, *,
                  device: str = "cpu", verbose: bool = True) -> None:

@@ -65,6 +65,13 @@ _INT8_COVERS = ("compute_dtype=\"int8\" covers Vision Transformer models that Fu
                 "no float32-input quantising LayerNorm)")
 
 
+# int8_smoothing=alpha with int8_calibration=patches | scales: per-input-channel smoothing of those three layers (SmoothQuant's recipe on
+# powers of two; architecture/vit_fused.py).  Opt-in beside compute_dtype="int8" only; what it does not cover is refused.
+_INT8_SMOOTH_COVERS = ("int8_smoothing=alpha (0 < alpha <= 1) smooths the qkv, fc1 and fc2 inputs of a compute_dtype=\"int8\" run per input "
+                       "channel and goes together with int8_calibration= (uint8 or float patches as a run takes them, or the scales dict "
+                       "of calibrate_int8_smoothing / engine.int8_smoothing_scales)")
+
+
 def _compute_name(compute_dtype) -> str:
     return str(compute_dtype).replace("torch.", "")
 
@@ -316,6 +323,10 @@ class EngineABC:
         # MI355X extensions (plain attributes, settable through run(**kwargs) like every other)
         self.compute_dtype = "float32"    # arithmetic type of the CNN forward
         self.residual_dtype = None        # "float32": FusedViT keeps its residual stream in float32 (ViT models, fp16 / bf16, CUDA)
+        self.int8_smoothing = None        # alpha in (0, 1]: per-input-channel smoothing of the INT8 layers (compute_dtype="int8" only)
+        self.int8_calibration = None      # its calibration: patches (as a run takes them) or a scales dict (calibrate_int8_smoothing)
+        self.int8_smoothing_scales = None  # the scales dict the last smoothed inference copy was prepared with
+        self._int8_calibrated = None      # ((patches, alpha, model, weights, device), scales) of the last calibration made here
         # float32 3x3 / stride-1 block convolutions: "auto" (default: Winograd F(2x2, 3x3) on every layer whose shape the committed
         # per-layer error-bound test covers -- tests/test_engine.py::test_winograd_conv_matches_torch_cpu_fp32, <= 1e-5 of the
         # output scale against torch-CPU float32 -- the direct implicit GEMM elsewhere), "direct" (audit mode: the reference's
@@ -492,9 +503,11 @@ class EngineABC:
             if (torch.device(self.device).type != "cuda" or not isinstance(getattr(self.model, "feat_extract", None), _ViT)
                     or resid is not None):
                 self.compute_dtype, self.residual_dtype = "float32", None  # (run kwargs persist: the rejected values are not left behind)
+                self.int8_smoothing = self.int8_calibration = None
                 msg = f"{_INT8_COVERS}; got {type(self.model).__name__} on {self.device} with residual_dtype={resid!r}."
                 raise ValueError(msg)
             dtype = torch.bfloat16
+        smooth = self._int8_smoothing_request(int8=int8)  # None, or (alpha, calibration); its own refusals
         if split:  # the rule of the FP8 option: what this one does not cover is refused, never run in another precision
             from tiatoolbox_amd.models.architecture.vit import VisionTransformer as _ViT
 
@@ -525,6 +538,10 @@ class EngineABC:
             return self.model
         key = (dtype, str(self.device), id(self.model), self.fold_batchnorm, _weights_version(self.model), algo,
                SPLIT_COMPUTE if split else (INT8_COMPUTE if int8 else fp8), resid)
+        scales = None
+        if smooth is not None:  # calibrated once per (patches, alpha, weights); the key carries alpha and the identity of the scales
+            scales = self._int8_scales_for(*smooth)
+            key = (*key, smooth[0], id(scales))
         if self._fast_key != key:
             import copy
 
@@ -555,6 +572,7 @@ class EngineABC:
                     except UnsupportedLayerError as exc:  # (the constructor's own refusal; any other error is a bug and propagates)
                         if int8:
                             self.compute_dtype, self.residual_dtype = "float32", None
+                            self.int8_smoothing = self.int8_calibration = None
                             msg = f"{_INT8_COVERS}; {type(self.model).__name__}: {exc}"
                             raise ValueError(msg) from exc
                         if fp8 or split:
@@ -636,7 +654,12 @@ class EngineABC:
                         mod.prepare(torch.float32, linear_dtype=SPLIT_COMPUTE)  # three bf16 planes per Linear; float32 everywhere else
                     elif type(mod).__name__ in ("FusedUNet", "FusedPlainUNet", "FusedHoVerNet", "FusedViT") and dtype != torch.float32:
                         if int8 and type(mod).__name__ == "FusedViT":
-                            mod.prepare(dtype, linear_dtype=INT8_COMPUTE)  # qkv / fc1 / fc2 as W8A8 int8, per token x per output channel
+                            # qkv / fc1 / fc2 as W8A8 int8, per token x per output channel (smoothed per input channel on request)
+                            try:
+                                mod.prepare(dtype, linear_dtype=INT8_COMPUTE, **({} if scales is None else {"smoothing": scales}))
+                            except ValueError:  # (a scales dict that does not fit the model: `prepare` names the entry)
+                                self.compute_dtype, self.int8_smoothing, self.int8_calibration = "float32", None, None
+                                raise
                         elif fp8 and type(mod).__name__ == "FusedViT":
                             mod.prepare(dtype, linear_dtype=FP8_COMPUTE)  # qkv / fc1 / fc2 quantised per output channel as well
                         elif resid is not None and type(mod).__name__ == "FusedViT":
@@ -649,6 +672,87 @@ class EngineABC:
             m.eval()
             self._fast_model, self._fast_key = m, key
         return self._fast_model
+
+    def _refuse_int8_smoothing(self, problem: str) -> None:
+        self.compute_dtype, self.residual_dtype = "float32", None  # (run kwargs persist: the rejected values are not left behind)
+        self.int8_smoothing = self.int8_calibration = None
+        msg = f"{_INT8_SMOOTH_COVERS}; {problem}"
+        raise ValueError(msg)
+
+    def _int8_smoothing_request(self, *, int8: bool):
+        """``(alpha, calibration)`` of a smoothed ``compute_dtype="int8"`` run, ``None`` without the two run kwargs; every combination
+        the option does not cover is refused here, after the refusals of ``compute_dtype="int8"`` itself."""
+        alpha, calib = getattr(self, "int8_smoothing", None), getattr(self, "int8_calibration", None)
+        if alpha is None and calib is None:
+            return None
+        name = _compute_name(self.compute_dtype)
+        if not int8:
+            self._refuse_int8_smoothing(f"got int8_smoothing={alpha!r} with compute_dtype={name!r}.")
+        if alpha is None:
+            self._refuse_int8_smoothing("got int8_calibration without int8_smoothing.")
+        if calib is None:
+            self._refuse_int8_smoothing(f"got int8_smoothing={alpha!r} without int8_calibration.")
+        if isinstance(alpha, bool) or not isinstance(alpha, (int, float)) or not 0.0 < float(alpha) <= 1.0:
+            self._refuse_int8_smoothing(f"got int8_smoothing={alpha!r}.")
+        if not isinstance(calib, (dict, np.ndarray, torch.Tensor)) or (not isinstance(calib, dict) and (calib.ndim != 4 or len(calib) == 0)):  # noqa: PLR2004
+            self._refuse_int8_smoothing(f"got int8_calibration of type {type(calib).__name__}"
+                                        f"{'' if isinstance(calib, dict) or not hasattr(calib, 'shape') else f', shape {tuple(calib.shape)}'}.")
+        return float(alpha), calib
+
+    def _int8_scales_for(self, alpha: float, calib):
+        """The scales dict of a smoothed run: ``calib`` itself when it is one, else the calibration of the model on those patches --
+        made once per (patches, alpha, model, weights, device) and kept as ``int8_smoothing_scales``."""
+        if isinstance(calib, dict):
+            self.int8_smoothing_scales = calib
+            return calib
+        source = (id(calib), alpha, id(self.model), _weights_version(self.model), str(self.device))
+        if self._int8_calibrated is None or self._int8_calibrated[0] != source:
+            self._int8_calibrated = (source, self._calibrate_int8_smoothing(alpha, calib))
+        self.int8_smoothing_scales = self._int8_calibrated[1]
+        return self.int8_smoothing_scales
+
+    def _calibrate_int8_smoothing(self, alpha: float, patches):
+        """Calibration patches take a batch's route -- ``preproc_func``, then the graph -- in chunks of ``batch_size``, through the
+        bfloat16 hand-written graph with the abs-max taps of ``FusedViT.begin_int8_calibration``."""
+        import copy
+
+        from tiatoolbox_amd.models.architecture.unet_fused import UnsupportedLayerError
+        from tiatoolbox_amd.models.architecture.vanilla import TimmModel
+        from tiatoolbox_amd.models.architecture.vit_fused import FusedViT, FusedViTClassifier
+
+        m = copy.deepcopy(self.model).to(device=self.device)
+        try:
+            if isinstance(m, TimmModel) and type(m).forward is TimmModel.forward:
+                m = FusedViTClassifier(m)
+            else:
+                m.feat_extract = FusedViT(m.feat_extract)
+        except UnsupportedLayerError as exc:
+            self.compute_dtype, self.residual_dtype = "float32", None
+            self.int8_smoothing = self.int8_calibration = None
+            msg = f"{_INT8_COVERS}; {type(self.model).__name__}: {exc}"
+            raise ValueError(msg) from exc
+        graph = m.feat_extract
+        graph.begin_int8_calibration()
+        dtype = torch.bfloat16
+        m = m.to(device=self.device).to(dtype=dtype).eval()
+        dataset = PatchDataset(inputs=patches)
+        dataset.preproc_func = self._get_model_attr("preproc_func")
+        infer_batch = self._get_model_attr("infer_batch")
+        self._set_defer_unit(m, dtype)
+        self._set_defer_norm(m)
+        feed, self._feed = getattr(self, "_feed", None), None
+        try:
+            bs = max(int(self.batch_size), 1)
+            for lo in range(0, len(patches), bs):
+                batch = self._preprocess_batch(dataset, lo, min(lo + bs, len(patches)), dtype)
+                self._forward_batch(m, infer_batch, batch)
+            return graph.int8_calibration_scales(alpha)
+        except ValueError:
+            self.compute_dtype, self.residual_dtype = "float32", None
+            self.int8_smoothing = self.int8_calibration = None
+            raise
+        finally:
+            self._feed = feed
 
     @contextlib.contextmanager
     def _miopen_scope(self):

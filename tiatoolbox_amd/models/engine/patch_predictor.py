@@ -21,7 +21,11 @@ class PatchPredictor(EngineABC):
     one -- compare both with "bfloat16" on your own checkpoint; not beside ``residual_dtype``), and "bfloat16x3": the same
     graph in float32 with every Linear on the split-bf16 GEMM and attention on the float32 MFMA kernel; a ``ValueError`` elsewhere),
     ``residual_dtype`` (``None`` | "float32": Vision Transformer models on a CUDA device in "float16" / "bfloat16" keep their residual
-    stream in float32, as the float32 module under ``torch.autocast`` does; a ``ValueError`` elsewhere) and ``stain_normalizer`` (a fitted :class:`~tiatoolbox_amd.tools.stainnorm.StainNormalizer`; shorthand
+    stream in float32, as the float32 module under ``torch.autocast`` does; a ``ValueError`` elsewhere), ``int8_smoothing`` (alpha in
+    (0, 1]) with ``int8_calibration`` (patches as a run takes them, or a scales dict of ``calibrate_int8_smoothing`` /
+    ``engine.int8_smoothing_scales``): per-input-channel smoothing of the INT8 layers beside "int8" only, calibrated once when the
+    inference copy is built, for checkpoints with outlier channels -- unmeasured on real ones; a ``ValueError`` in every other
+    combination) and ``stain_normalizer`` (a fitted :class:`~tiatoolbox_amd.tools.stainnorm.StainNormalizer`; shorthand
     for ``model.preproc_func = StainNormPreproc(normalizer, default_preproc)``).
 
     WSI mode (``patch_mode=False``) also takes ``merge_predictions=True`` with ``merge_resolution`` (default 1.25) and

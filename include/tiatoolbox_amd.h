@@ -53,7 +53,8 @@ extern "C" {
  * tia_linear_int8_rows, tia_linear_int8_pack_weights, tia_linear_int8_serves, tia_layernorm_rows_qi8, tia_gelu_rows_qi8,
  * tia_swiglu_rows_qi8 (the Vision Transformer linear layers on the INT8 matrix instruction); tia_gelu_rows_qi8_smooth,
  * tia_swiglu_rows_qi8_smooth, tia_layernorm_rows_absmax_h, tia_gelu_rows_absmax_h, tia_swiglu_rows_absmax_h (per-input-channel
- * smoothing of those layers and its calibration statistics). */
+ * smoothing of those layers and its calibration statistics); tia_mha_probs_h, tia_rollout_step_f32 (attention maps of the Vision
+ * Transformer runs: the probabilities tia_mha_fwd_h does not materialise, and attention rollout). */
 #define TIA_ABI_VERSION 6
 int tia_abi_version(void);
 
@@ -1216,6 +1217,31 @@ int tia_vit_patchify_f32(const float* d_x, float* d_tokens, int64_t n, int64_t h
  * pos_has_cls = 0 with host-folded cls / reg rows is the prefix_pos_embed form.  d % 4 == 0 and d <= 8192 (else TIA_ESIZE). */
 int tia_vit_assemble_f32(const float* d_tokens, const float* d_cls, const float* d_reg, const float* d_pos, int32_t pos_has_cls,
                          float* d_out, int64_t n, int64_t g, int64_t reg_tokens, int64_t d, void* stream);
+
+/* =======================================================================================
+ * Attention maps of the Vision Transformers (vit_attention_maps.hip; the engines' run kwarg return_attention).  Additive, same
+ * version (6).  Neither entry is launched by a run that asks for no maps; both are deterministic (no atomics).
+ * ===================================================================================== */
+
+/* The attention probabilities that tia_mha_fwd_h does not materialise, for the first q_rows queries:
+ *   p[b,h,i,j] = softmax_j(scale * q[b,i,h,:] . k[b,j,h,:]),  i < q_rows,  j < s
+ *   d_qkv [n, s, 3, heads, head_dim] of `dtype` (TIA_DT_F16 | TIA_DT_BF16; anything else TIA_EINVAL) -- tia_mha_fwd_h's input
+ *   d_out float32: head_mean = 0: [n, heads, q_rows, s];  head_mean = 1: [n, q_rows, s], (1 / heads) sum_h p, the heads added in
+ *   ascending order in float32 by the workgroup that owns the query tile and divided by heads once.
+ * Scores on v_mfma_f32_16x16x32_f16 / _bf16 with float32 accumulation; softmax in float32 in the base-2 domain over all s keys:
+ * t = score * (scale * log2 e), m = max_j t, e_j = exp2(t_j - m), l = sum_j e_j (an online sum over 64-key tiles, rescaled when m
+ * moves); every stored probability is e_j / l with ONE correctly rounded division.  Keys >= s contribute exactly 0.  Two passes
+ * over the keys (m and l, then the probabilities), so s has no ceiling: any s >= 1, 64-bit offsets.
+ * head_dim 64 or 80 (else TIA_ESIZE); head_mean = 1 takes at most 64 heads (TIA_ESIZE beyond: their (m, l) wait in LDS);
+ * 1 <= q_rows <= s, head_mean 0 | 1, scale finite and > 0, 16-byte aligned non-null pointers (else TIA_EINVAL). */
+int tia_mha_probs_h(const void* d_qkv, float* d_out, int64_t n, int64_t s, int64_t heads, int64_t head_dim, float scale, int64_t q_rows,
+                    int32_t head_mean, int32_t dtype, void* stream);
+
+/* One step of attention rollout (Abnar & Zuidema 2020) on n float32 [s, s] matrices:  R_out = 1/2 (A R_in) + 1/2 R_in.
+ * A R_in on v_mfma_f32_16x16x4_f32: every element is ONE float32 fma chain over k = 0 .. s - 1 in ascending order (exact products,
+ * one rounding per step); both halvings are exact and the final add rounds once.  d_r_in NULL means R_in = I.  Any s >= 1 (tails
+ * are zero-filled operands: exact).  Pointers 4-byte aligned; d_r_out overlapping d_a or d_r_in is TIA_EINVAL. */
+int tia_rollout_step_f32(const float* d_a, const float* d_r_in, float* d_r_out, int64_t n, int64_t s, void* stream);
 
 /* =======================================================================================
  * All borders of binary planes: cv2.findContours(layer, RETR_TREE, CHAIN_APPROX_NONE | _SIMPLE)

@@ -11,6 +11,8 @@ The fp16 / bf16 forward on the hand-written kernels is :class:`~tiatoolbox_amd.m
 
 from __future__ import annotations
 
+import contextlib
+
 import torch
 import torch.nn.functional as F  # noqa: N812
 from torch import nn
@@ -45,6 +47,7 @@ VIRCHOW_CONFIGS: dict[str, dict] = {
 }
 MLP_LAYERS = ("mlp", "swiglu_packed")
 GLOBAL_POOLS = ("token", "token_mean")
+ATTENTION_KINDS = ("class", "rollout")  # the maps of `forward_with_attention` (the engines' run kwarg `return_attention`)
 LN_EPS = 1e-6
 
 
@@ -260,6 +263,77 @@ class VisionTransformer(nn.Module):
         if self.global_pool == "token_mean":
             return torch.cat([x[:, 0], x[:, 1 + self.reg_tokens:].mean(1)], dim=-1)
         return x[:, 0]
+
+    def forward_with_attention(self, imgs: torch.Tensor, kind: str) -> tuple[torch.Tensor, torch.Tensor]:
+        """``(forward(imgs), maps)``: the features bit for bit, and float32 attention maps on the patch grid ``(gh, gw)`` of the input.
+        With ``S`` tokens, the prefix ``P = 1 + reg_tokens`` (class token, then registers), ``H`` heads and ``q``, ``k`` the ``qkv``
+        Linear's own output of a block (in the module's dtype):
+
+        * ``kind="class"`` -> ``[B, H, gh, gw]``: in the LAST block, per head, ``p = softmax_j(scale * q[0] . k[j])`` over all ``S``
+          keys, and ``p[P:]`` on the grid.  Not renormalised: a map sums to 1 minus the mass the class token puts on the prefix tokens.
+        * ``kind="rollout"`` -> ``[B, gh, gw]``: attention rollout (Abnar & Zuidema 2020) with mean head fusion and nothing discarded:
+          ``A_l = (1 / H) sum_h softmax(scale * Q_h K_h^T)`` (heads added in ascending order), ``R_1 = A_1 / 2 + I / 2``,
+          ``R_l = (A_l R_{l-1}) / 2 + R_{l-1} / 2``, no renormalisation (the rows sum to 1 already); the map is ``R_L[0, P:]``.
+
+        The probabilities are the softmax of the module's own scores, widened to float32; the head mean and ``R`` are float32
+        throughout.  A hook records what each block's ``qkv`` returns while ``forward`` itself runs, so the features cannot differ."""
+        if kind not in ATTENTION_KINDS:
+            msg = f"VisionTransformer.forward_with_attention: kind is one of {ATTENTION_KINDS}; got {kind!r}."
+            raise ValueError(msg)
+        gh, gw = self.grid_of(imgs.shape[-2], imgs.shape[-1])
+        prefix, heads = 1 + self.reg_tokens, self.num_heads
+        state: dict[str, torch.Tensor] = {}
+
+        def probs(attn: Attention, qkv: torch.Tensor, rows: int | None) -> torch.Tensor:  # float32 [B, H, rows or S, S]
+            b, s, _ = qkv.shape
+            q, k, _ = qkv.reshape(b, s, 3, heads, attn.head_dim).permute(2, 0, 3, 1, 4).unbind(0)
+            return ((q[:, :, :rows] * attn.scale) @ k.transpose(-2, -1)).softmax(dim=-1).to(torch.float32)
+
+        def tap(attn: Attention, last: bool):  # noqa: ANN202, FBT001
+            @torch.no_grad()
+            def hook(_mod: nn.Module, _inp: tuple, qkv: torch.Tensor) -> None:
+                if kind == "class":
+                    if last:
+                        state["class"] = probs(attn, qkv, 1)[:, :, 0, prefix:]
+                    return
+                p = probs(attn, qkv, None)
+                a = p[:, 0]
+                for h in range(1, heads):  # ascending head order, float32
+                    a = a + p[:, h]
+                a = a / heads
+                r = state.get("r")
+                if r is None:
+                    r = torch.eye(a.shape[-1], dtype=torch.float32, device=a.device).expand_as(a)
+                state["r"] = 0.5 * (a @ r) + 0.5 * r
+            return hook
+
+        handles = [blk.attn.qkv.register_forward_hook(tap(blk.attn, i == len(self.blocks) - 1)) for i, blk in enumerate(self.blocks)]
+        try:
+            feats = type(self).forward(self, imgs)  # (the class's own forward: `capturing_attention` shadows the instance's)
+        finally:
+            for h in handles:
+                h.remove()
+        if kind == "class":
+            return feats, state["class"].reshape(-1, heads, gh, gw).contiguous()
+        return feats, state["r"][:, 0, prefix:].reshape(-1, gh, gw).contiguous()
+
+    @contextlib.contextmanager
+    def capturing_attention(self, kind: str):  # noqa: ANN201
+        """Inside the scope every CALL of this module (``model(x)`` of whatever model holds it) returns ``forward``'s features and appends
+        the maps of :meth:`forward_with_attention` to the list the scope yields -- how an engine gets both from a model's own
+        ``infer_batch``.  ``forward`` itself is not touched: the scope shadows it on the instance and removes the shadow again."""
+        maps: list[torch.Tensor] = []
+
+        def forward(imgs: torch.Tensor) -> torch.Tensor:
+            feats, m = self.forward_with_attention(imgs, kind)
+            maps.append(m)
+            return feats
+
+        self.__dict__["forward"] = forward
+        try:
+            yield maps
+        finally:
+            self.__dict__.pop("forward", None)
 
 
 def create_vit(name: str, *, device: torch.device | str | None = None) -> VisionTransformer:

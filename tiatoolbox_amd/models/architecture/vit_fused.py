@@ -71,6 +71,13 @@ attention on ``tia_mha_fwd_f32`` (``v_mfma_f32_16x16x4_f32``); ``tia_gelu_rows_f
 and ``tia_vit_assemble_f32`` beside the float32 LayerNorm, pool and head that exist already.  The batch is the
 normalised float32 tensor; there is no uint8 im2col on this route.
 
+``return_attention`` (an attribute the engines set for a run: ``None`` | "class" | "rollout", their run kwarg of that name) makes every
+half route return attention maps beside its output, in ``attention_maps`` after each ``forward`` / ``forward_uint8``: behind step 3 the
+SAME qkv tensor goes to ``tia_mha_probs_h`` (the float32 probabilities attention never materialises: the class row per head in the last
+block, or all rows with the head mean in every block) and, for the rollout, ``tia_rollout_step_f32``
+(``R = (A R) / 2 + R / 2`` on ``v_mfma_f32_16x16x4_f32``).  They write buffers of their own, so the features are bit for bit those of the
+run without maps, and with ``None`` nothing is launched.  ``VisionTransformer.forward_with_attention`` states both maps; DESIGN 4.42.
+
 There is no library fall-back: a model the kernels do not take (``D / heads`` other than 64 or 80, channel counts off the GEMM's
 multiples) raises ``UnsupportedLayerError`` from the constructor.
 """
@@ -159,6 +166,51 @@ def hip_mha_fwd_h(qkv: torch.Tensor, heads: int, scale: float) -> torch.Tensor:
         rc = _lib.load().tia_mha_fwd_h(qkv.data_ptr(), out.data_ptr(), n, s, heads, head_dim, float(scale), _DT[qkv.dtype],
                                        _lib.current_stream())
     _lib.check(rc, "tia_mha_fwd_h")
+    return out
+
+
+MHA_PROBS_MEAN_HEADS = 64  # `tia_mha_probs_h` with head_mean keeps every head's (max, sum) of a query tile in LDS: at most 64 heads
+
+
+def hip_mha_probs_h(qkv: torch.Tensor, heads: int, scale: float, *, q_rows: int, head_mean: bool) -> torch.Tensor:
+    """The attention probabilities of ``hip_mha_fwd_h``'s input ``[n, S, 3 * heads * hd]`` for the first ``q_rows`` queries, float32:
+    ``[n, heads, q_rows, S]``, or with ``head_mean`` their mean over the heads ``[n, q_rows, S]`` (``tia_mha_probs_h``: float32
+    softmax over all ``S`` keys, every value ``e_j / sum e`` rounded once; heads added in ascending order)."""
+    from tiatoolbox_amd import _lib
+
+    _half_tokens("hip_mha_probs_h", qkv)
+    n, s, c3 = qkv.shape
+    head_dim = c3 // (3 * heads)
+    if not 1 <= q_rows <= s:
+        msg = f"hip_mha_probs_h: q_rows is between 1 and the {s} tokens; got {q_rows}."
+        raise ValueError(msg)
+    if head_mean and heads > MHA_PROBS_MEAN_HEADS:
+        msg = f"hip_mha_probs_h: the head mean takes at most {MHA_PROBS_MEAN_HEADS} heads; got {heads}."
+        raise ValueError(msg)
+    out = torch.empty((n, q_rows, s) if head_mean else (n, heads, q_rows, s), dtype=torch.float32, device=qkv.device)
+    with torch.cuda.device(qkv.device):
+        rc = _lib.load().tia_mha_probs_h(qkv.data_ptr(), out.data_ptr(), n, s, heads, head_dim, float(scale), q_rows, int(bool(head_mean)),
+                                         _DT[qkv.dtype], _lib.current_stream())
+    _lib.check(rc, "tia_mha_probs_h")
+    return out
+
+
+def hip_rollout_step_f32(a: torch.Tensor, r_in: torch.Tensor | None) -> torch.Tensor:
+    """One step of attention rollout on float32 ``[n, S, S]`` matrices: ``(a @ r_in) / 2 + r_in / 2``, ``r_in=None`` the identity
+    (``tia_rollout_step_f32``: one float32 fma chain per element, one final rounding)."""
+    from tiatoolbox_amd import _lib
+
+    for name, t in (("a", a), ("r_in", r_in)):
+        if t is not None and not (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and t.dim() == 3  # noqa: PLR2004
+                                  and t.shape[1] == t.shape[2] and t.shape == a.shape and t.device == a.device):
+            msg = f"hip_rollout_step_f32 expects contiguous float32 CUDA [n, S, S] matrices of one shape; got {name} {tuple(t.shape)}, " \
+                  f"{t.dtype} on {t.device}."
+            raise ValueError(msg)
+    n, s, _ = a.shape
+    out = torch.empty_like(a)
+    with torch.cuda.device(a.device):
+        rc = _lib.load().tia_rollout_step_f32(a.data_ptr(), _ptr(r_in), out.data_ptr(), n, s, _lib.current_stream())
+    _lib.check(rc, "tia_rollout_step_f32")
     return out
 
 
@@ -1135,6 +1187,11 @@ class FusedViT(nn.Module):
         self.smoothing: dict[str, torch.Tensor] | None = None  # the per-input-channel scales `prepare` applied (layer name -> [cin])
         self._taps: dict[str, torch.Tensor] | None = None      # calibration: layer name -> abs-max of its float32 input, per channel
         self._amax_w: dict[str, torch.Tensor] = {}             # calibration: layer name -> max_o |W[o, j]| of the weights to pack
+        # maps beside the output: the engine sets `return_attention` ("class" | "rollout") before a run and reads `attention_maps` after
+        # each forward (`forward` and `forward_uint8` alike); None: not one additional launch
+        self.return_attention: str | None = None
+        self.attention_maps: torch.Tensor | None = None
+        self._rollout: torch.Tensor | None = None
 
     def prepare(self, dtype: torch.dtype, linear_dtype: str | None = None, residual_dtype: str | None = None,
                 smoothing: dict[str, torch.Tensor] | None = None) -> None:
@@ -1396,6 +1453,9 @@ class FusedViT(nn.Module):
         LN -> qkv -> ``tia_mha_fwd_f32`` -> proj (+ x) -> LN -> fc1 -> GELU / SwiGLU -> fc2 (+ x), then the final norm or pool.  The
         residual adds are the GEMMs' ``d_residual``; the LayerNorm is ``tia_add_layernorm_rows_f32`` without a branch and with
         float32 output, the pooled end ``tia_vit_cls_mean_pool_f32`` without a branch."""
+        if self.return_attention is not None:
+            msg = "FusedViT: the float32 route (linear_dtype=\"bfloat16x3\") has no attention-map kernel; return_attention must be None."
+            raise ValueError(msg)
         p = self.patch_size
         _, _, h, w = imgs.shape
         if h % p != 0 or w % p != 0:
@@ -1495,6 +1555,7 @@ class FusedViT(nn.Module):
 
     def _from_patch_columns(self, cols: torch.Tensor, pos: torch.Tensor, grid: tuple[int, int]) -> torch.Tensor:
         """The graph from the token GEMM on: ``cols`` ``[n, g, 3 p^2 or k_pad]`` are the im2col rows of either input form."""
+        self._rollout = None  # (a forward that raised half way leaves nothing behind for the next one's recursion)
         if self.residual_dtype is not None:
             return self._from_patch_columns_f32(cols, pos, grid)
         n, d = cols.shape[0], self.embed_dim
@@ -1517,7 +1578,7 @@ class FusedViT(nn.Module):
             return hip_layernorm_rows_h(x, *norm, eps=LN_EPS, rows=n * s, row_stride=d).view(n, s, d)
 
         for layer in self.layers:
-            a = hip_mha_fwd_h(layer["qkv"](norm_for(layer["qkv"], layer["norm1"])), self.num_heads, self.scale)
+            a = self._attend(layer["qkv"](norm_for(layer["qkv"], layer["norm1"])), layer is self.layers[-1])
             x = layer["proj"](a, residual=x)
             a = layer["fc1"](norm_for(layer["fc1"], layer["norm2"]))
             if layer["fc2"].name in taps:
@@ -1529,9 +1590,41 @@ class FusedViT(nn.Module):
             else:
                 a = hip_swiglu_rows_h(a) if self.swiglu else hip_gelu_rows_h_(a)
             x = layer["fc2"](a, residual=x)
+        self._finish_attention(grid)
         if self.global_pool == "token_mean":
             return hip_vit_cls_mean_pool_h(x, *self._norm, eps=LN_EPS, skip=1 + self.reg_tokens)
         return hip_layernorm_rows_h(x, *self._norm, eps=LN_EPS, rows=n, row_stride=s * d, out_dtype=torch.float32)
+
+    def _attend(self, qkv: torch.Tensor, last: bool) -> torch.Tensor:  # noqa: FBT001
+        """``hip_mha_fwd_h`` of a block and -- only with ``return_attention`` -- the map kernels on the SAME ``qkv`` tensor, after it: they
+        read what attention read and write buffers of their own, so the maps describe the computation that ran, on every half
+        route.  "class": one ``tia_mha_probs_h`` launch in the last block (the class row, per head); "rollout": per block the head
+        mean of all rows and one ``tia_rollout_step_f32``."""
+        kind = self.return_attention
+        if kind not in (None, "class", "rollout"):
+            msg = f"FusedViT.return_attention is None, 'class' or 'rollout'; got {kind!r}."
+            raise ValueError(msg)
+        a = hip_mha_fwd_h(qkv, self.num_heads, self.scale)
+        if kind == "class":
+            if last:
+                self._rollout = hip_mha_probs_h(qkv, self.num_heads, self.scale, q_rows=1, head_mean=False)
+        elif kind == "rollout":
+            mean = hip_mha_probs_h(qkv, self.num_heads, self.scale, q_rows=qkv.shape[1], head_mean=True)
+            self._rollout = hip_rollout_step_f32(mean, self._rollout)
+        return a
+
+    def _finish_attention(self, grid: tuple[int, int]) -> None:
+        """``attention_maps`` of the forward that just ran: the patch columns (``[1 + R:]``) of the class row on the grid --
+        ``[n, H, gh, gw]`` of the last block's probabilities, or ``[n, gh, gw]`` of the rollout matrix."""
+        r, self._rollout = self._rollout, None
+        if self.return_attention is None:
+            self.attention_maps = None
+            return
+        prefix = 1 + self.reg_tokens
+        if self.return_attention == "class":
+            self.attention_maps = r[:, :, 0, prefix:].reshape(r.shape[0], self.num_heads, *grid).contiguous()
+        else:
+            self.attention_maps = r[:, 0, prefix:].reshape(r.shape[0], *grid).contiguous()
 
     def _from_patch_columns_f32(self, cols: torch.Tensor, pos: torch.Tensor, grid: tuple[int, int]) -> torch.Tensor:
         """``_from_patch_columns`` under ``residual_dtype="float32"``: ``x`` is a float32 ``[n, S, D]`` tensor that only
@@ -1554,11 +1647,12 @@ class FusedViT(nn.Module):
 
         b = None  # the branch not yet added to x (block 0's first pass has none: LayerNorm only)
         for layer in self.layers:
-            a = hip_mha_fwd_h(layer["qkv"](add_norm(b, layer["norm1"])), self.num_heads, self.scale)
+            a = self._attend(layer["qkv"](add_norm(b, layer["norm1"])), layer is self.layers[-1])
             b = layer["proj"](a)
             a = layer["fc1"](add_norm(b, layer["norm2"]))
             a = hip_swiglu_rows_h(a) if self.swiglu else hip_gelu_rows_h_(a)
             b = layer["fc2"](a)
+        self._finish_attention(grid)
         if self.global_pool == "token_mean":
             return hip_vit_cls_mean_pool_f32(x, b, *self._norm, eps=LN_EPS, skip=1 + self.reg_tokens, dtype=half)
         # the class rows only: the last branch is added to them (both strides S * D) and the final norm is written in float32
@@ -1601,6 +1695,19 @@ class FusedViTClassifier(nn.Module):
     @property
     def smoothing(self) -> dict[str, torch.Tensor] | None:
         return self.feat_extract.smoothing
+
+    @property
+    def return_attention(self) -> str | None:
+        return self.feat_extract.return_attention
+
+    @return_attention.setter
+    def return_attention(self, kind: str | None) -> None:
+        self.feat_extract.return_attention = kind
+
+    @property
+    def attention_maps(self) -> torch.Tensor | None:
+        """The backbone's maps of the forward that just ran (``FusedViT.attention_maps``); the head adds nothing to them."""
+        return self.feat_extract.attention_maps
 
     def prepare(self, dtype: torch.dtype, linear_dtype: str | None = None, residual_dtype: str | None = None,
                 smoothing: dict[str, torch.Tensor] | None = None) -> None:

@@ -29,7 +29,13 @@ class DeepFeatureExtractor(PatchPredictor):
     the scales dict of ``calibrate_int8_smoothing`` / of an earlier run's ``engine.int8_smoothing_scales``), beside "int8" only:
     per-input-channel smoothing of the three INT8 layers for checkpoints with outlier channels -- the patches are run once through
     the bfloat16 graph when the inference copy is built, and a later run with the same alpha and no new calibration reuses the copy.
-    Either kwarg without the other, without "int8" or with alpha outside (0, 1] is a ``ValueError``.  Unmeasured on real checkpoints."""
+    Either kwarg without the other, without "int8" or with alpha outside (0, 1] is a ``ValueError``.  Unmeasured on real checkpoints.
+    ``return_attention``: ``None`` | "class" | "rollout" (patch mode, Vision Transformer backbones, every ``compute_dtype`` but
+    "bfloat16x3"; per call): ``run()`` also returns ``"attention"``, float32 maps on the patch grid -- "class" ``[N, heads, gh, gw]``, the
+    class token's attention in the last block (not renormalised: a map sums to 1 minus the mass on the class and register tokens),
+    "rollout" ``[N, gh, gw]``, attention rollout with mean head fusion -- beside features that are bit for bit those of the run without
+    it.  On the hand-written graph the maps come from ``tia_mha_probs_h`` / ``tia_rollout_step_f32`` on the qkv tensors attention
+    itself read, so they describe the computation that ran, quantised routes included; a ``ValueError`` anywhere else."""
 
     def __init__(self, model, batch_size: int = 8, num_workers: int = 0, weights=None, *,
                  device: str = "cpu", verbose: bool = True) -> None:

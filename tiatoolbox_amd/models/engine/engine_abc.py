@@ -72,6 +72,12 @@ _INT8_SMOOTH_COVERS = ("int8_smoothing=alpha (0 < alpha <= 1) smooths the qkv, f
                        "of calibrate_int8_smoothing / engine.int8_smoothing_scales)")
 
 
+# return_attention="class" | "rollout": per-patch attention maps beside the output, under "attention" (architecture/vit.py states both;
+# on the hand-written graph tia_mha_probs_h / tia_rollout_step_f32 read the qkv tensor attention read).  Per call.
+_ATTENTION_COVERS = ("return_attention is None, \"class\" or \"rollout\" and covers patch-mode runs of models whose feat_extract is a "
+                     "VisionTransformer (TimmBackbone / TimmModel) in every compute_dtype but \"bfloat16x3\"")
+
+
 def _compute_name(compute_dtype) -> str:
     return str(compute_dtype).replace("torch.", "")
 
@@ -327,6 +333,7 @@ class EngineABC:
         self.int8_calibration = None      # its calibration: patches (as a run takes them) or a scales dict (calibrate_int8_smoothing)
         self.int8_smoothing_scales = None  # the scales dict the last smoothed inference copy was prepared with
         self._int8_calibrated = None      # ((patches, alpha, model, weights, device), scales) of the last calibration made here
+        self.return_attention = None      # "class" | "rollout": per-patch attention maps of a ViT model under "attention" (per call)
         # float32 3x3 / stride-1 block convolutions: "auto" (default: Winograd F(2x2, 3x3) on every layer whose shape the committed
         # per-layer error-bound test covers -- tests/test_engine.py::test_winograd_conv_matches_torch_cpu_fp32, <= 1e-5 of the
         # output scale against torch-CPU float32 -- the direct implicit GEMM elsewhere), "direct" (audit mode: the reference's
@@ -429,6 +436,8 @@ class EngineABC:
             # semantic_segmentor.py:795, multi_task_segmentor.py:982): a run without the kwarg drops the probabilities even if an
             # earlier run asked for them
             self.return_probabilities = bool(kwargs.get("return_probabilities", False))
+        # per call as well: a run without the kwarg returns no maps; what the option does not cover is refused before any launch
+        self.return_attention = self._checked_return_attention(kwargs.get("return_attention"), patch_mode=patch_mode)
         if "miopen_find" not in kwargs:
             self.miopen_find = None  # the process-global solver-search switch is chosen per run, never inherited
         if input_resolutions:
@@ -672,6 +681,52 @@ class EngineABC:
             m.eval()
             self._fast_model, self._fast_key = m, key
         return self._fast_model
+
+    def _checked_return_attention(self, kind, *, patch_mode: bool):
+        """The run kwarg ``return_attention`` of this call: ``None``, "class" or "rollout" (``VisionTransformer.forward_with_attention``
+        states both).  Anything it does not cover is a ``ValueError`` that leaves ``return_attention = None`` behind."""
+        if kind is None:
+            return None
+        from tiatoolbox_amd.models.architecture.vit import ATTENTION_KINDS
+        from tiatoolbox_amd.models.architecture.vit import VisionTransformer as _ViT
+
+        problem = None
+        if kind not in ATTENTION_KINDS:
+            problem = f"got return_attention={kind!r}"
+        elif not isinstance(getattr(self.model, "feat_extract", None), _ViT):
+            problem = f"got {type(self.model).__name__}, which has no VisionTransformer"
+        elif _compute_name(getattr(self, "compute_dtype", "float32")) == SPLIT_COMPUTE:
+            problem = f"got compute_dtype={SPLIT_COMPUTE!r}, whose float32 graph has no attention-map kernel"
+        elif not patch_mode:
+            problem = "got patch_mode=False"
+        if problem is not None:
+            self.return_attention = None  # (run kwargs persist as attributes: do not leave the rejected value behind)
+            msg = f"{_ATTENTION_COVERS}; {problem}."
+            raise ValueError(msg)
+        return kind
+
+    @contextlib.contextmanager
+    def _attention_scope(self, model):
+        """Yields ``take()``, which returns the maps of the forward that just ran (float32, on the device), or ``None`` when this run
+        asks for no maps.  A :class:`FusedViT` trunk writes them beside its output from its own kernels (``return_attention`` /
+        ``attention_maps``); a torch ``VisionTransformer`` -- the CPU, ``compute_dtype="float32"``, a model ``FusedViT`` refuses -- through
+        ``forward_with_attention``."""
+        kind = getattr(self, "return_attention", None)
+        if kind is None:
+            yield None
+            return
+        from tiatoolbox_amd.models.architecture.vit import VisionTransformer as _ViT
+
+        trunk = model.feat_extract
+        if isinstance(trunk, _ViT):
+            with trunk.capturing_attention(kind) as maps:
+                yield maps.pop
+            return
+        trunk.return_attention = kind  # (a FusedViT: a TimmBackbone's trunk or a FusedViTClassifier's)
+        try:
+            yield lambda: trunk.attention_maps
+        finally:
+            trunk.return_attention, trunk.attention_maps = None, None
 
     def _refuse_int8_smoothing(self, problem: str) -> None:
         self.compute_dtype, self.residual_dtype = "float32", None  # (run kwargs persist: the rejected values are not left behind)
@@ -965,8 +1020,9 @@ class EngineABC:
         self._set_defer_unit(model, dtype)
         self._set_defer_norm(model)
         self._shard_span, self._norm_cache = (lo, hi), None
+        maps = []  # return_attention: the per-batch maps stay on the device and are concatenated like the probabilities
         try:
-            with self._miopen_scope(), self._deferred_norm_checks(dataloader.preproc_func):
+            with self._miopen_scope(), self._deferred_norm_checks(dataloader.preproc_func), self._attention_scope(model) as take_maps:
                 cuts = self._batch_cuts(lo, hi)
                 for k, (s, e) in enumerate(zip(cuts[:-1], cuts[1:])):
                     if self._feed is not None:  # batch k+1 crosses PCIe while batch k computes
@@ -977,14 +1033,19 @@ class EngineABC:
                         batch = self._preprocess_batch(dataloader, s, e, dtype)
                     with tracing.range("cnn_forward"):
                         outs.append(self._forward_batch(model, infer_batch, batch))
+                    if take_maps is not None:
+                        maps.append(take_maps())
         finally:
             if self._feed is not None:
                 self._feed.close()
                 self._feed = None
             self._shard_span, self._norm_cache = None, None
         if not outs:  # empty shard: a one-patch probe supplies the row shapes
-            probe = self._forward_batch(model, infer_batch, self._preprocess_batch(dataloader, 0, 1, dtype))
-            outs = [tuple(p[:0] for p in probe) if isinstance(probe, tuple) else probe[:0]]
+            with self._attention_scope(model) as take_maps:
+                probe = self._forward_batch(model, infer_batch, self._preprocess_batch(dataloader, 0, 1, dtype))
+                outs = [tuple(p[:0] for p in probe) if isinstance(probe, tuple) else probe[:0]]
+                if take_maps is not None:
+                    maps.append(take_maps()[:0])
         multi_head = isinstance(outs[0], tuple)
         heads = list(zip(*outs)) if multi_head else [outs]
         gathered = []
@@ -1001,6 +1062,11 @@ class EngineABC:
             gathered.append(local)
         local = tuple(gathered) if multi_head else gathered[0]
         raw_predictions = {"probabilities": local}
+        if maps:
+            attention = torch.cat(maps)
+            if gather_now:
+                attention = tdist.all_gather_rows(attention.to(self.device) if dev.type == "cuda" else attention, n)
+            raw_predictions["attention"] = attention
         if world_size > 1 and not gather_now:
             raw_predictions["shard"] = (lo, hi, n)
         if self.return_labels and dataloader.labels is not None:

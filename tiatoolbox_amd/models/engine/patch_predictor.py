@@ -25,7 +25,12 @@ class PatchPredictor(EngineABC):
     (0, 1]) with ``int8_calibration`` (patches as a run takes them, or a scales dict of ``calibrate_int8_smoothing`` /
     ``engine.int8_smoothing_scales``): per-input-channel smoothing of the INT8 layers beside "int8" only, calibrated once when the
     inference copy is built, for checkpoints with outlier channels -- unmeasured on real ones; a ``ValueError`` in every other
-    combination) and ``stain_normalizer`` (a fitted :class:`~tiatoolbox_amd.tools.stainnorm.StainNormalizer`; shorthand
+    combination), ``return_attention`` (``None`` | "class" | "rollout", patch mode, models whose ``feat_extract`` is a
+    ``VisionTransformer``, every ``compute_dtype`` but "bfloat16x3"; decided per call like ``return_probabilities``: the result gets an
+    ``"attention"`` key, float32, one map per patch on the patch grid -- "class" ``[N, heads, gh, gw]``, the class token's attention
+    in the last block per head, NOT renormalised: a map sums to 1 minus the mass on the class and register tokens; "rollout"
+    ``[N, gh, gw]``, attention rollout with mean head fusion -- while every other key is bit for bit that of the run without it;
+    ``VisionTransformer.forward_with_attention`` states both; a ``ValueError`` elsewhere) and ``stain_normalizer`` (a fitted :class:`~tiatoolbox_amd.tools.stainnorm.StainNormalizer`; shorthand
     for ``model.preproc_func = StainNormPreproc(normalizer, default_preproc)``).
 
     WSI mode (``patch_mode=False``) also takes ``merge_predictions=True`` with ``merge_resolution`` (default 1.25) and

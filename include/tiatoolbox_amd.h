@@ -54,7 +54,8 @@ extern "C" {
  * tia_swiglu_rows_qi8 (the Vision Transformer linear layers on the INT8 matrix instruction); tia_gelu_rows_qi8_smooth,
  * tia_swiglu_rows_qi8_smooth, tia_layernorm_rows_absmax_h, tia_gelu_rows_absmax_h, tia_swiglu_rows_absmax_h (per-input-channel
  * smoothing of those layers and its calibration statistics); tia_mha_probs_h, tia_rollout_step_f32 (attention maps of the Vision
- * Transformer runs: the probabilities tia_mha_fwd_h does not materialise, and attention rollout). */
+ * Transformer runs: the probabilities tia_mha_fwd_h does not materialise, and attention rollout); tia_merge_patch_grids_f32 (those maps resampled into a
+ * whole-slide heat map). */
 #define TIA_ABI_VERSION 6
 int tia_abi_version(void);
 
@@ -416,6 +417,28 @@ int tia_canvas_finalize_f32(const float* d_row_a, const uint8_t* d_cnt_a, int64_
 int tia_merge_patch_rects_f32(const int32_t* d_rects, const float* d_values, int64_t n, int64_t c, int64_t h, int64_t w,
                               const int32_t* d_tile_offsets, const int32_t* d_tile_items, int64_t tile_h, int64_t tile_w,
                               float* d_sum, float* d_raw, int32_t* d_count, void* d_labels, int32_t label_bytes, void* stream);
+
+/*
+ * Per-patch attention grids resampled into a whole-slide map (PatchPredictor.merge_attention; additive at version 6).  The
+ * arithmetic is stated once, in the docstring of models/engine/_attention_merge.py.  Patch i covers the rectangle d_rects[i] as in
+ * tia_merge_patch_rects_f32 and brings d_maps[i] = c grids of gh x gw cells; a covered pixel (Y, X) samples them at
+ * gx = ax * float(X - x0) + cx, gy = ay * float(Y - y0) + cy with d_affine[i] = (ax, cx, ay, cy), clamped to [0, gw - 1] x
+ * [0, gh - 1], every float32 operation rounded on its own: mode 0 the nearest cell (floor(g + 0.5)), mode 1 bilinear between the
+ * four cells around (j0 = floor(g), weight g - j0, j1 = min(j0 + 1, g* - 1); top and bottom lerp in x, then one lerp in y, each
+ * a + t * (b - a)).  sum[k,Y,X] = the float32 sum of the samples over the covering patches, added one at a time in ascending i;
+ * count[Y,X] = their number; raw = float32(float64(sum) / (float64(count) + 1e-8)).  The tile lists are those of
+ * tia_merge_patch_rects_f32 (ASCENDING per tile: the caller's contract; an item outside [0, n) is skipped).  Outputs are planar.
+ * No atomics: two launches give the same bits.  Any of the three outputs may be NULL, not all.
+ *   d_rects [n,4] i32   d_affine [n,4] f32   d_maps [n,c,gh,gw] f32   d_tile_offsets [tiles_y*tiles_x+1] i32
+ *   d_tile_items [d_tile_offsets[last]] i32   d_sum, d_raw [c,h,w] f32   d_count [h,w] i32
+ * TIA_EINVAL: a null input or list pointer, all outputs NULL, n / c / gh / gw / h / w / tile_h / tile_w <= 0, mode not 0 or 1.
+ * TIA_ESIZE: h * w >= 2^31, n >= 2^31, c >= 2^31, gh * gw >= 2^31, gh or gw > 2^24 (the clamp's upper end must be a float32
+ * number), or 2^24 tiles or more.  Nothing is launched on an error.  With d_sum and d_raw both NULL nothing is sampled: the
+ * coverage count takes one walk of each list whatever c is.
+ */
+int tia_merge_patch_grids_f32(const int32_t* d_rects, const float* d_affine, const float* d_maps, int64_t n, int64_t c, int64_t gh,
+                              int64_t gw, int64_t h, int64_t w, const int32_t* d_tile_offsets, const int32_t* d_tile_items,
+                              int64_t tile_h, int64_t tile_w, int32_t mode, float* d_sum, float* d_raw, int32_t* d_count, void* stream);
 
 
 /* =======================================================================================

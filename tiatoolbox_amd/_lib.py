@@ -92,6 +92,7 @@ _SIGNATURES = {
     "tia_canvas_row_merge_f32": ([_P, _P, _I64, _I64, _I64, _I64, _I64, _P, _P, _P, _P], C.c_int),
     "tia_canvas_finalize_f32": ([_P, _P, _I64, _P, _P, _I64, _I64, _I64, _I64, _I64, _I64, _P, _P, _P], C.c_int),
     "tia_merge_patch_rects_f32": ([_P, _P, _I64, _I64, _I64, _I64, _P, _P, _I64, _I64, _P, _P, _P, _P, _I32, _P], C.c_int),
+    "tia_merge_patch_grids_f32": ([_P, _P, _P, _I64, _I64, _I64, _I64, _I64, _I64, _P, _P, _I64, _I64, _I32, _P, _P, _P, _P], C.c_int),
     "tia_gather_patches_u8": ([_P, _I64, _I64, _I64, _P, _I64, _I64, _I64, _I32, _P, _P], C.c_int),
     "tia_gather_area_patches_u8": ([_P, _I64, _I64, _I64, _P, _I64, _I64, _I64, _I64, _I32, _P, _P], C.c_int),
     "tia_gather_area_resize_u8": ([_P, _I64, _I64, _I64, _P, _I64, _I64, _I64, _I64, _I64, _I32, _P, _P], C.c_int),

@@ -6,6 +6,8 @@
 // Also here: merge_patch_rects_kernel, the patch classifier's merge_predictions (models/engine/patch_predictor.py:merge_predictions
 // of the reference: `out[y0:y1, x0:x1] += p[i]` in a loop over patches, then a divide by the coverage count and an argmax): one
 // workgroup per map tile walks the tile's ascending list of patch rectangles, so every pixel adds its patches in patch order;
+// merge_patch_grids_kernel, the same walk for merge_attention, where a patch brings a grid of attention cells that every covered
+// pixel samples (nearest or bilinear) instead of one row of values;
 // and the batched patch reads of the WSI engines (plain, area-resampled, bicubic) further down.
 #include <float.h>
 
@@ -144,6 +146,102 @@ __global__ __launch_bounds__(CT) void merge_patch_rects_kernel(const int* __rest
         }
         if (count) count[pix] = cnt;
         if (labels) labels[pix] = (L)(cnt > 0 ? best + 1 : 0);
+    }
+}
+
+
+// ---- merge_attention: per-patch attention grids resampled into a whole-slide map ------------------------------------------
+// The arithmetic is stated once, in models/engine/_attention_merge.py.  Patch i brings a grid maps[i, k, :, :] of gh x gw cells
+// instead of one row of values; a covered pixel (Y, X) samples it at gx = ax * float(X - X0) + cx, gy = ay * float(Y - Y0) + cy
+// (affine[i] = (ax, cx, ay, cy), made on the host; (X0, Y0) the rectangle's own corner), clamped to the grid, nearest or bilinear,
+// every float32 operation rounded on its own, so that NumPy float32 gives the same bits: plain operators under this file's
+// `#pragma clang fp contract(off)`.  (NOT __fmul_rn / __fadd_rn: in this toolchain's headers they are `x * y` / `x + y` compiled under the
+// headers' default contraction, and once inlined a __fadd_rn(__fmul_rn(..), ..) becomes one fma -- seen on the device as 295 differing
+// sums on a 64 x 48 map.)  The structure is merge_patch_rects_kernel's: a workgroup owns a tile and walks its ascending list;
+// the item, its rectangle and its affine are wave-uniform; a pixel computes its cell indices and weights once per patch and
+// uses them for up to kMergeChunk channels held in registers (further channels: further passes, order unchanged).  The clamp
+// keeps every index inside the grid whatever the affine holds (NaN included: fmaxf / fminf return the other operand; gw - 1 and
+// gh - 1 are exact in float32 because the entry point refuses a grid side above 2^24), so the gathers cannot leave `maps`; a
+// patch's grid is a few KB at most and stays in cache.  With neither `sum` nor `raw` wanted the walk only counts: one pass, no
+// gathers.  Outputs are planar ([c, h, w]): consecutive lanes take consecutive X and store consecutive floats.  No atomics.
+template <int MODE>
+__global__ __launch_bounds__(CT) void merge_patch_grids_kernel(const int* __restrict__ rects, const float* __restrict__ affine,
+                                                                const float* __restrict__ maps, int n, int c, int gh, int gw, int h, int w,
+                                                                const int* __restrict__ tile_offsets, const int* __restrict__ tile_items,
+                                                                int tile_h, int tile_w, int tiles_x, float* __restrict__ sum,
+                                                                float* __restrict__ raw, int* __restrict__ count) {
+    const int tile = (int)blockIdx.x;
+    const int ty = tile / tiles_x, tx = tile - ty * tiles_x;
+    const int y0 = ty * tile_h, x0 = tx * tile_w;
+    const int th = min(tile_h, h - y0), tw = min(tile_w, w - x0);
+    const int lb = tile_offsets[tile], le = tile_offsets[tile + 1];
+    const size_t cells = (size_t)gh * gw, plane = (size_t)h * w;
+    const float xmax = (float)(gw - 1), ymax = (float)(gh - 1);
+    const bool sample = sum != nullptr || raw != nullptr;
+    const int c_end = sample ? c : 1;  // (coverage alone: one walk of the list)
+    for (int p = threadIdx.x; p < th * tw; p += CT) {
+        const int py = p / tw;
+        const int X = x0 + (p - py * tw), Y = y0 + py;
+        const size_t pix = (size_t)Y * w + X;
+        int cnt = 0;
+        for (int c0 = 0; c0 < c_end; c0 += kMergeChunk) {
+            const int cc = min(kMergeChunk, c - c0);
+            float acc[kMergeChunk];
+#pragma unroll
+            for (int k = 0; k < kMergeChunk; ++k) acc[k] = 0.0f;
+            cnt = 0;
+            for (int j = lb; j < le; ++j) {
+                const int i = tile_items[j];
+                if ((unsigned)i >= (unsigned)n) continue;
+                const int* r = rects + (size_t)i * 4;
+                const int rx0 = r[0], ry0 = r[1];
+                if (!(X >= rx0 && X < r[2] && Y >= ry0 && Y < r[3])) continue;
+                ++cnt;
+                if (!sample) continue;
+                const float* a = affine + (size_t)i * 4;
+                float gx = a[0] * (float)(X - rx0) + a[1];  // (two roundings: see above)
+                float gy = a[2] * (float)(Y - ry0) + a[3];
+                gx = fminf(fmaxf(gx, 0.0f), xmax);
+                gy = fminf(fmaxf(gy, 0.0f), ymax);
+                const float* g = maps + ((size_t)i * c + c0) * cells;
+                if (MODE == 0) {
+                    const int jx = min((int)floorf(gx + 0.5f), gw - 1), jy = min((int)floorf(gy + 0.5f), gh - 1);
+                    const size_t o = (size_t)jy * gw + jx;
+#pragma unroll
+                    for (int k = 0; k < kMergeChunk; ++k) {
+                        if (k < cc) acc[k] = acc[k] + g[o];
+                        g += cells;  // (a running pointer: sixteen hoisted 64-bit channel offsets would not fit the scalar registers)
+                    }
+                } else {
+                    const int jx0 = (int)floorf(gx), jy0 = (int)floorf(gy);
+                    const float wx = gx - (float)jx0, wy = gy - (float)jy0;
+                    const int jx1 = min(jx0 + 1, gw - 1), jy1 = min(jy0 + 1, gh - 1);
+                    const size_t o00 = (size_t)jy0 * gw + jx0, o01 = (size_t)jy0 * gw + jx1;
+                    const size_t o10 = (size_t)jy1 * gw + jx0, o11 = (size_t)jy1 * gw + jx1;
+#pragma unroll
+                    for (int k = 0; k < kMergeChunk; ++k) {
+                        if (k < cc) {
+                            const float v00 = g[o00], v01 = g[o01], v10 = g[o10], v11 = g[o11];
+                            const float top = v00 + wx * (v01 - v00);
+                            const float bot = v10 + wx * (v11 - v10);
+                            acc[k] = acc[k] + (top + wy * (bot - top));
+                        }
+                        g += cells;
+                    }
+                }
+            }
+            const double den = (double)cnt + 1e-8;
+            size_t o = (size_t)c0 * plane + pix;
+#pragma unroll
+            for (int k = 0; k < kMergeChunk; ++k) {
+                if (k < cc) {
+                    if (sum) sum[o] = acc[k];
+                    if (raw) raw[o] = (float)((double)acc[k] / den);
+                }
+                o += plane;
+            }
+        }
+        if (count) count[pix] = cnt;
     }
 }
 
@@ -646,6 +744,32 @@ extern "C" int tia_merge_patch_rects_f32(const int32_t* d_rects, const float* d_
         hipLaunchKernelGGL(tia::merge_patch_rects_kernel<int32_t>, dim3((unsigned)(tiles_x * tiles_y)), dim3(tia::CT), 0, st, d_rects,
                            d_values, (int)n, (int)c, (int)h, (int)w, d_tile_offsets, d_tile_items, (int)th, (int)tw, (int)tiles_x, d_sum,
                            d_raw, d_count, (int32_t*)d_labels);
+    }
+    return hipGetLastError() == hipSuccess ? TIA_OK : TIA_ELAUNCH;
+}
+
+extern "C" int tia_merge_patch_grids_f32(const int32_t* d_rects, const float* d_affine, const float* d_maps, int64_t n, int64_t c,
+                                         int64_t gh, int64_t gw, int64_t h, int64_t w, const int32_t* d_tile_offsets,
+                                         const int32_t* d_tile_items, int64_t tile_h, int64_t tile_w, int32_t mode, float* d_sum,
+                                         float* d_raw, int32_t* d_count, void* stream) {
+    if (!d_rects || !d_affine || !d_maps || !d_tile_offsets || !d_tile_items) return TIA_EINVAL;
+    if (!d_sum && !d_raw && !d_count) return TIA_EINVAL;
+    if (n <= 0 || c <= 0 || gh <= 0 || gw <= 0 || h <= 0 || w <= 0 || tile_h <= 0 || tile_w <= 0) return TIA_EINVAL;
+    if (mode != 0 && mode != 1) return TIA_EINVAL;
+    if (h > 0x7fffffffL || w > 0x7fffffffL || h * w > 0x7fffffffL || n > 0x7fffffffL || c > 0x7fffffffL) return TIA_ESIZE;
+    if (gh > (1L << 24) || gw > (1L << 24) || gh * gw > 0x7fffffffL) return TIA_ESIZE;  // (a side above 2^24: gw - 1 is no float32 number)
+    const long th = tile_h < h ? tile_h : h, tw = tile_w < w ? tile_w : w;
+    const long tiles_x = (w + tw - 1) / tw, tiles_y = (h + th - 1) / th;
+    if (tiles_x * tiles_y >= (1L << 24)) return TIA_ESIZE;
+    hipStream_t st = (hipStream_t)stream;
+    if (mode == 0) {
+        hipLaunchKernelGGL(tia::merge_patch_grids_kernel<0>, dim3((unsigned)(tiles_x * tiles_y)), dim3(tia::CT), 0, st, d_rects, d_affine,
+                           d_maps, (int)n, (int)c, (int)gh, (int)gw, (int)h, (int)w, d_tile_offsets, d_tile_items, (int)th, (int)tw,
+                           (int)tiles_x, d_sum, d_raw, d_count);
+    } else {
+        hipLaunchKernelGGL(tia::merge_patch_grids_kernel<1>, dim3((unsigned)(tiles_x * tiles_y)), dim3(tia::CT), 0, st, d_rects, d_affine,
+                           d_maps, (int)n, (int)c, (int)gh, (int)gw, (int)h, (int)w, d_tile_offsets, d_tile_items, (int)th, (int)tw,
+                           (int)tiles_x, d_sum, d_raw, d_count);
     }
     return hipGetLastError() == hipSuccess ? TIA_OK : TIA_ELAUNCH;
 }

@@ -35,7 +35,11 @@ class DeepFeatureExtractor(PatchPredictor):
     class token's attention in the last block (not renormalised: a map sums to 1 minus the mass on the class and register tokens),
     "rollout" ``[N, gh, gw]``, attention rollout with mean head fusion -- beside features that are bit for bit those of the run without
     it.  On the hand-written graph the maps come from ``tia_mha_probs_h`` / ``tia_rollout_step_f32`` on the qkv tensors attention
-    itself read, so they describe the computation that ran, quantised routes included; a ``ValueError`` anywhere else."""
+    itself read, so they describe the computation that ran, quantised routes included; a ``ValueError`` anywhere else.
+    ``merge_attention``: ``None`` | "class" | "rollout", the same maps for WSI-mode runs (``patch_mode=False``; with
+    ``attention_interpolation``, ``merge_resolution`` and ``merge_units``): every slide's ``.npz`` also holds ``attention``,
+    ``merged_attention`` -- the slide-level heat map of :meth:`PatchPredictor.merge_attention`, merged on the device by
+    ``tia_merge_patch_grids_f32`` -- and ``attention_coverage``.  ``merge_predictions`` stays refused here: features have no class map."""
 
     def __init__(self, model, batch_size: int = 8, num_workers: int = 0, weights=None, *,
                  device: str = "cpu", verbose: bool = True) -> None:

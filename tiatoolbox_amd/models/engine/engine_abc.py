@@ -76,6 +76,11 @@ _INT8_SMOOTH_COVERS = ("int8_smoothing=alpha (0 < alpha <= 1) smooths the qkv, f
 # on the hand-written graph tia_mha_probs_h / tia_rollout_step_f32 read the qkv tensor attention read).  Per call.
 _ATTENTION_COVERS = ("return_attention is None, \"class\" or \"rollout\" and covers patch-mode runs of models whose feat_extract is a "
                      "VisionTransformer (TimmBackbone / TimmModel) in every compute_dtype but \"bfloat16x3\"")
+# merge_attention="class" | "rollout": the same maps in WSI mode, kept on the device and resampled into a slide-level heat map
+# (engine/_attention_merge.py, tia_merge_patch_grids_f32).  Per call; a name of its own, since return_attention stays patch-mode.
+_MERGE_ATTENTION_COVERS = ("merge_attention is None, \"class\" or \"rollout\" and covers WSI-mode runs (patch_mode=False) of models whose "
+                           "feat_extract is a VisionTransformer (TimmBackbone / TimmModel) in every compute_dtype but \"bfloat16x3\", with "
+                           "attention_interpolation \"nearest\" or \"bilinear\"")
 
 
 def _compute_name(compute_dtype) -> str:
@@ -705,13 +710,39 @@ class EngineABC:
             raise ValueError(msg)
         return kind
 
+    def _checked_merge_attention(self, kind, interpolation, *, patch_mode: bool, compute_dtype):
+        """The run kwarg ``merge_attention`` of this call (``None``, "class" or "rollout") after ``return_attention``'s own checks, with
+        ``patch_mode=False`` required instead of refused.  Anything else is a ``ValueError`` before any launch and before any other
+        kwarg of the call becomes an attribute (``compute_dtype`` is the value this call would run with)."""
+        if kind is None:
+            return None
+        from tiatoolbox_amd.models.architecture.vit import ATTENTION_KINDS
+        from tiatoolbox_amd.models.architecture.vit import VisionTransformer as _ViT
+        from tiatoolbox_amd.models.engine._attention_merge import INTERPOLATIONS
+
+        problem = None
+        if kind not in ATTENTION_KINDS:
+            problem = f"got merge_attention={kind!r}"
+        elif interpolation not in INTERPOLATIONS:
+            problem = f"got attention_interpolation={interpolation!r}"
+        elif not isinstance(getattr(self.model, "feat_extract", None), _ViT):
+            problem = f"got {type(self.model).__name__}, which has no VisionTransformer"
+        elif _compute_name(compute_dtype) == SPLIT_COMPUTE:
+            problem = f"got compute_dtype={SPLIT_COMPUTE!r}, whose float32 graph has no attention-map kernel"
+        elif patch_mode:
+            problem = "got patch_mode=True (patch mode has return_attention)"
+        if problem is not None:
+            msg = f"{_MERGE_ATTENTION_COVERS}; {problem}."
+            raise ValueError(msg)
+        return kind
+
     @contextlib.contextmanager
-    def _attention_scope(self, model):
+    def _attention_scope(self, model, kind=None):
         """Yields ``take()``, which returns the maps of the forward that just ran (float32, on the device), or ``None`` when this run
         asks for no maps.  A :class:`FusedViT` trunk writes them beside its output from its own kernels (``return_attention`` /
         ``attention_maps``); a torch ``VisionTransformer`` -- the CPU, ``compute_dtype="float32"``, a model ``FusedViT`` refuses -- through
-        ``forward_with_attention``."""
-        kind = getattr(self, "return_attention", None)
+        ``forward_with_attention``.  ``kind`` overrides the run's ``return_attention`` (WSI mode: ``merge_attention``)."""
+        kind = kind if kind is not None else getattr(self, "return_attention", None)
         if kind is None:
             yield None
             return
@@ -1182,7 +1213,9 @@ class EngineABC:
         size = (int(c_np[0, 2] - c_np[0, 0]), int(c_np[0, 3] - c_np[0, 1])) if len(c_np) else (0, 0)
         uniform = len(c_np) > 0 and bool(np.all(c_np[:, 2] - c_np[:, 0] == size[0]) and np.all(c_np[:, 3] - c_np[:, 1] == size[1]))
         coords_dev = torch.from_numpy(c_np).to(dev) if uniform else None
-        with self._miopen_scope(), self._deferred_norm_checks(hook):
+        kind = getattr(self, "_merge_attention", None)  # merge_attention: the per-batch maps stay on the device, like the rows
+        maps = []
+        with self._miopen_scope(), self._deferred_norm_checks(hook), self._attention_scope(model, kind) as take_maps:
             for s in range(lo, hi, self.batch_size):
                 e = min(s + self.batch_size, hi)
                 raw = (reader.read_bounds_batch(coords_dev[s - lo:e - lo], size=size) if coords_dev is not None
@@ -1192,14 +1225,23 @@ class EngineABC:
                 else:  # arbitrary user hook: per patch on the host, as Dataset.__getitem__ does in the reference
                     batch = torch.stack([torch.as_tensor(np.asarray(hook(p))) for p in raw.cpu().numpy()]).to(dev)
                 outs.append(self._forward_batch(model, infer_batch, batch))
+                if take_maps is not None:
+                    maps.append(take_maps())
         if not outs:
             probe = reader.read_bounds_batch(coords[:1])
             probe = self._device_preproc(hook, probe, dtype) if device_batch is not None else probe
-            outs = [self._forward_batch(model, infer_batch, probe)[:0]]
+            with self._attention_scope(model, kind) as take_maps:
+                outs = [self._forward_batch(model, infer_batch, probe)[:0]]
+                if take_maps is not None:
+                    maps.append(take_maps()[:0])
         local = torch.cat([o if isinstance(o, torch.Tensor) else torch.from_numpy(np.asarray(o)) for o in outs])
         if world_size > 1:
             local = tdist.all_gather_rows(local.to(dev), n)
-        return {"probabilities": local, "coordinates": coords}
+        result = {"probabilities": local, "coordinates": coords}
+        if maps:
+            attention = torch.cat(maps).to(dev)
+            result["attention"] = tdist.all_gather_rows(attention, n) if world_size > 1 else attention
+        return result
 
     def post_process_wsi(self, processed: dict, *, base, reader) -> dict:  # noqa: ARG002
         """Slide-level step of WSI mode after ``post_process_patches``: ``base`` is the slide as opened, ``reader`` the reader

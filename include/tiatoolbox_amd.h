@@ -55,7 +55,8 @@ extern "C" {
  * tia_swiglu_rows_qi8_smooth, tia_layernorm_rows_absmax_h, tia_gelu_rows_absmax_h, tia_swiglu_rows_absmax_h (per-input-channel
  * smoothing of those layers and its calibration statistics); tia_mha_probs_h, tia_rollout_step_f32 (attention maps of the Vision
  * Transformer runs: the probabilities tia_mha_fwd_h does not materialise, and attention rollout); tia_merge_patch_grids_f32 (those maps resampled into a
- * whole-slide heat map). */
+ * whole-slide heat map); tia_mha_probs_fused_h, tia_rollout_discard_normalize_f32, tia_rollout_product_f32 (rollout with max / min
+ * head fusion and a discard ratio). */
 #define TIA_ABI_VERSION 6
 int tia_abi_version(void);
 
@@ -1265,6 +1266,39 @@ int tia_mha_probs_h(const void* d_qkv, float* d_out, int64_t n, int64_t s, int64
  * one rounding per step); both halvings are exact and the final add rounds once.  d_r_in NULL means R_in = I.  Any s >= 1 (tails
  * are zero-filled operands: exact).  Pointers 4-byte aligned; d_r_out overlapping d_a or d_r_in is TIA_EINVAL. */
 int tia_rollout_step_f32(const float* d_a, const float* d_r_in, float* d_r_out, int64_t n, int64_t s, void* stream);
+
+/* ---- rollout with another head fusion or a discard ratio (the engines' attention_head_fusion / attention_discard_ratio; additive,
+ * same version 6; models/engine/_rollout_options.py states the arithmetic).  A run with the default options launches none of these. */
+#define TIA_FUSE_MEAN 0
+#define TIA_FUSE_MAX 1
+#define TIA_FUSE_MIN 2
+
+/* The probabilities of ALL s query rows fused over the heads: d_out float32 [n, s, s].
+ *   TIA_FUSE_MEAN: tia_mha_probs_h(q_rows = s, head_mean = 1), the same kernel: bit for bit.
+ *   TIA_FUSE_MAX / _MIN: the exact element-wise maximum / minimum over the heads of the values tia_mha_probs_h(head_mean = 0) writes
+ *   (the same two passes, e_j / l with one division per head and element).
+ * The limits and codes of tia_mha_probs_h with head_mean = 1 (head_dim 64 or 80, at most 64 heads: TIA_ESIZE); fusion outside the
+ * three values is TIA_EINVAL. */
+int tia_mha_probs_fused_h(const void* d_qkv, float* d_out, int64_t n, int64_t s, int64_t heads, int64_t head_dim, float scale,
+                          int32_t fusion, int32_t dtype, void* stream);
+
+/* Discard and normalise n float32 [s, s] matrices F of finite values >= 0 (one or two launches):
+ *   k >= 1: v[b] = the k-th smallest (1-based, duplicates counted) of the s * s entries of F[b] -- an exact order statistic, found by
+ *   a radix select on the bit patterns (digits of 12, 10, 10 bits, histograms in LDS; integer atomics only, so the result does not
+ *   depend on scheduling) and written to d_v [n]; F'[i][j] = 0 where F[i][j] <= v and (i, j) != (0, 0), F elsewhere.  k = 0: F' = F,
+ *   nothing is selected and d_v may be NULL.
+ *   A^ = (F' + I) / 2 (the halving exact);  s_i = sum_j A^[i][j] in this order of float32 additions: 64 partial sums p[l] = entries
+ *   j = l, l + 64, ... added in ascending order to 0, folded by p[l] += p[l ^ 32], then ^ 16, 8, 4, 2, 1;  d_out[i][j] = A^[i][j] / s_i,
+ *   one correctly rounded division each.
+ * Any n >= 1 and 1 <= s <= 65535 (TIA_ESIZE beyond: the counts are 32-bit), 64-bit offsets.  Values outside the domain (negative,
+ * NaN) give unspecified values, never an access outside the buffers.  TIA_EINVAL, with nothing launched: a null d_f / d_out, d_v null
+ * with k >= 1, k < 0 or k >= s * s, pointers not 4-byte aligned, d_out overlapping d_f, d_v overlapping either. */
+int tia_rollout_discard_normalize_f32(const float* d_f, float* d_out, float* d_v, int64_t n, int64_t s, int64_t k, void* stream);
+
+/* R_out = A R_in on n float32 [s, s] matrices: tia_rollout_step_f32's product (v_mfma_f32_16x16x4_f32, one float32 fma chain over
+ * k = 0 .. s - 1 in ascending order per element, zero-filled tails) without its blend.  d_r_in NULL means R_out = A.  The same
+ * limits, alignment and overlap rules. */
+int tia_rollout_product_f32(const float* d_a, const float* d_r_in, float* d_r_out, int64_t n, int64_t s, void* stream);
 
 /* =======================================================================================
  * All borders of binary planes: cv2.findContours(layer, RETR_TREE, CHAIN_APPROX_NONE | _SIMPLE)

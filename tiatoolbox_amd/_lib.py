@@ -192,6 +192,9 @@ _SIGNATURES = {
     "tia_vit_assemble_f32": ([_P, _P, _P, _P, _I32, _P, _I64, _I64, _I64, _I64, _P], C.c_int),
     "tia_mha_probs_h": ([_P, _P, _I64, _I64, _I64, _I64, C.c_float, _I64, _I32, _I32, _P], C.c_int),
     "tia_rollout_step_f32": ([_P, _P, _P, _I64, _I64, _P], C.c_int),
+    "tia_mha_probs_fused_h": ([_P, _P, _I64, _I64, _I64, _I64, C.c_float, _I32, _I32, _P], C.c_int),
+    "tia_rollout_discard_normalize_f32": ([_P, _P, _P, _I64, _I64, _I64, _P], C.c_int),
+    "tia_rollout_product_f32": ([_P, _P, _P, _I64, _I64, _P], C.c_int),
     "tia_bias_act_nhwc": ([_P, _P, _P, _I64, _I64, _I32, _I32, _P], C.c_int),
     "tia_bias_relu_maxpool_nhwc": ([_P, _P, _I64, _I64, _I64, _I64, _I32, _P, _P], C.c_int),
     "tia_hover_instance_stats": ([_P, _P, _I64, _I64, _I64, _I32, _I32, _P, _P, _P], C.c_int),

@@ -25,6 +25,11 @@
 // fma chain per output element: vit_f32.hip is the other user).  One workgroup = a 64 x 64 tile of one matrix, each wave 16 rows x
 // 64 columns in four accumulators; A and R_in come in 32-deep k tiles through LDS, zero-filled beyond s (0 * 0 adds an exact zero),
 // or -- R_in = I, d_r_in null -- R's tile is written as the identity's.  The epilogue halves both terms exactly and adds once.
+//
+// The rollout's other forms (max / min head fusion, a discard ratio; models/engine/_rollout_options.py states them) are siblings of
+// these two: tia_mha_probs_fused_h is the probabilities kernel with another way of joining the heads (FUSE), tia_rollout_product_f32
+// the step kernel without its blend (BLEND), and tia_rollout_discard_normalize_f32 a radix select per image (kth_smallest_kernel)
+// in front of a row pass (discard_normalize_kernel).  A run with the default options launches none of them.
 #include "conv_device.hpp"
 #include "wide_io.hpp"
 
@@ -111,7 +116,12 @@ __device__ __forceinline__ void score_tile(const unsigned short* k_lds, const v4
     }
 }
 
-template <bool BF, int HD>
+// FUSE: what pass 2 does with the heads of a workgroup -- FUSE_SUM adds them (one head: 0 + p = p exactly; head_mean: / heads at the
+// end), FUSE_MAX / FUSE_MIN keep the exact element-wise maximum / minimum of the SAME per-head values (head_mean geometry: one
+// workgroup owns every head; nothing is divided).
+constexpr int FUSE_SUM = 0, FUSE_MAX = 1, FUSE_MIN = 2;
+
+template <bool BF, int HD, int FUSE>
 __global__ __launch_bounds__(AT) void mha_probs_kernel(const unsigned short* __restrict__ qkv, float* __restrict__ out, int s, int heads,
                                                         int q_rows, int q_tiles, int head_mean, float scale_log2e) {
     using G = Geo<HD>;
@@ -173,7 +183,10 @@ __global__ __launch_bounds__(AT) void mha_probs_kernel(const unsigned short* __r
     for (int k0 = 0; k0 < s; k0 += KV_TILE) {
         f32x4 acc[4];
 #pragma unroll
-        for (int kt = 0; kt < 4; ++kt) acc[kt] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+        for (int kt = 0; kt < 4; ++kt) {
+            const float first = FUSE == FUSE_MIN ? INFINITY : 0.0f;  // (every p is >= +0: max(0, p) = p)
+            acc[kt] = f32x4{first, first, first, first};
+        }
         for (int hl = 0; hl < nh; ++hl) {
             const unsigned short* base = image + (long)(h0 + hl) * HD;
             const unsigned short* kbase = base + (long)heads * HD;
@@ -186,11 +199,18 @@ __global__ __launch_bounds__(AT) void mha_probs_kernel(const unsigned short* __r
 #pragma unroll
             for (int kt = 0; kt < 4; ++kt)
 #pragma unroll
-                for (int r = 0; r < 4; ++r) acc[kt][r] += __builtin_amdgcn_exp2f(t[kt][r] - m) / l;  // (one head: 0 + p = p exactly)
+                for (int r = 0; r < 4; ++r) {
+                    if constexpr (FUSE == FUSE_SUM) {
+                        acc[kt][r] += __builtin_amdgcn_exp2f(t[kt][r] - m) / l;  // (one head: 0 + p = p exactly)
+                    } else {
+                        const float p = __builtin_amdgcn_exp2f(t[kt][r] - m) / l;
+                        acc[kt][r] = FUSE == FUSE_MAX ? fmaxf(acc[kt][r], p) : fminf(acc[kt][r], p);
+                    }
+                }
         }
 #pragma unroll
         for (int kt = 0; kt < 4; ++kt) {
-            if (head_mean) {
+            if (FUSE == FUSE_SUM && head_mean) {
 #pragma unroll
                 for (int r = 0; r < 4; ++r) acc[kt][r] = acc[kt][r] / count;
             }
@@ -215,6 +235,8 @@ constexpr int RK = 32;        // k tile
 constexpr int A_PITCH = 34;   // floats: lane (row r, k q) of a half wave reads bank 2 r + q -- 32 distinct
 constexpr int R_PITCH = 80;   // floats: lane (k q, column c) of a half wave reads bank 16 q + c -- 32 distinct
 
+// BLEND: the epilogue of tia_rollout_step_f32 (1/2 (A R) + 1/2 R); without it the product alone, R_out = A R (tia_rollout_product_f32)
+template <bool BLEND>
 __global__ __launch_bounds__(AT) void rollout_step_kernel(const float* __restrict__ a, const float* __restrict__ r_in, float* __restrict__ r_out,
                                                            int s, int tiles) {
     __shared__ float a_lds[RT * A_PITCH];  // [row][k]
@@ -267,21 +289,117 @@ __global__ __launch_bounds__(AT) void rollout_step_kernel(const float* __restric
             const int row = row0 + wave * 16 + 4 * quarter + r, col = col0 + 16 * c + r16;
             if (row < s && col < s) {
                 const long at = mat + (long)row * s + col;
-                const float prev = r_in ? r_in[at] : (row == col ? 1.0f : 0.0f);
-                r_out[at] = 0.5f * acc[c][r] + 0.5f * prev;  // both halvings exact: one rounding
+                if constexpr (BLEND) {
+                    const float prev = r_in ? r_in[at] : (row == col ? 1.0f : 0.0f);
+                    r_out[at] = 0.5f * acc[c][r] + 0.5f * prev;  // both halvings exact: one rounding
+                } else {
+                    r_out[at] = acc[c][r];  // (R_in = I: a + 0 * x = a, the matrix itself)
+                }
             }
         }
 }
 
-bool overlap(const void* p, const void* q, uint64_t bytes) {
-    const uintptr_t a = reinterpret_cast<uintptr_t>(p), b = reinterpret_cast<uintptr_t>(q);
-    return a < b + bytes && b < a + bytes;
+// ---- discard and normalise (tia_rollout_discard_normalize_f32) -------------------------------------------------------------------
+// kth_smallest_kernel: one workgroup of 1024 threads per image finds the k-th smallest (1-based, duplicates counted) of its s * s
+// float32 values.  They are finite and >= 0, so their bit patterns order as unsigned integers: a radix select from the top, digits
+// of 12, 10 and 10 bits (the first one holds the exponent and four mantissa bits: probabilities of one magnitude still spread over
+// some tens of counters).  Per digit: a histogram in LDS of the values that carry the digits chosen so far (integer atomic adds:
+// the counts do not depend on their order), then one lane walks the cumulative counts to the bin that holds the rank.  Any bit
+// pattern indexes inside the histogram, and the walks are bounded by the bins a lane owns.
+constexpr int ST = 1024;        // threads of the selection
+constexpr int SEL_BINS = 4096;  // counters: 2^12, the widest digit
+constexpr int SEL_GROUP = ST / 64;  // threads whose bin sums one lane of wave 0 adds up
+
+__global__ __launch_bounds__(ST) void kth_smallest_kernel(const float* __restrict__ f, float* __restrict__ v_out, long count, unsigned k) {
+    __shared__ unsigned hist[SEL_BINS];
+    __shared__ unsigned part[ST];  // a thread's bins added up
+    __shared__ unsigned chosen[2];  // the bin that holds the rank, and the rank inside it
+
+    const int tid = threadIdx.x, lane = tid & 63;
+    const unsigned* x = reinterpret_cast<const unsigned*>(f) + (long)blockIdx.x * count;
+    unsigned prefix = 0u, mask = 0u, rank = k;
+#pragma unroll 1
+    for (int pass = 0; pass < 3; ++pass) {
+        const int shift = pass == 0 ? 20 : (pass == 1 ? 10 : 0);
+        const int bins = pass == 0 ? SEL_BINS : 1024, per = bins / ST;
+        for (int i = tid; i < SEL_BINS; i += ST) hist[i] = 0u;
+        if (tid == 0) { chosen[0] = 0u; chosen[1] = 1u; }
+        __syncthreads();
+        for (long i = tid; i < count; i += ST) {
+            const unsigned u = x[i];
+            if ((u & mask) == prefix) atomicAdd(&hist[(u >> shift) & (unsigned)(bins - 1)], 1u);
+        }
+        __syncthreads();
+        unsigned mine = 0u;
+        for (int i = 0; i < per; ++i) mine += hist[tid * per + i];
+        part[tid] = mine;
+        __syncthreads();
+        if (tid < 64) {
+            unsigned group = 0u;
+            for (int i = 0; i < SEL_GROUP; ++i) group += part[lane * SEL_GROUP + i];
+            unsigned incl = group;
+            for (int off = 1; off < 64; off <<= 1) {
+                const unsigned o = __shfl_up(incl, off, 64);
+                if (lane >= off) incl += o;
+            }
+            const unsigned excl = incl - group;
+            if (rank > excl && rank <= incl) {  // one lane: 1 <= rank <= the number of values counted
+                unsigned r = rank - excl;
+                int t = lane * SEL_GROUP;
+                while (t < lane * SEL_GROUP + SEL_GROUP - 1 && r > part[t]) r -= part[t++];
+                int b = t * per;
+                while (b < t * per + per - 1 && r > hist[b]) r -= hist[b++];
+                chosen[0] = (unsigned)b;
+                chosen[1] = r;
+            }
+        }
+        __syncthreads();
+        prefix |= chosen[0] << shift;
+        mask |= (unsigned)(bins - 1) << shift;
+        rank = chosen[1];
+        __syncthreads();  // (chosen and hist are rewritten by the next digit)
+    }
+    if (tid == 0) v_out[blockIdx.x] = __uint_as_float(prefix);
 }
 
-}  // namespace
+// discard_normalize_kernel: one wave per row i of one image.  A^[i][j] = ((F'[i][j] + [i == j]) / 2) / s_i with F' = F, but 0 where
+// F <= v and (i, j) != (0, 0) (has_v), and s_i the row sum in THIS order: lane l adds its entries j = l, l + 64, ... in ascending
+// order to 0, then the 64 partial sums fold by the exchange tree p[l] += p[l ^ 32], ^ 16, ^ 8, ^ 4, ^ 2, ^ 1 (every lane ends with
+// the same bits: the additions of a level commute).  The row is read twice and written once; s_i >= 1/2.
+__device__ __forceinline__ float halved_entry(float x, float thr, bool has_v, bool origin, bool diagonal) {
+    const float kept = (has_v && x <= thr && !origin) ? 0.0f : x;
+    return 0.5f * (kept + (diagonal ? 1.0f : 0.0f));
+}
 
-extern "C" int tia_mha_probs_h(const void* d_qkv, float* d_out, int64_t n, int64_t s, int64_t heads, int64_t head_dim, float scale,
-                               int64_t q_rows, int32_t head_mean, int32_t dtype, void* stream) {
+__global__ __launch_bounds__(AT) void discard_normalize_kernel(const float* __restrict__ f, const float* __restrict__ v, float* __restrict__ out,
+                                                                int s, int has_v, long rows) {
+#pragma clang fp contract(off)
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const long row = (long)blockIdx.x * 4 + wave;  // of all n * s rows
+    if (row >= rows) return;                       // (a whole wave: nothing below is a workgroup barrier)
+    const long b = row / s;
+    const int i = (int)(row - b * s);
+    const float thr = has_v ? v[b] : 0.0f;
+    const float* src = f + row * s;
+    float* dst = out + row * s;
+    float sum = 0.0f;
+    for (int j = lane; j < s; j += 64) sum += halved_entry(src[j], thr, has_v != 0, (i | j) == 0, i == j);
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) sum += __shfl_xor(sum, off, 64);
+    for (int j = lane; j < s; j += 64) dst[j] = halved_entry(src[j], thr, has_v != 0, (i | j) == 0, i == j) / sum;
+}
+
+bool overlap(const void* p, uint64_t p_bytes, const void* q, uint64_t q_bytes) {
+    const uintptr_t a = reinterpret_cast<uintptr_t>(p), b = reinterpret_cast<uintptr_t>(q);
+    return a < b + q_bytes && b < a + p_bytes;
+}
+
+bool overlap(const void* p, const void* q, uint64_t bytes) { return overlap(p, bytes, q, bytes); }
+
+// the checks and the launch of both forms of the probabilities kernel: q_rows queries per head or head mean (FUSE_SUM), or all rows
+// with the heads' maximum / minimum
+int launch_probs(const void* d_qkv, float* d_out, int64_t n, int64_t s, int64_t heads, int64_t head_dim, float scale, int64_t q_rows,
+                 int32_t head_mean, int fuse, int32_t dtype, void* stream) {
     if (!d_qkv || !d_out || n <= 0 || s <= 0 || heads <= 0 || head_dim <= 0) return TIA_EINVAL;
     if (dtype != TIA_DT_F16 && dtype != TIA_DT_BF16) return TIA_EINVAL;
     if (!(scale > 0.0f) || !(scale < INFINITY)) return TIA_EINVAL;
@@ -297,14 +415,22 @@ extern "C" int tia_mha_probs_h(const void* d_qkv, float* d_out, int64_t n, int64
     const size_t stat_bytes = (size_t)(head_mean ? heads : 1) * 64 * 2 * sizeof(float);
     const float scale_log2e = scale * 1.44269504088896340736f;
     const bool bf = dtype == TIA_DT_BF16;
-    const auto kernel = head_dim == 80 ? (bf ? mha_probs_kernel<true, 80> : mha_probs_kernel<false, 80>)
-                                       : (bf ? mha_probs_kernel<true, 64> : mha_probs_kernel<false, 64>);
+    auto kernel = head_dim == 80 ? (bf ? mha_probs_kernel<true, 80, FUSE_SUM> : mha_probs_kernel<false, 80, FUSE_SUM>)
+                                 : (bf ? mha_probs_kernel<true, 64, FUSE_SUM> : mha_probs_kernel<false, 64, FUSE_SUM>);
+    if (fuse == FUSE_MAX)
+        kernel = head_dim == 80 ? (bf ? mha_probs_kernel<true, 80, FUSE_MAX> : mha_probs_kernel<false, 80, FUSE_MAX>)
+                                : (bf ? mha_probs_kernel<true, 64, FUSE_MAX> : mha_probs_kernel<false, 64, FUSE_MAX>);
+    else if (fuse == FUSE_MIN)
+        kernel = head_dim == 80 ? (bf ? mha_probs_kernel<true, 80, FUSE_MIN> : mha_probs_kernel<false, 80, FUSE_MIN>)
+                                : (bf ? mha_probs_kernel<true, 64, FUSE_MIN> : mha_probs_kernel<false, 64, FUSE_MIN>);
     hipLaunchKernelGGL(kernel, dim3((unsigned)blocks), dim3(AT), stat_bytes, (hipStream_t)stream, (const unsigned short*)d_qkv, d_out,
                        (int)s, (int)heads, (int)q_rows, (int)q_tiles, (int)head_mean, scale_log2e);
     return hipGetLastError() == hipSuccess ? TIA_OK : TIA_ELAUNCH;
 }
 
-extern "C" int tia_rollout_step_f32(const float* d_a, const float* d_r_in, float* d_r_out, int64_t n, int64_t s, void* stream) {
+// the checks and the launch of both epilogues of the rollout matrix product
+template <bool BLEND>
+int launch_rollout(const float* d_a, const float* d_r_in, float* d_r_out, int64_t n, int64_t s, void* stream) {
     if (!d_a || !d_r_out || n <= 0 || s <= 0) return TIA_EINVAL;
     if ((reinterpret_cast<uintptr_t>(d_a) | reinterpret_cast<uintptr_t>(d_r_in) | reinterpret_cast<uintptr_t>(d_r_out)) & 3) return TIA_EINVAL;
     if (s > 0x7fffffffL - RT) return TIA_ESIZE;
@@ -313,7 +439,49 @@ extern "C" int tia_rollout_step_f32(const float* d_a, const float* d_r_in, float
     if (n > INT64_MAX / 4 / s / s) return TIA_ESIZE;
     const uint64_t bytes = (uint64_t)n * s * s * sizeof(float);
     if (overlap(d_r_out, d_a, bytes) || (d_r_in && overlap(d_r_out, d_r_in, bytes))) return TIA_EINVAL;
-    hipLaunchKernelGGL(rollout_step_kernel, dim3((unsigned)(n * tiles * tiles)), dim3(AT), 0, (hipStream_t)stream, d_a, d_r_in, d_r_out,
-                       (int)s, (int)tiles);
+    hipLaunchKernelGGL(rollout_step_kernel<BLEND>, dim3((unsigned)(n * tiles * tiles)), dim3(AT), 0, (hipStream_t)stream, d_a, d_r_in,
+                       d_r_out, (int)s, (int)tiles);
+    return hipGetLastError() == hipSuccess ? TIA_OK : TIA_ELAUNCH;
+}
+
+}  // namespace
+
+extern "C" int tia_mha_probs_h(const void* d_qkv, float* d_out, int64_t n, int64_t s, int64_t heads, int64_t head_dim, float scale,
+                               int64_t q_rows, int32_t head_mean, int32_t dtype, void* stream) {
+    return launch_probs(d_qkv, d_out, n, s, heads, head_dim, scale, q_rows, head_mean, FUSE_SUM, dtype, stream);
+}
+
+extern "C" int tia_mha_probs_fused_h(const void* d_qkv, float* d_out, int64_t n, int64_t s, int64_t heads, int64_t head_dim, float scale,
+                                     int32_t fusion, int32_t dtype, void* stream) {
+    if (fusion != TIA_FUSE_MEAN && fusion != TIA_FUSE_MAX && fusion != TIA_FUSE_MIN) return TIA_EINVAL;
+    const int fuse = fusion == TIA_FUSE_MAX ? FUSE_MAX : (fusion == TIA_FUSE_MIN ? FUSE_MIN : FUSE_SUM);
+    return launch_probs(d_qkv, d_out, n, s, heads, head_dim, scale, s, 1, fuse, dtype, stream);
+}
+
+extern "C" int tia_rollout_step_f32(const float* d_a, const float* d_r_in, float* d_r_out, int64_t n, int64_t s, void* stream) {
+    return launch_rollout<true>(d_a, d_r_in, d_r_out, n, s, stream);
+}
+
+extern "C" int tia_rollout_product_f32(const float* d_a, const float* d_r_in, float* d_r_out, int64_t n, int64_t s, void* stream) {
+    return launch_rollout<false>(d_a, d_r_in, d_r_out, n, s, stream);
+}
+
+extern "C" int tia_rollout_discard_normalize_f32(const float* d_f, float* d_out, float* d_v, int64_t n, int64_t s, int64_t k, void* stream) {
+    if (!d_f || !d_out || n <= 0 || s <= 0 || k < 0 || (k > 0 && !d_v)) return TIA_EINVAL;
+    if ((reinterpret_cast<uintptr_t>(d_f) | reinterpret_cast<uintptr_t>(d_out) | reinterpret_cast<uintptr_t>(d_v)) & 3) return TIA_EINVAL;
+    if (s > 0xffff) return TIA_ESIZE;  // s * s < 2^32: the selection counts in 32 bits
+    if (k >= s * s) return TIA_EINVAL;
+    if (n > 0x7fffffffL || n > INT64_MAX / 4 / s / s) return TIA_ESIZE;
+    const long rows = n * s, blocks = (rows + 3) / 4;
+    if (blocks > 0x7fffffffL) return TIA_ESIZE;  // one grid dimension
+    const uint64_t bytes = (uint64_t)n * s * s * sizeof(float), v_bytes = (uint64_t)n * sizeof(float);
+    if (overlap(d_out, d_f, bytes)) return TIA_EINVAL;
+    if (k > 0 && (overlap(d_v, v_bytes, d_f, bytes) || overlap(d_v, v_bytes, d_out, bytes))) return TIA_EINVAL;
+    if (k > 0) {
+        hipLaunchKernelGGL(kth_smallest_kernel, dim3((unsigned)n), dim3(ST), 0, (hipStream_t)stream, d_f, d_v, (long)(s * s), (unsigned)k);
+        if (hipGetLastError() != hipSuccess) return TIA_ELAUNCH;
+    }
+    hipLaunchKernelGGL(discard_normalize_kernel, dim3((unsigned)blocks), dim3(AT), 0, (hipStream_t)stream, d_f, (const float*)d_v, d_out,
+                       (int)s, (int)(k > 0), rows);
     return hipGetLastError() == hipSuccess ? TIA_OK : TIA_ELAUNCH;
 }

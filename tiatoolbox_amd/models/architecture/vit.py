@@ -264,7 +264,8 @@ class VisionTransformer(nn.Module):
             return torch.cat([x[:, 0], x[:, 1 + self.reg_tokens:].mean(1)], dim=-1)
         return x[:, 0]
 
-    def forward_with_attention(self, imgs: torch.Tensor, kind: str) -> tuple[torch.Tensor, torch.Tensor]:
+    def forward_with_attention(self, imgs: torch.Tensor, kind: str, head_fusion: str = "mean", discard_ratio: float = 0.0, *,
+                               trace: dict | None = None) -> tuple[torch.Tensor, torch.Tensor]:
         """``(forward(imgs), maps)``: the features bit for bit, and float32 attention maps on the patch grid ``(gh, gw)`` of the input.
         With ``S`` tokens, the prefix ``P = 1 + reg_tokens`` (class token, then registers), ``H`` heads and ``q``, ``k`` the ``qkv``
         Linear's own output of a block (in the module's dtype):
@@ -275,10 +276,25 @@ class VisionTransformer(nn.Module):
           ``A_l = (1 / H) sum_h softmax(scale * Q_h K_h^T)`` (heads added in ascending order), ``R_1 = A_1 / 2 + I / 2``,
           ``R_l = (A_l R_{l-1}) / 2 + R_{l-1} / 2``, no renormalisation (the rows sum to 1 already); the map is ``R_L[0, P:]``.
 
+          ``head_fusion`` ("mean" | "max" | "min") and ``discard_ratio`` (``0 <= r < 1``) are the other forms of the rollout
+          (``models/engine/_rollout_options.py`` states them): the heads' maximum or minimum in place of their mean; per block the
+          ``k = min(int(r S^2), S^2 - 1)`` smallest entries of the fused ``S x S`` matrix set to 0 (``torch.kthvalue`` on the flattened
+          matrix gives ``v``; everything ``<= v`` goes, entry ``(0, 0)`` never); then ``A^ = (F' + I) / 2`` with every row divided by
+          its sum, ``R_1 = A^_1``, ``R_l = A^_l R_{l-1}``.  "mean" with ``k == 0`` is the path above, untouched.  A ``ValueError``
+          that names the option for anything else, and for a non-default value beside ``kind="class"``.  ``trace``, a dict, receives
+          the per-block lists ``"fused"`` (``F``) and ``"normalised"`` (``A^``) of that route.
+
         The probabilities are the softmax of the module's own scores, widened to float32; the head mean and ``R`` are float32
         throughout.  A hook records what each block's ``qkv`` returns while ``forward`` itself runs, so the features cannot differ."""
+        from tiatoolbox_amd.models.engine import _rollout_options as ro
+
         if kind not in ATTENTION_KINDS:
             msg = f"VisionTransformer.forward_with_attention: kind is one of {ATTENTION_KINDS}; got {kind!r}."
+            raise ValueError(msg)
+        head_fusion, discard_ratio = ro.check_options(head_fusion, discard_ratio, who="VisionTransformer.forward_with_attention")
+        if kind != "rollout" and not ro.is_default(head_fusion, discard_ratio):
+            msg = (f"VisionTransformer.forward_with_attention: attention_head_fusion={head_fusion!r} / attention_discard_ratio="
+                   f"{discard_ratio!r} apply to kind=\"rollout\" only; got kind={kind!r}.")
             raise ValueError(msg)
         gh, gw = self.grid_of(imgs.shape[-2], imgs.shape[-1])
         prefix, heads = 1 + self.reg_tokens, self.num_heads
@@ -297,6 +313,12 @@ class VisionTransformer(nn.Module):
                         state["class"] = probs(attn, qkv, 1)[:, :, 0, prefix:]
                     return
                 p = probs(attn, qkv, None)
+                k = ro.discard_count(discard_ratio, p.shape[-1])
+                if head_fusion != "mean" or k:
+                    a = _discard_normalise(_fuse_heads(p, head_fusion), k, trace)
+                    r = state.get("r")
+                    state["r"] = a if r is None else a @ r
+                    return
                 a = p[:, 0]
                 for h in range(1, heads):  # ascending head order, float32
                     a = a + p[:, h]
@@ -318,14 +340,14 @@ class VisionTransformer(nn.Module):
         return feats, state["r"][:, 0, prefix:].reshape(-1, gh, gw).contiguous()
 
     @contextlib.contextmanager
-    def capturing_attention(self, kind: str):  # noqa: ANN201
+    def capturing_attention(self, kind: str, head_fusion: str = "mean", discard_ratio: float = 0.0):  # noqa: ANN201
         """Inside the scope every CALL of this module (``model(x)`` of whatever model holds it) returns ``forward``'s features and appends
         the maps of :meth:`forward_with_attention` to the list the scope yields -- how an engine gets both from a model's own
         ``infer_batch``.  ``forward`` itself is not touched: the scope shadows it on the instance and removes the shadow again."""
         maps: list[torch.Tensor] = []
 
         def forward(imgs: torch.Tensor) -> torch.Tensor:
-            feats, m = self.forward_with_attention(imgs, kind)
+            feats, m = self.forward_with_attention(imgs, kind, head_fusion, discard_ratio)
             maps.append(m)
             return feats
 
@@ -334,6 +356,44 @@ class VisionTransformer(nn.Module):
             yield maps
         finally:
             self.__dict__.pop("forward", None)
+
+
+def _fuse_heads(p: torch.Tensor, head_fusion: str) -> torch.Tensor:
+    """``[B, H, S, S]`` float32 -> ``[B, S, S]``: the heads' mean (added in ascending order, one division), maximum or minimum."""
+    if head_fusion == "max":
+        return p.amax(1)
+    if head_fusion == "min":
+        return p.amin(1)
+    a = p[:, 0]
+    for h in range(1, p.shape[1]):
+        a = a + p[:, h]
+    return a / p.shape[1]
+
+
+def _discard_normalise(f: torch.Tensor, k: int, trace: dict | None) -> torch.Tensor:
+    """``A^`` ``[B, S, S]`` of the fused matrices ``f`` (``_rollout_options``: ``discard`` and ``normalise``).  The row sums follow the
+    stated order -- 64 strided partial sums, folded by the exchange tree -- so that this route, the NumPy statement and the kernel
+    agree bit for bit from the same ``f``."""
+    b, s, _ = f.shape
+    kept = f
+    if k:
+        v = torch.kthvalue(f.reshape(b, s * s), k, dim=1).values.reshape(b, 1, 1)
+        drop = f <= v
+        drop[:, 0, 0] = False
+        kept = torch.where(drop, torch.zeros((), dtype=f.dtype, device=f.device), f)
+    a = (kept + torch.eye(s, dtype=f.dtype, device=f.device)) * 0.5
+    parts = torch.zeros((b, s, 64), dtype=f.dtype, device=f.device)
+    for j0 in range(0, s, 64):
+        chunk = a[:, :, j0:j0 + 64]
+        parts[:, :, :chunk.shape[-1]] += chunk
+    lanes = torch.arange(64, device=f.device)
+    for off in (32, 16, 8, 4, 2, 1):
+        parts = parts + parts[:, :, lanes ^ off]
+    a = a / parts[:, :, :1]
+    if trace is not None:
+        trace.setdefault("fused", []).append(f)
+        trace.setdefault("normalised", []).append(a)
+    return a
 
 
 def create_vit(name: str, *, device: torch.device | str | None = None) -> VisionTransformer:

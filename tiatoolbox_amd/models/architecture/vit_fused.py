@@ -77,6 +77,10 @@ SAME qkv tensor goes to ``tia_mha_probs_h`` (the float32 probabilities attention
 block, or all rows with the head mean in every block) and, for the rollout, ``tia_rollout_step_f32``
 (``R = (A R) / 2 + R / 2`` on ``v_mfma_f32_16x16x4_f32``).  They write buffers of their own, so the features are bit for bit those of the
 run without maps, and with ``None`` nothing is launched.  ``VisionTransformer.forward_with_attention`` states both maps; DESIGN 4.42.
+``attention_head_fusion`` ("mean" | "max" | "min") and ``attention_discard_ratio`` (attributes the engines set beside it) are the
+rollout's other forms: with anything but ("mean", a discard count of 0) a block launches ``tia_mha_probs_fused_h``,
+``tia_rollout_discard_normalize_f32`` and, after the first block, ``tia_rollout_product_f32`` in place of those two kernels -- and
+with the defaults exactly those two.  ``models/engine/_rollout_options.py`` states the arithmetic; DESIGN 4.44.
 
 There is no library fall-back: a model the kernels do not take (``D / heads`` other than 64 or 80, channel counts off the GEMM's
 multiples) raises ``UnsupportedLayerError`` from the constructor.
@@ -211,6 +215,70 @@ def hip_rollout_step_f32(a: torch.Tensor, r_in: torch.Tensor | None) -> torch.Te
     with torch.cuda.device(a.device):
         rc = _lib.load().tia_rollout_step_f32(a.data_ptr(), _ptr(r_in), out.data_ptr(), n, s, _lib.current_stream())
     _lib.check(rc, "tia_rollout_step_f32")
+    return out
+
+
+def hip_mha_probs_fused_h(qkv: torch.Tensor, heads: int, scale: float, head_fusion: str) -> torch.Tensor:
+    """The probabilities of all ``S`` query rows of ``hip_mha_fwd_h``'s input fused over the heads, float32 ``[n, S, S]``
+    (``tia_mha_probs_fused_h``): "mean" is ``hip_mha_probs_h(head_mean=True)`` bit for bit, "max" / "min" the exact element-wise
+    maximum / minimum of its per-head values."""
+    from tiatoolbox_amd import _lib
+    from tiatoolbox_amd.models.engine._rollout_options import FUSION_CODES
+
+    _half_tokens("hip_mha_probs_fused_h", qkv)
+    if head_fusion not in FUSION_CODES:
+        msg = f"hip_mha_probs_fused_h: head_fusion is one of {tuple(FUSION_CODES)}; got {head_fusion!r}."
+        raise ValueError(msg)
+    if heads > MHA_PROBS_MEAN_HEADS:
+        msg = f"hip_mha_probs_fused_h: a fused output takes at most {MHA_PROBS_MEAN_HEADS} heads; got {heads}."
+        raise ValueError(msg)
+    n, s, c3 = qkv.shape
+    out = torch.empty((n, s, s), dtype=torch.float32, device=qkv.device)
+    with torch.cuda.device(qkv.device):
+        rc = _lib.load().tia_mha_probs_fused_h(qkv.data_ptr(), out.data_ptr(), n, s, heads, c3 // (3 * heads), float(scale),
+                                               FUSION_CODES[head_fusion], _DT[qkv.dtype], _lib.current_stream())
+    _lib.check(rc, "tia_mha_probs_fused_h")
+    return out
+
+
+def _rollout_matrices(who: str, **tensors: torch.Tensor | None) -> tuple[int, int]:
+    first = next(iter(tensors.values()))
+    for name, t in tensors.items():
+        if t is not None and not (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and t.dim() == 3  # noqa: PLR2004
+                                  and t.shape[1] == t.shape[2] and t.shape == first.shape and t.device == first.device):
+            msg = f"{who} expects contiguous float32 CUDA [n, S, S] matrices of one shape; got {name} {tuple(t.shape)}, {t.dtype} on {t.device}."
+            raise ValueError(msg)
+    return first.shape[0], first.shape[1]
+
+
+def hip_rollout_discard_normalize_f32(f: torch.Tensor, k: int, *, return_threshold: bool = False):
+    """``A^`` of the fused float32 ``[n, S, S]`` matrices ``f`` (``tia_rollout_discard_normalize_f32``): with ``k >= 1`` everything
+    ``<=`` the ``k``-th smallest entry of an image is set to 0 (entry ``(0, 0)`` never); then ``(F' + I) / 2`` with every row divided
+    by its sum.  ``return_threshold`` also returns the ``[n]`` order statistics (``None`` for ``k = 0``)."""
+    from tiatoolbox_amd import _lib
+
+    n, s = _rollout_matrices("hip_rollout_discard_normalize_f32", f=f)
+    if not 0 <= k < s * s:
+        msg = f"hip_rollout_discard_normalize_f32: k is between 0 and S * S - 1 = {s * s - 1}; got {k}."
+        raise ValueError(msg)
+    out = torch.empty_like(f)
+    v = torch.empty((n,), dtype=torch.float32, device=f.device) if k else None
+    with torch.cuda.device(f.device):
+        rc = _lib.load().tia_rollout_discard_normalize_f32(f.data_ptr(), out.data_ptr(), _ptr(v), n, s, k, _lib.current_stream())
+    _lib.check(rc, "tia_rollout_discard_normalize_f32")
+    return (out, v) if return_threshold else out
+
+
+def hip_rollout_product_f32(a: torch.Tensor, r_in: torch.Tensor | None) -> torch.Tensor:
+    """``a @ r_in`` on float32 ``[n, S, S]`` matrices, ``r_in=None`` the identity (``tia_rollout_product_f32``: one float32 fma chain
+    per element, ``k`` ascending)."""
+    from tiatoolbox_amd import _lib
+
+    n, s = _rollout_matrices("hip_rollout_product_f32", a=a, r_in=r_in)
+    out = torch.empty_like(a)
+    with torch.cuda.device(a.device):
+        rc = _lib.load().tia_rollout_product_f32(a.data_ptr(), _ptr(r_in), out.data_ptr(), n, s, _lib.current_stream())
+    _lib.check(rc, "tia_rollout_product_f32")
     return out
 
 
@@ -1190,6 +1258,9 @@ class FusedViT(nn.Module):
         # maps beside the output: the engine sets `return_attention` ("class" | "rollout") before a run and reads `attention_maps` after
         # each forward (`forward` and `forward_uint8` alike); None: not one additional launch
         self.return_attention: str | None = None
+        # the rollout's other forms (the engines' `attention_head_fusion` / `attention_discard_ratio`); the defaults are today's path
+        self.attention_head_fusion: str = "mean"
+        self.attention_discard_ratio: float = 0.0
         self.attention_maps: torch.Tensor | None = None
         self._rollout: torch.Tensor | None = None
 
@@ -1599,7 +1670,8 @@ class FusedViT(nn.Module):
         """``hip_mha_fwd_h`` of a block and -- only with ``return_attention`` -- the map kernels on the SAME ``qkv`` tensor, after it: they
         read what attention read and write buffers of their own, so the maps describe the computation that ran, on every half
         route.  "class": one ``tia_mha_probs_h`` launch in the last block (the class row, per head); "rollout": per block the head
-        mean of all rows and one ``tia_rollout_step_f32``."""
+        mean of all rows and one ``tia_rollout_step_f32`` -- or, with another ``attention_head_fusion`` or a discard count ``k >= 1``,
+        ``tia_mha_probs_fused_h``, ``tia_rollout_discard_normalize_f32`` and (from the second block on) ``tia_rollout_product_f32``."""
         kind = self.return_attention
         if kind not in (None, "class", "rollout"):
             msg = f"FusedViT.return_attention is None, 'class' or 'rollout'; got {kind!r}."
@@ -1609,8 +1681,16 @@ class FusedViT(nn.Module):
             if last:
                 self._rollout = hip_mha_probs_h(qkv, self.num_heads, self.scale, q_rows=1, head_mean=False)
         elif kind == "rollout":
-            mean = hip_mha_probs_h(qkv, self.num_heads, self.scale, q_rows=qkv.shape[1], head_mean=True)
-            self._rollout = hip_rollout_step_f32(mean, self._rollout)
+            from tiatoolbox_amd.models.engine import _rollout_options as ro
+
+            fusion, ratio = ro.check_options(self.attention_head_fusion, self.attention_discard_ratio, who="FusedViT")
+            k = ro.discard_count(ratio, qkv.shape[1])
+            if fusion == "mean" and k == 0:  # today's launches and no other
+                mean = hip_mha_probs_h(qkv, self.num_heads, self.scale, q_rows=qkv.shape[1], head_mean=True)
+                self._rollout = hip_rollout_step_f32(mean, self._rollout)
+            else:  # R_1 = A^_1 needs no product
+                a_hat = hip_rollout_discard_normalize_f32(hip_mha_probs_fused_h(qkv, self.num_heads, self.scale, fusion), k)
+                self._rollout = a_hat if self._rollout is None else hip_rollout_product_f32(a_hat, self._rollout)
         return a
 
     def _finish_attention(self, grid: tuple[int, int]) -> None:

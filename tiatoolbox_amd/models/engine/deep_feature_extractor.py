@@ -39,7 +39,11 @@ class DeepFeatureExtractor(PatchPredictor):
     ``merge_attention``: ``None`` | "class" | "rollout", the same maps for WSI-mode runs (``patch_mode=False``; with
     ``attention_interpolation``, ``merge_resolution`` and ``merge_units``): every slide's ``.npz`` also holds ``attention``,
     ``merged_attention`` -- the slide-level heat map of :meth:`PatchPredictor.merge_attention`, merged on the device by
-    ``tia_merge_patch_grids_f32`` -- and ``attention_coverage``.  ``merge_predictions`` stays refused here: features have no class map."""
+    ``tia_merge_patch_grids_f32`` -- and ``attention_coverage``.  ``merge_predictions`` stays refused here: features have no class map.
+    ``attention_head_fusion``: "mean" | "max" | "min" and ``attention_discard_ratio``: ``0 <= r < 1`` shape the rollout maps of either
+    option (per call; :class:`PatchPredictor` describes them, ``engine/_rollout_options.py`` states them; on the hand-written graph
+    ``tia_mha_probs_fused_h``, ``tia_rollout_discard_normalize_f32`` and ``tia_rollout_product_f32``); the defaults are today's maps,
+    a non-default value without a rollout request is a ``ValueError``."""
 
     def __init__(self, model, batch_size: int = 8, num_workers: int = 0, weights=None, *,
                  device: str = "cpu", verbose: bool = True) -> None:

@@ -46,6 +46,15 @@ class PatchPredictor(EngineABC):
     ``return_attention`` returns them), ``merged_attention`` (:meth:`merge_attention` of them: ``[heads, H, W]`` or ``[H, W]`` float32) and
     ``attention_coverage`` (``[H, W]`` int32, the number of patches over each pixel).  The maps never leave HBM before the merge.  It may
     be combined with ``merge_predictions=True``; a ``ValueError`` before any launch where it does not apply.
+
+    Rollout maps -- ``return_attention="rollout"`` in patch mode, ``merge_attention="rollout"`` in WSI mode, where the per-patch
+    ``attention`` and the ``merged_attention`` built from it both follow -- also take ``attention_head_fusion`` ("mean" | "max" | "min",
+    default "mean") and ``attention_discard_ratio`` (``0 <= r < 1``, default 0): the heads' maximum or minimum in place of their mean,
+    and per block the ``min(int(r S^2), S^2 - 1)`` smallest entries of the fused ``S x S`` matrix set to 0 (ties with the last one
+    included, entry (0, 0) never) before ``(F' + I) / 2`` is normalised by rows and multiplied into the rollout;
+    ``engine/_rollout_options.py`` states the arithmetic.  Decided per call and never attributes; with the defaults the maps are bit for
+    bit those of a call without the two kwargs.  A ``ValueError`` that names the option for a non-default value without a rollout
+    request (beside "class" too), a fusion outside the three names, a ratio that is no real number in ``[0, 1)``.
     """
 
     def __init__(self, model, batch_size: int = 8, num_workers: int = 0, weights=None, *,

@@ -56,7 +56,7 @@ extern "C" {
  * smoothing of those layers and its calibration statistics); tia_mha_probs_h, tia_rollout_step_f32 (attention maps of the Vision
  * Transformer runs: the probabilities tia_mha_fwd_h does not materialise, and attention rollout); tia_merge_patch_grids_f32 (those maps resampled into a
  * whole-slide heat map); tia_mha_probs_fused_h, tia_rollout_discard_normalize_f32, tia_rollout_product_f32 (rollout with max / min
- * head fusion and a discard ratio). */
+ * head fusion and a discard ratio); tia_cam_nhwc_f32, tia_cam_nhwc_h (class activation maps of the CNN classifiers). */
 #define TIA_ABI_VERSION 6
 int tia_abi_version(void);
 
@@ -1299,6 +1299,25 @@ int tia_rollout_discard_normalize_f32(const float* d_f, float* d_out, float* d_v
  * k = 0 .. s - 1 in ascending order per element, zero-filled tails) without its blend.  d_r_in NULL means R_out = A.  The same
  * limits, alignment and overlap rules. */
 int tia_rollout_product_f32(const float* d_a, const float* d_r_in, float* d_r_out, int64_t n, int64_t s, void* stream);
+
+/* =======================================================================================
+ * Class activation maps of the CNN classifiers (cnn_cam.hip; the engines' run kwargs return_cam / merge_cam;
+ * models/engine/_cam.py states the quantity).  Additive, same version (6).  A run that asks for no maps launches neither.
+ * ===================================================================================== */
+
+/* The classifier applied at every position of the trunk's last feature map (Zhou et al. 2016):
+ *   d_out[b, j, p] = sum_c d_w[j, c] * d_x[b, p, c]          no bias, no ReLU, nothing renormalised
+ *   d_x [n, hw, c] channels-last: float32 (tia_cam_nhwc_f32) or `dtype` = TIA_DT_F16 | TIA_DT_BF16 (tia_cam_nhwc_h; anything
+ *   else TIA_EINVAL), widened exactly;   d_w [k, c] float32;   d_out [n, k, hw] float32.
+ * float32 multiply-adds (fmaf): lane l of a wave takes the 16-byte vectors l, l + 64, ... of a row in ascending c, the 64 partial
+ * sums are added as v[l] + v[l ^ 32], then ^ 16, 8, 4, 2, 1.  That order depends on c alone -- not on n, the row's place in the batch
+ * or the grid -- so a patch gives the same bits in any batch.  d_x is read once per tile of classes (12 classes, fewer where
+ * k * c * 4 bytes exceed 144 KB of LDS).  No atomics, no allocation, no synchronisation; 64-bit offsets.
+ * TIA_EINVAL: a null pointer, n / hw / c / k <= 0, d_x or d_w not 16-byte aligned, d_out not 4-byte aligned.
+ * TIA_ESIZE: c % 64 != 0 or c > 8192; n >= 2^31 or hw * k >= 2^31.  Nothing is launched on an error. */
+int tia_cam_nhwc_f32(const float* d_x, const float* d_w, float* d_out, int64_t n, int32_t hw, int32_t c, int32_t k, void* stream);
+int tia_cam_nhwc_h(const void* d_x, const float* d_w, float* d_out, int64_t n, int32_t hw, int32_t c, int32_t k, int32_t dtype,
+                   void* stream);
 
 /* =======================================================================================
  * All borders of binary planes: cv2.findContours(layer, RETR_TREE, CHAIN_APPROX_NONE | _SIMPLE)

@@ -195,6 +195,8 @@ _SIGNATURES = {
     "tia_mha_probs_fused_h": ([_P, _P, _I64, _I64, _I64, _I64, C.c_float, _I32, _I32, _P], C.c_int),
     "tia_rollout_discard_normalize_f32": ([_P, _P, _P, _I64, _I64, _I64, _P], C.c_int),
     "tia_rollout_product_f32": ([_P, _P, _P, _I64, _I64, _P], C.c_int),
+    "tia_cam_nhwc_f32": ([_P, _P, _P, _I64, _I32, _I32, _I32, _P], C.c_int),
+    "tia_cam_nhwc_h": ([_P, _P, _P, _I64, _I32, _I32, _I32, _I32, _P], C.c_int),
     "tia_bias_act_nhwc": ([_P, _P, _P, _I64, _I64, _I32, _I32, _P], C.c_int),
     "tia_bias_relu_maxpool_nhwc": ([_P, _P, _I64, _I64, _I64, _I64, _I32, _P, _P], C.c_int),
     "tia_hover_instance_stats": ([_P, _P, _I64, _I64, _I64, _I32, _I32, _P, _P, _P], C.c_int),

@@ -106,6 +106,58 @@ def hip_bias_relu_maxpool(x: torch.Tensor, bias: torch.Tensor) -> torch.Tensor:
     return out
 
 
+CAM_MAX_CHANNELS = 8192  # (cnn_cam.hip: at least one class of the weights per workgroup's LDS tile)
+
+
+def hip_cam(feat: torch.Tensor, weight: torch.Tensor, out: torch.Tensor | None = None) -> torch.Tensor:
+    """Class activation maps ``cam[n, k, y, x] = sum_c weight[k, c] * feat[n, c, y, x]`` (``models/engine/_cam.py``), float32
+    ``[N, K, h, w]``, in one launch of ``tia_cam_nhwc_f32`` / ``tia_cam_nhwc_h``.  ``feat``: the NCHW view of a channels-last CUDA
+    tensor, float32 / fp16 / bf16 (any other layout is copied to channels-last first); ``weight``: float32 ``[K, C]`` on the same
+    device; ``out``: a contiguous float32 ``[N, K, h, w]`` tensor there to write into instead of a new one (the engines' buffer of a
+    whole run).  ``C`` is a multiple of 64 up to 8192."""
+    from tiatoolbox_amd import _lib
+
+    if not (isinstance(feat, torch.Tensor) and isinstance(weight, torch.Tensor) and feat.is_cuda and weight.is_cuda):
+        msg = "hip_cam expects CUDA tensors (there is no CPU fallback: models/engine/_cam.py has the torch form)."
+        raise ValueError(msg)
+    if feat.dim() != 4 or feat.dtype not in _DT:  # noqa: PLR2004
+        msg = f"hip_cam expects a feature map [N, C, h, w] in float32, float16 or bfloat16; got {tuple(feat.shape)} {feat.dtype}."
+        raise ValueError(msg)
+    if weight.dtype != torch.float32 or weight.dim() != 2 or weight.device != feat.device:  # noqa: PLR2004
+        msg = f"hip_cam expects float32 weights [K, C] on the feature map's device; got {tuple(weight.shape)} {weight.dtype} on {weight.device}."
+        raise ValueError(msg)
+    n, c, h, w = feat.shape
+    k = weight.shape[0]
+    if weight.shape[1] != c:
+        msg = f"hip_cam: the feature map has {c} channels and the weights {weight.shape[1]}."
+        raise ValueError(msg)
+    if min(n, c, h, w, k) <= 0:
+        msg = f"hip_cam: empty feature map {tuple(feat.shape)} or weights {tuple(weight.shape)}."
+        raise ValueError(msg)
+    if not feat.is_contiguous(memory_format=torch.channels_last):
+        feat = feat.contiguous(memory_format=torch.channels_last)
+    weight = weight.detach().contiguous()
+    if out is None:
+        out = torch.empty((n, k, h, w), dtype=torch.float32, device=feat.device)
+    elif not (out.dtype == torch.float32 and out.device == feat.device and tuple(out.shape) == (n, k, h, w) and out.is_contiguous()):
+        msg = f"hip_cam: `out` must be a contiguous float32 tensor {(n, k, h, w)} on {feat.device}; got {tuple(out.shape)} {out.dtype} on {out.device}."
+        raise ValueError(msg)
+    with torch.cuda.device(feat.device):
+        if feat.dtype == torch.float32:
+            name = "tia_cam_nhwc_f32"
+            rc = _lib.load().tia_cam_nhwc_f32(feat.data_ptr(), weight.data_ptr(), out.data_ptr(), n, h * w, c, k, _lib.current_stream())
+        else:
+            name = "tia_cam_nhwc_h"
+            rc = _lib.load().tia_cam_nhwc_h(feat.data_ptr(), weight.data_ptr(), out.data_ptr(), n, h * w, c, k, _DT[feat.dtype],
+                                            _lib.current_stream())
+    if rc == _lib.TIA_ESIZE:
+        msg = (f"hip_cam: {name} takes channel counts that are multiples of 64 up to {CAM_MAX_CHANNELS} (and fewer than 2^31 patches "
+               f"and h * w * K entries per patch); got C = {c}, N = {n}, h * w * K = {h * w * k}.")
+        raise ValueError(msg)
+    _lib.check(rc, name)
+    return out
+
+
 # ------------------------------------------------------------------------------------------------
 # Hand-written MFMA convolutions (conv_mfma.hip): float32 implicit GEMM with the epilogue fused in
 # ------------------------------------------------------------------------------------------------

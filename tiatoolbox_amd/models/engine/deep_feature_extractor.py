@@ -43,7 +43,9 @@ class DeepFeatureExtractor(PatchPredictor):
     ``attention_head_fusion``: "mean" | "max" | "min" and ``attention_discard_ratio``: ``0 <= r < 1`` shape the rollout maps of either
     option (per call; :class:`PatchPredictor` describes them, ``engine/_rollout_options.py`` states them; on the hand-written graph
     ``tia_mha_probs_fused_h``, ``tia_rollout_discard_normalize_f32`` and ``tia_rollout_product_f32``); the defaults are today's maps,
-    a non-default value without a rollout request is a ``ValueError``."""
+    a non-default value without a rollout request is a ``ValueError``.
+    ``return_cam`` / ``merge_cam`` (the class activation maps of :class:`PatchPredictor`) are refused here: a feature extractor has no
+    classifier to map."""
 
     def __init__(self, model, batch_size: int = 8, num_workers: int = 0, weights=None, *,
                  device: str = "cpu", verbose: bool = True) -> None:
@@ -57,6 +59,11 @@ class DeepFeatureExtractor(PatchPredictor):
         if kwargs.get("merge_predictions"):
             msg = "merge_predictions merges class probabilities into a tissue-type map; feature vectors have no such map."
             raise ValueError(msg)
+        for option in ("return_cam", "merge_cam"):
+            if kwargs.get(option, False) is not False:
+                msg = (f"{option} maps the classifier of a CNNModel over its trunk's last feature map (PatchPredictor); a feature "
+                       f"extractor has no classifier; got {option}={kwargs[option]!r} for DeepFeatureExtractor.")
+                raise ValueError(msg)
         return super()._update_run_params(images, **kwargs)
 
     def post_process_patches(self, raw_predictions: dict, **_) -> dict:

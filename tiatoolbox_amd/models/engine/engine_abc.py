@@ -82,6 +82,13 @@ _MERGE_ATTENTION_COVERS = ("merge_attention is None, \"class\" or \"rollout\" an
                            "feat_extract is a VisionTransformer (TimmBackbone / TimmModel) in every compute_dtype but \"bfloat16x3\", with "
                            "attention_interpolation \"nearest\" or \"bilinear\"")
 
+# return_cam=True (patch mode) / merge_cam=True (WSI mode): class activation maps of a CNN classifier beside the output, under "cam"
+# (engine/_cam.py states the quantity; on a CUDA device tia_cam_nhwc_f32 / tia_cam_nhwc_h read the feature map the forward left in HBM;
+# DESIGN 4.45).  Per call, options of PatchPredictor.run.
+_CAM_COVERS = ("return_cam (patch mode) and merge_cam (WSI mode, patch_mode=False, with cam_interpolation \"bilinear\" or \"nearest\") are "
+               "bool and cover CNNModel classifiers -- trunk, AdaptiveAvgPool2d((1, 1)), nn.Linear, softmax with the stock forward -- on "
+               "the CPU and, on a CUDA device, in compute_dtype \"float32\", \"float16\" and \"bfloat16\"")
+
 
 def _compute_name(compute_dtype) -> str:
     return str(compute_dtype).replace("torch.", "")
@@ -757,6 +764,85 @@ class EngineABC:
             raise ValueError(msg)
         return kind
 
+    def _checked_cam(self, option: str, value, *, patch_mode: bool, interpolation: str = "bilinear") -> bool:
+        """The run kwarg ``return_cam`` (patch mode) or ``merge_cam`` (WSI mode) of this call: a ``bool``.  ``True`` for anything the
+        option does not cover is a ``ValueError`` that names the option and says what it got, raised before any launch and before any
+        kwarg of the call becomes an attribute."""
+        from tiatoolbox_amd.models.architecture.vanilla import CNNBackbone, TimmBackbone, TimmModel
+        from tiatoolbox_amd.models.engine import _cam
+        from tiatoolbox_amd.models.engine._attention_merge import INTERPOLATIONS
+
+        problem = None
+        model = self.model.module if hasattr(self.model, "module") else self.model
+        name = type(model).__name__
+        if not isinstance(value, bool):
+            problem = f"got {option}={value!r}"
+        elif not value:
+            return False
+        elif option == "merge_cam" and interpolation not in INTERPOLATIONS:
+            problem = f"got cam_interpolation={interpolation!r}"
+        elif isinstance(model, TimmModel):
+            problem = (f"got {option}=True for {name}, a Vision Transformer classifier whose head reads the class token: "
+                       f"{'return_attention' if option == 'return_cam' else 'merge_attention'} gives its maps")
+        elif isinstance(model, (CNNBackbone, TimmBackbone)) or not hasattr(model, "classifier"):
+            problem = f"got {option}=True for {name}, a feature extractor: it has no classifier"
+        elif not _cam.is_cam_model(model):
+            problem = f"got {option}=True for {name}, which is no CNNModel with the stock forward, pool and nn.Linear classifier"
+        elif option == "return_cam" and not patch_mode:
+            problem = "got return_cam=True with patch_mode=False (WSI mode has merge_cam)"
+        elif option == "merge_cam" and patch_mode:
+            problem = "got merge_cam=True with patch_mode=True (patch mode has return_cam)"
+        if problem is not None:
+            msg = f"{_CAM_COVERS}; {problem}."
+            raise ValueError(msg)
+        return True
+
+    @contextlib.contextmanager
+    def _cam_scope(self, model, on=None):
+        """Yields ``take(rows, at)``, or ``None`` when this call asks for no class activation maps.  ``take`` writes the maps of the
+        forward that just ran (float32 ``[n, K, h, w]``) into rows ``at .. at + n`` of one ``[rows, K, h, w]`` buffer on the device,
+        allocated with the first batch, and ``take.maps()`` returns that buffer: nothing is concatenated afterwards.  A forward hook on
+        the inference copy's ``feat_extract`` keeps the feature map of the forward that ran -- the trunk is not run twice --, and the
+        copy's classifier weights are applied to it: ``hip_cam`` (one ``tia_cam_nhwc_*`` launch) on a CUDA device,
+        ``_cam.cam_torch`` on the CPU.  In fp16 / bf16 the weights are the copy's half weights widened to float32, once per
+        inference copy."""
+        on = bool(getattr(self, "_return_cam", False)) if on is None else bool(on)
+        if not on:
+            yield None
+            return
+        from tiatoolbox_amd.models.engine import _cam
+
+        kept: list = []
+        handle = model.feat_extract.register_forward_hook(lambda _mod, _inp, out: kept.append(out))
+        weight = model.classifier.weight.detach()
+        if weight.dtype != torch.float32 or not weight.is_contiguous():  # widened once per inference copy, not per run
+            key = (id(model), weight.data_ptr(), weight._version, weight.dtype, str(weight.device))  # noqa: SLF001
+            cached = getattr(self, "_cam_weight", None)
+            if cached is None or cached[0] != key:
+                self._cam_weight = cached = (key, weight.float().contiguous())
+            weight = cached[1]
+        buffer: list = []
+
+        def take(rows: int, at: int) -> None:
+            feat = kept.pop()
+            kept.clear()
+            n, _, h, w = feat.shape
+            if not buffer:
+                buffer.append(torch.empty((max(rows, n), weight.shape[0], h, w), dtype=torch.float32, device=feat.device))
+            out = buffer[0][at:at + n]
+            if feat.is_cuda:
+                from tiatoolbox_amd.models.architecture.fused import hip_cam
+
+                hip_cam(feat, weight, out=out)
+            else:
+                out.copy_(_cam.cam_torch(feat, weight))
+
+        take.maps = lambda: buffer[0]
+        try:
+            yield take
+        finally:
+            handle.remove()
+
     @contextlib.contextmanager
     def _attention_scope(self, model, kind=None):
         """Yields ``take()``, which returns the maps of the forward that just ran (float32, on the device), or ``None`` when this run
@@ -1076,8 +1162,10 @@ class EngineABC:
         self._set_defer_norm(model)
         self._shard_span, self._norm_cache = (lo, hi), None
         maps = []  # return_attention: the per-batch maps stay on the device and are concatenated like the probabilities
+        cam = None  # return_cam: the maps of every batch go into one buffer on the device
         try:
-            with self._miopen_scope(), self._deferred_norm_checks(dataloader.preproc_func), self._attention_scope(model) as take_maps:
+            with self._miopen_scope(), self._deferred_norm_checks(dataloader.preproc_func), self._attention_scope(model) as take_maps, \
+                    self._cam_scope(model) as take_cam:
                 cuts = self._batch_cuts(lo, hi)
                 for k, (s, e) in enumerate(zip(cuts[:-1], cuts[1:])):
                     if self._feed is not None:  # batch k+1 crosses PCIe while batch k computes
@@ -1090,17 +1178,24 @@ class EngineABC:
                         outs.append(self._forward_batch(model, infer_batch, batch))
                     if take_maps is not None:
                         maps.append(take_maps())
+                    if take_cam is not None:
+                        take_cam(hi - lo, s - lo)
+                if take_cam is not None and hi > lo:
+                    cam = take_cam.maps()
         finally:
             if self._feed is not None:
                 self._feed.close()
                 self._feed = None
             self._shard_span, self._norm_cache = None, None
         if not outs:  # empty shard: a one-patch probe supplies the row shapes
-            with self._attention_scope(model) as take_maps:
+            with self._attention_scope(model) as take_maps, self._cam_scope(model) as take_cam:
                 probe = self._forward_batch(model, infer_batch, self._preprocess_batch(dataloader, 0, 1, dtype))
                 outs = [tuple(p[:0] for p in probe) if isinstance(probe, tuple) else probe[:0]]
                 if take_maps is not None:
                     maps.append(take_maps()[:0])
+                if take_cam is not None:
+                    take_cam(1, 0)
+                    cam = take_cam.maps()[:0]
         multi_head = isinstance(outs[0], tuple)
         heads = list(zip(*outs)) if multi_head else [outs]
         gathered = []
@@ -1122,6 +1217,10 @@ class EngineABC:
             if gather_now:
                 attention = tdist.all_gather_rows(attention.to(self.device) if dev.type == "cuda" else attention, n)
             raw_predictions["attention"] = attention
+        if cam is not None:
+            if gather_now:
+                cam = tdist.all_gather_rows(cam.to(self.device) if dev.type == "cuda" else cam, n)
+            raw_predictions["cam"] = cam
         if world_size > 1 and not gather_now:
             raw_predictions["shard"] = (lo, hi, n)
         if self.return_labels and dataloader.labels is not None:
@@ -1239,7 +1338,10 @@ class EngineABC:
         coords_dev = torch.from_numpy(c_np).to(dev) if uniform else None
         kind = getattr(self, "_merge_attention", None)  # merge_attention: the per-batch maps stay on the device, like the rows
         maps = []
-        with self._miopen_scope(), self._deferred_norm_checks(hook), self._attention_scope(model, kind) as take_maps:
+        cam_on = bool(getattr(self, "_merge_cam", False))  # merge_cam: the maps of every batch go into one buffer on the device
+        cam = None
+        with self._miopen_scope(), self._deferred_norm_checks(hook), self._attention_scope(model, kind) as take_maps, \
+                self._cam_scope(model, cam_on) as take_cam:
             for s in range(lo, hi, self.batch_size):
                 e = min(s + self.batch_size, hi)
                 raw = (reader.read_bounds_batch(coords_dev[s - lo:e - lo], size=size) if coords_dev is not None
@@ -1251,13 +1353,20 @@ class EngineABC:
                 outs.append(self._forward_batch(model, infer_batch, batch))
                 if take_maps is not None:
                     maps.append(take_maps())
+                if take_cam is not None:
+                    take_cam(hi - lo, s - lo)
+            if take_cam is not None and hi > lo:
+                cam = take_cam.maps()
         if not outs:
             probe = reader.read_bounds_batch(coords[:1])
             probe = self._device_preproc(hook, probe, dtype) if device_batch is not None else probe
-            with self._attention_scope(model, kind) as take_maps:
+            with self._attention_scope(model, kind) as take_maps, self._cam_scope(model, cam_on) as take_cam:
                 outs = [self._forward_batch(model, infer_batch, probe)[:0]]
                 if take_maps is not None:
                     maps.append(take_maps()[:0])
+                if take_cam is not None:
+                    take_cam(1, 0)
+                    cam = take_cam.maps()[:0]
         local = torch.cat([o if isinstance(o, torch.Tensor) else torch.from_numpy(np.asarray(o)) for o in outs])
         if world_size > 1:
             local = tdist.all_gather_rows(local.to(dev), n)
@@ -1265,6 +1374,8 @@ class EngineABC:
         if maps:
             attention = torch.cat(maps).to(dev)
             result["attention"] = tdist.all_gather_rows(attention, n) if world_size > 1 else attention
+        if cam is not None:
+            result["cam"] = tdist.all_gather_rows(cam, n) if world_size > 1 else cam
         return result
 
     def post_process_wsi(self, processed: dict, *, base, reader) -> dict:  # noqa: ARG002

@@ -55,6 +55,19 @@ class PatchPredictor(EngineABC):
     ``engine/_rollout_options.py`` states the arithmetic.  Decided per call and never attributes; with the defaults the maps are bit for
     bit those of a call without the two kwargs.  A ``ValueError`` that names the option for a non-default value without a rollout
     request (beside "class" too), a fusion outside the three names, a ratio that is no real number in ``[0, 1)``.
+
+    ``return_cam=True`` (patch mode; a ``bool`` decided per call, never an attribute) is the heat map of the ``CNNModel`` classifiers
+    -- the ResNet, ResNeXt and Wide-ResNet kather100k models: the result gains ``"cam"``, float32 ``[N, K, h, w]`` on the trunk's output
+    grid (7 x 7 at 224 x 224, 8 x 8 at 256 x 256), ``cam[n, k, y, x] = sum_c W[k, c] F[n, c, y, x]`` with ``F`` the feature map of the
+    forward that ran and ``W`` the classifier weights of the inference copy (``engine/_cam.py`` states it): no bias, no ReLU, nothing
+    renormalised, ``mean(cam) + b`` is the logit.  Raw logit contributions: comparable across classes within a patch, across patches
+    only as logits are.  Every other key is bit for bit that of the run without it; on a CUDA device (``compute_dtype`` "float32",
+    "float16", "bfloat16") one ``tia_cam_nhwc_f32`` / ``tia_cam_nhwc_h`` launch per batch is all that is added.  ``merge_cam=True``
+    (WSI mode, with ``cam_interpolation`` "bilinear" | "nearest" and ``merge_resolution`` / ``merge_units``; may be combined with
+    ``merge_predictions=True``): every slide's ``.npz`` also holds ``cam`` (the per-patch maps, as ``return_cam`` returns them),
+    ``merged_cam`` (:meth:`merge_cam` of them, ``[K, H, W]`` float32) and ``cam_coverage`` (``[H, W]`` int32).  A ``ValueError`` before
+    any launch that names the option for anything else: a ``TimmModel`` (``return_attention`` gives its maps), a feature extractor
+    (no classifier), any other model class, the wrong ``patch_mode``, an unknown interpolation, a value that is no ``bool``.
     """
 
     def __init__(self, model, batch_size: int = 8, num_workers: int = 0, weights=None, *,
@@ -79,6 +92,15 @@ class PatchPredictor(EngineABC):
         self._merge_attention = self._checked_merge_attention(
             attention_kind, self._attention_interpolation, patch_mode=bool(kwargs.get("patch_mode")),
             compute_dtype=kwargs.get("compute_dtype", getattr(self, "compute_dtype", "float32")))
+        # return_cam / merge_cam / cam_interpolation likewise: this call's alone, refused before anything of the call is taken over
+        self._return_cam = self._merge_cam = False
+        return_cam, merge_cam = kwargs.pop("return_cam", False), kwargs.pop("merge_cam", False)
+        self._cam_interpolation = "bilinear"
+        cam_interpolation = kwargs.pop("cam_interpolation", "bilinear")
+        self._return_cam = self._checked_cam("return_cam", return_cam, patch_mode=bool(kwargs.get("patch_mode")))
+        self._merge_cam = self._checked_cam("merge_cam", merge_cam, patch_mode=bool(kwargs.get("patch_mode")),
+                                            interpolation=cam_interpolation)
+        self._cam_interpolation = cam_interpolation
         out = super()._update_run_params(images, **kwargs)
         if not self.return_probabilities:
             self.drop_keys.append("probabilities")
@@ -110,9 +132,11 @@ class PatchPredictor(EngineABC):
         with ``return_probabilities``) at ``merge_resolution`` / ``merge_units``.  The patch space is that of ``reader``, the
         reader the grid was made on; the canvas is the slide ``base`` at the merge resolution.  Under ``torch.distributed``
         every rank holds all rows after the all-gather and merges them; rank 0 writes.  ``merge_attention=...``: the slide's
-        per-patch maps, where ``infer_wsi`` left them, merged into ``merged_attention`` and ``attention_coverage`` on the same canvas."""
+        per-patch maps, where ``infer_wsi`` left them, merged into ``merged_attention`` and ``attention_coverage`` on the same canvas.
+        ``merge_cam=True``: the same merge of the class activation maps into ``merged_cam`` and ``cam_coverage``."""
         merge_on, attention_on = getattr(self, "_merge_on", False), getattr(self, "_merge_attention", None) is not None
-        if not (merge_on or attention_on):
+        cam_on = bool(getattr(self, "_merge_cam", False))
+        if not (merge_on or attention_on or cam_on):
             return processed
         from tiatoolbox_amd.wsicore import _resolution_ratio
 
@@ -126,6 +150,9 @@ class PatchPredictor(EngineABC):
         if attention_on:
             merged = _merge_attention_output(processed, reader.slide_dimensions, canvas_wh, self._attention_interpolation)
             processed["merged_attention"], processed["attention_coverage"] = merged["raw"], merged["count"]
+        if cam_on:
+            merged = _merge_attention_output(processed, reader.slide_dimensions, canvas_wh, self._cam_interpolation, key="cam")
+            processed["merged_cam"], processed["cam_coverage"] = merged["raw"], merged["count"]
         return processed
 
     @staticmethod
@@ -146,28 +173,24 @@ class PatchPredictor(EngineABC):
         Returns ``[heads, H, W]`` or ``[H, W]`` float32 of the kind of ``attention`` (0 where nothing covers); with
         ``return_count=True`` the pair ``(map, coverage [H, W] int32)``.  CUDA maps are merged on their device by
         ``tia_merge_patch_grids_f32`` and never visit the host."""
-        if isinstance(output, (str, Path)):
-            with np.load(output) as data:
-                output = {k: data[k] for k in data.files}
-        missing = [k for k in ("resolution", "units") if k not in output]
-        if missing:
-            msg = (f"`output` lacks {missing}: merge_attention needs output['resolution'] and output['units'], the resolution "
-                   "the patch coordinates are in (ioconfig.input_resolutions[0]).")
-            raise ValueError(msg)
-        if "coordinates" not in output or "attention" not in output:
-            msg = "`output` needs 'coordinates' and 'attention'."
-            raise ValueError(msg)
-        from tiatoolbox_amd.wsicore import _resolution_ratio
+        return _merge_maps_of(img, output, "attention", "merge_attention", resolution, units, interpolation, return_count=return_count)
 
-        reader = img if hasattr(img, "slide_dimensions") else open_slide(img)
-        dims = reader.slide_dimensions
-        patch_units = output["units"]
-        patch_units = patch_units.item() if isinstance(patch_units, np.ndarray) else patch_units
-        patch_wh = _patch_merge.canvas_size(dims, _resolution_ratio(float(np.asarray(output["resolution"])), str(patch_units),
-                                                                    reader.mpp, reader.power))
-        canvas_wh = _patch_merge.canvas_size(dims, _resolution_ratio(resolution, units, reader.mpp, reader.power))
-        merged = _merge_attention_output(output, patch_wh, canvas_wh, interpolation)
-        return (merged["raw"], merged["count"]) if return_count else merged["raw"]
+    @staticmethod
+    def merge_cam(img, output, resolution: float = 1.25, units: str = "power", interpolation: str = "bilinear",
+                  return_count: bool = False):  # noqa: FBT001, FBT002  (a sibling of merge_attention)
+        """Merge the per-patch class activation maps of a run into a heat map of the slide at ``(resolution, units)``.
+
+        ``img``: the slide, as :meth:`merge_predictions` takes it.  ``output``: a ``dict`` or the path of an ``.npz`` with
+        ``coordinates`` ``[N, 4]``, ``cam`` ``[N, K, h, w]`` (what ``return_cam=True`` / ``merge_cam=True`` return), plus ``resolution``
+        and ``units``: the resolution the patches were read at (their coordinates' pixel space).
+
+        Canvas, patch space, coverage, sampling and averaging are those of :meth:`merge_attention`
+        (``engine/_attention_merge.py`` states every operation).  Nothing is renormalised: the values are raw logit contributions
+        (``engine/_cam.py``), comparable across classes within a patch and across patches only as logits are.
+
+        Returns ``[K, H, W]`` float32 (0 where nothing covers); with ``return_count=True`` the pair ``(map, coverage [H, W] int32)``.
+        CUDA maps are merged on their device by ``tia_merge_patch_grids_f32`` and never visit the host."""
+        return _merge_maps_of(img, output, "cam", "merge_cam", resolution, units, interpolation, return_count=return_count)
 
     @staticmethod
     def merge_predictions(img, output, resolution: float = 1.25, units: str = "power", postproc_func=None,
@@ -253,14 +276,42 @@ def _merge_output(output: dict, patch_wh, canvas_wh, *, want_raw: bool = False, 
     return _patch_merge.merge_patch_rects(rects, values, (h, w), want=("sum",))
 
 
-def _merge_attention_output(output: dict, patch_wh, canvas_wh, interpolation: str) -> dict:
-    """``raw`` and ``count`` of :func:`_attention_merge.merge_patch_grids` for one slide's ``coordinates`` + ``attention``."""
+def _merge_maps_of(img, output, key: str, who: str, resolution, units, interpolation: str, *, return_count: bool):
+    """The static ``merge_attention`` / ``merge_cam``: the maps ``output[key]`` of a dict or an ``.npz`` merged on the canvas of
+    ``img`` at ``(resolution, units)``."""
+    if isinstance(output, (str, Path)):
+        with np.load(output) as data:
+            output = {k: data[k] for k in data.files}
+    missing = [k for k in ("resolution", "units") if k not in output]
+    if missing:
+        msg = (f"`output` lacks {missing}: {who} needs output['resolution'] and output['units'], the resolution "
+               "the patch coordinates are in (ioconfig.input_resolutions[0]).")
+        raise ValueError(msg)
+    if "coordinates" not in output or key not in output:
+        msg = f"`output` needs 'coordinates' and '{key}'."
+        raise ValueError(msg)
+    from tiatoolbox_amd.wsicore import _resolution_ratio
+
+    reader = img if hasattr(img, "slide_dimensions") else open_slide(img)
+    dims = reader.slide_dimensions
+    patch_units = output["units"]
+    patch_units = patch_units.item() if isinstance(patch_units, np.ndarray) else patch_units
+    patch_wh = _patch_merge.canvas_size(dims, _resolution_ratio(float(np.asarray(output["resolution"])), str(patch_units),
+                                                                reader.mpp, reader.power))
+    canvas_wh = _patch_merge.canvas_size(dims, _resolution_ratio(resolution, units, reader.mpp, reader.power))
+    merged = _merge_attention_output(output, patch_wh, canvas_wh, interpolation, key=key)
+    return (merged["raw"], merged["count"]) if return_count else merged["raw"]
+
+
+def _merge_attention_output(output: dict, patch_wh, canvas_wh, interpolation: str, *, key: str = "attention") -> dict:
+    """``raw`` and ``count`` of :func:`_attention_merge.merge_patch_grids` for one slide's ``coordinates`` + ``attention`` (or the maps
+    under another ``key``: ``cam``)."""
     w, h = int(canvas_wh[0]), int(canvas_wh[1])
     if min(w, h, int(patch_wh[0]), int(patch_wh[1])) <= 0:
         msg = (f"the merged map ({w} x {h}) or the patch space ({patch_wh[0]} x {patch_wh[1]}) has a zero dimension at the "
                "requested resolution.")
         raise ValueError(msg)
-    maps = output["attention"]
+    maps = output[key]
     maps = maps if isinstance(maps, torch.Tensor) else np.asarray(maps, dtype=np.float32)
     return _attention_merge.merge_patch_grids(output["coordinates"], maps, patch_wh, (h, w), interpolation=interpolation,
                                               want=("raw", "count"))

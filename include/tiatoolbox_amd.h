@@ -384,7 +384,8 @@ int tia_hover_contour_write(const int32_t* d_inst, int64_t n, int64_t h, int64_t
  * Horizontal merge of one patch row (merge_batch_to_canvas / merge_horizontal): every pixel of the
  * row canvas sums, in patch order, the blocks covering it; all-zero blocks are skipped
  * (:1178-1179); x-extents are clipped to the canvas width.
- *   d_blocks [n,oh,ow,c] f32   d_xs [n] i32 (output x0 of each block, ascending)
+ *   d_blocks [n,oh,ow,c] f32   d_xs [n] i32 (output x0 of each block, in any order: a pixel adds its
+ *   blocks in the order they are given, as the reference's loop does); c <= 8, n <= 65535
  *   d_row [oh,W,c] f32 (overwritten)   d_cnt [oh,W] u8 (overwritten)   d_flags [n] i32 scratch
  */
 int tia_canvas_row_merge_f32(const float* d_blocks, const int32_t* d_xs, int64_t n, int64_t oh, int64_t ow,
@@ -394,8 +395,9 @@ int tia_canvas_row_merge_f32(const float* d_blocks, const int32_t* d_xs, int64_t
 /*
  * Vertical merge + normalisation + argmax for canvas rows [y_begin, y_end)
  * (merge_vertical_chunkwise + post_process_wsi): value = rowA[y-ysA] (+ rowB[y-ysB] where the next
- * patch row overlaps), prob = value / max(count,1) (f32), prediction = argmax over channels (uint8).
- * d_row_b may be NULL.  d_probs ([H,W,c] f32) may be NULL.
+ * patch row overlaps), prob = value / max(count,1) (f32; the count is the uint8 sum of the two
+ * counts, which wraps), prediction = np.argmax over channels (uint8): the first NaN, else the first
+ * maximum.  d_row_b may be NULL.  d_probs ([H,W,c] f32) may be NULL.
  */
 int tia_canvas_finalize_f32(const float* d_row_a, const uint8_t* d_cnt_a, int64_t ys_a, const float* d_row_b,
                             const uint8_t* d_cnt_b, int64_t ys_b, int64_t oh, int64_t width, int64_t c,

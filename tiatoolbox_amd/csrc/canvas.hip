@@ -71,7 +71,8 @@ __global__ __launch_bounds__(CT) void finalize_kernel(const float* __restrict__ 
             if (has_b) v = v + row_b[((size_t)yb * width + x) * c + k];
             v = v / denom;
             if (probs) probs[((size_t)y * width + x) * c + k] = v;
-            if (k == 0 || v > bestv) {
+            // np.argmax: the first NaN wins, else the first maximum (a NaN, once held, is never replaced: both tests are false)
+            if (k == 0 || v > bestv || (v != v && bestv == bestv)) {
                 bestv = v;
                 best = k;
             }

@@ -26,7 +26,8 @@ from tiatoolbox_amd.wsicore import ArrayWSIReader
 def merge_batch_to_canvas(blocks, output_locations, merged_shape):
     """Row merge of the reference (:1141-1183) on the GPU; NumPy in/out for API compatibility.
 
-    Blocks must share one shape and one ``ys`` (a patch row), as in every call the reference makes.
+    Blocks must share one shape and one ``ys`` (a patch row), as in every call the reference makes.  They are added in the
+    order given, as the reference's loop adds them: with three or more blocks on a pixel the order shows in the last bit.
     """
     blocks_t = torch.as_tensor(np.asarray(blocks, dtype=np.float32))
     locs = np.asarray(output_locations).reshape(-1, 4).astype(np.int64)
@@ -36,8 +37,7 @@ def merge_batch_to_canvas(blocks, output_locations, merged_shape):
     dev = default_device()
     if blocks_t.shape[0] == 0:
         return np.zeros(merged_shape, dtype=np.asarray(blocks).dtype), np.zeros((h, w, 1), dtype=np.uint8)
-    order = np.argsort(locs[:, 0], kind="stable")
-    row, cnt = _row_merge(blocks_t[order].to(dev), locs[order, 0], w)
+    row, cnt = _row_merge(blocks_t.to(dev), locs[:, 0], w)
     canvas = row[:h].cpu().numpy().astype(np.asarray(blocks).dtype)
     return canvas, cnt[:h].cpu().numpy()[..., None]
 
@@ -71,6 +71,20 @@ def _finalize(row_a, cnt_a, ys_a, row_b, cnt_b, ys_b, y0, y1, probs, pred, *, y_
             cnt_b.data_ptr() if cnt_b is not None else 0, int(ys_b) - y_base, oh, width, c, int(y0) - y_base, int(y1) - y_base,
             probs.data_ptr() if probs is not None else 0, pred.data_ptr(), _lib.current_stream())
     _lib.check(rc, "tia_canvas_finalize_f32")
+
+
+def check_patch_row_overlap(out_bounds: np.ndarray, ioconfig) -> None:
+    """``ValueError`` when three or more patch rows would cover one canvas row (a vertical stride below half the output height).
+    ``infer_wsi`` finalises a canvas row from the previous and the current patch row, as the reference's
+    ``merge_vertical_chunkwise`` does; a third row's sums and counts would be dropped without a trace, so such a configuration
+    is refused before anything is inferred (the reference fails on it too, with a broadcast error inside the merge)."""
+    row_ys = np.unique(np.asarray(out_bounds).reshape(-1, 4)[:, 1])
+    oh = int(ioconfig.patch_output_shape[0])
+    if len(row_ys) > 2 and bool(np.any(row_ys[2:] < row_ys[:-2] + oh)):
+        msg = (f"`patch_output_shape` {[int(v) for v in ioconfig.patch_output_shape]} with `stride_shape` "
+               f"{[int(v) for v in ioconfig.stride_shape]} puts three or more patch rows over one canvas row; the stitching adds "
+               "at most two.  Use a vertical stride of at least half the output height.")
+        raise ValueError(msg)
 
 
 def band_plan(row_ys: np.ndarray, oh: int, height: int, rank: int, world: int) -> dict:
@@ -290,6 +304,7 @@ class SemanticSegmentor(PatchPredictor):
         infer_batch = self._get_model_attr("infer_batch")
         w, h = reader.slide_dimensions
         in_b, out_b, keep = self.get_coordinates(reader, mask_reader)
+        check_patch_row_overlap(out_b, self._ioconfig)
         row_ys = np.unique(out_b[:, 1])
         oh = int(self._ioconfig.patch_output_shape[0])
         rank, world = tdist.world() if self.distributed else (0, 1)

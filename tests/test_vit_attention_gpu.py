@@ -14,7 +14,7 @@ from _vit_attention_ref import map_error, maps64_of
 from _vit_foundation_ref import TINY_REG, tiny_foundation
 from _vit_ref import tiny_vit
 from _vit_virchow_ref import TINY_V2, tiny_virchow
-from test_vit_gpu import _banned, _device_kernels
+from test_vit_gpu import _banned, _device_kernels, _mha_head_dims
 
 from tiatoolbox_amd.models.dataset.classification import timm_preproc_func
 
@@ -202,4 +202,5 @@ def test_bf16_forward_with_rollout_launches_only_handwritten_kernels():
         kernels = _device_kernels(lambda: fused(x))
     for wanted in ("mha_fwd_h_kernel", "mha_probs_kernel", "rollout_step_kernel", "layernorm_rows_h_kernel", "conv_mfma_h"):
         assert any(wanted in k for k in kernels), (wanted, kernels)
+    assert _mha_head_dims(kernels) == {64}, kernels  # (the head_dim-64 instantiation of the one attention kernel, and no other)
     assert not {k for k in kernels if _banned(k) or "softmax" in k.lower()}, kernels

@@ -14,7 +14,7 @@ import torch
 from _vit_classifier_ref import redraw_classifier, timm_model
 from _vit_ref import randomise
 from _vit_virchow_ref import TINY_V2, tiny_virchow
-from test_vit_gpu import _banned, _device_kernels
+from test_vit_gpu import _banned, _device_kernels, _mha_head_dims
 
 pytestmark = pytest.mark.gpu
 
@@ -95,6 +95,7 @@ def test_patch_predictor_runs_from_bytes_to_probabilities_on_the_kernels(runs, n
     kernels = _device_kernels(lambda: eng.infer_patches(eng.dataloader))
     for wanted in ("vit_patchify_norm_u8_h_kernel", "linear_softmax_rows_f32_kernel", "mha_fwd_h_kernel", "conv_mfma_h"):
         assert any(wanted in k for k in kernels), (wanted, kernels)
+    assert _mha_head_dims(kernels) == {64}, kernels  # (the head_dim-64 instantiation of the one attention kernel, and no other)
     assert not {k for k in kernels if _banned(k) or _torch_kernel(k)}, kernels
     assert not any("vit_patchify_h_kernel" in k for k in kernels), kernels
     # a batch that is already on the device takes the same route to the same bits

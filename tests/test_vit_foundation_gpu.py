@@ -12,7 +12,7 @@ import pytest
 import torch
 
 from _vit_foundation_ref import TINY_GIGA, TINY_REG, tiny_foundation
-from test_vit_gpu import _banned, _device_kernels, _parity
+from test_vit_gpu import _banned, _device_kernels, _mha_head_dims, _parity
 
 pytestmark = pytest.mark.gpu
 
@@ -60,6 +60,7 @@ def test_bf16_forward_launches_the_new_kernels_and_no_library():
     for wanted in ("mha_fwd_h_kernel", "layernorm_rows_h_kernel", "conv_mfma_h", "swiglu_rows_h_kernel", "vit_patchify_pad_h_kernel",
                    "vit_assemble_prefix_h_kernel"):
         assert any(wanted in k for k in kernels), (wanted, kernels)
+    assert _mha_head_dims(kernels) == {64}, kernels  # (the head_dim-64 instantiation of the one attention kernel, and no other)
     assert not {k for k in kernels if "gelu_rows_h_kernel" in k or "vit_assemble_tokens_h_kernel" in k}, kernels
     assert not {k for k in kernels if _banned(k)}, kernels
 

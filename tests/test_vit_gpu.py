@@ -5,6 +5,7 @@ from __future__ import annotations
 
 import copy
 import logging
+import re
 
 import numpy as np
 import pytest
@@ -153,6 +154,12 @@ def _banned(name: str) -> bool:
     return any(b in low for b in ("cijk_", "rocblas", "hipblaslt", "gemm", "fmha", "miopen")) or ("attention" in low and "ck" in low)
 
 
+def _mha_head_dims(kernels) -> set[int]:
+    """The ``head_dim`` of every ``mha_fwd_h_kernel<BF, HD>`` instantiation among ``kernels``: the profiler prints the template
+    arguments, and a name without them counts as no instantiation at all."""
+    return {int(m.group(1)) for m in (re.search(r"mha_fwd_h_kernel<[^>]*\b(\d+)>", k) for k in kernels) if m}
+
+
 def test_bf16_forward_launches_only_handwritten_kernels():
     from tiatoolbox_amd.models.architecture.vit_fused import FusedViT
 
@@ -166,4 +173,5 @@ def test_bf16_forward_launches_only_handwritten_kernels():
     for wanted in ("mha_fwd_h_kernel", "layernorm_rows_h_kernel", "conv_mfma_h", "gelu_rows_h_kernel", "vit_patchify_h_kernel",
                    "vit_assemble_tokens_h_kernel"):
         assert any(wanted in k for k in kernels), (wanted, kernels)
+    assert _mha_head_dims(kernels) == {64}, kernels  # (the head_dim-64 instantiation of the one attention kernel, and no other)
     assert not {k for k in kernels if _banned(k)}, kernels

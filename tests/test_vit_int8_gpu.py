@@ -18,7 +18,7 @@ from _vit_foundation_ref import TINY_REG, tiny_foundation
 from _vit_int8_ref import fake_quantised_module, rel_error
 from _vit_ref import randomise, tiny_vit
 from _vit_virchow_ref import TINY_V2, tiny_virchow
-from test_vit_gpu import _banned, _device_kernels
+from test_vit_gpu import _banned, _device_kernels, _mha_head_dims
 
 pytestmark = pytest.mark.gpu
 
@@ -113,6 +113,7 @@ def test_int8_forward_launches_the_int8_kernels_and_no_library():
     for wanted in ("linear_rows_kernel<tia::q8::Int8", "layernorm_rows_kernel<tia::q8::Int8", "act_rows_kernel<tia::q8::Int8", "mha_fwd_h_kernel", "conv_mfma_h"):
         assert any(wanted in k for k in kernels), (wanted, kernels)
         assert any(wanted in k for k in kernels_swiglu), (wanted, kernels_swiglu)
+    assert _mha_head_dims(kernels) == _mha_head_dims(kernels_swiglu) == {64}, (kernels, kernels_swiglu)  # (head_dim 64: that instantiation and no other)
     assert {k for k in kernels if "act_rows_kernel<tia::q8::Int8" in k} != {k for k in kernels_swiglu if "act_rows_kernel<tia::q8::Int8" in k}
     for ks in (kernels, kernels_swiglu):  # every INT8 layer's producer is the quantising one; nothing of the FP8 route runs
         assert not {k for k in ks if "gelu_rows_h_kernel" in k or "swiglu_rows_h_kernel" in k or "fp8" in k or "tia::q8::E4m3" in k}, ks

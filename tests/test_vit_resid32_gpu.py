@@ -17,6 +17,7 @@ from _vit_foundation_ref import TINY_REG, tiny_foundation
 from _vit_ref import forward64, randomise, tiny_vit
 from _vit_resid32_ref import autocast_features, cast_features, fused_graph, rel_error, scale_layer_scale
 from _vit_virchow_ref import TINY_V1, TINY_V2, tiny_virchow
+from test_vit_gpu import _mha_head_dims
 
 pytestmark = pytest.mark.gpu
 
@@ -124,9 +125,10 @@ def test_none_is_the_default_graph(form, dtype):
     assert k_plain == k_given and not [k for k in k_given if any(new in k for new in NEW_KERNELS)], k_given
     wanted = (["vit_patchify_h_kernel", "vit_assemble_tokens_h_kernel", "gelu_rows_h_kernel", "mha_fwd_h_kernel"] if form == "tiny-ls" else
               ["vit_patchify_pad_h_kernel", "vit_assemble_prefix_h_kernel", "swiglu_rows_h_kernel", "vit_cls_mean_pool_h_kernel",
-               "mha_fwd_h80_kernel"])  # (80 dimensions per head: the attention kernel's second form)
+               "mha_fwd_h_kernel"])
     for name in [*wanted, "layernorm_rows_h_kernel", "conv_mfma_h"]:
         assert any(name in k for k in k_given), (name, k_given)
+    assert _mha_head_dims(k_given) == ({64} if form == "tiny-ls" else {80}), k_given  # (80 dimensions per head: the attention kernel's other instantiation)
 
 
 @pytest.mark.parametrize("form", ["tiny-ls", "tiny-v2"])
@@ -140,8 +142,9 @@ def test_forward_launches_the_new_kernels_and_none_they_replace(form):
         assert any(wanted in k for k in kernels), (wanted, kernels)
     assert not [k for k in kernels if any(old in k for old in REPLACED)], kernels
     assert not {k for k in kernels if _banned(k)}, kernels
-    for wanted in ("mha_fwd_h_kernel" if form == "tiny-ls" else "mha_fwd_h80_kernel", "conv_mfma_h"):
+    for wanted in ("mha_fwd_h_kernel", "conv_mfma_h"):
         assert any(wanted in k for k in kernels), (wanted, kernels)
+    assert _mha_head_dims(kernels) == ({64} if form == "tiny-ls" else {80}), kernels
 
 
 @pytest.mark.parametrize("dtype", DTYPES, ids=IDS)

@@ -13,7 +13,7 @@ import pytest
 import torch
 
 from _vit_virchow_ref import NO_PAD, TINY_V1, TINY_V2, tiny_virchow
-from test_vit_gpu import _banned, _device_kernels, _parity
+from test_vit_gpu import _banned, _device_kernels, _mha_head_dims, _parity
 
 pytestmark = pytest.mark.gpu
 
@@ -79,8 +79,9 @@ def test_engine_runs_virchow2_on_the_fused_graph_in_bf16(caplog):
     xin = x.contiguous(memory_format=torch.channels_last)
     with torch.inference_mode():
         kernels = _device_kernels(lambda: fast.feat_extract(xin))
-    for wanted in ("mha_fwd_h80_kernel", "vit_cls_mean_pool_h_kernel", "layernorm_rows_h_kernel", "conv_mfma_h", "swiglu_rows_h_kernel",
+    for wanted in ("mha_fwd_h_kernel", "vit_cls_mean_pool_h_kernel", "layernorm_rows_h_kernel", "conv_mfma_h", "swiglu_rows_h_kernel",
                    "vit_patchify_pad_h_kernel", "vit_assemble_prefix_h_kernel"):
         assert any(wanted in k for k in kernels), (wanted, kernels)
-    assert not {k for k in kernels if "mha_fwd_h_kernel" in k or "vit_assemble_tokens_h_kernel" in k or "gelu_rows_h_kernel" in k}, kernels
+    assert _mha_head_dims(kernels) == {80}, kernels  # (the head_dim-80 instantiation of the one attention kernel, and none with 64)
+    assert not {k for k in kernels if "vit_assemble_tokens_h_kernel" in k or "gelu_rows_h_kernel" in k}, kernels
     assert not {k for k in kernels if _banned(k)}, kernels

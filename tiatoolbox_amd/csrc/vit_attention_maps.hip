@@ -9,12 +9,13 @@
 // operand (lane l: query l & 15, dims 32 step + 8 (l >> 4) .. + 7), K in 64-key tiles through LDS as the A operand, so that
 //   sc[kt][r] = score(query l & 15, key k0 + 16 kt + 4 (l >> 4) + r)
 // and a query's 64 scores of a tile sit in the four lanes l & 15 (+ 16, 32, 48).  head_dim 80 is three k-steps whose dims 80..95 are
-// exact zeros in both operands (lane quarters 2 and 3 of step 2 substitute a zero register), as in mha_fwd_h80_kernel.
+// exact zeros in both operands (lane quarters 2 and 3 of step 2 substitute a zero register).  All of that IS the forward's code:
+// geometry, decode, Q load, K staging, score tile and online maximum come from vit_attention_tile.hpp, as mha_fwd_h_kernel's do.
 //
 // Two passes, so that no S-wide row has to live anywhere and s has no ceiling:
 //   1. per head, the online maximum m and sum l of a query row over all key tiles (float32, base-2 domain: t = dot * scale * log2 e,
 //      l = sum exp2(t - m), rescaled by exp2(m_old - m_new) when the maximum moves); (m, l) of every (head, query) go to LDS.
-//   2. per key tile, for every head in ascending order: the scores again (the same instructions on the same operands: the same
+//   2. per key tile, for every head in ascending order: the scores again (the same score_tile on the same operands: the same
 //      bits), p = exp2(t - m) / l -- ONE correctly rounded division, e_j / sum e rounded once -- and, with head_mean, acc += p in
 //      float32 and acc / heads at the end.  The tile goes through LDS once (transposed so that a wave stores 64 consecutive floats
 //      of a row) and is written once.  Nothing is accumulated in memory: no atomics, two launches agree bit for bit.
@@ -30,91 +31,15 @@
 // these two: tia_mha_probs_fused_h is the probabilities kernel with another way of joining the heads (FUSE), tia_rollout_product_f32
 // the step kernel without its blend (BLEND), and tia_rollout_discard_normalize_f32 a radix select per image (kth_smallest_kernel)
 // in front of a row pass (discard_normalize_kernel).  A run with the default options launches none of them.
-#include "conv_device.hpp"
-#include "wide_io.hpp"
+#include "vit_attention_tile.hpp"
 
 namespace {
 
 using namespace tia;
-using f32x4 = __attribute__((ext_vector_type(4))) float;
+using namespace tia::mha;  // AT, KV_TILE, Geo, decode, load_q, stage_tile, score_tile, online_max: mha_fwd_h_kernel's own pieces
 
-constexpr int AT = 256;       // threads: 4 waves x 16 query rows
-constexpr int KV_TILE = 64;   // keys per LDS tile
 constexpr int T_PITCH = 68;   // floats per row of the transposed output tile (16-byte aligned rows)
 constexpr int MAX_MEAN_HEADS = 64;  // head_mean keeps (m, l) of 64 queries per head in LDS: 512 bytes a head
-
-template <bool BF>
-__device__ __forceinline__ f32x4 mma16(const v4u& a, const v4u& b, const f32x4& c) {
-    if constexpr (BF)
-        return __builtin_amdgcn_mfma_f32_16x16x32_bf16(*reinterpret_cast<const b8*>(&a), *reinterpret_cast<const b8*>(&b), c, 0, 0, 0);
-    else
-        return __builtin_amdgcn_mfma_f32_16x16x32_f16(*reinterpret_cast<const h8*>(&a), *reinterpret_cast<const h8*>(&b), c, 0, 0, 0);
-}
-
-// HD 64: rows of 64 + 8 halves (the pitch of mha_fwd_h_kernel); HD 80: 80, conflict-free without a pad (mha_fwd_h80_kernel's count)
-template <int HD>
-struct Geo {
-    static constexpr int PITCH = HD == 64 ? 72 : 80;
-    static constexpr int STEPS = HD == 64 ? 2 : 3;
-    static constexpr int VEC = HD / 8;                          // 16-byte vectors per row
-    static constexpr int ROUNDS = (KV_TILE * VEC + AT - 1) / AT;  // staging rounds of the workgroup
-};
-
-template <int HD>
-__device__ __forceinline__ void load_q(const unsigned short* base, long row_stride, int query, int q_rows, int quarter,
-                                       v4u (&qf)[Geo<HD>::STEPS]) {
-    const v4u zero4 = {0u, 0u, 0u, 0u};
-#pragma unroll
-    for (int st = 0; st < Geo<HD>::STEPS; ++st) {
-        const bool real = query < q_rows && 32 * st + 8 * quarter < HD;
-        qf[st] = real ? *reinterpret_cast<const v4u*>(base + (long)query * row_stride + 32 * st + 8 * quarter) : zero4;
-    }
-}
-
-// keys k0 .. k0 + 63 of one head into k_lds ([key][dim]), zeros beyond s; both barriers are inside
-template <int HD>
-__device__ __forceinline__ void stage_keys(const unsigned short* kbase, long row_stride, int k0, int s, int tid, unsigned short* k_lds) {
-    using G = Geo<HD>;
-    const v4u zero4 = {0u, 0u, 0u, 0u};
-    v4u kreg[G::ROUNDS];
-#pragma unroll
-    for (int i = 0; i < G::ROUNDS; ++i) {
-        const int v = tid + AT * i, row = v / G::VEC, c = v % G::VEC, key = k0 + row;
-        kreg[i] = (v < KV_TILE * G::VEC && key < s) ? *reinterpret_cast<const v4u*>(kbase + (long)key * row_stride + 8 * c) : zero4;
-    }
-    __syncthreads();  // every wave has finished reading the previous tile
-#pragma unroll
-    for (int i = 0; i < G::ROUNDS; ++i) {
-        const int v = tid + AT * i, row = v / G::VEC, c = v % G::VEC;
-        if (v < KV_TILE * G::VEC) *reinterpret_cast<v4u*>(&k_lds[row * G::PITCH + 8 * c]) = kreg[i];
-    }
-    __syncthreads();
-}
-
-// t[kt][r] = scale * log2 e * score(query l & 15, key k0 + 16 kt + 4 quarter + r), -inf for keys >= s
-template <bool BF, int HD>
-__device__ __forceinline__ void score_tile(const unsigned short* k_lds, const v4u (&qf)[Geo<HD>::STEPS], int k0, int s, int r16, int quarter,
-                                           float scale_log2e, f32x4 (&t)[4]) {
-    using G = Geo<HD>;
-    const v4u zero4 = {0u, 0u, 0u, 0u};
-#pragma unroll
-    for (int kt = 0; kt < 4; ++kt) {
-        f32x4 acc = {0.0f, 0.0f, 0.0f, 0.0f};
-#pragma unroll
-        for (int st = 0; st < G::STEPS; ++st) {
-            // (HD 80, step 2: quarters 2 and 3 are dims 80..95 -- they read the address of quarter & 1 and substitute zeros)
-            const int q_read = 32 * st + 8 * quarter < HD ? quarter : (quarter & 1);
-            v4u a = *reinterpret_cast<const v4u*>(&k_lds[(16 * kt + r16) * G::PITCH + 32 * st + 8 * q_read]);
-            if (32 * st + 8 * quarter >= HD) a = zero4;
-            acc = mma16<BF>(a, qf[st], acc);
-        }
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            const int key = k0 + 16 * kt + 4 * quarter + r;
-            t[kt][r] = key < s ? acc[r] * scale_log2e : -INFINITY;
-        }
-    }
-}
 
 // FUSE: what pass 2 does with the heads of a workgroup -- FUSE_SUM adds them (one head: 0 + p = p exactly; head_mean: / heads at the
 // end), FUSE_MAX / FUSE_MIN keep the exact element-wise maximum / minimum of the SAME per-head values (head_mean geometry: one
@@ -129,17 +54,13 @@ __global__ __launch_bounds__(AT) void mha_probs_kernel(const unsigned short* __r
     __shared__ __attribute__((aligned(16))) float t_lds[64 * T_PITCH];                 // [query][key]: the tile on its way out
     extern __shared__ float stat_lds[];                                                // [head of this workgroup][query][m, l]
 
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int r16 = lane & 15, quarter = lane >> 4;
-    const long bid = blockIdx.x;
-    const int qt = (int)(bid % q_tiles);
-    const long rest = bid / q_tiles;
-    const int h0 = head_mean ? 0 : (int)(rest % heads);  // the first head of this workgroup, and how many it owns
+    const Where w = decode(q_tiles);  // rest = (image, head), or -- head_mean -- the image
+    const int tid = w.tid, lane = w.lane, wave = w.wave, r16 = w.r16, quarter = w.quarter, qt = w.qt, query = w.query;
+    const int h0 = head_mean ? 0 : (int)(w.rest % heads);  // the first head of this workgroup, and how many it owns
     const int nh = head_mean ? heads : 1;
-    const long b = head_mean ? rest : rest / heads;
+    const long b = head_mean ? w.rest : w.rest / heads;
     const long row_stride = 3L * heads * HD;  // halves between consecutive tokens of qkv
     const unsigned short* image = qkv + b * s * row_stride;
-    const int query = qt * 64 + wave * 16 + r16;
 
     // pass 1: the maximum and the sum of every (head, query) row
     for (int hl = 0; hl < nh; ++hl) {
@@ -147,30 +68,20 @@ __global__ __launch_bounds__(AT) void mha_probs_kernel(const unsigned short* __r
         const unsigned short* kbase = base + (long)heads * HD;
         v4u qf[G::STEPS];
         load_q<HD>(base, row_stride, query, q_rows, quarter, qf);
-        float m_run = -INFINITY, l_run = 0.0f;  // l_run: this lane's share of the row sum (its 16 keys per tile)
+        float m_run = -INFINITY, l_run = 0.0f;
         for (int k0 = 0; k0 < s; k0 += KV_TILE) {
-            stage_keys<HD>(kbase, row_stride, k0, s, tid, k_lds);
+            stage_tile<HD, false>(kbase, nullptr, row_stride, k0, s, tid, k_lds, nullptr);
             f32x4 t[4];
-            score_tile<BF, HD>(k_lds, qf, k0, s, r16, quarter, scale_log2e, t);
-            float t_max = -INFINITY;
-#pragma unroll
-            for (int kt = 0; kt < 4; ++kt)
-#pragma unroll
-                for (int r = 0; r < 4; ++r) t_max = fmaxf(t_max, t[kt][r]);
-            t_max = fmaxf(t_max, __shfl_xor(t_max, 16, 64));
-            t_max = fmaxf(t_max, __shfl_xor(t_max, 32, 64));
-            const float m_new = fmaxf(m_run, t_max);                    // finite: the tile holds a real key
-            const float alpha = __builtin_amdgcn_exp2f(m_run - m_new);  // first tile: exp2(-inf) = 0
-            m_run = m_new;
+            const float t_max = score_tile<BF, HD>(k_lds, qf, k0, s, r16, quarter, scale_log2e, t);
+            const float alpha = online_max(t_max, m_run);
             float p_sum = 0.0f;
 #pragma unroll
             for (int kt = 0; kt < 4; ++kt)
 #pragma unroll
-                for (int r = 0; r < 4; ++r) p_sum += __builtin_amdgcn_exp2f(t[kt][r] - m_new);
+                for (int r = 0; r < 4; ++r) p_sum += __builtin_amdgcn_exp2f(t[kt][r] - m_run);
             l_run = l_run * alpha + p_sum;
         }
-        float l_tot = l_run + __shfl_xor(l_run, 16, 64);
-        l_tot += __shfl_xor(l_tot, 32, 64);
+        const float l_tot = row_sum(l_run);
         if (quarter == 0) {
             stat_lds[(hl * 64 + wave * 16 + r16) * 2] = m_run;
             stat_lds[(hl * 64 + wave * 16 + r16) * 2 + 1] = l_tot;
@@ -192,7 +103,7 @@ __global__ __launch_bounds__(AT) void mha_probs_kernel(const unsigned short* __r
             const unsigned short* kbase = base + (long)heads * HD;
             v4u qf[G::STEPS];
             load_q<HD>(base, row_stride, query, q_rows, quarter, qf);
-            stage_keys<HD>(kbase, row_stride, k0, s, tid, k_lds);
+            stage_tile<HD, false>(kbase, nullptr, row_stride, k0, s, tid, k_lds, nullptr);
             f32x4 t[4];
             score_tile<BF, HD>(k_lds, qf, k0, s, r16, quarter, scale_log2e, t);
             const float m = stat_lds[(hl * 64 + wave * 16 + r16) * 2], l = stat_lds[(hl * 64 + wave * 16 + r16) * 2 + 1];
@@ -400,17 +311,13 @@ bool overlap(const void* p, const void* q, uint64_t bytes) { return overlap(p, b
 // with the heads' maximum / minimum
 int launch_probs(const void* d_qkv, float* d_out, int64_t n, int64_t s, int64_t heads, int64_t head_dim, float scale, int64_t q_rows,
                  int32_t head_mean, int fuse, int32_t dtype, void* stream) {
-    if (!d_qkv || !d_out || n <= 0 || s <= 0 || heads <= 0 || head_dim <= 0) return TIA_EINVAL;
-    if (dtype != TIA_DT_F16 && dtype != TIA_DT_BF16) return TIA_EINVAL;
-    if (!(scale > 0.0f) || !(scale < INFINITY)) return TIA_EINVAL;
+    // (own checks around the shared ones: the first stands among check_args's leading TIA_EINVALs, the last among its trailing TIA_ESIZEs)
     if (q_rows < 1 || q_rows > s || (head_mean != 0 && head_mean != 1)) return TIA_EINVAL;
-    if (head_dim != 64 && head_dim != 80) return TIA_ESIZE;
-    if ((reinterpret_cast<uintptr_t>(d_qkv) | reinterpret_cast<uintptr_t>(d_out)) & 15) return TIA_EINVAL;
-    if (s > 0x7fffffffL - KV_TILE || heads > 0x7fffffffL / (3 * head_dim)) return TIA_ESIZE;
-    if (head_mean && heads > MAX_MEAN_HEADS) return TIA_ESIZE;
-    const long q_tiles = (q_rows + 63) / 64;
     const long groups = head_mean ? 1 : heads;  // workgroups per (image, query tile)
-    if (n > 0x7fffffffL / groups || n * groups > 0x7fffffffL / q_tiles) return TIA_ESIZE;  // one grid dimension
+    long q_tiles;
+    const int code = check_args(d_qkv, d_out, n, s, heads, head_dim, scale, dtype == TIA_DT_F16 || dtype == TIA_DT_BF16, q_rows, groups, &q_tiles);
+    if (code != TIA_OK) return code;
+    if (head_mean && heads > MAX_MEAN_HEADS) return TIA_ESIZE;
     const long blocks = n * groups * q_tiles;
     const size_t stat_bytes = (size_t)(head_mean ? heads : 1) * 64 * 2 * sizeof(float);
     const float scale_log2e = scale * 1.44269504088896340736f;

@@ -57,6 +57,7 @@
 // the first tile on: m_old - m_new is -inf - finite there, never inf - inf.  Query rows >= s compute on zeros and are not stored.
 #include "conv_device.hpp"
 #include "half_rows.hpp"
+#include "vit_attention_tile.hpp"  // (mha::check_args)
 #include "wide_io.hpp"
 
 namespace {
@@ -293,14 +294,9 @@ unsigned stream_blocks(long items) {
 
 extern "C" int tia_mha_fwd_f32(const float* d_qkv, float* d_out, int64_t n, int64_t s, int64_t heads, int64_t head_dim, float scale,
                                int32_t dtype, void* stream) {
-    if (!d_qkv || !d_out || n <= 0 || s <= 0 || heads <= 0 || head_dim <= 0) return TIA_EINVAL;
-    if (dtype != TIA_DT_F32) return TIA_EINVAL;
-    if (!(scale > 0.0f) || !(scale < INFINITY)) return TIA_EINVAL;
-    if (head_dim != 64 && head_dim != 80) return TIA_ESIZE;
-    if ((reinterpret_cast<uintptr_t>(d_qkv) | reinterpret_cast<uintptr_t>(d_out)) & 15) return TIA_EINVAL;
-    if (s > 0x7fffffffL - KV_TILE || heads > 0x7fffffffL / (3 * head_dim)) return TIA_ESIZE;
-    const long q_tiles = (s + 63) / 64;
-    if (n > 0x7fffffffL / heads || n * heads > 0x7fffffffL / q_tiles) return TIA_ESIZE;  // one grid dimension
+    long q_tiles;
+    const int code = mha::check_args(d_qkv, d_out, n, s, heads, head_dim, scale, dtype == TIA_DT_F32, s, heads, &q_tiles);
+    if (code != TIA_OK) return code;
     const long blocks = n * heads * q_tiles;
     const float scale_log2e = scale * 1.44269504088896340736f;
     const auto kernel = head_dim == 80 ? mha_fwd_f32_kernel<80> : mha_fwd_f32_kernel<64>;

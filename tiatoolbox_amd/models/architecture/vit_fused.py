@@ -33,7 +33,7 @@ half a unit of ``dtype`` at ``x`` is rounded away by the default graph and kept 
 
 ``Virchow`` / ``Virchow2`` (ViT-H/14, 1280 / 16 = 80 per head) change four more, all on the host in float32 before the one rounding:
 
-* ``head_dim`` 80: ``tia_mha_fwd_h``'s second kernel form; ``scale = 80 ** -0.5``;
+* ``head_dim`` 80: the other instantiation of ``tia_mha_fwd_h``'s kernel; ``scale = 80 ** -0.5``;
 * a packed SwiGLU whose half (3416) is off the GEMM's multiple of 32: each half of ``fc1`` is padded with zero rows and zero bias to
   3424 and ``fc2`` with zero columns (``pad_swiglu``; halves below 512 are not padded) -- a pad lane is ``silu(0) * 0 = 0`` exactly;
 * ``prefix_pos_embed`` (register tokens with entries of their own in the position table): ``cls + pos[0]`` and ``reg + pos[1 : 1 + R]``

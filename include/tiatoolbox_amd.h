@@ -56,7 +56,8 @@ extern "C" {
  * smoothing of those layers and its calibration statistics); tia_mha_probs_h, tia_rollout_step_f32 (attention maps of the Vision
  * Transformer runs: the probabilities tia_mha_fwd_h does not materialise, and attention rollout); tia_merge_patch_grids_f32 (those maps resampled into a
  * whole-slide heat map); tia_mha_probs_fused_h, tia_rollout_discard_normalize_f32, tia_rollout_product_f32 (rollout with max / min
- * head fusion and a discard ratio); tia_cam_nhwc_f32, tia_cam_nhwc_h (class activation maps of the CNN classifiers). */
+ * head fusion and a discard ratio); tia_cam_nhwc_f32, tia_cam_nhwc_h (class activation maps of the CNN classifiers); tia_peak_chunks,
+ * tia_peak_scan_f32, tia_peak_write_f32, tia_peak_resolve_host (peak_local_max on probability maps). */
 #define TIA_ABI_VERSION 6
 int tia_abi_version(void);
 
@@ -1340,6 +1341,45 @@ int tia_label_first_pixel_i32(const int32_t* d_labels, int64_t n, int64_t h, int
 int tia_border_trace_u8(const uint8_t* d_mask, int64_t n, int64_t h, int64_t w, const int32_t* d_starts, int64_t nb,
                         int32_t simple, int32_t* d_counts, const int64_t* d_offsets, int64_t capacity,
                         int32_t* d_points, void* stream);
+
+/* =======================================================================================
+ * Peak detection on probability maps: skimage.feature.peak_local_max with a square footprint, p_norm = inf, no labels
+ * (what the reference's detection models call in postproc; additive at version 6).  tiatoolbox_amd/utils/_peaks.py
+ * states the result and is the contract.
+ * ===================================================================================== */
+
+/* Candidates of n float32 planes [n,h,w], in two calls around one read of d_totals (the count pass and the write pass of
+ * tia_hover_contour_scan / _write: raster order without order-dependent atomics).
+ *   scan : threshold t = threshold_abs if has_threshold_abs else the plane's minimum; with has_threshold_rel
+ *          t = max(t, threshold_rel * the plane's maximum) (float32).  A pixel is a candidate when it equals the maximum of its
+ *          (2 min_distance + 1)^2 window (edge-replicated), the plane is not constant (a 1-pixel plane: no such condition),
+ *          it is > t (strict) and it lies outside the first and last `border` rows and columns.
+ *          d_state [n,h,w] u8 = 0 no candidate, 1 candidate, 2 contested candidate: another candidate lies at Chebyshev distance
+ *          < min_distance (only these take part in the spacing walk, see tia_peak_resolve_host).
+ *          d_minmax [n,2] u32, d_flags [n,h,w] u8: scratch.  d_offsets [n, tia_peak_chunks(h, w)] i32: for the write pass.
+ *          d_totals [n] i64 = candidates per plane.
+ *   write: d_bases [n] i64 = row of each plane's first candidate in the outputs (the exclusive prefix sum of d_totals);
+ *          candidate j of plane p in raster order goes to row d_bases[p] + j of d_yx [capacity,2] i32 (row, column),
+ *          d_value [capacity] f32 and d_contested [capacity] u8; rows at or beyond `capacity` are not written.
+ * 1 <= min_distance <= 64 and h * w < 2^31, else TIA_ESIZE (also: n * tiles of 32 x 32 pixels >= 2^31).  TIA_EINVAL: a null
+ * pointer, n / h / w <= 0, border < 0, capacity < 0.  Nothing is launched on an error.  Offsets into the batch are 64-bit.
+ * NaN is outside the domain: with a NaN in a plane its result is unspecified, but every access stays in bounds (no index
+ * depends on a pixel's value).  +-inf and +-0 are inside it (-0 == +0). */
+size_t tia_peak_chunks(int64_t h, int64_t w);
+int tia_peak_scan_f32(const float* d_image, int64_t n, int64_t h, int64_t w, int32_t min_distance,
+                      int32_t has_threshold_abs, float threshold_abs, int32_t has_threshold_rel, float threshold_rel,
+                      int32_t border, uint32_t* d_minmax, uint8_t* d_flags, uint8_t* d_state, int32_t* d_offsets,
+                      int64_t* d_totals, void* stream);
+int tia_peak_write_f32(const float* d_image, const uint8_t* d_state, int64_t n, int64_t h, int64_t w,
+                       const int32_t* d_offsets, const int64_t* d_bases, int64_t capacity, int32_t* d_yx,
+                       float* d_value, uint8_t* d_contested, void* stream);
+
+/* The spacing walk of peak_local_max over the contested candidates of ONE plane, on the HOST (no device call; all pointers
+ * are host memory): yx [k,2] i32 (row, column) in strictly ascending raster order, plane width w; accept[i] = 1 when no
+ * candidate accepted before it lies at Chebyshev distance < min_distance, else 0.  Two candidates that close have equal
+ * values, so raster order is the statement's order among them.  TIA_EINVAL: k < 0, w <= 0, min_distance < 1, a null
+ * pointer with k > 0, a column outside [0, w), a negative row, or rows not in raster order. */
+int tia_peak_resolve_host(const int32_t* yx, int64_t k, int64_t w, int32_t min_distance, uint8_t* accept);
 
 #ifdef __cplusplus
 }

@@ -204,6 +204,10 @@ _SIGNATURES = {
     "tia_label_first_pixel_i32": ([_P, _I64, _I64, _I64, _I32, _P, _P, _P], C.c_int),
     "tia_border_trace_u8": ([_P, _I64, _I64, _I64, _P, _I64, _I32, _P, _P, _I64, _P, _P], C.c_int),
     "tia_hover_contour_write": ([_P, _I64, _I64, _I64, _I32, _P, _P, _I64, _P, _P], C.c_int),
+    "tia_peak_chunks": ([_I64, _I64], C.c_size_t),
+    "tia_peak_scan_f32": ([_P, _I64, _I64, _I64, _I32, _I32, C.c_float, _I32, C.c_float, _I32, _P, _P, _P, _P, _P, _P], C.c_int),
+    "tia_peak_write_f32": ([_P, _P, _I64, _I64, _I64, _P, _P, _I64, _P, _P, _P, _P], C.c_int),
+    "tia_peak_resolve_host": ([_P, _I64, _I64, _I32, _P], C.c_int),
 }
 
 

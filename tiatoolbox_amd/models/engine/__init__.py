@@ -4,7 +4,7 @@ from __future__ import annotations
 
 import importlib
 
-__all__ = ["engine_abc", "io_config", "multi_task_segmentor", "nucleus_instance_segmentor", "patch_predictor",
+__all__ = ["engine_abc", "io_config", "multi_task_segmentor", "nucleus_detector", "nucleus_instance_segmentor", "patch_predictor",
            "semantic_segmentor"]
 
 
